@@ -10,7 +10,8 @@ One "step" is one full sweep of the fit over the resident video, the unit the re
 ``update_footprints(iter_c=50, gamma_c=0)``.  N=1 workload = BASELINE.json configs[2]: 512x512 (Z=1),
 T=4000, K=100, fp32.  N>1: the T axis is sharded, every rank holds 4000 frames of one 4000*N-frame video
 (weak scaling); there is no data-path collective (frames are independent in both steps), only the timing
-barrier.  The video is generated on the GPU before the timed region starts (inputs resident in HBM).
+barrier.  The video is generated on the GPU before the timed region starts (inputs resident in HBM).  The fit
+restarts from its initial state every SWEEPS_PER_FIT (25) sweeps, so any --steps times sweeps of a sane fit.
 
 ``--with-spatial`` adds the footprint update the reference leaves commented out (Demix/dNMF.py:169-176) to every
 sweep: K7 registration, K5, ONE all-reduce of the A1 | C_s buffer over the ranks (RCCL for N > 1) and K6 -- the only
@@ -18,15 +19,24 @@ collective the path has; it is a separate mode, never the headline value.
 
 Rank 0 prints ONE JSON line; it also carries
   roofline      the dominant kernel (the Gram kernel K3n / K3s / K3) timed with HIP events on its stream
-  cpu_baseline  the CPU oracle (reference op sequence) timed on this host on a bounded sample, N=1 only
   ranks         (N > 1) world size, backend and the (rank, device, PCI bus) rows all-gathered over the process group
-  extras        (default N=1 run only, outside the timed region, a few sweeps each; --no-extras skips them)
+A plain run does only what the headline needs: set-up, warm-up, the timed sweeps, the outputs (--dump-outputs DIR) and
+the line.  --full adds the measurements that take work of their own, after the timed region:
+  roofline_dense_kernel  one launch of the dense Gram kernel K3 (--no-extras skips it)
+  cpu_baseline  the CPU oracle (reference op sequence) timed on this host on a bounded sample, N=1 only
+                (--no-cpu-baseline skips it)
+  extras        (default N=1 workload only, a few sweeps each; --no-extras skips them)
                 depth2: the same sweep at 512x512x2 -- the smallest volume the reference itself can run, 8-tap kernels;
                 with_spatial: the sweep of --with-spatial with its kernel times;
                 stock_dataloader: the sweep driven by a plain torch DataLoader over a HOST video as in demo.py:33-35
                 (configs[1] whole, a 400-frame subset of configs[2]): PCIe- and host-inclusive frames/s
+
+--dump-outputs DIR writes, after the timed sweeps, the fit state the last sweep left (rank 0): DIR/beta.npy (10,3,T) and
+DIR/C.npy (K,T), and with --with-spatial DIR/footprints.npy; float32, an array above DUMP_MAX_ENTRIES entries as a fixed
+seeded sample of its flattened entries.  The inputs depend on the arguments only (seeded simulator, seeded loaders).
 """
 import argparse
+import copy
 import gc
 import json
 import os
@@ -65,7 +75,11 @@ def parse():
                          "number on a 512 x 512 volume is 2.6 px per step, and the fit (the reference's too) throws whole "
                          "footprints out of the volume within one epoch, after which traces overflow and beta turns NaN")
     ap.add_argument("--iter-c", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the dense Gram kernel's roofline launch, the CPU baseline and the extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fit state of the last timed sweep as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to "
                     "rehearse the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument("--gram", choices=["auto", "dense", "sparse", "lists"], default="auto",
@@ -84,8 +98,12 @@ def parse():
                     help="displaced: every frame starts from a smooth warp about a voxel away from the identity (shift, linear "
                          "and quadratic terms) instead of the identity")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements of the default N=1 run (Z = 2 line, spatial mode, stock DataLoader)")
-    return ap.parse_args()
+                    help="with --full: skip the dense Gram kernel's launch and the secondary measurements of the default "
+                         "N=1 run (Z = 2 line, spatial mode, stock DataLoader)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Traffic:
@@ -296,6 +314,10 @@ def displaced_beta(T, sz, device, seed=7):
     return (ident + d).to(device).contiguous()
 
 
+# sweeps of one fit before the benchmark restarts it (warm-up + timed sweeps of the default run)
+SWEEPS_PER_FIT = 25
+
+
 def run_sweeps(args, sz, K, T_loc, steps, warmup, rank, world, group, with_spatial=False, loader="resident",
                beta_init="identity", footprint_floor=0.0):
     """Build the workload (synthetic video resident in HBM, model, loaders) and time `steps` sweeps after `warmup`.
@@ -343,10 +365,26 @@ def run_sweeps(args, sz, K, T_loc, steps, warmup, rank, world, group, with_spati
             host = HostVideo(frames.cpu(), sz)
         del frames
         frames = None
-        train = torch.utils.data.DataLoader(host, batch_size=bs, shuffle=True, generator=torch.Generator().manual_seed(1234))
+        gen = torch.Generator().manual_seed(1234)
+        train = torch.utils.data.DataLoader(host, batch_size=bs, shuffle=True, generator=gen)
         test = torch.utils.data.DataLoader(host, batch_size=bs, shuffle=False)
+    # the fit is restarted every SWEEPS_PER_FIT sweeps (warm-up included) from the state it started in: traces, warps,
+    # footprints (--with-spatial updates them), Adam's moments and the loader's shuffle.  Every sweep then works on a fit
+    # as young as the default run's, whatever --steps is (see parse(): after ~100 sweeps the fit is no longer the
+    # workload and its traces overflow).
+    start = (dn.C.clone(), copy.deepcopy(opt.state_dict()), gen.get_state(), dn.fp.A.clone() if with_spatial else None)
+    sweeps = [0]
 
     def step():
+        if sweeps[0] and sweeps[0] % SWEEPS_PER_FIT == 0:
+            with torch.no_grad():
+                dn.fp.beta.copy_(beta_start)
+                if start[3] is not None:
+                    dn.fp.A.copy_(start[3])
+            dn.C = start[0].clone()
+            opt.load_state_dict(start[1])
+            gen.set_state(start[2])
+        sweeps[0] += 1
         dn.update_motion(train, opt, gamma=1, epochs=1)
         dn.update_footprints(test, bs, sz, gamma_c=0, gamma_a=1.0, iter_c=args.iter_c, return_dense=False,
                              live_spatial=with_spatial)
@@ -480,6 +518,20 @@ def short_line(res, steps, rooflines=None):
     return out
 
 
+DUMP_MAX_ENTRIES = 4 << 20   # float32 entries per dumped array: the three arrays stay below 64 MB
+
+
+def dump_outputs(outdir, arrays):
+    """Write every (name, tensor) as outdir/<name>.npy in float32; a tensor of more than DUMP_MAX_ENTRIES entries is
+    written as the entries at a fixed seeded choice of flat indices (sorted), the same for every run of the same shape."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays:
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ENTRIES:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ENTRIES, replace=False))]
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
     # torch sizes its CPU thread pool by the host's core count; under a smaller cgroup quota every CPU op then gets
@@ -512,11 +564,14 @@ def main():
     res = run_sweeps(args, sz, K, T_loc, args.steps, args.warmup, rank, world, group, with_spatial=args.with_spatial,
                      beta_init=args.beta_init)
     elapsed, evs, dn, frames, positions0 = res["elapsed"], res["evs"], res["dn"], res["frames"], res["positions0"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     [("beta", dn.fp.beta), ("C", dn.C)] + ([("footprints", dn.fp.A)] if args.with_spatial else []))
 
     # one launch of the dense Gram kernel outside the timed region, for the roofline of the kernel that
     # evaluates every product (the timed sweeps may have used the zero-skipping kernel instead)
     dense_ms = None
-    if rank == 0 and K <= 127 and not args.no_extras:  # one K3 launch holds at most 127 neurons
+    if args.full and rank == 0 and K <= 127 and not args.no_extras:  # one K3 launch holds at most 127 neurons
         torch.cuda.synchronize()
         ops.TIMING = {}
         ops.warp_gram_rhs(dn.fp.packed_footprints(), K, sz, dn.fp.beta.detach(), None, frames)
@@ -612,11 +667,11 @@ def main():
             line["invalid"] = "fit_sanity.ok is false: the sweeps did not work on a sane fit, the rate is not a measurement"
         if tjson.note():
             line["traffic_note"] = tjson.note()
-        if world == 1 and not args.no_cpu_baseline and Z == 1:
+        if args.full and world == 1 and not args.no_cpu_baseline and Z == 1:
             line["cpu_baseline"] = cpu_baseline(size, K, bs, args.iter_c, positions0.numpy(), frames[:bs].cpu().numpy(), res["lr"])
 
     # ---- secondary measurements (N = 1, default workload): never part of `value` -----------------------------------
-    if world == 1 and not args.no_extras and not args.with_spatial and Z == 1 and size == 512 and K == 100:
+    if args.full and world == 1 and not args.no_extras and not args.with_spatial and Z == 1 and size == 512 and K == 100:
         del res, dn, frames
         torch.cuda.empty_cache()
         extras = {}

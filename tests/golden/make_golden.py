@@ -9,6 +9,9 @@ touching its files: ``Demix/dNMF.py:7`` imports ``Methods.Demix.WUtils`` -- a pa
 not exist in the tree -- so ``WUtils`` is registered under that name in ``sys.modules``; and the module
 global ``device`` (``Demix/dNMF.py:16``, 'cuda') is set to 'cpu' after import (it is read at call time).
 
+MKL runs its AVX2 branch in strict mode (``MKL_CBWR``, as tests/conftest.py sets it for the tests): its default
+branch depends on the CPU, and the oracle tests compare bit for bit.
+
 Only data (inputs and the reference's outputs) is written; no reference source is copied.
 Fixture labels follow SURVEY.md section 8(c): G1..G10.
 """
@@ -17,8 +20,10 @@ import sys
 import types
 import warnings
 
-import numpy as np
-import torch
+os.environ["MKL_CBWR"] = "AVX2,STRICT"   # before MKL's first call
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
