@@ -301,15 +301,19 @@ __global__ void mc_window_kernel(int *win, int items, int nbox, const float *rig
 // item.  STAGE 0: cc over the window `win` -> peak index per axis, and the numerators of the 15 fractional positions
 // around it for the upsampled pass (register_translation_3d :757-768: offset = dftshift - shift uf).  STAGE 1: cc over
 // those -> the shift (:771-781), written with the signs `sgn` (total_shifts :1596 is (-x, -y, +z); the rigid shift is
-// kept as it is).
+// kept as it is), and, when `turn` is given, exp(i diffphase) (:781, :797) as (cos, sin): diffphase is the argument of cc.max()
+// over the upsampled grid -- numpy's complex max, the largest real part, then the largest imaginary part; 0 for uf == 1, where
+// the reference takes the max of the real cross-correlation at integer shifts.
 template <int STAGE>
 __global__ __launch_bounds__(256) void mc_peak_kernel(const float2 *cc, int m, const int *win, int win_item_stride, int *peak,
-                                                      int *pos_up, int uf, int region, McBoxes bx, float *shifts, float3 sgn) {
+                                                      int *pos_up, int uf, int region, McBoxes bx, float *shifts, float3 sgn,
+                                                      float2 *turn) {
     const int item = blockIdx.x;
     const float2 *c = cc + (long)item * m * m * m;
     const int *w = win + (long)item * win_item_stride;
     float best = -1.0f;
     int besti = INT_MAX;
+    float2 cmax = make_float2(-__builtin_inff(), -__builtin_inff());
     for (int e = threadIdx.x; e < m * m * m; e += 256) {
         const int i0 = e / (m * m), i1 = (e / m) % m, i2 = e % m;
         if (STAGE == 0 && (w[i0] == INT_MIN || w[MC_MW + i1] == INT_MIN || w[2 * MC_MW + i2] == INT_MIN)) continue;
@@ -317,16 +321,20 @@ __global__ __launch_bounds__(256) void mc_peak_kernel(const float2 *cc, int m, c
         const float2 v = c[e];
         const float a = fmaf(v.x, v.x, v.y * v.y);
         if (a > best || (a == best && e < besti)) best = a, besti = e;   // (e ascending per thread: only the first test fires)
+        if (v.x > cmax.x || (v.x == cmax.x && v.y > cmax.y)) cmax = v;
     }
     __shared__ float sb[256];
     __shared__ int si[256];
-    sb[threadIdx.x] = best, si[threadIdx.x] = besti;
+    __shared__ float2 sc[256];
+    sb[threadIdx.x] = best, si[threadIdx.x] = besti, sc[threadIdx.x] = cmax;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if (threadIdx.x < s) {
             const float ob = sb[threadIdx.x + s];
             const int oi = si[threadIdx.x + s];
             if (ob > sb[threadIdx.x] || (ob == sb[threadIdx.x] && oi < si[threadIdx.x])) sb[threadIdx.x] = ob, si[threadIdx.x] = oi;
+            const float2 oc = sc[threadIdx.x + s];
+            if (oc.x > sc[threadIdx.x].x || (oc.x == sc[threadIdx.x].x && oc.y > sc[threadIdx.x].y)) sc[threadIdx.x] = oc;
         }
         __syncthreads();
     }
@@ -350,6 +358,10 @@ __global__ __launch_bounds__(256) void mc_peak_kernel(const float2 *cc, int m, c
         for (int d = 0; d < 3; ++d) {
             const float s = (float)peak[item * 3 + d] + (float)(i[d] - region / 2) / (float)uf;
             shifts[(long)item * 3 + d] = bx.n[d] == 1 ? 0.0f : sg[d] * s;
+        }
+        if (turn) {
+            const float a = sqrtf(fmaf(sc[0].x, sc[0].x, sc[0].y * sc[0].y));
+            turn[item] = uf == 1 || !(a > 0.0f) || a == __builtin_inff() ? make_float2(1.0f, 0.0f) : make_float2(sc[0].x / a, sc[0].y / a);
         }
     }
 }
@@ -402,15 +414,26 @@ static bool mc_use_mfma() {
     return !(e && e[0] == '1');
 }
 
-static void mc_launch_axis(McAxis a, int items, size_t maxD_bytes, hipStream_t st) {
+// a buffer of the workspace and the float2 values it holds
+struct McBuf {
+    float2 *p;
+    size_t cap;
+};
+
+// One axis pass writing McAxis.out = (items, outer, m, inner) into `out`; a pass that would write past the buffer is refused.
+static int mc_launch_axis(McAxis a, int items, McBuf out, hipStream_t st) {
+    const size_t extent = (size_t)items * a.outer * a.m * a.inner;
+    DNMF_REQUIRE(extent <= out.cap, DNMF_E_WORKSPACE, "K8: an axis pass writes %zu values into a buffer of %zu", extent, out.cap);
+    a.out = out.p;
     const long ncol = (long)a.outer * a.inner;
     if (mc_use_mfma()) {
         dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((a.m + 63) / 64), (unsigned)items);
         hipLaunchKernelGGL(mc_axis_mfma_kernel, grid, dim3(256), (size_t)a.n * a.uf * sizeof(float2), st, a);
-        return;
+        return 0;
     }
     dim3 grid((unsigned)((ncol + MC_TC - 1) / MC_TC), (unsigned)((a.m + MC_RTILE - 1) / MC_RTILE), (unsigned)items);
     hipLaunchKernelGGL(mc_axis_kernel, grid, dim3(256), (size_t)a.n * a.uf * sizeof(float2), st, a);
+    return 0;
 }
 
 // numerators of the positions r + s_d of a frame's shifted grid: pos[(item 3 + d) nmax + r] = r uf + round(s_d uf)
@@ -422,12 +445,17 @@ __global__ void mc_shift_pos_kernel(const float *shifts, int uf, McBoxes bx, int
     pos[((long)item * 3 + d) * nmax + r] = r < bx.n[d] ? r * uf + sn : INT_MIN;
 }
 
-// smallest finite real part of every frame of (nf, P) complex values -> fmin[f] (initialised to +inf by the caller): the
-// np.nanmin of border_nan='min' (:1121)
-__global__ __launch_bounds__(256) void mc_frame_min_kernel(const float2 *img, long P, float *fmin) {
+// real part of t v, t = exp(i diffphase) of the frame (apply_shifts_dft :1097, then np.real :1099)
+__device__ __forceinline__ float mc_real_turned(float2 v, float2 t) { return fmaf(t.x, v.x, -t.y * v.y); }
+
+// smallest finite value of every frame of (nf, P) complex values turned by turn[f] -> fmin[f] (initialised to +inf by
+// the caller): the np.nanmin of border_nan='min' (:1121)
+__global__ __launch_bounds__(256) void mc_frame_min_kernel(const float2 *img, long P, const float2 *turn, float *fmin) {
     const int f = blockIdx.y;
+    const float2 t = turn[f];
     float m = __builtin_inff();
-    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < P; g += (long)gridDim.x * 256) m = fminf(m, img[(long)f * P + g].x);
+    for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < P; g += (long)gridDim.x * 256)
+        m = fminf(m, mc_real_turned(img[(long)f * P + g], t));
     __shared__ float sm[256];
     sm[threadIdx.x] = m;
     __syncthreads();
@@ -451,11 +479,12 @@ __global__ __launch_bounds__(256) void mc_frame_min_kernel(const float2 *img, lo
 // swapped pair on the axes in order).  border: 0 leave, 1 NaN (border_nan=True), 2 the frame's smallest value ('min'),
 // 3 the nearest row / column / slice inside ('copy': the reference copies axis by axis, which composes to clamping each
 // index).  Written to `corrected` and / or added into the per-voxel sums and counts of the finite values (the nanmean of
-// tile_and_correct_wrapper :2057).  The factor exp(i diffphase) of :1097 is left out: diffphase is the argument of the
-// correlation's peak value, zero up to rounding for real images (1e-8 here), and it multiplies a real image.
+// tile_and_correct_wrapper :2057).  The moved image is turned by exp(i diffphase) (:1097) before its real part is taken:
+// diffphase, the argument of the upsampled correlation's peak value, is zero up to rounding for most real images, but not
+// where an axis of even length carries a fractional shift -- the Nyquist term of the upsampled DFT is not Hermitian.
 __global__ __launch_bounds__(256) void mc_shifted_frames_kernel(const float2 *img, int nf, int X, int Y, int Z, const float *shifts,
-                                                                float add, int border, const float *fmin, float *corrected, long ldc,
-                                                                float *tsum, int *tcount) {
+                                                                const float2 *turn, float add, int border, const float *fmin,
+                                                                float *corrected, long ldc, float *tsum, int *tcount) {
     const long P = (long)X * Y * Z;
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= P) return;
@@ -463,7 +492,8 @@ __global__ __launch_bounds__(256) void mc_shifted_frames_kernel(const float2 *im
     float acc = 0.0f;
     int cnt = 0;
     for (int f = 0; f < nf; ++f) {
-        float v = img[(long)f * P + g].x - add;
+        const float2 t = turn[f];
+        float v = mc_real_turned(img[(long)f * P + g], t) - add;
         if (border) {
             const float s0 = shifts[3 * f], s1 = shifts[3 * f + 1], s2 = shifts[3 * f + 2];
             const int max_h = (int)ceilf(fmaxf(0.0f, s1)), min_h = (int)floorf(fminf(0.0f, s1));
@@ -477,7 +507,8 @@ __global__ __launch_bounds__(256) void mc_shifted_frames_kernel(const float2 *im
             if (out && border == 3) {
                 const int xs = min(max(x, max_h), X + min_h - 1), ys = min(max(y, max_w), Y + min_w - 1),
                           zs = min(max(z, max_d), Z + min_d - 1);
-                v = img[(long)f * P + ((long)min(max(xs, 0), X - 1) * Y + min(max(ys, 0), Y - 1)) * Z + min(max(zs, 0), Z - 1)].x - add;
+                v = mc_real_turned(img[(long)f * P + ((long)min(max(xs, 0), X - 1) * Y + min(max(ys, 0), Y - 1)) * Z + min(max(zs, 0), Z - 1)],
+                                   t) - add;
             }
         }
         if (corrected) corrected[(long)f * ldc + g] = v;
@@ -486,62 +517,99 @@ __global__ __launch_bounds__(256) void mc_shifted_frames_kernel(const float2 *im
     if (tsum) tsum[g] += acc, tcount[g] += cnt;
 }
 
-// The transforms of one call: buffers carved from its workspace, and the passes built from mc_axis_kernel.
+// The transforms of one call: buffers carved from its workspace, and the passes built from mc_axis_kernel.  Every pass
+// returns 0 or the error of the launch it refused.
 struct McRun {
     hipStream_t st;
     int X, Y, Z, uf, region, max_dev;
     float add;
-    float2 *bufA, *bufB, *inv1, *inv2, *cc;
-    int *win, *pos_up, *peak, *iota, *mshift;
+    McBuf bufA, bufB, inv1, inv2, cc, tF_full, tF_patch;
+    int *win, *pos_up, *peak, *iota, *mshift, *starts, *spos;
+    float *fmin;              // (rigid correction) per frame of a chunk: smallest value, exp(i diffphase)
+    float2 *turn;
 
     // forward DFT of `nitems` boxes of frames [first, ...) (or of the template when ld == 0): voxels -> spectrum in A
-    void forward(const McBoxes &bx, const float *src, long ld, const int *ids, int first, int nitems, float2 *A, float2 *Bf) const {
+    int forward(const McBoxes &bx, const float *src, long ld, const int *ids, int first, int nitems, McBuf A, McBuf Bf) const {
         McAxis a{};
         a.bx = bx, a.X = X, a.Y = Y, a.Z = Z, a.add = add, a.first_frame = first;
         a.uf = 1, a.sign = -1, a.scale = 1.0f, a.pos = iota, a.pos_item_stride = 0, a.pos_off = 0;
         // z: voxels -> A
         a.mode = 0, a.frames = src, a.ldf = ld, a.frame_ids = ids;
-        a.outer = bx.n[0] * bx.n[1], a.n = bx.n[2], a.inner = 1, a.m = bx.n[2], a.out = A;
-        mc_launch_axis(a, nitems, 0, st);
+        a.outer = bx.n[0] * bx.n[1], a.n = bx.n[2], a.inner = 1, a.m = bx.n[2];
+        int rc = mc_launch_axis(a, nitems, A, st);
         // y: A -> B
-        a.mode = 1, a.in = A, a.outer = bx.n[0], a.n = bx.n[1], a.inner = bx.n[2], a.m = bx.n[1], a.out = Bf;
-        mc_launch_axis(a, nitems, 0, st);
+        a.mode = 1, a.in = A.p, a.outer = bx.n[0], a.n = bx.n[1], a.inner = bx.n[2], a.m = bx.n[1];
+        if (rc == 0) rc = mc_launch_axis(a, nitems, Bf, st);
         // x: B -> A
-        a.in = Bf, a.outer = 1, a.n = bx.n[0], a.inner = bx.n[1] * bx.n[2], a.m = bx.n[0], a.out = A;
-        mc_launch_axis(a, nitems, 0, st);
+        a.in = Bf.p, a.outer = 1, a.n = bx.n[0], a.inner = bx.n[1] * bx.n[2], a.m = bx.n[0];
+        return rc == 0 ? mc_launch_axis(a, nitems, A, st) : rc;
     }
     // P = spec conj(tspec) onto mm positions per axis (numerators in posbuf (items or 1, 3, MC_MW), over ufac) -> cc (items, mm^3)
-    void inverse(const McBoxes &bx, const float2 *spec, const float2 *tspec, const int *posbuf, int pstride, int mm, int ufac,
-                 int nitems) const {
+    int inverse(const McBoxes &bx, const float2 *spec, const float2 *tspec, const int *posbuf, int pstride, int mm, int ufac,
+                int nitems) const {
         McAxis a{};
         a.bx = bx, a.uf = ufac, a.sign = 1, a.pos = posbuf, a.pos_item_stride = pstride, a.m = mm;
         // x (with the product): (1, n0, n1 n2) -> (1, mm, n1 n2)
         a.mode = 2, a.in = spec, a.other = tspec, a.outer = 1, a.n = bx.n[0], a.inner = bx.n[1] * bx.n[2], a.pos_off = 0;
-        a.scale = 1.0f / (float)bx.n[0], a.out = inv1;
-        mc_launch_axis(a, nitems, 0, st);
+        a.scale = 1.0f / (float)bx.n[0];
+        int rc = mc_launch_axis(a, nitems, inv1, st);
         // y: (mm, n1, n2) -> (mm, mm, n2)
-        a.mode = 1, a.in = inv1, a.outer = mm, a.n = bx.n[1], a.inner = bx.n[2], a.pos_off = MC_MW;
-        a.scale = 1.0f / (float)bx.n[1], a.out = inv2;
-        mc_launch_axis(a, nitems, 0, st);
+        a.mode = 1, a.in = inv1.p, a.outer = mm, a.n = bx.n[1], a.inner = bx.n[2], a.pos_off = MC_MW;
+        a.scale = 1.0f / (float)bx.n[1];
+        if (rc == 0) rc = mc_launch_axis(a, nitems, inv2, st);
         // z: (mm mm, n2, 1) -> (mm mm, mm, 1)
-        a.in = inv2, a.outer = mm * mm, a.n = bx.n[2], a.inner = 1, a.pos_off = 2 * MC_MW;
-        a.scale = 1.0f / (float)bx.n[2], a.out = cc;
-        mc_launch_axis(a, nitems, 0, st);
+        a.in = inv2.p, a.outer = mm * mm, a.n = bx.n[2], a.inner = 1, a.pos_off = 2 * MC_MW;
+        a.scale = 1.0f / (float)bx.n[2];
+        return rc == 0 ? mc_launch_axis(a, nitems, cc, st) : rc;
     }
     // one registration pass over `nitems` boxes: window -> peak -> upsampled -> shifts
-    void registration(const McBoxes &bx, const float2 *spec, const float2 *tspec, const float *rigid, int first, int nitems,
-                      float *shifts_out, float3 sgn) const {
+    int registration(const McBoxes &bx, const float2 *spec, const float2 *tspec, const float *rigid, int first, int nitems,
+                     float *shifts_out, float3 sgn) const {
         const int witems = rigid ? nitems : 1;
         hipLaunchKernelGGL(mc_window_kernel, dim3((unsigned)((witems * 3 + 63) / 64)), dim3(64), 0, st, win, witems, bx.nbox,
                            rigid ? rigid + (long)first * 3 : nullptr, max_dev, mshift, bx);
-        inverse(bx, spec, tspec, win, rigid ? 3 * MC_MW : 0, MC_MW, 1, nitems);
-        hipLaunchKernelGGL((mc_peak_kernel<0>), dim3((unsigned)nitems), dim3(256), 0, st, cc, MC_MW, win, rigid ? 3 * MC_MW : 0, peak,
-                           pos_up, uf, region, bx, (float *)nullptr, sgn);
-        inverse(bx, spec, tspec, pos_up, 3 * MC_MW, region, uf, nitems);
-        hipLaunchKernelGGL((mc_peak_kernel<1>), dim3((unsigned)nitems), dim3(256), 0, st, cc, region, win, 0, peak, pos_up, uf, region,
-                           bx, shifts_out, sgn);
+        int rc = inverse(bx, spec, tspec, win, rigid ? 3 * MC_MW : 0, MC_MW, 1, nitems);
+        if (rc) return rc;
+        hipLaunchKernelGGL((mc_peak_kernel<0>), dim3((unsigned)nitems), dim3(256), 0, st, cc.p, MC_MW, win, rigid ? 3 * MC_MW : 0, peak,
+                           pos_up, uf, region, bx, (float *)nullptr, sgn, (float2 *)nullptr);
+        rc = inverse(bx, spec, tspec, pos_up, 3 * MC_MW, region, uf, nitems);
+        if (rc) return rc;
+        hipLaunchKernelGGL((mc_peak_kernel<1>), dim3((unsigned)nitems), dim3(256), 0, st, cc.p, region, win, 0, peak, pos_up, uf, region,
+                           bx, shifts_out, sgn, turn);
+        return 0;
     }
 };
+
+// Bump allocation of a call's buffers from its workspace (base == nullptr: only the size is counted).
+struct McCarve {
+    char *base;
+    size_t at;
+    template <class T>
+    T *take(size_t count) {
+        T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += mc_round(count * sizeof(T));
+        return p;
+    }
+    McBuf buf(size_t count) { return McBuf{take<float2>(count), count}; }
+};
+
+// The two partial inverses of a registration of `items` boxes of n0 x n1 x n2 (McRun::inverse): the x pass writes
+// (items, 1, mm, n1 n2), the y pass (items, mm, mm, n2) -- unused window slots included, as zeros -- with mm <= MC_MW.
+// inv2 is held to (items, mm, max(n1, mm), n2).  Raised to the largest box of the call.
+static void mc_inverse_need(long items, const int n[3], size_t &inv1, size_t &inv2) {
+    const size_t a = (size_t)items * MC_MW * n[1] * n[2];
+    const size_t b = (size_t)items * MC_MW * (n[1] > MC_MW ? n[1] : MC_MW) * n[2];
+    inv1 = inv1 > a ? inv1 : a;
+    inv2 = inv2 > b ? inv2 : b;
+}
+
+// indices of an axis of n voxels that the max_shifts window keeps (register_translation_3d :727-747): cc[m:-m] = 0 leaves
+// [0, m) and [n - m, n), and the whole axis when the slice is empty (m == 0, since -0 is 0, or 2 m >= n)
+static int mc_kept(int n, int m) { return (m == 0 || 2 * m >= n) ? n : 2 * m; }
+
+// side of the upsampled grid: ceil(1.5 uf) (:763); for uf == 1 the reference keeps the integer peak (no upsampled pass,
+// :756), which a grid of one position -- the peak itself -- reproduces
+static int mc_region(int uf) { return uf == 1 ? 1 : (uf * 3 + 1) / 2; }
 
 }  // namespace dnmf
 
@@ -578,27 +646,45 @@ static int mc_chunk(long vox_per_frame, int B, int NP) {
     return (int)c;
 }
 
+// The buffers of a dnmf_register_patches call of Bc frames per chunk, for the workspace query (ws == nullptr) and the carve
+// alike: the whole volume is registered as Bc items, the patches as Bc NP items of w0 x w1 x w2.
+static size_t mc_patches_layout(int X, int Y, int Z, const int w[3], int NP, int Bc, char *ws, dnmf::McRun &r) {
+    using namespace dnmf;
+    const long P = (long)X * Y * Z;
+    const long pvox = (long)NP * w[0] * w[1] * w[2];
+    const long per_frame = P > pvox ? P : pvox;
+    const long items_max = (long)Bc * NP;
+    const int n_full[3] = {X, Y, Z};
+    size_t inv1 = 0, inv2 = 0;
+    mc_inverse_need(Bc, n_full, inv1, inv2);
+    mc_inverse_need(items_max, w, inv1, inv2);
+    McCarve c{ws, 0};
+    r.bufA = c.buf((size_t)Bc * per_frame);                  // spectra, ping-pong
+    r.bufB = c.buf((size_t)Bc * per_frame);
+    r.tF_full = c.buf((size_t)P);                            // template spectra
+    r.tF_patch = c.buf((size_t)pvox);
+    r.inv1 = c.buf(inv1);                                    // partial inverses (two stages)
+    r.inv2 = c.buf(inv2);
+    r.cc = c.buf((size_t)items_max * MC_MW * MC_MW * MC_MW); // cc on the window / the upsampled grid
+    r.win = c.take<int>((size_t)items_max * 3 * MC_MW);      // window indices, upsampled positions
+    r.pos_up = c.take<int>((size_t)items_max * 3 * MC_MW);
+    r.peak = c.take<int>((size_t)items_max * 3);
+    r.iota = c.take<int>(16384);
+    r.starts = c.take<int>((size_t)(NP + 1) * 3);
+    r.mshift = c.take<int>(16);
+    return c.at;
+}
+
 size_t dnmf_register_patches_workspace(int X, int Y, int Z, const int *strides, const int *overlaps, int B) {
     using namespace dnmf;
     int dims[3];
     const int NP = dnmf_register_patches_grid(X, Y, Z, strides, overlaps, dims, nullptr);
     if (NP <= 0 || B <= 0) return 0;
     const long P = (long)X * Y * Z;
-    const long w[3] = {strides[0] + overlaps[0], strides[1] + overlaps[1], strides[2] + overlaps[2]};
+    const int w[3] = {strides[0] + overlaps[0], strides[1] + overlaps[1], strides[2] + overlaps[2]};
     const long pvox = (long)NP * w[0] * w[1] * w[2];
-    const long per_frame = P > pvox ? P : pvox;
-    const int Bc = mc_chunk(per_frame, B, NP);
-    const long items = (long)Bc * NP;
-    const long biggest_n12 = (long)Y * Z > w[1] * w[2] ? (long)Y * Z : w[1] * w[2];
-    size_t b = 0;
-    b += 2 * mc_round((size_t)Bc * per_frame * sizeof(float2));                     // spectra, ping-pong
-    b += mc_round((size_t)P * sizeof(float2)) + mc_round((size_t)pvox * sizeof(float2)); // template spectra
-    b += 2 * mc_round((size_t)items * MC_MW * biggest_n12 * sizeof(float2));         // partial inverses (two stages)
-    b += mc_round((size_t)items * MC_MW * MC_MW * MC_MW * sizeof(float2));           // cc on the window / the upsampled grid
-    b += 2 * mc_round((size_t)items * 3 * MC_MW * sizeof(int));                      // window indices, upsampled positions
-    b += mc_round((size_t)items * 3 * sizeof(int)) + mc_round((size_t)16384 * sizeof(int)) + mc_round((size_t)(NP + 1) * 3 * sizeof(int)) +
-         mc_round(64);
-    return b;
+    McRun r{};
+    return mc_patches_layout(X, Y, Z, w, NP, mc_chunk(P > pvox ? P : pvox, B, NP), nullptr, r);
 }
 
 int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
@@ -620,7 +706,7 @@ int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, i
     for (int d = 0; d < 3; ++d) {
         DNMF_REQUIRE(S[d] * upsample_factor <= MC_MAXD, DNMF_E_UNSUPPORTED,
                      "dnmf_register_patches: axis %d of %d voxels x upsample factor %d > %d", d, S[d], upsample_factor, MC_MAXD);
-        DNMF_REQUIRE(max_shifts[d] >= 0 && (S[d] <= MC_MW || 2 * max_shifts[d] <= MC_MW) && max_deviation_rigid >= 1 &&
+        DNMF_REQUIRE(max_shifts[d] >= 0 && mc_kept(S[d], max_shifts[d]) <= MC_MW && max_deviation_rigid >= 1 &&
                          (w[d] <= MC_MW || 2 * max_deviation_rigid + 1 <= MC_MW),
                      DNMF_E_UNSUPPORTED, "dnmf_register_patches: search window of axis %d wider than %d shifts", d, MC_MW);
     }
@@ -629,29 +715,12 @@ int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, i
                  dnmf_register_patches_workspace(X, Y, Z, strides, overlaps, B));
     McRun r{};
     r.st = (hipStream_t)stream, r.X = X, r.Y = Y, r.Z = Z, r.add = add_to_movie, r.uf = upsample_factor;
-    r.region = (upsample_factor * 3 + 1) / 2, r.max_dev = max_deviation_rigid;   // ceil(1.5 uf)
+    r.region = mc_region(upsample_factor), r.max_dev = max_deviation_rigid;
     const long P = (long)X * Y * Z;
     const long pvox = (long)NP * w[0] * w[1] * w[2];
-    const long per_frame = P > pvox ? P : pvox;
-    const int Bc = mc_chunk(per_frame, B, NP);
-    const long items_max = (long)Bc * NP;
-    const long biggest_n12 = (long)Y * Z > (long)w[1] * w[2] ? (long)Y * Z : (long)w[1] * w[2];
-    // carve the workspace
-    char *at = static_cast<char *>(workspace);
-    auto take = [&](size_t bytes) { char *p = at; at += mc_round(bytes); return p; };
-    r.bufA = reinterpret_cast<float2 *>(take((size_t)Bc * per_frame * sizeof(float2)));
-    r.bufB = reinterpret_cast<float2 *>(take((size_t)Bc * per_frame * sizeof(float2)));
-    float2 *tF_full = reinterpret_cast<float2 *>(take((size_t)P * sizeof(float2)));
-    float2 *tF_patch = reinterpret_cast<float2 *>(take((size_t)pvox * sizeof(float2)));
-    r.inv1 = reinterpret_cast<float2 *>(take((size_t)items_max * MC_MW * biggest_n12 * sizeof(float2)));
-    r.inv2 = reinterpret_cast<float2 *>(take((size_t)items_max * MC_MW * biggest_n12 * sizeof(float2)));
-    r.cc = reinterpret_cast<float2 *>(take((size_t)items_max * MC_MW * MC_MW * MC_MW * sizeof(float2)));
-    r.win = reinterpret_cast<int *>(take((size_t)items_max * 3 * MC_MW * sizeof(int)));
-    r.pos_up = reinterpret_cast<int *>(take((size_t)items_max * 3 * MC_MW * sizeof(int)));
-    r.peak = reinterpret_cast<int *>(take((size_t)items_max * 3 * sizeof(int)));
-    r.iota = reinterpret_cast<int *>(take((size_t)16384 * sizeof(int)));
-    int *starts = reinterpret_cast<int *>(take((size_t)(NP + 1) * 3 * sizeof(int)));
-    r.mshift = reinterpret_cast<int *>(take(64));
+    const int Bc = mc_chunk(P > pvox ? P : pvox, B, NP);
+    mc_patches_layout(X, Y, Z, w, NP, Bc, static_cast<char *>(workspace), r);
+    int *starts = r.starts;
 
     // patch starts (the whole-volume box is entry NP), max_shifts, the forward DFT's positions: small host -> device copies
     {
@@ -675,18 +744,21 @@ int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, i
     pat.n[0] = w[0], pat.n[1] = w[1], pat.n[2] = w[2], pat.nbox = NP, pat.start = starts;
 
     // template spectra (once)
-    r.forward(full, tmpl, 0, nullptr, 0, 1, tF_full, r.bufB);
-    r.forward(pat, tmpl, 0, nullptr, 0, NP, tF_patch, r.bufB);
-    for (int f0 = 0; f0 < B; f0 += Bc) {
+    int rc = r.forward(full, tmpl, 0, nullptr, 0, 1, r.tF_full, r.bufB);
+    if (rc == 0) rc = r.forward(pat, tmpl, 0, nullptr, 0, NP, r.tF_patch, r.bufB);
+    for (int f0 = 0; f0 < B && rc == 0; f0 += Bc) {
         const int nf = B - f0 < Bc ? B - f0 : Bc;
         // rigid shift of every frame of the chunk (:1559-1560), kept with its own sign
-        r.forward(full, frames, ldf, frame_ids, f0, nf, r.bufA, r.bufB);
-        r.registration(full, r.bufA, tF_full, nullptr, f0, nf, rigid_shifts + (long)f0 * 3, make_float3(1.0f, 1.0f, 1.0f));
+        rc = r.forward(full, frames, ldf, frame_ids, f0, nf, r.bufA, r.bufB);
+        if (rc == 0)
+            rc = r.registration(full, r.bufA.p, r.tF_full.p, nullptr, f0, nf, rigid_shifts + (long)f0 * 3, make_float3(1.0f, 1.0f, 1.0f));
         // one shift per patch inside the window around the frame's rigid shift (:1562-1583), signs of :1596
-        r.forward(pat, frames, ldf, frame_ids, f0, nf * NP, r.bufA, r.bufB);
-        r.registration(pat, r.bufA, tF_patch, rigid_shifts, f0, nf * NP, patch_shifts + (long)f0 * NP * 3,
-                       make_float3(-1.0f, -1.0f, 1.0f));
+        if (rc == 0) rc = r.forward(pat, frames, ldf, frame_ids, f0, nf * NP, r.bufA, r.bufB);
+        if (rc == 0)
+            rc = r.registration(pat, r.bufA.p, r.tF_patch.p, rigid_shifts, f0, nf * NP, patch_shifts + (long)f0 * NP * 3,
+                                make_float3(-1.0f, -1.0f, 1.0f));
     }
+    if (rc) return rc;
     return check_launch("dnmf_register_patches");
 }
 
@@ -699,21 +771,39 @@ static int mc_rigid_chunk(long P, int B) {
     return (int)c;
 }
 
+// The buffers of a dnmf_rigid_correct call of Bc frames per chunk, for the workspace query (ws == nullptr) and the carve.
+static size_t mc_rigid_layout(int X, int Y, int Z, int Bc, char *ws, dnmf::McRun &r) {
+    using namespace dnmf;
+    const long P = (long)X * Y * Z;
+    int nmax = X > Y ? X : Y;
+    nmax = nmax > Z ? nmax : Z;
+    const int n_full[3] = {X, Y, Z};
+    size_t inv1 = 0, inv2 = 0;
+    mc_inverse_need(Bc, n_full, inv1, inv2);
+    McCarve c{ws, 0};
+    r.bufA = c.buf((size_t)Bc * P);
+    r.bufB = c.buf((size_t)Bc * P);
+    r.tF_full = c.buf((size_t)P);
+    r.inv1 = c.buf(inv1);
+    r.inv2 = c.buf(inv2);
+    r.cc = c.buf((size_t)Bc * MC_MW * MC_MW * MC_MW);
+    r.win = c.take<int>((size_t)Bc * 3 * MC_MW);
+    r.pos_up = c.take<int>((size_t)Bc * 3 * MC_MW);
+    r.peak = c.take<int>((size_t)Bc * 3);
+    r.iota = c.take<int>(16384);
+    r.starts = c.take<int>(16);
+    r.mshift = c.take<int>(16);
+    r.spos = c.take<int>((size_t)Bc * 3 * nmax);
+    r.fmin = c.take<float>((size_t)Bc);
+    r.turn = c.take<float2>((size_t)Bc);
+    return c.at;
+}
+
 size_t dnmf_rigid_correct_workspace(int X, int Y, int Z, int B) {
     using namespace dnmf;
     if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0) return 0;
-    const long P = (long)X * Y * Z;
-    const int Bc = mc_rigid_chunk(P, B);
-    int nmax = X > Y ? X : Y;
-    nmax = nmax > Z ? nmax : Z;
-    size_t b = 0;
-    b += 2 * mc_round((size_t)Bc * P * sizeof(float2)) + mc_round((size_t)P * sizeof(float2));
-    b += 2 * mc_round((size_t)Bc * MC_MW * Y * Z * sizeof(float2));
-    b += mc_round((size_t)Bc * MC_MW * MC_MW * MC_MW * sizeof(float2));
-    b += 2 * mc_round((size_t)Bc * 3 * MC_MW * sizeof(int)) + mc_round((size_t)Bc * 3 * sizeof(int));
-    b += mc_round((size_t)16384 * sizeof(int)) + mc_round(64) + mc_round(64) + mc_round((size_t)Bc * 3 * nmax * sizeof(int));
-    b += mc_round((size_t)Bc * sizeof(float));
-    return b;
+    McRun r{};
+    return mc_rigid_layout(X, Y, Z, mc_rigid_chunk((long)X * Y * Z, B), nullptr, r);
 }
 
 int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
@@ -733,33 +823,20 @@ int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int 
     for (int d = 0; d < 3; ++d) {
         DNMF_REQUIRE(S[d] * upsample_factor <= MC_MAXD, DNMF_E_UNSUPPORTED,
                      "dnmf_rigid_correct: axis %d of %d voxels x upsample factor %d > %d", d, S[d], upsample_factor, MC_MAXD);
-        DNMF_REQUIRE(max_shifts[d] >= 0 && (S[d] <= MC_MW || 2 * max_shifts[d] <= MC_MW), DNMF_E_UNSUPPORTED,
+        DNMF_REQUIRE(max_shifts[d] >= 0 && mc_kept(S[d], max_shifts[d]) <= MC_MW, DNMF_E_UNSUPPORTED,
                      "dnmf_rigid_correct: search window of axis %d wider than %d shifts", d, MC_MW);
     }
     DNMF_REQUIRE(workspace_bytes >= dnmf_rigid_correct_workspace(X, Y, Z, B), DNMF_E_WORKSPACE,
                  "dnmf_rigid_correct: workspace %zu < %zu bytes", workspace_bytes, dnmf_rigid_correct_workspace(X, Y, Z, B));
     McRun r{};
     r.st = (hipStream_t)stream, r.X = X, r.Y = Y, r.Z = Z, r.add = add_to_movie, r.uf = upsample_factor;
-    r.region = (upsample_factor * 3 + 1) / 2, r.max_dev = 0;
+    r.region = mc_region(upsample_factor), r.max_dev = 0;
     const int Bc = mc_rigid_chunk(P, B);
     int nmax = X > Y ? X : Y;
     nmax = nmax > Z ? nmax : Z;
-    char *at = static_cast<char *>(workspace);
-    auto take = [&](size_t bytes) { char *p = at; at += mc_round(bytes); return p; };
-    r.bufA = reinterpret_cast<float2 *>(take((size_t)Bc * P * sizeof(float2)));
-    r.bufB = reinterpret_cast<float2 *>(take((size_t)Bc * P * sizeof(float2)));
-    float2 *tF_full = reinterpret_cast<float2 *>(take((size_t)P * sizeof(float2)));
-    r.inv1 = reinterpret_cast<float2 *>(take((size_t)Bc * MC_MW * Y * Z * sizeof(float2)));
-    r.inv2 = reinterpret_cast<float2 *>(take((size_t)Bc * MC_MW * Y * Z * sizeof(float2)));
-    r.cc = reinterpret_cast<float2 *>(take((size_t)Bc * MC_MW * MC_MW * MC_MW * sizeof(float2)));
-    r.win = reinterpret_cast<int *>(take((size_t)Bc * 3 * MC_MW * sizeof(int)));
-    r.pos_up = reinterpret_cast<int *>(take((size_t)Bc * 3 * MC_MW * sizeof(int)));
-    r.peak = reinterpret_cast<int *>(take((size_t)Bc * 3 * sizeof(int)));
-    r.iota = reinterpret_cast<int *>(take((size_t)16384 * sizeof(int)));
-    int *starts = reinterpret_cast<int *>(take(64));
-    r.mshift = reinterpret_cast<int *>(take(64));
-    int *spos = reinterpret_cast<int *>(take((size_t)Bc * 3 * nmax * sizeof(int)));
-    float *fmin = reinterpret_cast<float *>(take((size_t)Bc * sizeof(float)));
+    mc_rigid_layout(X, Y, Z, Bc, static_cast<char *>(workspace), r);
+    int *starts = r.starts, *spos = r.spos;
+    float *fmin = r.fmin;
     {
         hipError_t e = hipMemsetAsync(starts, 0, 3 * sizeof(int), r.st);
         if (e == hipSuccess) e = hipMemcpyAsync(r.mshift, max_shifts, 3 * sizeof(int), hipMemcpyHostToDevice, r.st);
@@ -768,33 +845,35 @@ int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int 
     hipLaunchKernelGGL(mc_iota_kernel, dim3((unsigned)((nmax + 255) / 256)), dim3(256), 0, r.st, r.iota, nmax);
     McBoxes full;
     full.n[0] = X, full.n[1] = Y, full.n[2] = Z, full.nbox = 1, full.start = starts;
-    r.forward(full, tmpl, 0, nullptr, 0, 1, tF_full, r.bufB);
-    for (int f0 = 0; f0 < B; f0 += Bc) {
+    int rc = r.forward(full, tmpl, 0, nullptr, 0, 1, r.tF_full, r.bufB);
+    for (int f0 = 0; f0 < B && rc == 0; f0 += Bc) {
         const int nf = B - f0 < Bc ? B - f0 : Bc;
         float *sh = rigid_shifts + (long)f0 * 3;
-        r.forward(full, frames, ldf, frame_ids, f0, nf, r.bufA, r.bufB);
-        r.registration(full, r.bufA, tF_full, nullptr, f0, nf, sh, make_float3(1.0f, 1.0f, 1.0f));
-        if (!corrected && !tsum) continue;
+        rc = r.forward(full, frames, ldf, frame_ids, f0, nf, r.bufA, r.bufB);
+        if (rc == 0) rc = r.registration(full, r.bufA.p, r.tF_full.p, nullptr, f0, nf, sh, make_float3(1.0f, 1.0f, 1.0f));
+        if (rc || (!corrected && !tsum)) continue;
         // apply_shifts_dft :1083-1097: the spectrum times exp(+2 pi i f s / n) per axis, inverse transform = the inverse
         // DFT evaluated at the positions r + s_d, numerators (r uf + s_d uf) over uf (s_d is a multiple of 1 / uf)
         hipLaunchKernelGGL(mc_shift_pos_kernel, dim3((unsigned)((3 * nmax + 255) / 256), (unsigned)nf), dim3(256), 0, r.st, sh, r.uf,
                            full, nmax, spos);
         McAxis a{};
         a.bx = full, a.uf = r.uf, a.sign = 1, a.pos = spos, a.pos_item_stride = 3 * nmax, a.mode = 1;
-        a.in = r.bufA, a.outer = 1, a.n = X, a.inner = Y * Z, a.m = X, a.pos_off = 0, a.scale = 1.0f / (float)X, a.out = r.bufB;
-        mc_launch_axis(a, nf, 0, r.st);
-        a.in = r.bufB, a.outer = X, a.n = Y, a.inner = Z, a.m = Y, a.pos_off = nmax, a.scale = 1.0f / (float)Y, a.out = r.bufA;
-        mc_launch_axis(a, nf, 0, r.st);
-        a.in = r.bufA, a.outer = X * Y, a.n = Z, a.inner = 1, a.m = Z, a.pos_off = 2 * nmax, a.scale = 1.0f / (float)Z, a.out = r.bufB;
-        mc_launch_axis(a, nf, 0, r.st);
+        a.in = r.bufA.p, a.outer = 1, a.n = X, a.inner = Y * Z, a.m = X, a.pos_off = 0, a.scale = 1.0f / (float)X;
+        rc = mc_launch_axis(a, nf, r.bufB, r.st);
+        a.in = r.bufB.p, a.outer = X, a.n = Y, a.inner = Z, a.m = Y, a.pos_off = nmax, a.scale = 1.0f / (float)Y;
+        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufA, r.st);
+        a.in = r.bufA.p, a.outer = X * Y, a.n = Z, a.inner = 1, a.m = Z, a.pos_off = 2 * nmax, a.scale = 1.0f / (float)Z;
+        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufB, r.st);
+        if (rc) break;
         if (border_nan == 2) {
             hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, r.st, fmin, nf, __builtin_inff());
             const unsigned nb = (unsigned)(P / 4096 > 256 ? 256 : (P + 4095) / 4096);
-            hipLaunchKernelGGL(mc_frame_min_kernel, dim3(nb, (unsigned)nf), dim3(256), 0, r.st, r.bufB, P, fmin);
+            hipLaunchKernelGGL(mc_frame_min_kernel, dim3(nb, (unsigned)nf), dim3(256), 0, r.st, r.bufB.p, P, r.turn, fmin);
         }
-        hipLaunchKernelGGL(mc_shifted_frames_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, r.st, r.bufB, nf, X, Y, Z, sh,
-                           add_to_movie, border_nan, fmin, corrected ? corrected + (long)f0 * ldc : nullptr, ldc, tsum, tcount);
+        hipLaunchKernelGGL(mc_shifted_frames_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, r.st, r.bufB.p, nf, X, Y, Z, sh,
+                           r.turn, add_to_movie, border_nan, fmin, corrected ? corrected + (long)f0 * ldc : nullptr, ldc, tsum, tcount);
     }
+    if (rc) return rc;
     return check_launch("dnmf_rigid_correct");
 }
 

@@ -356,7 +356,9 @@ int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs
  * dnmf_register_patches: frames (>= B rows of ldf floats, voxel p = (x Y + y) Z + z; row frame_ids[b] or b), tmpl (X Y Z)
  * -> rigid_shifts (B,3) as register_translation_3d returns them, patch_shifts (B,NP,3) with the signs of
  * tile_and_correct_3d's total_shifts (-x, -y, +z), i.e. what the class stores in x/y/z_shifts_els.  strides, overlaps,
- * max_shifts: 3 host ints each.  All device buffers fp32. */
+ * max_shifts: 3 host ints each.  All device buffers fp32.  A search window holds at most 32 shifts per axis: max_shifts = 0
+ * searches the whole axis, as numpy's empty slice cc[0:-0] does in the reference, and is refused (DNMF_E_UNSUPPORTED) on
+ * an axis longer than 32 voxels.  upsample_factor = 1 returns the integer peak of the window, as the reference does. */
 int dnmf_register_patches_grid(int X, int Y, int Z, const int *strides, const int *overlaps, int *dims, int *starts);
 size_t dnmf_register_patches_workspace(int X, int Y, int Z, const int *strides, const int *overlaps, int B);
 int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,

@@ -227,3 +227,83 @@ def test_patch_grid_and_workspaces_of_the_position_initialiser(lib):
     assert lib.dnmf_register_patches_grid(32, 32, 2, I3(24, 24, 1), I3(16, 16, 1), None, None) == 0      # 40 > 32: no window fits
     assert lib.dnmf_register_patches_workspace(32, 32, 2, I3(24, 24, 1), I3(16, 16, 1), 4) == 0
     assert lib.dnmf_rigid_correct_workspace(0, 4, 4, 1) == 0
+
+
+def _r256(b):
+    return (b + 255) // 256 * 256
+
+
+def k8_pass_needs(boxes, uf=10):
+    """float2 values each buffer of one K8 registration receives, from the launch shapes of McRun (register_patches.hip): an
+    axis pass writes McAxis.out = (items, outer, m, inner).  boxes: [(items, (n0, n1, n2))].  The forward transform writes
+    items n0 n1 n2 three times (spectra, ping-pong); the windowed inverse, with mm = 32 kept indices per axis (unused window
+    slots are written as zeros), writes (items, 1, mm, n1 n2) to inv1, (items, mm, mm, n2) to inv2 and (items, mm mm, mm, 1)
+    to cc; the upsampled inverse the same with mm = ceil(1.5 uf) <= 32.  inv2 is held to mm max(n1, mm) n2."""
+    need = {"spec": 0, "inv1": 0, "inv2": 0, "cc": 0}
+    region = (3 * uf + 1) // 2
+    for items, (n0, n1, n2) in boxes:
+        for mm in (32, region):
+            need["spec"] = max(need["spec"], items * n0 * n1 * n2)
+            need["inv1"] = max(need["inv1"], items * mm * n1 * n2)
+            need["inv2"] = max(need["inv2"], items * mm * max(n1, mm) * n2)
+            need["cc"] = max(need["cc"], items * mm ** 3)
+    return need
+
+
+# (size, strides, overlaps): boxes whose second axis is shorter than the 32 kept window indices, the existing geometries, and
+# the size the README gives for the initialiser
+K8_GEOMETRIES = (
+    ((64, 16, 4), None, None), ((20, 20, 1), (8, 8, 1), (4, 4, 0)), ((40, 8, 16), None, None),
+    ((36, 20, 8), (12, 6, 4), (6, 4, 4)), ((40, 20, 3), (28, 12, 2), (12, 8, 1)),
+    ((48, 40, 2), (16, 12, 1), (8, 8, 1)), ((40, 36, 5), (12, 12, 2), (8, 6, 1)), ((64, 64, 1), (24, 24, 1), (8, 8, 0)),
+    ((72, 50, 3), (20, 14, 2), (10, 8, 1)), ((64, 56, 1), (24, 20, 1), (8, 8, 0)), ((64, 64, 2), (16, 16, 1), (16, 16, 1)),
+    ((512, 512, 2), (24, 24, 1), (8, 8, 1)), ((512, 512, 2), (96, 96, 1), (32, 32, 1)),
+)
+
+
+@pytest.mark.parametrize("sz,strides,overlaps", K8_GEOMETRIES)
+def test_position_initialiser_workspace_holds_what_its_passes_write(lib, sz, strides, overlaps):
+    """The workspaces of dnmf_register_patches / dnmf_rigid_correct against a model of what every pass writes (one frame, so
+    one frame per chunk whatever the chunk policy): at least the sum of the 256-byte-rounded needs -- a box whose second
+    axis is shorter than 32 writes (items, 32, 32, n2) partial inverses, more than (items, 32, n1, n2) -- and not much
+    more, so that the partial inverses are not sized for the whole volume times every patch."""
+    I3 = ctypes.c_int * 3
+    X, Y, Z = sz
+    P = X * Y * Z
+    nmax = max(sz)
+    f2, i4 = 8, 4
+    if strides is None:       # a rigid-only geometry: the volume is its own single patch
+        strides, overlaps = (X, Y, Z), (0, 0, 0)
+    NP = lib.dnmf_register_patches_grid(X, Y, Z, I3(*strides), I3(*overlaps), None, None)
+    assert NP > 0
+    w = tuple(s + o for s, o in zip(strides, overlaps))
+    full = k8_pass_needs([(1, (X, Y, Z))])
+    both = k8_pass_needs([(1, (X, Y, Z)), (NP, w)])
+    spec = max(P, NP * w[0] * w[1] * w[2])
+    need_p = (2 * _r256(spec * f2) + _r256(P * f2) + _r256(NP * w[0] * w[1] * w[2] * f2)
+              + _r256(both["inv1"] * f2) + _r256(both["inv2"] * f2) + _r256(both["cc"] * f2)
+              + 2 * _r256(NP * 3 * 32 * i4) + _r256(NP * 3 * i4) + _r256(16384 * i4) + _r256((NP + 1) * 3 * i4) + _r256(64))
+    need_r = (3 * _r256(full["spec"] * f2) + _r256(full["inv1"] * f2) + _r256(full["inv2"] * f2) + _r256(full["cc"] * f2)
+              + 2 * _r256(3 * 32 * i4) + _r256(3 * i4) + _r256(16384 * i4) + 2 * _r256(64) + _r256(3 * nmax * i4) + _r256(4) + _r256(f2))
+    for name, got, need in (("register_patches", lib.dnmf_register_patches_workspace(X, Y, Z, I3(*strides), I3(*overlaps), 1), need_p),
+                            ("rigid_correct", lib.dnmf_rigid_correct_workspace(X, Y, Z, 1), need_r)):
+        assert got >= need, f"{name} {sz}: workspace {got} < {need} bytes the passes write"
+        assert got <= 1.25 * need + (1 << 20), f"{name} {sz}: workspace {got} bytes for {need} needed"
+
+
+def test_position_initialiser_refuses_windows_it_cannot_hold(lib):
+    """max_shifts = 0 zeroes nothing in the reference (numpy's cc[0:-0] is empty): the whole axis is searched, which K8
+    holds only up to 32 voxels.  Refused before any HIP call."""
+    I3 = ctypes.c_int * 3
+    buf = ctypes.create_string_buffer(64)
+    a = ctypes.addressof(buf)
+    for ms, rc in (((0, 5, 1), -3), ((5, 0, 1), -3), ((17, 5, 1), -3)):
+        assert lib.dnmf_register_patches(a, 64 * 40 * 2, None, 1, a, 64, 40, 2, I3(16, 12, 1), I3(8, 8, 1), I3(*ms), 3, 10, 0.0,
+                                         a, a, a, 64, None) == rc, ms
+        assert lib.dnmf_rigid_correct(a, 64 * 40 * 2, None, 1, a, 64, 40, 2, I3(*ms), 10, 0.0, 1, a, None, 0, None, None, a, 64,
+                                      None) == rc, ms
+    # an axis of at most 32 voxels is searched whole whatever max_shifts says; a small workspace is then the only objection
+    assert lib.dnmf_register_patches(a, 20 * 20, None, 1, a, 20, 20, 1, I3(8, 8, 1), I3(4, 4, 0), I3(0, 12, 0), 3, 10, 0.0,
+                                     a, a, a, 64, None) == -4
+    assert lib.dnmf_rigid_correct(a, 20 * 20, None, 1, a, 20, 20, 1, I3(0, 12, 0), 10, 0.0, 1, a, None, 0, None, None, a, 64,
+                                  None) == -4
