@@ -22,12 +22,24 @@ on its own (``shifts_rig``, ``total_template_rig``, ``templates_rig``; the corre
 registered as one slice of the same kernels: ``motion_correct_pwrigid(template=...)`` fills ``x_shifts_els`` /
 ``y_shifts_els``.  (``apply_shifts_points`` is 3-D in the reference too.)
 
-Not offered (``NotImplementedError``): the piecewise-corrected movie (``cv2.remap``), the 2-D rigid correction
-(``cv2.warpAffine``), ``shifts_opencv=False`` (cubic resize of the shift field), memory-mapped files, ``dview``, ``gSig_filt``.
+The piecewise-rigid corrected movie of a 3-D video (``tile_and_correct_3d`` ``:1639-1654``: the patch shifts resized to a
+full-size field, the frame warped through it with a cubic B-spline, clipped to its range) runs on the GPU too (K9
+``dnmf_apply_pwrigid``, ``csrc/apply_pwrigid.hip``): ``motion_correct_pwrigid`` with ``save_corrected=True`` fills ``mc_els``,
+``templates_els`` and -- without a template -- ``total_template_els`` from it; ``apply_shifts_movie(video)`` applies the
+stored (possibly edited) shifts to a video.  Deviations from the reference: the movie goes to ``mc_els``, not ``mc`` (the
+reference's piecewise pass leaves ``mc`` to the rigid pass, ``:328`` is commented out); ``total_template_els`` is the 3-D
+chunk template, where the reference's ``np.dstack`` (``motion_correct_batch_pwrigid`` ``:1970``) collapses a 3-D template
+to (X, Y) -- a bug of the reference (its rigid path stacks correctly, ``:1860``); the warp sums in fp32 where skimage uses
+float64 (within 1e-5 of the frame's range).
 
-Parity: the reference module cannot be imported in the build container (cv2, skimage and ``past`` are absent, ``np.int``
-is gone from numpy 2) and ships no fixture; this class is checked against ``oracle/motion_oracle.py``, a numpy restatement
-of the same functions -- **parity unpinned**.
+Not offered (``NotImplementedError``): the 2-D piecewise-corrected movie (``cv2.resize`` + ``cv2.remap``), the 2-D rigid
+correction (``cv2.warpAffine``), ``shifts_opencv=False`` (cubic resize of the shift field), memory-mapped files, ``dview``,
+``gSig_filt``.
+
+Parity: the 3-D piecewise path -- K8's patch shifts and K9's corrected movie and chunk template -- is pinned by the G11
+fixtures (``tests/golden/make_golden_motion.py``: the reference module itself, run under a Python with scikit-image, with
+a stub for cv2, which that path never calls).  The rest of the class is checked against ``oracle/motion_oracle.py``, a
+numpy restatement of the same functions.
 """
 from __future__ import annotations
 
@@ -173,11 +185,17 @@ class MotionCorrect(object):
     def motion_correct_pwrigid(self, template=None, show_template=False):
         """Reference :260-328: fills ``x_shifts_els``, ``y_shifts_els``, ``z_shifts_els`` (one (NP,) array per frame),
         ``shifts_rig`` (the rigid shift of every frame), ``coord_shifts_els`` (the patch grid indices) and
-        ``total_template_els``."""
+        ``total_template_els``.  3-D videos with ``save_corrected=True`` also get the piecewise-rigid corrected movie (K9):
+        ``mc_els`` (one (X, Y, Z, T) float32 array per video; ``mc`` keeps the rigid pass's movie, as the reference leaves
+        it, :328), ``templates_els`` (one (X, Y, Z) chunk template per video, the NaN-aware mean of the corrected frames,
+        :2057-2058) and, when ``template`` is None, ``total_template_els`` = that template."""
         self.x_shifts_els, self.y_shifts_els = [], []
         if self.is3D:
             self.z_shifts_els = []
         self.coord_shifts_els = []
+        corrected = self.save_corrected and self.is3D
+        if corrected:
+            self.mc_els, self.templates_els = [], []
         strides, overlaps, max_shifts = self._p3()
         for video_cur in self.video:
             frames, sz = self._frames(video_cur)
@@ -204,6 +222,41 @@ class MotionCorrect(object):
                     self.z_shifts_els.append(p[t, :, 2].copy())
                 self.coord_shifts_els.append(grid)
             self._patch_shifts = patch                       # (T, NP, 3) on the GPU, for apply_shifts_points
+            if corrected:
+                movie, new_temp = self._corrected_movie(frames, sz, patch)
+                self.mc_els.append(movie)
+                self.templates_els.append(new_temp.cpu().numpy())
+                if template is None:
+                    self.total_template_els = new_temp
+
+    def _corrected_movie(self, frames, sz, patch):
+        """K9 on (T, P) rows and their (T, NP, 3) shifts, in pieces of at most 1 GiB of output: (the corrected movie as
+        (X, Y, Z, T) float32 numpy, its chunk template (X, Y, Z) on the GPU -- nanmean over the frames, NaN -> nanmin)."""
+        strides, overlaps, _ = self._p3()
+        add = float(np.float32(-self.min_mov))               # (:2122: passed on as a float32)
+        T, P = frames.shape
+        step = max(1, min(T, (1 << 30) // (4 * P)))
+        tsum = tcount = None
+        moved = []
+        for f0 in range(0, T, step):
+            out, tsum, tcount = ops.apply_pwrigid(frames[f0:f0 + step], patch[f0:f0 + step].contiguous(), sz, strides, overlaps,
+                                                  add_to_movie=add, tsum=tsum, tcount=tcount)
+            moved.append(out.cpu())
+        new_temp = tsum / tcount                             # nanmean :2057 (0 / 0: NaN)
+        new_temp = torch.where(torch.isnan(new_temp), new_temp[~torch.isnan(new_temp)].min(), new_temp)   # :2058
+        return torch.cat(moved).view(-1, *sz).permute(1, 2, 3, 0).numpy(), new_temp.view(*sz)
+
+    def apply_shifts_movie(self, video):
+        """The video (T, X, Y, Z) moved by the STORED piecewise shifts ``x/y/z_shifts_els`` (a caller may have edited them):
+        tile_and_correct_3d :1639-1654 per frame, with add_to_movie = -min_mov.  (X, Y, Z, T) float32 numpy, like ``mc``."""
+        if not self.is3D:
+            raise NotImplementedError("MotionCorrect.apply_shifts_movie: the 2-D piecewise-corrected movie (cv2.resize + "
+                                      "cv2.remap, reference :1405-1410) is not built")
+        frames, sz = self._frames(video)
+        if self.min_mov is None:
+            self.min_mov = float(frames.min())
+        movie, _ = self._corrected_movie(frames, sz, self._shift_table(frames.shape[0]))
+        return movie
 
     def _centers(self, sz):
         _, starts = ops.patch_grid(sz, self.strides, self.overlaps)

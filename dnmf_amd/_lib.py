@@ -73,6 +73,8 @@ SIGNATURES = {
     "dnmf_register_patches": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
     "dnmf_rigid_correct_workspace": (_sz, [_i, _i, _i, _i]),
     "dnmf_rigid_correct": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _i, C.c_float, _i, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_apply_pwrigid_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),
+    "dnmf_apply_pwrigid": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "dnmf_apply_shifts_points": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),

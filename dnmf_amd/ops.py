@@ -638,6 +638,42 @@ def rigid_correct(frames, tmpl, sz, max_shifts, upsample_factor=10, add_to_movie
     return rigid, out, tsum, tcount
 
 
+def apply_pwrigid(frames, patch_shifts, sz, strides, overlaps, add_to_movie=0.0, frame_ids=None, out=None, tsum=None, tcount=None):
+    """K9.  frames (>=B, P) fp32 CUDA rows, patch_shifts (B,NP,3) with the signs of x/y/z_shifts_els (-x, -y, +z) -> (the
+    piecewise-rigid corrected frames out (B,P) (or (>=B, ldo) given), tsum (P) fp32, tcount (P) int32): the per-voxel sums and
+    counts of the finite corrected values are ADDED into ``tsum`` / ``tcount`` when given, else start from zero."""
+    import ctypes
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
+        raise ValueError("apply_pwrigid: frames must be float32 CUDA with unit inner stride")
+    dev = frames.device
+    sh = _f32(patch_shifts, "patch_shifts")
+    fid = _i32(frame_ids, dev) if frame_ids is not None else None
+    B = fid.numel() if fid is not None else frames.shape[0]
+    st = (ctypes.c_int * 3)(*[int(v) for v in strides])
+    ov = (ctypes.c_int * 3)(*[int(v) for v in overlaps])
+    lib = _lib.load()
+    NP = lib.dnmf_register_patches_grid(X, Y, Z, st, ov, None, None)
+    if NP <= 0:
+        raise ValueError(f"apply_pwrigid: windows of strides {tuple(strides)} + overlaps {tuple(overlaps)} do not fit the volume")
+    if tuple(sh.shape) != (B, NP, 3):
+        raise ValueError(f"apply_pwrigid: patch_shifts must be ({B}, {NP}, 3), got {tuple(sh.shape)}")
+    if out is None:
+        out = torch.empty((B, P), dtype=torch.float32, device=dev)
+    if out.shape[0] < B or out.stride(0) < P or out.stride(1) != 1 or out.dtype != torch.float32:
+        raise ValueError("apply_pwrigid: out must be float32 (>=B, ld) with ld >= P")
+    if tsum is None:
+        tsum, tcount = torch.zeros(P, dtype=torch.float32, device=dev), torch.zeros(P, dtype=torch.int32, device=dev)
+    ws = torch.empty((lib.dnmf_apply_pwrigid_workspace(X, Y, Z, st, ov, B),), dtype=torch.uint8, device=dev)
+    with _timed("apply_pwrigid"):
+        rc = lib.dnmf_apply_pwrigid(frames.data_ptr(), frames.stride(0), _ptr(fid), B, X, Y, Z, st, ov, sh.data_ptr(),
+                                    float(add_to_movie), out.data_ptr(), out.stride(0), tsum.data_ptr(), tcount.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "dnmf_apply_pwrigid")
+    return out, tsum, tcount
+
+
 def apply_shifts_points(points, patch_shifts, centers):
     """points (K,3), patch_shifts (T,NP,3), centers (NP,3) -> (K,3,T) fp32 (MotionCorrect.apply_shifts_points)."""
     pts, sh, ce = _f32(points, "points"), _f32(patch_shifts, "patch_shifts"), _f32(centers, "centers")

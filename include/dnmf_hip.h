@@ -385,6 +385,26 @@ int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int 
 int dnmf_apply_shifts_points(const float *points, int K, const float *patch_shifts, int T, int NP, const float *centers, float *out,
                              dnmf_stream_t stream);
 
+/* ---- K9: the piecewise-rigid corrected movie ---------------------------------------------------------
+ * Reference: Demix/MotionCorrect.py, tile_and_correct_3d :1639-1654 (shifts_opencv=True, the class default), the chunk
+ * template of tile_and_correct_wrapper :2057-2058.  Per frame img (+ add_to_movie):
+ *   field  the patch shifts on the grid of dnmf_register_patches_grid (dims, x outermost), moving the image by (+x, +y, +z)
+ *          = (-s0, -s1, +s2) of patch_shifts, resized to (X, Y, Z) as skimage's resize (order 1, mode 'reflect') does:
+ *          linear interpolation at c_d = (dims_d / N_d) (o + 0.5) - 0.5 with the edge mirrored;
+ *   warp   skimage's warp (order 3, mode 'constant', cval 0) at (x + fx, y + fy, z + fz), fp32 sums: the cubic B-spline of
+ *          the mirror-extended frame; a sample with any coordinate < 0 or > n - 1 is 0;
+ *   clip   _clip_warp_output: 0 stays 0, the rest is clipped to [min, max] of img + add_to_movie;
+ *   out    warp - add_to_movie (samples from outside the volume come out as -add_to_movie).
+ * frames: >= B rows of ldf floats (voxel p = (x Y + y) Z + z; row frame_ids[b] or b), patch_shifts (B,NP,3) with the signs of
+ * x/y/z_shifts_els (-x, -y, +z) as dnmf_register_patches returns them, strides / overlaps 3 host ints each, out B rows of ldo
+ * floats.  tsum / tcount (both NULL, or P floats / ints): += the finite corrected values and their number per voxel (the
+ * chunk template is tsum / tcount).  The workspace (dnmf_apply_pwrigid_workspace) holds the prefiltered frames of a chunk
+ * of frames, at most 512 MiB; the call walks the frames in such chunks. */
+size_t dnmf_apply_pwrigid_workspace(int X, int Y, int Z, const int *strides, const int *overlaps, int B);
+int dnmf_apply_pwrigid(const float *frames, long ldf, const int *frame_ids, int B, int X, int Y, int Z, const int *strides,
+                       const int *overlaps, const float *patch_shifts, float add_to_movie, float *out, long ldo, float *tsum,
+                       int *tcount, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
