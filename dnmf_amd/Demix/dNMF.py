@@ -118,12 +118,13 @@ class ExponentialFP(nn.Module):
         self._sparse_pairs_version = None
         self._lists = None
         self._lists_version = None
+        self._lists_exact = None   # (key, layout) of every non-zero value while footprint_floor > 0 (the footprint update's)
         self.use_lists = True   # reconstruction image from neuron lists when the footprints are compact
 
     def invalidate_layouts(self):
         """Forget every packed copy of ``A``.  The packed copies are keyed on ``(A.data_ptr(), A._version)``, which a
         kernel that writes ``A`` through its raw pointer (K6) does not change: such callers say so here."""
-        self._packed = self._sparse = self._sparse_pairs = self._lists = None
+        self._packed = self._sparse = self._sparse_pairs = self._lists = self._lists_exact = None
 
     @staticmethod
     def quadratic_basis(P):
@@ -204,24 +205,33 @@ class ExponentialFP(nn.Module):
             self._sparse_version = key
         return self._sparse
 
-    # Footprint values below ``footprint_floor`` are left out of the neuron lists (K3n, the list reconstruction, the list
-    # form of the footprint update): 0.0 -- the default -- keeps every non-zero value.  A Gaussian footprint exp(-d^2 / 9)
+    # Footprint values below ``footprint_floor`` are left out of the neuron lists (K3n, the list reconstruction): 0.0 -- the
+    # default -- keeps every non-zero value.  The footprint update (K5 / K6, spatial_step) is not affected: it takes its tile
+    # lists and values from the layout of every non-zero value, packed_lists(floor=0).  A Gaussian footprint exp(-d^2 / 9)
     # is a non-zero fp32 number out to 30 voxels (1e-45), so its box is 61 x 61; the values beyond ~15 voxels (1e-10) enter
     # sums of order 1-10 and cannot change an fp32 result except through the ORDER of the summation (measured: the Gram
     # data and the traces move by 4e-7 relative, as they do between K3n's own launch forms).  An extension: the reference
     # has no such knob.  bench.py reports it as ``extras.footprint_floor``; the headline runs with 0.0.
     footprint_floor = 0.0
 
-    def packed_lists(self):
-        """Layout of the neuron-list Gram kernel K3n (``ops.pack_footprints_lists``), rebuilt when ``A`` changes."""
-        key = (self.A.data_ptr(), self.A._version, float(self.footprint_floor))
-        if self._lists is None or self._lists_version != key:
-            A = self.A.contiguous()
-            if self.footprint_floor > 0:
-                A = torch.where(A < self.footprint_floor, torch.zeros((), dtype=A.dtype, device=A.device), A)
-            self._lists = ops.pack_footprints_lists(A, self.sz_list)
-            self._lists_version = key
-        return self._lists
+    def packed_lists(self, floor=None):
+        """Layout of the neuron-list Gram kernel K3n (``ops.pack_footprints_lists``) of the values >= ``floor`` (None:
+        ``footprint_floor``), rebuilt when ``A`` changes.  With ``footprint_floor == 0`` every floor of 0 is one layout."""
+        floor = float(self.footprint_floor if floor is None else floor)
+        key = (self.A.data_ptr(), self.A._version, floor)
+        own = floor == float(self.footprint_floor)
+        cached = (self._lists_version, self._lists) if own else (self._lists_exact or (None, None))
+        if cached[1] is not None and cached[0] == key:
+            return cached[1]
+        A = self.A.contiguous()
+        if floor > 0:
+            A = torch.where(A < floor, torch.zeros((), dtype=A.dtype, device=A.device), A)
+        ly = ops.pack_footprints_lists(A, self.sz_list)
+        if own:
+            self._lists, self._lists_version = ly, key
+        else:
+            self._lists_exact = (key, ly)
+        return ly
 
     def packed_sparse_pairs(self, group=64):
         """K > 128: the neurons, in Z-order, are cut into groups of ``group`` and every pair of groups gets its own
@@ -444,7 +454,8 @@ class DeformableNMF:
                 self._D_dev = (D, torch.as_tensor(D).to(device, torch.float32).reshape(P, K).contiguous())
             Dd = self._D_dev[1]
         if sl is not None:
-            ops.mu_spatial_lists(A2, fp.packed_lists(), sl, A1, Cs, fp.sz_list, Dd, gamma)
+            # the values and boxes of the true A (not the floored lists of K3n): a sub-floor value is updated like any other
+            ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
         else:
             ops.mu_spatial(A2, A1, Cs, Dd, gamma)
         fp.A = A2.view(*fp.sz_list, K)
@@ -455,16 +466,16 @@ class DeformableNMF:
     def _spatial_lists(self):
         """Tile lists of the list-form footprint update (``ops.spatial_lists_setup``) when ``spatial_kernel`` allows it and
         the footprints are compact (the rule of the Gram kernel: few boxes per voxel; no tile with more than 32 neurons),
-        else None: dense K5 / K6."""
+        else None: dense K5 / K6.  The boxes are those of every non-zero value, whatever ``fp.footprint_floor``."""
         fp = self.fp
         if self.spatial_kernel not in ('auto', 'lists') or fp.K > 256 or fp.P * 32 >= 2 ** 31 or fp.sz_list[1] * fp.sz_list[2] < 4:
             return None
-        ly = fp.packed_lists()
+        ly = fp.packed_lists(floor=0.0)
         if self.spatial_kernel == 'auto' and ly["boxfrac"] >= LISTS_BOXFRAC_LIMIT:
             return None
-        key = (fp.A.data_ptr(), fp.A._version)
-        if getattr(self, "_sl", None) is None or self._sl[0] != key:
-            self._sl = (key, ops.spatial_lists_setup(ly, fp.K, fp.sz_list))
+        # keyed on the layout itself: it is rebuilt whenever A is replaced, edited or invalidated
+        if getattr(self, "_sl", None) is None or self._sl[0] is not ly:
+            self._sl = (ly, ops.spatial_lists_setup(ly, fp.K, fp.sz_list))
         sl = self._sl[1]
         if sl["total"] <= 0:
             if self.spatial_kernel == 'lists':
@@ -978,7 +989,7 @@ class MultiChannelDNMF(DeformableNMF):
             for c in range(self.colours.shape[0]):
                 f = copy.copy(self.fp)  # shares beta (the caller's optimiser steps one tensor) and the lattice
                 f.A = self.fp.A * self.colours[c]
-                f._packed = f._sparse = f._sparse_pairs = f._lists = None
+                f._packed = f._sparse = f._sparse_pairs = f._lists = f._lists_exact = None
                 self._chan_fp.append((f, slice(c * P, (c + 1) * P)))
             self._chan_key = key
         return self._chan_fp

@@ -307,3 +307,46 @@ def test_position_initialiser_refuses_windows_it_cannot_hold(lib):
                                      a, a, a, 64, None) == -4
     assert lib.dnmf_rigid_correct(a, 20 * 20, None, 1, a, 20, 20, 1, I3(0, 12, 0), 10, 0.0, 1, a, None, 0, None, None, a, 64,
                                   None) == -4
+
+
+def sl_splits(X, Y, Z, T):
+    """Python restatement of csrc/spatial_update.hip:sl_splits -- the frame splits of the list-form K5: enough (tile, split)
+    waves to fill the GPU (>= 8192, at most 64 splits), but whole runs of 64 frames per split."""
+    ntiles = (X + 3) // 4 * ((Y * Z + 63) // 64)
+    s = min(max((8192 + ntiles - 1) // ntiles, 1), 64)
+    while s > 1 and T // s < 64:
+        s -= 1
+    return s
+
+
+# (X, Y, Z, T, splits, frames per split): the ragged case (a full run and a run of 3 per split, a last split of 62), exactly
+# two runs, one frame short of them, the bench geometry (GPU tests: T = 600; bench: T = 4000), a volume deeper than a tile
+SL_SPLIT_CASES = (
+    (32, 32, 2, 1000, 15, 67), (32, 32, 2, 128, 2, 64), (32, 32, 2, 127, 1, 127), (32, 32, 2, 70, 1, 70),
+    (512, 512, 1, 600, 8, 75), (512, 512, 1, 4000, 8, 500), (12, 3, 80, 300, 4, 75), (20, 16, 2, 160, 2, 80),
+)
+
+
+@pytest.mark.parametrize("X,Y,Z,T,ns,fps", SL_SPLIT_CASES)
+def test_spatial_lists_frame_splits_and_workspace(lib, X, Y, Z, T, ns, fps):
+    """The split count of the list-form K5 against its Python restatement and the counts the GPU tests
+    (tests/test_gpu_spatial_lists.py) rely on; the workspace holds one compact buffer per split (none for one split); a
+    workspace one float short is refused before any launch."""
+    assert sl_splits(X, Y, Z, T) == ns and -(-T // ns) == fps
+    assert lib.dnmf_spatial_lists_tiles(X, Y, Z) == (X + 3) // 4 * ((Y * Z + 63) // 64)
+    total = 256 * 3 * lib.dnmf_spatial_lists_tiles(X, Y, Z)
+    need = lib.dnmf_spatial_accum_lists_workspace(X, Y, Z, total, T)
+    assert need == (ns * total * 4 if ns > 1 else 0)
+    assert lib.dnmf_spatial_accum_lists_workspace(X, Y, Z, -1, T) == 0          # a list overflowed: no list form at all
+    assert lib.dnmf_spatial_accum_lists_workspace(X, Y, Z, total, 0) == 0
+    if ns == 1:
+        return
+    buf = ctypes.create_string_buffer(64)
+    a = ctypes.addressof(buf)
+    P, K = X * Y * Z, 5
+    for ws, nbytes in ((None, 0), (a, need - 4)):
+        rc = lib.dnmf_spatial_accum_lists(a, P, None, a, T, None, T, X, Y, Z, K, a, total, a, a, ws, nbytes, None)
+        assert rc == -4 and b"workspace" in lib.dnmf_last_error()
+    # and the shape checks come first
+    assert lib.dnmf_spatial_accum_lists(a, P - 1, None, a, T, None, T, X, Y, Z, K, a, total, a, a, None, 0, None) == -2
+    assert lib.dnmf_spatial_accum_lists(None, P, None, a, T, None, T, X, Y, Z, K, a, total, a, a, None, 0, None) == -1
