@@ -287,6 +287,37 @@ class ExponentialFP(nn.Module):
             Yi_list.append(Yi.view(len(times), X, Y_, Z).permute(1, 2, 3, 0).double().cpu().numpy())
         return np.concatenate(A_list, 4), np.concatenate(Yi_list, 3), np.concatenate(Y_list, 3)
 
+    @staticmethod
+    def image_iwarp(im, flow, grid):
+        """Reference :95-103: the value of ``im`` at the flow point nearest to each query of ``grid`` (scipy's
+        NearestNDInterpolator), reshaped to ``im.shape``.  ``im`` (X,Y,Z) values, ``flow`` (X,Y,Z,3) the position of every
+        voxel of ``im`` (same order), ``grid`` (..., 3) query points, integer or float, one per voxel of ``im``.
+
+        K10 (``ops.nearest_points``): float64 distances on the flow as stored, exact; exact ties go to the lowest voxel index
+        (cKDTree leaves that choice unspecified).  numpy or CPU-torch ``im`` gives a numpy array of ``im``'s dtype, as the
+        reference does; a CUDA ``im`` gives a CUDA tensor (an extension of the reference).  Raises ValueError when the
+        number of flow points or queries is not ``im``'s size, or when a coordinate is not finite."""
+        on_gpu = isinstance(im, torch.Tensor) and im.is_cuda
+        vals = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+        shape = tuple(vals.shape)
+        n = vals.numel()
+        fl = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow))
+        if fl.dtype not in (torch.float32, torch.float64):
+            fl = fl.double()
+        pts = fl.to(device).reshape(-1, 3)
+        q = torch.as_tensor(np.asarray(grid) if not isinstance(grid, torch.Tensor) else grid)
+        q = q.to(device=device, dtype=torch.float64).reshape(-1, 3)
+        if pts.shape[0] != n or q.shape[0] != n:
+            raise ValueError(f"image_iwarp: {pts.shape[0]} flow points and {q.shape[0]} queries for an image of {n} values")
+        if vals.dtype == torch.float32:
+            _, out = ops.nearest_points(pts[None], q, values=vals.to(device).reshape(1, n))
+            out = out.reshape(shape)
+        else:
+            idx = ops.nearest_points(pts[None], q)
+            flat = vals.reshape(-1)
+            out = torch.take(flat, idx.reshape(-1).to(device=flat.device, dtype=torch.int64)).reshape(shape)
+        return out if on_gpu else out.cpu().numpy()
+
 
 class DeformableNMF:
     """Reference ``Demix/dNMF.py:124-194``: owns the spatial model ``fp`` and the traces ``C`` (K,T)."""

@@ -76,6 +76,8 @@ SIGNATURES = {
     "dnmf_apply_pwrigid_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),
     "dnmf_apply_pwrigid": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "dnmf_apply_shifts_points": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "dnmf_nearest_points_workspace": (_sz, [_i, _i]),
+    "dnmf_nearest_points": (_i, [_vp, _i, _l, _i, _vp, _l, _i, _i, _vp, _l, _vp, _l, _vp, _l, _vp, _sz, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

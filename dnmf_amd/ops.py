@@ -556,6 +556,58 @@ def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, 
     return out
 
 
+def nearest_points(points, queries, values=None, out_index=None, out=None, _workspace_bytes=None):
+    """K10.  points (B,N,3) fp32 or fp64 CUDA, queries (Q,3) (one set for every frame) or (B,Q,3), converted to float64 ->
+    ``index`` (B,Q) int32: per frame and query the point of the smallest float64 (d2, index), exact, ties to the lowest index;
+    with ``values`` (B,N) fp32 also ``vals`` (B,Q) = values[b][index], returned as ``(index, vals)``.  ``out_index`` /
+    ``out``: (B,Q) outputs to fill (row strides allowed).  Raises ValueError on a non-finite point or query.
+    ``_workspace_bytes``: a smaller workspace than the call's 512 MiB chunk (tests: several chunks of frames per call)."""
+    if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype in (torch.float32, torch.float64)
+            and points.dim() == 3 and points.shape[2] == 3):
+        raise ValueError("nearest_points: points must be a (B,N,3) float32 or float64 CUDA tensor")
+    dev = points.device
+    B, N = points.shape[0], points.shape[1]
+    if N < 1:
+        raise ValueError("nearest_points: need at least one point per frame")
+    if points.stride(2) != 1 or points.stride(1) != 3:
+        points = points.contiguous()
+    q = torch.as_tensor(queries).to(device=dev, dtype=torch.float64)
+    if q.dim() not in (2, 3) or q.shape[-1] != 3 or (q.dim() == 3 and q.shape[0] != B):
+        raise ValueError(f"nearest_points: queries must be (Q,3) or ({B},Q,3), got {tuple(q.shape)}")
+    q = q.contiguous()
+    Q = q.shape[-2]
+    if not bool(torch.isfinite(points).all()) or not bool(torch.isfinite(q).all()):
+        raise ValueError("nearest_points: points and queries must be finite")
+    if out_index is None:
+        out_index = torch.empty((B, Q), dtype=torch.int32, device=dev)
+    if (out_index.dtype != torch.int32 or not out_index.is_cuda or out_index.dim() != 2 or out_index.shape[0] < B
+            or out_index.shape[1] < Q or (Q > 1 and out_index.stride(1) != 1)):
+        raise ValueError("nearest_points: out_index must be int32 CUDA (>=B, >=Q) with unit inner stride")
+    if values is not None:
+        if (values.dtype != torch.float32 or not values.is_cuda or values.dim() != 2 or values.shape[0] < B
+                or values.shape[1] != N or (N > 1 and values.stride(1) != 1)):
+            raise ValueError(f"nearest_points: values must be float32 CUDA ({B},{N}) with unit inner stride")
+        if out is None:
+            out = torch.empty((B, Q), dtype=torch.float32, device=dev)
+        if (out.dtype != torch.float32 or not out.is_cuda or out.dim() != 2 or out.shape[0] < B or out.shape[1] < Q
+                or (Q > 1 and out.stride(1) != 1)):
+            raise ValueError("nearest_points: out must be float32 CUDA (>=B, >=Q) with unit inner stride")
+    if B == 0 or Q == 0:
+        return out_index if values is None else (out_index, out)
+    lib = _lib.load()
+    need = lib.dnmf_nearest_points_workspace(N, B)
+    if _workspace_bytes is not None:
+        need = min(need, max(int(_workspace_bytes), lib.dnmf_nearest_points_workspace(N, 1)))
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    with _timed("nearest_points"):
+        rc = lib.dnmf_nearest_points(points.data_ptr(), int(points.dtype == torch.float64), points.stride(0), N, q.data_ptr(),
+                                     0 if q.dim() == 2 else q.stride(0), Q, B, _ptr(values),
+                                     0 if values is None else values.stride(0), out_index.data_ptr(), out_index.stride(0),
+                                     _ptr(out), Q if out is None else out.stride(0), ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "dnmf_nearest_points")
+    return out_index if values is None else (out_index, out)
+
+
 def patch_grid(sz, strides, overlaps):
     """The patch grid of the reference's ``sliding_window_3d`` (MotionCorrect.py:1190-1221): ``(dims (3,), starts (NP,3))`` as
     numpy int arrays, patches in the reference's order (x outermost)."""

@@ -405,6 +405,26 @@ int dnmf_apply_pwrigid(const float *frames, long ldf, const int *frame_ids, int 
                        const int *overlaps, const float *patch_shifts, float add_to_movie, float *out, long ldo, float *tsum,
                        int *tcount, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K10: nearest point of an arbitrary point cloud ---------------------------------------------------------------------
+ * ExponentialFP.image_iwarp on any flow (Demix/dNMF.py:95-103: scipy's NearestNDInterpolator, a cKDTree query in float64).
+ * Per frame b < B: N points (x, y, z) at points + b ldp (fp32, or fp64 with points_f64 != 0; element stride 3), Q queries
+ * (x, y, z) fp64 at queries + b ldq (ldq == 0: one query set for every frame).  For every query, the index i of the
+ * smallest (d2, i) in lexicographic order, d2 = ((qx - px)^2 + (qy - py)^2) + (qz - pz)^2 in float64 on the coordinates as
+ * stored: exact, ties to the lowest index, independent of the launch shape and of the order of atomics.
+ *   index_out (B,Q) int32, row stride ldi >= Q;  values: NULL (indices only), or (B,N) fp32 with row stride ldv >= N,
+ *   and then value_out (B,Q) fp32, row stride ldo >= Q, gets values[b][index] in the same pass (both NULL or both set);
+ *   strides in elements: ldp >= 3N, ldq == 0 or >= 3Q;
+ *   workspace: 256-byte aligned, at least dnmf_nearest_points_workspace(N, 1) bytes (one frame); the call walks the frames in
+ *   chunks of what the workspace holds, at most dnmf_nearest_points_workspace(N, B) bytes (<= 512 MiB, or one frame);
+ *   Q == 0 or B == 0: nothing to do (DNMF_OK);  N <= 0, Q < 0, B < 0 or a stride below a row: DNMF_E_SHAPE;  N >= 2^30:
+ *   DNMF_E_UNSUPPORTED;  a short or misaligned workspace: DNMF_E_WORKSPACE.
+ * Non-finite coordinates keep every access in bounds but give unspecified indices (dnmf_amd.ops refuses them).  A cloud
+ * whose points crowd into few cells (duplicates, a line, one far outlier) costs up to O(N) per query. */
+size_t dnmf_nearest_points_workspace(int N, int B);
+int dnmf_nearest_points(const void *points, int points_f64, long ldp, int N, const double *queries, long ldq, int Q, int B,
+                        const float *values, long ldv, int *index_out, long ldi, float *value_out, long ldo, void *workspace,
+                        size_t workspace_bytes, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
