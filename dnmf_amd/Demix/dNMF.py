@@ -449,10 +449,7 @@ class DeformableNMF:
         # A1 and C_s live in one buffer so that the exchange is a single collective; with compact footprints A1 exists
         # only for (tile, listed neuron) pairs -- a few floats per voxel instead of K (3 MB instead of 105 MB at cfg 3)
         n1 = sl["total"] if sl is not None else P * K
-        if self._spatial_buf is None or self._spatial_buf.numel() != n1 + K * K:
-            self._spatial_buf = None
-            self._spatial_buf = torch.empty((n1 + K * K,), dtype=torch.float32, device=device)
-        buf = self._spatial_buf
+        buf = self._spatial_buffer(n1 + K * K)
         Cs = buf[n1:].view(K, K)
         if sl is not None:
             A1 = buf[:n1]
@@ -460,14 +457,43 @@ class DeformableNMF:
                                                         Cs=Cs, workspace=getattr(self, "_ws_k5", None))
         else:
             A1 = buf[:n1].view(P, K)
-            if K <= 128:
-                ops.spatial_accum(registered, C, frame_ids=frame_ids, times=times, A1=A1, Cs=Cs, accumulate=False)
-            else:  # K5 holds 8 trace blocks per wave: columns of A1 by groups of 128 neurons; C C^T is tiny
-                Cl = C[:, :registered.shape[0]] if times is None else C[:, torch.as_tensor(times, device=C.device).long()]
-                for s0 in range(0, K, 128):
-                    part, _ = ops.spatial_accum(registered, C[s0:s0 + 128].contiguous(), frame_ids=frame_ids, times=times)
-                    A1[:, s0:s0 + 128] = part
-                Cs.copy_((Cl.double() @ Cl.double().T).float())
+            self._spatial_accum_dense(registered, C, A1, Cs, frame_ids, times)
+        self._allreduce_spatial(buf)
+        A2 = fp.A.reshape(P, K).contiguous()
+        Dd = self._device_D(D)
+        if sl is not None:
+            # the values and boxes of the true A (not the floored lists of K3n): a sub-floor value is updated like any other
+            ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
+        else:
+            ops.mu_spatial(A2, A1, Cs, Dd, gamma)
+        fp.A = A2.view(*fp.sz_list, K)
+        fp.invalidate_layouts()   # K6 wrote through the raw pointer: the packed copies are stale
+        self._sl = None
+        return fp.A
+
+    def _spatial_buffer(self, n):
+        """The one buffer of spatial_step (A1 | C_s: one collective), kept while its size holds."""
+        if self._spatial_buf is None or self._spatial_buf.numel() != n:
+            self._spatial_buf = None
+            self._spatial_buf = torch.empty((n,), dtype=torch.float32, device=device)
+        return self._spatial_buf
+
+    @staticmethod
+    def _spatial_accum_dense(registered, C, A1, Cs, frame_ids, times):
+        """Dense K5 into A1 (P,K) and Cs (K,K): one launch up to 128 neurons, else columns of A1 by groups of 128 (K5 holds
+        8 trace blocks per wave) and C C^T in float64 (it is tiny)."""
+        K = C.shape[0]
+        if K <= 128:
+            ops.spatial_accum(registered, C, frame_ids=frame_ids, times=times, A1=A1, Cs=Cs, accumulate=False)
+            return
+        Cl = C[:, :registered.shape[0]] if times is None else C[:, torch.as_tensor(times, device=C.device).long()]
+        for s0 in range(0, K, 128):
+            part, _ = ops.spatial_accum(registered, C[s0:s0 + 128].contiguous(), frame_ids=frame_ids, times=times)
+            A1[:, s0:s0 + 128] = part
+        Cs.copy_((Cl.double() @ Cl.double().T).float())
+
+    def _allreduce_spatial(self, buf):
+        """Sum spatial_step's buffer over ``self.group`` when the T axis is sharded (nothing to do otherwise)."""
         if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
             if self.collective == "c1" and torch.distributed.get_backend(self.group) == "nccl":
                 # the library's own RCCL communicator (C1 of the C ABI: what a host without torch would call), built on
@@ -478,21 +504,15 @@ class DeformableNMF:
             else:  # the caller's process group: RCCL when its backend is "nccl" (one process per GPU), gloo in rehearsals
                 with ops._timed("allreduce"):
                     torch.distributed.all_reduce(buf, group=self.group)
-        A2 = fp.A.reshape(P, K).contiguous()
-        Dd = None
-        if D is not None:   # the fp32 device copy is kept while the caller hands in the same object (105 MB at cfg 3)
-            if self._D_dev is None or self._D_dev[0] is not D:
-                self._D_dev = (D, torch.as_tensor(D).to(device, torch.float32).reshape(P, K).contiguous())
-            Dd = self._D_dev[1]
-        if sl is not None:
-            # the values and boxes of the true A (not the floored lists of K3n): a sub-floor value is updated like any other
-            ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
-        else:
-            ops.mu_spatial(A2, A1, Cs, Dd, gamma)
-        fp.A = A2.view(*fp.sz_list, K)
-        fp.invalidate_layouts()   # K6 wrote through the raw pointer: the packed copies are stale
-        self._sl = None
-        return fp.A
+
+    def _device_D(self, D):
+        """``D`` as fp32 (P,K) on the device, or None; the copy is kept while the caller hands in the same object (105 MB
+        at cfg 3)."""
+        if D is None:
+            return None
+        if self._D_dev is None or self._D_dev[0] is not D:
+            self._D_dev = (D, torch.as_tensor(D).to(device, torch.float32).reshape(self.fp.P, self.fp.K).contiguous())
+        return self._D_dev[1]
 
     def _spatial_lists(self):
         """Tile lists of the list-form footprint update (``ops.spatial_lists_setup``) when ``spatial_kernel`` allows it and
@@ -566,10 +586,11 @@ class DeformableNMF:
             C[:, order.long()] = Cnew
             self.C = C
             if live_spatial:
-                if self._reg_buf is None or self._reg_buf.shape != (T_loc, P):
+                nch = self._nchan()   # channels share the warp: one K7 search per lattice point serves all of them
+                if self._reg_buf is None or self._reg_buf.shape != (T_loc, nch * P):
                     self._reg_buf = None
-                    self._reg_buf = torch.empty((T_loc, P), dtype=torch.float32, device=device)
-                ops.image_iwarp(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf)
+                    self._reg_buf = torch.empty((T_loc, nch * P), dtype=torch.float32, device=device)
+                ops.image_iwarp(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
                 for _ in range(iter_a):
                     self.spatial_step(self._reg_buf, D=self.D, gamma=gamma_a, times=order)
             if return_dense is None:
@@ -618,6 +639,10 @@ class DeformableNMF:
         """``[(spatial model, slice of a frame row)]``: one entry, the whole row, for the reference's single-channel
         model; MultiChannelDNMF lists its colour channels here."""
         return [(self.fp, None)]
+
+    def _nchan(self):
+        """Channels of a frame row (P floats each)."""
+        return 1
 
     def _note_once(self, key, text):
         """One line on stdout the first time ``key`` comes up (kernel choices that cost a factor and would otherwise
@@ -1025,12 +1050,18 @@ class MultiChannelDNMF(DeformableNMF):
             self._chan_key = key
         return self._chan_fp
 
-    def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=False):
-        """As DeformableNMF.update_footprints on the channel sums; the dense ``A_t`` return is not offered."""
+    def _nchan(self):
+        return self.colours.shape[0]
+
+    def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=False,
+                          live_spatial=False, iter_a=1):
+        """As DeformableNMF.update_footprints on the channel sums; the dense ``A_t`` return is not offered.  With
+        ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel) and
+        ``fp.A`` takes ``iter_a`` steps of ``spatial_step``."""
         if return_dense:
             raise NotImplementedError("MultiChannelDNMF.update_footprints: return_dense")
         return super().update_footprints(testloader, batch_size, sz, gamma_c=gamma_c, gamma_a=gamma_a, iter_c=iter_c,
-                                         return_dense=False)
+                                         return_dense=False, live_spatial=live_spatial, iter_a=iter_a)
 
     def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
         """One multiplicative update of the (uncoloured) footprints ``fp.A`` from the registered frames of ALL channels
@@ -1039,40 +1070,46 @@ class MultiChannelDNMF(DeformableNMF):
 
             A <- A * (sum_c colours_c (Y_i^c C^T)) / (A (C C^T * colours^T colours) + gamma D + 1e-32)
 
-        (numerator: K5 per channel, scaled by the channel's colours; denominator: K6 with C_s multiplied entry by entry by
-        the Gram matrix of the colours).  One all-reduce of the A1 | C_s buffer over ``self.group`` like the single-channel
-        step.  Not in the reference (no channel axis there): checked against this formula in float64 and, for one channel of
-        colour 1, against ``DeformableNMF.spatial_step``."""
+        (numerator: K5 over the channels, weighted by their colours; denominator: K6 with C_s multiplied entry by entry by
+        the Gram matrix of the colours).  The form is chosen as in DeformableNMF.spatial_step (``_spatial_lists``): the list
+        form folds the colours into one channel K5 launch (``dnmf_spatial_accum_lists_channels``), the dense form runs K5
+        per channel (by groups of 128 neurons beyond K = 128).  One all-reduce of the A1 | C_s buffer over ``self.group``
+        like the single-channel step.  Not in the reference (no channel axis there): checked against this formula in
+        float64 and, for one channel of colour 1, against ``DeformableNMF.spatial_step``."""
         fp = self.fp
         P, K = fp.P, fp.K
         NC = self.colours.shape[0]
         if registered.shape[1] != NC * P:
             raise ValueError(f"MultiChannelDNMF.spatial_step: rows of {registered.shape[1]} floats, expected {NC} x {P}")
-        if K > 128:
-            raise NotImplementedError("MultiChannelDNMF.spatial_step: K > 128")
         C = self.C.to(device, torch.float32).contiguous()
         if times is None:
             times = frame_ids
-        if self._spatial_buf is None or self._spatial_buf.numel() != P * K + K * K:
-            self._spatial_buf = None
-            self._spatial_buf = torch.empty((P * K + K * K,), dtype=torch.float32, device=device)
-        buf = self._spatial_buf
-        A1, Cs = buf[:P * K].view(P, K), buf[P * K:].view(K, K)
-        A1.zero_()
-        for c in range(NC):
-            part, cs = ops.spatial_accum(registered[:, c * P:(c + 1) * P], C, frame_ids=frame_ids, times=times)
-            A1.addcmul_(part, self.colours[c][None, :])
-            if c == 0:
-                Cs.copy_(cs)
-        if self.group is not None and torch.distributed.get_world_size(self.group) > 1:
-            with ops._timed("allreduce"):
-                torch.distributed.all_reduce(buf, group=self.group)
+        sl = self._spatial_lists()
+        n1 = sl["total"] if sl is not None else P * K
+        buf = self._spatial_buffer(n1 + K * K)
+        Cs = buf[n1:].view(K, K)
+        if sl is not None:
+            A1 = buf[:n1]
+            _, _, self._ws_k5 = ops.spatial_accum_lists_channels(registered, C, self.colours, sl, fp.sz_list, K, frame_ids=frame_ids,
+                                                                 times=times, A1c=A1, Cs=Cs, workspace=getattr(self, "_ws_k5", None))
+        else:
+            A1 = buf[:n1].view(P, K)
+            A1.zero_()
+            part = torch.empty((P, K), dtype=torch.float32, device=device)
+            for c in range(NC):
+                self._spatial_accum_dense(registered[:, c * P:(c + 1) * P], C, part, Cs, frame_ids, times)
+                A1.addcmul_(part, self.colours[c][None, :])
+        self._allreduce_spatial(buf)
         Cs.mul_(self.colours.T @ self.colours)
         A2 = fp.A.reshape(P, K).contiguous()
-        Dd = None if D is None else torch.as_tensor(D).to(device, torch.float32).reshape(P, K).contiguous()
-        ops.mu_spatial(A2, A1, Cs, Dd, gamma)
+        Dd = self._device_D(D)
+        if sl is not None:
+            ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
+        else:
+            ops.mu_spatial(A2, A1, Cs, Dd, gamma)
         fp.A = A2.view(*fp.sz_list, K)
         fp.invalidate_layouts()
+        self._sl = None
         self._chan_fp = None
         return fp.A
 

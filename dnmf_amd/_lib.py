@@ -50,6 +50,8 @@ SIGNATURES = {
     "dnmf_mu_spatial": (_i, [_vp, _vp, _vp, _vp, _d, _l, _i, _vp]),
     "dnmf_image_iwarp_workspace": (_sz, [_i, _i, _i, _i]),
     "dnmf_image_iwarp": (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _vp, _sz, _i, _vp, _vp]),
+    "dnmf_image_iwarp_channels": (_i, [_vp, _l, _l, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _l, _vp, _sz, _i, _vp,
+                                        _vp]),
     "dnmf_adam_epoch_workspace": (_sz, [_i]),
     "dnmf_adam_epoch": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp, _i, _d, _d, _d, _d, _i, _vp, _sz, _vp]),
     "dnmf_render_frames": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _d, _d, _vp, _l, _vp]),
@@ -67,6 +69,8 @@ SIGNATURES = {
     "dnmf_spatial_lists_setup": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "dnmf_spatial_accum_lists_workspace": (_sz, [_i, _i, _i, _l, _i]),
     "dnmf_spatial_accum_lists": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_spatial_accum_lists_channels": (_i, [_vp, _l, _l, _i, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp,
+                                                _vp, _sz, _vp]),
     "dnmf_mu_spatial_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _vp]),
     "dnmf_register_patches_grid": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "dnmf_register_patches_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),

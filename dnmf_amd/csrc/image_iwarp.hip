@@ -165,9 +165,13 @@ struct IwarpScale {
     float k[3], hk[3];   // (S-1)/S and S/(2 (S-1)) per axis (1 and 1/2 along a pinned z)
 };
 
+// Channels (CH, every kernel below): the frame row holds `nchan` channels that share the warp, channel c at c ldc_in
+// (output: c ldc_out).  The search runs once per lattice point; its result is gathered from every channel.  Without CH the
+// kernels are the single-channel ones (nchan, ldc_in, ldc_out unused).
+
 // One thread per lattice point: pre-image estimate, its cell, the box if it is larger; todo[g] = 1 where the box would
 // be too large.
-template <bool HASZ>
+template <bool HASZ, bool CH>
 __global__ __launch_bounds__(256) void image_iwarp_window_kernel(const float *__restrict__ frames, long ldf,
                                                                  const int *__restrict__ frame_ids, Volume vol,
                                                                  const float *__restrict__ beta, int T,
@@ -175,7 +179,8 @@ __global__ __launch_bounds__(256) void image_iwarp_window_kernel(const float *__
                                                                  const float *__restrict__ inv_stretch, IwarpScale sc,
                                                                  float *__restrict__ out, long ldo,
                                                                  unsigned char *__restrict__ todo,
-                                                                 unsigned *__restrict__ marked) {
+                                                                 unsigned *__restrict__ marked, int nchan, long ldc_in,
+                                                                 long ldc_out) {
     const int b = blockIdx.y;
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= vol.P) return;
@@ -291,7 +296,11 @@ __global__ __launch_bounds__(256) void image_iwarp_window_kernel(const float *__
             for (int yy = lo[1]; yy <= hi[1]; ++yy)
                 for (int z = lo[2]; z <= hi[2]; ++z) candidate(x, yy, z);
     }
-    out[(long)b * ldo + g] = y[arg];
+    if (CH) {
+        for (int c = 0; c < nchan; ++c) out[(long)b * ldo + c * ldc_out + g] = y[c * ldc_in + arg];
+    } else {
+        out[(long)b * ldo + g] = y[arg];
+    }
     *flag = 0;
 }
 
@@ -324,13 +333,14 @@ constexpr int IW_ROWS = DNMF_IW_ROWS;
 #endif
 constexpr int IW_SHARE = DNMF_IW_SHARE;   // lanes of a wave whose boxes the wave searches together
 
-template <bool HASZ, int FAST>
+template <bool HASZ, int FAST, bool CH>
 __global__ __launch_bounds__(256) void image_iwarp_rows_kernel(const float *__restrict__ frames, long ldf,
                                                                const int *__restrict__ frame_ids, Volume vol,
                                                                const float *__restrict__ beta, int T, const int *__restrict__ times,
                                                                const float *__restrict__ inv_stretch, IwarpScale sc,
                                                                float *__restrict__ out, long ldo, unsigned char *__restrict__ todo,
-                                                               unsigned *__restrict__ marked, int nyb) {
+                                                               unsigned *__restrict__ marked, int nyb, int nchan, long ldc_in,
+                                                               long ldc_out) {
     constexpr int ND = HASZ ? 3 : 2;
     constexpr int NC = HASZ ? 8 : 4;     // cell corners, index = 4 (x corner) + 2 (y corner) + (z corner) for Z > 1, 2 (x) + (y) else
     constexpr int NF = NC / 2;           // corners of one x-face
@@ -601,19 +611,25 @@ __global__ __launch_bounds__(256) void image_iwarp_rows_kernel(const float *__re
                     }
         }
         if (valid && !far) {
-            out_b[g] = y[(unsigned)arg];
+            if (CH) {
+                for (int c = 0; c < nchan; ++c) out_b[c * ldc_out + g] = y[c * ldc_in + (unsigned)arg];
+            } else {
+                out_b[g] = y[(unsigned)arg];
+            }
             *flag = 0;
         }
     }
 }
 
 // The exhaustive search (P candidates per lattice point, tiles of warped positions in LDS) for the marked points.
+template <bool CH>
 __global__ __launch_bounds__(256) void image_iwarp_full_kernel(const float *__restrict__ frames, long ldf,
                                                                const int *__restrict__ frame_ids, Volume vol,
                                                                const float *__restrict__ beta, int T,
                                                                const int *__restrict__ times, float *__restrict__ out,
                                                                long ldo, const unsigned char *__restrict__ todo,
-                                                               const unsigned *__restrict__ marked, int B) {
+                                                               const unsigned *__restrict__ marked, int B, int nchan,
+                                                               long ldc_in, long ldc_out) {
     __shared__ float sx[IW_TILE], sy[IW_TILE], sz[IW_TILE];
     const long g = (long)blockIdx.x * blockDim.x + threadIdx.x;  // lattice point served by this thread
     int gx = 0, gy = 0, gz = 0;
@@ -650,7 +666,13 @@ __global__ __launch_bounds__(256) void image_iwarp_full_kernel(const float *__re
                 }
             }
         }
-        if (mine) out[(long)b * ldo + g] = y[arg];
+        if (mine) {
+            if (CH) {
+                for (int c = 0; c < nchan; ++c) out[(long)b * ldo + c * ldc_out + g] = y[c * ldc_in + arg];
+            } else {
+                out[(long)b * ldo + g] = y[arg];
+            }
+        }
         __syncthreads();   // the tiles in LDS are rewritten for the next frame
     }
 }
@@ -678,17 +700,24 @@ size_t dnmf_image_iwarp_workspace(int X, int Y, int Z, int B) {
     return iwarp_flag_bytes(X, Y, Z, B) + (dnmf::IW_NK * sizeof(float) + sizeof(unsigned)) * (size_t)B + sizeof(unsigned);
 }
 
-int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X, int Y, int Z, const float *beta, int T,
-                     const int *times, int B, float *out, long ldo, void *workspace, size_t workspace_bytes, int exhaustive,
-                     unsigned long long *fallback_count, dnmf_stream_t stream) {
+// dnmf_image_iwarp is the one-channel call (CH off: the single-channel kernels) of the same launches
+static int iwarp_run(const char *who, const float *frames, long ldf, long ldc_in, int nchan, const int *frame_ids, int X, int Y,
+                     int Z, const float *beta, int T, const int *times, int B, float *out, long ldo, long ldc_out, void *workspace,
+                     size_t workspace_bytes, int exhaustive, unsigned long long *fallback_count, dnmf_stream_t stream) {
     using namespace dnmf;
-    DNMF_REQUIRE(frames && beta && times && out && workspace, DNMF_E_NULL, "dnmf_image_iwarp: NULL buffer");
-    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && T > 0 && B > 0 && B <= 65535, DNMF_E_SHAPE,
-                 "dnmf_image_iwarp: X=%d Y=%d Z=%d T=%d B=%d", X, Y, Z, T, B);
+    DNMF_REQUIRE(frames && beta && times && out && workspace, DNMF_E_NULL, "%s: NULL buffer", who);
+    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && T > 0 && B > 0 && B <= 65535, DNMF_E_SHAPE, "%s: X=%d Y=%d Z=%d T=%d B=%d", who, X,
+                 Y, Z, T, B);
     const Volume vol = make_volume(X, Y, Z);
-    DNMF_REQUIRE(ldf >= vol.P && ldo >= vol.P, DNMF_E_SHAPE, "dnmf_image_iwarp: ldf=%ld ldo=%ld < P=%ld", ldf, ldo, vol.P);
-    DNMF_REQUIRE(workspace_bytes >= dnmf_image_iwarp_workspace(X, Y, Z, B), DNMF_E_WORKSPACE,
-                 "dnmf_image_iwarp: workspace %zu < %zu bytes", workspace_bytes, dnmf_image_iwarp_workspace(X, Y, Z, B));
+    DNMF_REQUIRE(ldf >= vol.P && ldo >= vol.P, DNMF_E_SHAPE, "%s: ldf=%ld ldo=%ld < P=%ld", who, ldf, ldo, vol.P);
+    DNMF_REQUIRE(nchan >= 1 && (nchan == 1 || (ldc_in >= vol.P && ldc_out >= vol.P)), DNMF_E_SHAPE,
+                 "%s: nchan=%d ldc_in=%ld ldc_out=%ld (P=%ld)", who, nchan, ldc_in, ldc_out, vol.P);
+    DNMF_REQUIRE(ldf >= (nchan - 1) * ldc_in + vol.P && ldo >= (nchan - 1) * ldc_out + vol.P, DNMF_E_SHAPE,
+                 "%s: rows of ldf=%ld / ldo=%ld floats cannot hold %d channels %ld / %ld apart", who, ldf, ldo, nchan, ldc_in,
+                 ldc_out);
+    DNMF_REQUIRE(workspace_bytes >= dnmf_image_iwarp_workspace(X, Y, Z, B), DNMF_E_WORKSPACE, "%s: workspace %zu < %zu bytes",
+                 who, workspace_bytes, dnmf_image_iwarp_workspace(X, Y, Z, B));
+    const bool ch = nchan > 1;
     hipStream_t st = (hipStream_t)stream;
     unsigned char *todo = static_cast<unsigned char *>(workspace);
     const dim3 grid((unsigned)((vol.P + 255) / 256), (unsigned)B);
@@ -697,7 +726,7 @@ int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X,
     if (exhaustive) {
         marked = nullptr;
         hipError_t e = hipMemsetAsync(todo, 1, (size_t)vol.P * B, st);
-        DNMF_REQUIRE(e == hipSuccess, (int)e, "dnmf_image_iwarp: hipMemsetAsync: %s", hipGetErrorString(e));
+        DNMF_REQUIRE(e == hipSuccess, (int)e, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
     } else {
         hipLaunchKernelGGL(iwarp_stretch_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, beta, T, times, B, vol, stretch,
                            marked);
@@ -710,22 +739,33 @@ int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X,
         }                                                                       // the volume goes to the exhaustive search
         const int nyb = (Y * Z + 255) / 256;
         const dim3 rgrid((unsigned)(nyb * ((X + IW_ROWS - 1) / IW_ROWS)), (unsigned)B);
-#define DNMF_IW_ROWS_LAUNCH(HZ, FD)                                                                                              \
-    hipLaunchKernelGGL((image_iwarp_rows_kernel<HZ, FD>), rgrid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T, times,  \
-                       stretch, sc, out, ldo, todo, marked, nyb)
+#define DNMF_IW_ROWS_LAUNCH(HZ, FD, CH)                                                                                          \
+    hipLaunchKernelGGL((image_iwarp_rows_kernel<HZ, FD, CH>), rgrid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T,     \
+                       times, stretch, sc, out, ldo, todo, marked, nyb, nchan, ldc_in, ldc_out)
+#define DNMF_IW_WINDOW_LAUNCH(HZ, CH)                                                                                            \
+    hipLaunchKernelGGL((image_iwarp_window_kernel<HZ, CH>), grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T, times, \
+                       stretch, sc, out, ldo, todo, marked, nchan, ldc_in, ldc_out)
         if (X == 1 || Y == 1 || vol.P >= (1L << 29)) {   // an axis of one voxel (its hk is infinite: every point is marked), or voxel
                                                           // indices beyond the rows kernel's 32 bits: one point per thread
-            if (Z > 1)
-                hipLaunchKernelGGL(image_iwarp_window_kernel<true>, grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T,
-                                   times, stretch, sc, out, ldo, todo, marked);
-            else
-                hipLaunchKernelGGL(image_iwarp_window_kernel<false>, grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T,
-                                   times, stretch, sc, out, ldo, todo, marked);
+            if (Z > 1) {
+                if (ch) DNMF_IW_WINDOW_LAUNCH(true, true); else DNMF_IW_WINDOW_LAUNCH(true, false);
+            } else {
+                if (ch) DNMF_IW_WINDOW_LAUNCH(false, true); else DNMF_IW_WINDOW_LAUNCH(false, false);
+            }
         } else if (Z > 1) {
-            if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(true, 1); else DNMF_IW_ROWS_LAUNCH(true, 0);
+            if (ch) {
+                if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(true, 1, true); else DNMF_IW_ROWS_LAUNCH(true, 0, true);
+            } else {
+                if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(true, 1, false); else DNMF_IW_ROWS_LAUNCH(true, 0, false);
+            }
         } else {
-            if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(false, 1); else DNMF_IW_ROWS_LAUNCH(false, 0);
+            if (ch) {
+                if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(false, 1, true); else DNMF_IW_ROWS_LAUNCH(false, 0, true);
+            } else {
+                if (vol.fastdiv) DNMF_IW_ROWS_LAUNCH(false, 1, false); else DNMF_IW_ROWS_LAUNCH(false, 0, false);
+            }
         }
+#undef DNMF_IW_WINDOW_LAUNCH
 #undef DNMF_IW_ROWS_LAUNCH
     }
     if (fallback_count && marked) {
@@ -737,9 +777,27 @@ int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X,
     // every frame by its own blocks when all points are searched exhaustively, else 64 frames' worth of blocks that walk
     // over the frames and skip those without marks
     const dim3 full_grid(grid.x, exhaustive ? (unsigned)B : (unsigned)(B < 64 ? B : 64));
-    hipLaunchKernelGGL(image_iwarp_full_kernel, full_grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T, times, out,
-                       ldo, todo, marked, B);
-    return check_launch("dnmf_image_iwarp");
+    if (ch)
+        hipLaunchKernelGGL(image_iwarp_full_kernel<true>, full_grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T, times,
+                           out, ldo, todo, marked, B, nchan, ldc_in, ldc_out);
+    else
+        hipLaunchKernelGGL(image_iwarp_full_kernel<false>, full_grid, dim3(256), 0, st, frames, ldf, frame_ids, vol, beta, T, times,
+                           out, ldo, todo, marked, B, nchan, ldc_in, ldc_out);
+    return check_launch(who);
+}
+
+int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X, int Y, int Z, const float *beta, int T,
+                     const int *times, int B, float *out, long ldo, void *workspace, size_t workspace_bytes, int exhaustive,
+                     unsigned long long *fallback_count, dnmf_stream_t stream) {
+    return iwarp_run("dnmf_image_iwarp", frames, ldf, 0, 1, frame_ids, X, Y, Z, beta, T, times, B, out, ldo, 0, workspace,
+                     workspace_bytes, exhaustive, fallback_count, stream);
+}
+
+int dnmf_image_iwarp_channels(const float *frames, long ldf, long ldc_in, int nchan, const int *frame_ids, int X, int Y, int Z,
+                              const float *beta, int T, const int *times, int B, float *out, long ldo, long ldc_out, void *workspace,
+                              size_t workspace_bytes, int exhaustive, unsigned long long *fallback_count, dnmf_stream_t stream) {
+    return iwarp_run("dnmf_image_iwarp_channels", frames, ldf, ldc_in, nchan, frame_ids, X, Y, Z, beta, T, times, B, out, ldo,
+                     ldc_out, workspace, workspace_bytes, exhaustive, fallback_count, stream);
 }
 
 }  // extern "C"

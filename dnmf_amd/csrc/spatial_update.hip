@@ -256,12 +256,17 @@ __global__ __launch_bounds__(256) void sl_scan_kernel(const int *__restrict__ ti
 typedef float sl_f4 __attribute__((ext_vector_type(4)));
 
 // One wave per (tile, split of the frames): partial sums of A1 for the tile's listed neurons over frames [t0, t1).
-template <bool ALIGNED>
+// CH (colour channels that share the traces): the row of a frame holds `nchan` channels ldyc floats apart, and the sums
+// run over the channels too, channel c's value weighted by colours[c, k] (ldcol floats per channel).  The colour is folded
+// into the trace scalar of a run of frames (one multiply per neuron and run), so each channel's tile is read once per
+// frame and the accumulators are the same eight.  Without CH: one channel, no colours (nchan, ldyc, colours unused).
+template <bool ALIGNED, bool CH>
 __global__ __launch_bounds__(256) void spatial_accum_lists_kernel(const float *__restrict__ Y, long ldy, const int *__restrict__ frame_ids,
                                                                   const float *__restrict__ C, long ldc, const int *__restrict__ times,
                                                                   int T, SlGeom g, const int *__restrict__ tile_n,
                                                                   const int *__restrict__ tile_off, const int *__restrict__ tile_list,
-                                                                  float *__restrict__ out, long out_split_stride, int frames_per_split) {
+                                                                  float *__restrict__ out, long out_split_stride, int frames_per_split,
+                                                                  int nchan, long ldyc, const float *__restrict__ colours, long ldcol) {
     const int lane = threadIdx.x & 63;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= g.ntiles) return;
@@ -296,34 +301,39 @@ __global__ __launch_bounds__(256) void spatial_accum_lists_kernel(const float *_
             const int bl = min(bb + lane, t1 - 1);
             const long tcol = times ? times[bl] : bl;
             const int myrow = frame_ids ? frame_ids[bl] : bl;
-            float cv[SL_NG];
+            float ct[SL_NG];
 #pragma unroll
-            for (int i = 0; i < SL_NG; ++i) cv[i] = ks[i] >= 0 ? C[(long)ks[i] * ldc + tcol] : 0.0f;
+            for (int i = 0; i < SL_NG; ++i) ct[i] = ks[i] >= 0 ? C[(long)ks[i] * ldc + tcol] : 0.0f;
             const int nb = min(64, t1 - bb);
-            for (int j0 = 0; j0 < nb; j0 += 4) {
-                sl_f4 y[4];
+            for (int ch = 0; ch < (CH ? nchan : 1); ++ch) {
+                float cv[SL_NG];
 #pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {     // four frames requested together
-                    const int j = min(j0 + jj, nb - 1);
-                    const float *src = Y + (long)__builtin_amdgcn_readlane(myrow, j) * ldy;
-                    if (ALIGNED) {
-                        y[jj] = *reinterpret_cast<const sl_f4 *>(src + p);
-                    } else {
-                        src += prow;
-                        y[jj] = sl_f4{src[pu[0]], src[pu[1]], src[pu[2]], src[pu[3]]};
+                for (int i = 0; i < SL_NG; ++i) cv[i] = CH ? (ks[i] >= 0 ? colours[ch * ldcol + ks[i]] * ct[i] : 0.0f) : ct[i];
+                for (int j0 = 0; j0 < nb; j0 += 4) {
+                    sl_f4 y[4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {     // four frames requested together
+                        const int j = min(j0 + jj, nb - 1);
+                        const float *src = Y + (long)__builtin_amdgcn_readlane(myrow, j) * ldy + (CH ? ch * ldyc : 0);
+                        if (ALIGNED) {
+                            y[jj] = *reinterpret_cast<const sl_f4 *>(src + p);
+                        } else {
+                            src += prow;
+                            y[jj] = sl_f4{src[pu[0]], src[pu[1]], src[pu[2]], src[pu[3]]};
+                        }
+                    }
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        if (j0 + jj >= nb) break;       // wave-uniform
+#pragma unroll
+                        for (int i = 0; i < SL_NG; ++i) {
+                            const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cv[i]), j0 + jj));
+#pragma unroll
+                            for (int v = 0; v < 4; ++v) acc[i][v] = fmaf(y[jj][v], c, acc[i][v]);
+                        }
                     }
                 }
-#pragma unroll
-                for (int jj = 0; jj < 4; ++jj) {
-                    if (j0 + jj >= nb) break;       // wave-uniform
-#pragma unroll
-                    for (int i = 0; i < SL_NG; ++i) {
-                        const float c = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cv[i]), j0 + jj));
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) acc[i][v] = fmaf(y[jj][v], c, acc[i][v]);
-                    }
-                }
-            }
+            }   // channels
         }
 #pragma unroll
         for (int i = 0; i < SL_NG; ++i)
@@ -480,35 +490,59 @@ size_t dnmf_spatial_accum_lists_workspace(int X, int Y, int Z, long total, int T
     return s > 1 ? (size_t)s * total * sizeof(float) : 0;
 }
 
-int dnmf_spatial_accum_lists(const float *Y, long ldy, const int *frame_ids, const float *C, long ldc, const int *times, int T, int X,
-                             int Yd, int Z, int K, const int *tables, long total, float *A1c, float *Cs, void *workspace,
-                             size_t workspace_bytes, dnmf_stream_t stream) {
+// dnmf_spatial_accum_lists is the one-channel, colourless call (CH off: the single-channel kernel) of the same launches
+static int sl_accum_run(const char *who, const float *Y, long ldy, long ldyc, int nchan, const float *colours, const int *frame_ids,
+                        const float *C, long ldc, const int *times, int T, int X, int Yd, int Z, int K, const int *tables, long total,
+                        float *A1c, float *Cs, void *workspace, size_t workspace_bytes, dnmf_stream_t stream) {
     using namespace dnmf;
-    DNMF_REQUIRE(Y && C && tables && A1c && Cs, DNMF_E_NULL, "dnmf_spatial_accum_lists: NULL buffer");
+    DNMF_REQUIRE(Y && C && tables && A1c && Cs, DNMF_E_NULL, "%s: NULL buffer", who);
     DNMF_REQUIRE(T > 0 && X > 0 && Yd > 0 && Z > 0 && K > 0 && total > 0 && ldy >= (long)X * Yd * Z && ldc > 0, DNMF_E_SHAPE,
-                 "dnmf_spatial_accum_lists: T=%d X=%d Y=%d Z=%d K=%d total=%ld ldy=%ld", T, X, Yd, Z, K, total, ldy);
+                 "%s: T=%d X=%d Y=%d Z=%d K=%d total=%ld ldy=%ld", who, T, X, Yd, Z, K, total, ldy);
+    const long P = (long)X * Yd * Z;
+    DNMF_REQUIRE(nchan >= 1 && (nchan == 1 || ldyc >= P) && ldy >= (nchan - 1) * ldyc + P, DNMF_E_SHAPE,
+                 "%s: nchan=%d ldyc=%ld ldy=%ld (P=%ld)", who, nchan, ldyc, ldy, P);
+    DNMF_REQUIRE(colours || nchan == 1, DNMF_E_NULL, "%s: NULL colours for %d channels", who, nchan);
     const SlGeom g = sl_geom(X, Yd, Z);
-    DNMF_REQUIRE(g.YZ >= 4, DNMF_E_UNSUPPORTED, "dnmf_spatial_accum_lists: Y*Z = %d < 4", g.YZ);
+    DNMF_REQUIRE(g.YZ >= 4, DNMF_E_UNSUPPORTED, "%s: Y*Z = %d < 4", who, g.YZ);
     const int ns = sl_splits(g.ntiles, T);
     DNMF_REQUIRE(ns == 1 || (workspace && workspace_bytes >= (size_t)ns * total * sizeof(float)), DNMF_E_WORKSPACE,
-                 "dnmf_spatial_accum_lists: workspace %zu < %zu bytes", workspace_bytes, (size_t)ns * total * sizeof(float));
+                 "%s: workspace %zu < %zu bytes", who, workspace_bytes, (size_t)ns * total * sizeof(float));
     const int *tile_n = tables, *tile_off = tables + g.ntiles, *tile_list = tables + 2 * g.ntiles + 2;
     hipStream_t st = (hipStream_t)stream;
     const int fps = (T + ns - 1) / ns;
     float *out = ns > 1 ? static_cast<float *>(workspace) : A1c;
     const dim3 grid((unsigned)((g.ntiles + 3) / 4), (unsigned)ns);
-    const bool aligned = (g.YZ & 3) == 0 && (ldy & 3) == 0 && ((size_t)Y & 15) == 0;
+    const bool ch = colours != nullptr;
+    const bool aligned = (g.YZ & 3) == 0 && (ldy & 3) == 0 && ((size_t)Y & 15) == 0 && (!ch || (ldyc & 3) == 0);
     // entries of tiles the kernel leaves (none listed) do not exist; every existing entry is written by every split
-    if (aligned)
-        hipLaunchKernelGGL((spatial_accum_lists_kernel<true>), grid, dim3(256), 0, st, Y, ldy, frame_ids, C, ldc, times, T, g, tile_n,
-                           tile_off, tile_list, out, total, fps);
-    else
-        hipLaunchKernelGGL((spatial_accum_lists_kernel<false>), grid, dim3(256), 0, st, Y, ldy, frame_ids, C, ldc, times, T, g, tile_n,
-                           tile_off, tile_list, out, total, fps);
+#define DNMF_SL_LAUNCH(AL, CH)                                                                                                  \
+    hipLaunchKernelGGL((spatial_accum_lists_kernel<AL, CH>), grid, dim3(256), 0, st, Y, ldy, frame_ids, C, ldc, times, T, g, tile_n, \
+                       tile_off, tile_list, out, total, fps, nchan, ldyc, colours, (long)K)
+    if (ch) {
+        if (aligned) DNMF_SL_LAUNCH(true, true); else DNMF_SL_LAUNCH(false, true);
+    } else {
+        if (aligned) DNMF_SL_LAUNCH(true, false); else DNMF_SL_LAUNCH(false, false);
+    }
+#undef DNMF_SL_LAUNCH
     if (ns > 1) hipLaunchKernelGGL(sl_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, out, total, ns, total, A1c);
     hipLaunchKernelGGL(trace_gram_kernel, dim3((unsigned)K, (unsigned)((K + TG_L - 1) / TG_L)), dim3(256), 0, st, C, ldc, times, T, K,
                        Cs, 0);
-    return check_launch("dnmf_spatial_accum_lists");
+    return check_launch(who);
+}
+
+int dnmf_spatial_accum_lists(const float *Y, long ldy, const int *frame_ids, const float *C, long ldc, const int *times, int T, int X,
+                             int Yd, int Z, int K, const int *tables, long total, float *A1c, float *Cs, void *workspace,
+                             size_t workspace_bytes, dnmf_stream_t stream) {
+    return sl_accum_run("dnmf_spatial_accum_lists", Y, ldy, 0, 1, nullptr, frame_ids, C, ldc, times, T, X, Yd, Z, K, tables, total,
+                        A1c, Cs, workspace, workspace_bytes, stream);
+}
+
+int dnmf_spatial_accum_lists_channels(const float *Y, long ldy, long ldyc, int nchan, const float *colours, const int *frame_ids,
+                                      const float *C, long ldc, const int *times, int T, int X, int Yd, int Z, int K, const int *tables,
+                                      long total, float *A1c, float *Cs, void *workspace, size_t workspace_bytes,
+                                      dnmf_stream_t stream) {
+    return sl_accum_run("dnmf_spatial_accum_lists_channels", Y, ldy, ldyc, nchan, colours, frame_ids, C, ldc, times, T, X, Yd, Z, K,
+                        tables, total, A1c, Cs, workspace, workspace_bytes, stream);
 }
 
 int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs, const float *D, double gamma, int X, int Y, int Z,

@@ -381,6 +381,41 @@ def spatial_accum_lists(Y, C, sl, sz, K, frame_ids=None, times=None, A1c=None, C
     return A1c, Cs, workspace
 
 
+def spatial_accum_lists_channels(Y, C, colours, sl, sz, K, frame_ids=None, times=None, A1c=None, Cs=None, workspace=None):
+    """K5, list form over colour channels: Y (>=T, ldy) rows of NC channels of P floats, colours (NC,K) ->
+    A1c (total) = sum_c colours[c,k] (Y^c C^T) at the listed entries, Cs (K,K) = C C^T."""
+    X, Yd, Z = (int(s) for s in sz)
+    P = X * Yd * Z
+    _f32(colours, "colours")
+    NC = colours.shape[0]
+    if colours.dim() != 2 or colours.shape[1] != K:
+        raise ValueError(f"spatial_accum_lists_channels: colours must be (NC, K={K}), got {tuple(colours.shape)}")
+    if Y.dtype != torch.float32 or Y.stride(-1) != 1 or not Y.is_cuda or Y.shape[-1] < NC * P:
+        raise ValueError(f"spatial_accum_lists_channels: Y must be float32 CUDA with unit inner stride and rows of {NC} x {P}")
+    if C.dtype != torch.float32 or C.stride(-1) != 1 or not C.is_cuda:
+        raise ValueError("spatial_accum_lists_channels: C must be float32 CUDA with unit inner stride")
+    dev = Y.device
+    fid = _i32(frame_ids, dev) if frame_ids is not None else None
+    tt = _i32(times, dev) if times is not None else None
+    T = fid.numel() if fid is not None else (tt.numel() if tt is not None else Y.shape[0])
+    total = sl["total"]
+    if A1c is None:
+        A1c = torch.empty((total,), dtype=torch.float32, device=dev)
+        Cs = torch.empty((K, K), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    need = lib.dnmf_spatial_accum_lists_workspace(X, Yd, Z, total, T)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    with _timed("spatial_accum_lists"):
+        rc = lib.dnmf_spatial_accum_lists_channels(Y.data_ptr(), Y.stride(0), P, NC, colours.data_ptr(), _ptr(fid), C.data_ptr(),
+                                                   C.stride(0), _ptr(tt), T, X, Yd, Z, K, sl["tables"].data_ptr(), total,
+                                                   A1c.data_ptr(), Cs.data_ptr(), _ptr(workspace),
+                                                   0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                                   _stream())
+    _lib.check(rc, "dnmf_spatial_accum_lists_channels")
+    return A1c, Cs, workspace
+
+
 def mu_spatial_lists(A, layout, sl, A1c, Cs, sz, D=None, gamma=0.0):
     """K6, list form: A (P,K) updated in place at the entries the tiles list; A1c is overwritten with the new values."""
     X, Y, Z = (int(s) for s in sz)
@@ -522,23 +557,30 @@ class Communicator:
             self._handle = None
 
 
-def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, count=None):
+def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, count=None, nchan=1):
     """K7.  Registered frames (B,P): nearest-neighbour inverse warp under beta[:, :, times].  ``exhaustive``: search
     all P candidates for every lattice point (the checker of the window search); ``count``: int64[1] CUDA tensor
-    incremented by the lattice points that needed the exhaustive search."""
+    incremented by the lattice points that needed the exhaustive search.  ``nchan`` > 1: a frame row holds that many
+    channels of P floats that share the warp (MultiChannelDNMF), one search per lattice point serves all of them
+    (``dnmf_image_iwarp_channels``) and the result is (B, nchan*P)."""
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
+    nchan = int(nchan)
+    if nchan < 1:
+        raise ValueError(f"image_iwarp: nchan={nchan}")
     _f32(beta, "beta")
     if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
         raise ValueError("image_iwarp: frames must be float32 CUDA with unit inner stride")
+    if nchan > 1 and frames.shape[-1] < nchan * P:
+        raise ValueError(f"image_iwarp: rows of {frames.shape[-1]} floats cannot hold {nchan} channels of {P}")
     dev = frames.device
     tt = _i32(times, dev)
     fid = _i32(frame_ids, dev) if frame_ids is not None else None
     B = tt.numel()
     if out is None:
-        out = torch.empty((B, P), dtype=torch.float32, device=dev)
-    if out.shape[0] < B or out.stride(0) < P or out.stride(1) != 1:
-        raise ValueError("image_iwarp: out must be (>=B, ld) with ld >= P")
+        out = torch.empty((B, nchan * P), dtype=torch.float32, device=dev)
+    if out.shape[0] < B or out.stride(0) < nchan * P or out.stride(1) != 1:
+        raise ValueError(f"image_iwarp: out must be (>=B, ld) with ld >= {nchan} x P")
     lib = _lib.load()
     # frames per launch (gridDim.y); one flag byte per lattice point of the launch: at most 256 MiB of flags (a 512x512x20
     # volume would otherwise ask for 86 GB per 16384-frame launch)
@@ -548,10 +590,16 @@ def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, 
         n = min(step, B - s)
         src = frames if fid is not None else frames[s:]   # without ids, frame b of a launch is its row b
         with _timed("image_iwarp"):
-            rc = (lib.dnmf_image_iwarp(src.data_ptr(), frames.stride(0), 0 if fid is None else fid[s:].data_ptr(), X, Y, Z,
-                                        beta.data_ptr(), beta.shape[2], tt[s:].data_ptr(), n, out[s:].data_ptr(),
-                                        out.stride(0), ws.data_ptr(), ws.numel(), int(bool(exhaustive)), _ptr(count),
-                                        _stream()))
+            if nchan == 1:
+                rc = (lib.dnmf_image_iwarp(src.data_ptr(), frames.stride(0), 0 if fid is None else fid[s:].data_ptr(), X, Y, Z,
+                                            beta.data_ptr(), beta.shape[2], tt[s:].data_ptr(), n, out[s:].data_ptr(),
+                                            out.stride(0), ws.data_ptr(), ws.numel(), int(bool(exhaustive)), _ptr(count),
+                                            _stream()))
+            else:
+                rc = (lib.dnmf_image_iwarp_channels(src.data_ptr(), frames.stride(0), P, nchan,
+                                                     0 if fid is None else fid[s:].data_ptr(), X, Y, Z, beta.data_ptr(),
+                                                     beta.shape[2], tt[s:].data_ptr(), n, out[s:].data_ptr(), out.stride(0), P,
+                                                     ws.data_ptr(), ws.numel(), int(bool(exhaustive)), _ptr(count), _stream()))
         _lib.check(rc, "dnmf_image_iwarp")
     return out
 

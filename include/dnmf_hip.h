@@ -293,6 +293,14 @@ size_t dnmf_image_iwarp_workspace(int X, int Y, int Z, int B);
 int dnmf_image_iwarp(const float *frames, long ldf, const int *frame_ids, int X, int Y, int Z, const float *beta,
                      int T, const int *times, int B, float *out, long ldo, void *workspace, size_t workspace_bytes,
                      int exhaustive, unsigned long long *fallback_count, dnmf_stream_t stream);
+/* dnmf_image_iwarp over colour channels that share the warp: frame row b holds `nchan` channels, channel c at
+ * frames[row + c ldc_in]; the search runs once per lattice point and channel c of out row b (at c ldc_out) gathers from channel c
+ * of the frame.  Otherwise as dnmf_image_iwarp (the same workspace; the fallback count is per lattice point, not per channel):
+ * nchan >= 1; for nchan > 1 ldc_in, ldc_out >= P, ldf >= (nchan-1) ldc_in + P, ldo >= (nchan-1) ldc_out + P.  Channel by channel
+ * the result equals dnmf_image_iwarp's on that channel. */
+int dnmf_image_iwarp_channels(const float *frames, long ldf, long ldc_in, int nchan, const int *frame_ids, int X, int Y, int Z,
+                              const float *beta, int T, const int *times, int B, float *out, long ldo, long ldc_out, void *workspace,
+                              size_t workspace_bytes, int exhaustive, unsigned long long *fallback_count, dnmf_stream_t stream);
 
 /* ---- Adam on beta for one epoch of mini-batches ------------------------------------------------------
  * update_motion steps the caller's torch.optim.Adam once per mini-batch on the whole (10,3,T) tensor
@@ -339,6 +347,16 @@ size_t dnmf_spatial_accum_lists_workspace(int X, int Y, int Z, long total, int T
 int dnmf_spatial_accum_lists(const float *Y, long ldy, const int *frame_ids, const float *C, long ldc, const int *times, int T, int X,
                              int Yd, int Z, int K, const int *tables, long total, float *A1c, float *Cs, void *workspace,
                              size_t workspace_bytes, dnmf_stream_t stream);
+/* dnmf_spatial_accum_lists over colour channels that share the traces: row b of Y holds `nchan` channels ldyc floats apart and
+ *   A1c[(tile, listed k)] = sum_c colours[c,k] sum_t Y^c_t[v] C[k,t],   Cs = C C^T as above;
+ * colours (nchan, K) fp32 on the device, not NULL for nchan > 1 (NULL with nchan = 1: dnmf_spatial_accum_lists; colour 1
+ * gives the same bits);
+ * ldyc >= P and ldy >= (nchan-1) ldyc + P for nchan > 1.  Same tables, workspace and dnmf_mu_spatial_lists (with Cs multiplied
+ * entry by entry by colours^T colours) as the single-channel form. */
+int dnmf_spatial_accum_lists_channels(const float *Y, long ldy, long ldyc, int nchan, const float *colours, const int *frame_ids,
+                                      const float *C, long ldc, const int *times, int T, int X, int Yd, int Z, int K, const int *tables,
+                                      long total, float *A1c, float *Cs, void *workspace, size_t workspace_bytes,
+                                      dnmf_stream_t stream);
 int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs, const float *D, double gamma, int X, int Y, int Z,
                           int K, const int *tables, dnmf_stream_t stream);
 
