@@ -259,6 +259,31 @@ class ExponentialFP(nn.Module):
         A_t, grid = ops.warp_gather(self.A.contiguous(), self.beta.detach(), times)
         return A_tC, A_t, grid, reg
 
+    def beta_from_positions(self, P_T, ref=None, order='quadratic', ridge=0.0):
+        """The warp that tracks imply: per frame t the least-squares ``beta_t`` with ``q_t(P_T[k,:,t]) = ref[k]`` (K11,
+        ``ops.fit_quadratic_warp``).  ``P_T`` (K,3,T) positions of the neurons in every frame, voxel indices (what
+        ``MotionCorrect.apply_shifts_points`` and the simulator produce; numpy or torch; NaN = not tracked in that frame),
+        ``ref`` (K,3) the footprint centres (default ``self.pos``), ``order`` 'translation' / 'affine' / 'quadratic',
+        ``ridge`` >= 0 pulls the fit to the identity.  Returns ``(beta (10,3,T) fp32 CUDA, ok (T) bool CUDA)``; a frame
+        whose system is singular has the identity and ok False.  Nothing of the model is changed."""
+        P = P_T if isinstance(P_T, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(P_T))
+        if P.dtype not in (torch.float32, torch.float64):
+            P = P.double()
+        P = P.to(device)
+        if P.dim() != 3 or P.shape[0] != self.K or P.shape[1] != 3:
+            raise ValueError(f"beta_from_positions: positions must be ({self.K}, 3, T), got {tuple(P.shape)}")
+        return ops.fit_quadratic_warp(P, self.pos if ref is None else ref, self.sz_list, order=order, ridge=ridge)
+
+    def positions(self, points=None, times=None, start=None, tol=1e-6):
+        """Where the model sees ``points`` (K,3) (default ``self.pos``, the footprint centres) in the frames ``times``
+        (default all): the ``x*`` with ``q_t(x*) = points[k]`` under the current ``beta`` (K12, ``ops.invert_quadratic_warp``:
+        Newton's method in float64 from ``start`` (K,3,B), default the points themselves).  Returns (K,3,B) float64 numpy in
+        the layout of ``dataset.positions``; NaN where the warp has no solution Newton finds."""
+        pts = self.pos if points is None else points
+        if times is not None:
+            times = [int(t) for t in (times.tolist() if hasattr(times, 'tolist') else times)]
+        return ops.invert_quadratic_warp(self.beta.detach(), pts, times=times, start=start, tol=tol).cpu().numpy()
+
     @staticmethod
     def log_det_jac(B, P):
         """log|det J| of the quadratic map at ``P`` (reference :107-122, with its 8/9 row convention)."""
@@ -781,6 +806,29 @@ class DeformableNMF:
                 total["loss"] += out["loss"]
                 total["frame_loss"] += out["frame_loss"]
         return total
+
+    def init_motion(self, P_T, order='quadratic', ridge=0.0):
+        """Start the warp from tracks: ``fp.beta`` takes, in place, the ``beta`` that ``fp.beta_from_positions(P_T, order=order,
+        ridge=ridge)`` fits to the positions ``P_T`` (K,3,T) (``MotionCorrect.apply_shifts_points``, the simulator, any
+        tracker).  The leaf stays the same tensor object, so an optimiser built on ``[fp.beta]`` keeps working; ``.grad`` is
+        cleared; frames the fit could not solve (``ok`` False) keep the coefficients they had.  Returns ``ok`` (T) bool.
+
+        Call it before the first ``update_motion``: the optimiser's state (Adam's moments, its step count) is not touched,
+        and moments gathered around another ``beta`` would pull the first steps the wrong way.  Nothing else needs
+        resetting: every fit step reads ``fp.beta`` when it runs (the fused motion epoch coasts from the tensor itself, the
+        reconstruction images depend on ``A`` and ``C`` only).  With the T axis sharded over ranks every rank passes the
+        tracks of its own frames."""
+        beta, ok = self.fp.beta_from_positions(P_T, order=order, ridge=ridge)
+        if beta.shape != self.fp.beta.shape:
+            raise ValueError(f"init_motion: tracks of {beta.shape[2]} frames for a model of {self.fp.beta.shape[2]}")
+        with torch.no_grad():
+            self.fp.beta.copy_(torch.where(ok[None, None, :], beta, self.fp.beta))
+        self.fp.beta.grad = None
+        return ok
+
+    def positions(self, points=None, times=None, start=None, tol=1e-6):
+        """``fp.positions``: where the fitted warp puts the neurons in every frame, (K,3,T) float64 numpy."""
+        return self.fp.positions(points=points, times=times, start=start, tol=tol)
 
     def update_motion(self, dataloader, optimizer, gamma=0, epochs=20):
         """Reference :181-194: mini-batch steps of the caller's optimiser on ``fp.beta`` against

@@ -102,6 +102,27 @@ def generate_video(K, T, sz=[20, 20, 1], shape_std=3, density=.1, bg_snr=-1, tra
     return frames.permute(1, 2, 3, 0), positions, tr
 
 
+def get_roi_signals(video, P, window=np.array([3, 3, 0])):
+    """Reference ``WUtils/Simulator.py:230-240``: the signal of every tracked neuron as the mean of a box of voxels around
+    its position -- the baseline read-out dNMF traces are judged against.  ``video`` (X,Y,Z,T) and ``P`` (K,3,T), numpy or
+    torch, host or CUDA; ``window`` (wx, wy, wz): the box has 2 w + 1 voxels per axis around the position rounded half to
+    even; voxels of the box outside the volume count as zeros (the reference pads its patch, ``Utils.py:44-50``).  Returns
+    (K,T) float64 numpy.  K13 (``ops.roi_signals``; callers that hold resident frames call that directly, without the
+    copy made here), float64 sums where the reference sums in float32.  Deviations: a position that rounds to outside the
+    volume gives NaN (the reference slices an empty array there), and a NaN voxel is left out of its box's mean (the
+    reference's spline prefilter smears it over the whole box)."""
+    from .. import ops
+    vid = video if isinstance(video, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(video))
+    if vid.dim() != 4:
+        raise ValueError(f"get_roi_signals: video must be (X,Y,Z,T), got {tuple(vid.shape)}")
+    X, Y, Z, T = vid.shape
+    frames = vid.to('cuda', torch.float32).permute(3, 0, 1, 2).reshape(T, X * Y * Z).contiguous()
+    pos = P if isinstance(P, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(P))
+    if pos.dtype not in (torch.float32, torch.float64):
+        pos = pos.double()
+    return ops.roi_signals(frames, (X, Y, Z), pos.to('cuda'), window=[int(w) for w in np.asarray(window).tolist()]).cpu().numpy()
+
+
 def generate_video_resident(K, T, sz, shape_std=3, density=.1, bg_snr=-1, motion_par=None, device='cuda',
                             t0=0, t1=None, noise=None, group=None):
     """``generate_video(traces='exp', motion='gp')`` rendered on the GPU, frame-major and resident.

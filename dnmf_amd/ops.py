@@ -784,6 +784,118 @@ def apply_shifts_points(points, patch_shifts, centers):
     return out
 
 
+WARP_ORDERS = {"translation": 0, "affine": 1, "quadratic": 2}
+
+
+def warp_free_rows(sz, order):
+    """Rows of beta that ``fit_quadratic_warp`` fits: those of ``order`` without every row that involves an axis of extent 1."""
+    rows = {"translation": [0], "affine": [0, 1, 2, 3], "quadratic": list(range(10))}[order]
+    for d, uses in enumerate(((1, 4, 7, 8), (2, 5, 7, 9), (3, 6, 8, 9))):
+        if int(sz[d]) == 1:
+            rows = [r for r in rows if r not in uses]
+    return rows
+
+
+def _tracks(P, name):
+    """(K,3,T) float32 or float64 CUDA, contiguous."""
+    if not (isinstance(P, torch.Tensor) and P.is_cuda and P.dtype in (torch.float32, torch.float64) and P.dim() == 3
+            and P.shape[1] == 3):
+        raise ValueError(f"{name}: tracks must be a (K,3,T) float32 or float64 CUDA tensor")
+    if P.shape[0] < 1 or P.shape[2] < 1:
+        raise ValueError(f"{name}: tracks of shape {tuple(P.shape)}: need K >= 1 and T >= 1")
+    return P.contiguous()
+
+
+def fit_quadratic_warp(P, targets, sz, order="quadratic", ridge=0.0):
+    """K11.  P (K,3,T) fp32 / fp64 CUDA tracks (NaN = neuron k not tracked in frame t), targets (K,3) -> ``(beta (10,3,T)
+    fp32, ok (T) bool)``: per frame the least-squares beta_t with q_t(P[k,:,t]) = targets[k] over the free rows of ``order``
+    ('translation', 'affine', 'quadratic'), pulled to the identity by ``ridge`` (see include/dnmf_hip.h).  Frames whose
+    system is singular get the identity and ok = False.  ValueError when ridge == 0 and every frame has fewer tracked
+    neurons than free rows."""
+    if order not in WARP_ORDERS:
+        raise ValueError(f"fit_quadratic_warp: order must be one of {sorted(WARP_ORDERS)}, got {order!r}")
+    if not (float(ridge) >= 0.0 and float(ridge) != float("inf")):
+        raise ValueError(f"fit_quadratic_warp: ridge={ridge} must be >= 0 and finite")
+    P = _tracks(P, "fit_quadratic_warp")
+    K, _, T = P.shape
+    X, Y, Z = (int(s) for s in sz)
+    R = torch.as_tensor(targets).to(device=P.device, dtype=torch.float64).contiguous()
+    if tuple(R.shape) != (K, 3):
+        raise ValueError(f"fit_quadratic_warp: targets must be ({K}, 3), got {tuple(R.shape)}")
+    if ridge == 0:
+        nfree = len(warp_free_rows((X, Y, Z), order))
+        most = int(torch.isfinite(P).all(1).sum(0).max())
+        if most < nfree:
+            raise ValueError(f"fit_quadratic_warp: at most {most} tracked neurons per frame for {nfree} free rows "
+                             f"(order={order!r}) and ridge = 0")
+    beta = torch.empty((10, 3, T), dtype=torch.float32, device=P.device)
+    ok = torch.empty((T,), dtype=torch.uint8, device=P.device)
+    with _timed("fit_quadratic_warp"):
+        rc = _lib.load().dnmf_fit_quadratic_warp(P.data_ptr(), int(P.dtype == torch.float64), K, T, R.data_ptr(), X, Y, Z,
+                                                 WARP_ORDERS[order], float(ridge), beta.data_ptr(), ok.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_fit_quadratic_warp")
+    return beta, ok.bool()
+
+
+def invert_quadratic_warp(beta, targets, times=None, start=None, tol=1e-6):
+    """K12.  beta (10,3,T) fp32 CUDA, targets (K,3) -> (K,3,B) fp64 CUDA: for every neuron and every frame of ``times`` (None:
+    all T) the x* with q_t(x*) = targets[k], by Newton's method from ``start`` (K,3,B) (None: the target); NaN where it did
+    not converge within 32 steps or met a vanishing Jacobian."""
+    beta = _f32(beta, "beta")
+    if beta.dim() != 3 or tuple(beta.shape[:2]) != (10, 3):
+        raise ValueError(f"invert_quadratic_warp: beta must be (10,3,T), got {tuple(beta.shape)}")
+    T = beta.shape[2]
+    dev = beta.device
+    R = torch.as_tensor(targets).to(device=dev, dtype=torch.float64).contiguous()
+    if R.dim() != 2 or R.shape[1] != 3 or R.shape[0] < 1:
+        raise ValueError(f"invert_quadratic_warp: targets must be (K,3) with K >= 1, got {tuple(R.shape)}")
+    K = R.shape[0]
+    tt = None
+    if times is not None:
+        tt = _i32(times, dev)
+        if tt.numel() and (int(tt.min()) < 0 or int(tt.max()) >= T):
+            raise ValueError(f"invert_quadratic_warp: times outside [0, {T})")
+    B = T if tt is None else tt.numel()
+    if not float(tol) > 0.0:
+        raise ValueError(f"invert_quadratic_warp: tol={tol} must be positive")
+    st = None
+    if start is not None:
+        st = torch.as_tensor(start).to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(st.shape) != (K, 3, B):
+            raise ValueError(f"invert_quadratic_warp: start must be ({K}, 3, {B}), got {tuple(st.shape)}")
+    out = torch.empty((K, 3, B), dtype=torch.float64, device=dev)
+    with _timed("invert_quadratic_warp"):
+        rc = _lib.load().dnmf_invert_quadratic_warp(beta.data_ptr(), T, _ptr(tt), B, R.data_ptr(), K, _ptr(st), float(tol),
+                                                    out.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_invert_quadratic_warp")
+    return out
+
+
+def roi_signals(frames, sz, P, window=(3, 3, 0)):
+    """K13.  frames (T, ld >= X Y Z) fp32 CUDA rows (row t = frame t; ``ResidentLoader.frames_2d()`` /
+    ``device_frames()``), P (K,3,T) fp32 / fp64 CUDA tracks -> (K,T) fp64 CUDA: the reference's ``get_roi_signals`` -- the
+    mean of the box of 2 window + 1 voxels per axis around the rounded position, zeros outside the volume, NaN voxels left
+    out, NaN for a position outside the volume."""
+    import ctypes
+    X, Y, Z = (int(s) for s in sz)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2
+            and frames.stride(1) == 1 and frames.stride(0) >= X * Y * Z and frames.shape[1] >= X * Y * Z):
+        raise ValueError("roi_signals: frames must be float32 CUDA (T, ld) rows with unit inner stride and ld >= X Y Z")
+    P = _tracks(P, "roi_signals")
+    K, _, T = P.shape
+    if frames.shape[0] < T:
+        raise ValueError(f"roi_signals: {frames.shape[0]} frames for tracks of {T} frames")
+    w = [int(v) for v in window]
+    if len(w) != 3 or min(w) < 0:
+        raise ValueError(f"roi_signals: window must be three integers >= 0, got {window}")
+    out = torch.empty((K, T), dtype=torch.float64, device=frames.device)
+    with _timed("roi_signals"):
+        rc = _lib.load().dnmf_roi_signals(frames.data_ptr(), frames.stride(0), X, Y, Z, P.data_ptr(), int(P.dtype == torch.float64),
+                                          K, T, (ctypes.c_int * 3)(*w), out.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_roi_signals")
+    return out
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The position initialiser end to end: simulate a moving video, register it piecewise-rigidly (``MotionCorrect``, the
 class of the reference's ``Demix/MotionCorrect.py``, on the GPU), move the first frame's neuron centres by the shifts of
-their patches (``apply_shifts_points``) and compare with the simulator's own per-frame centres.  Needs an MI355X.
+their patches (``apply_shifts_points``) and compare with the simulator's own per-frame centres; then start the warp of a
+``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
+MI355X.
 
     python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12]
 """
@@ -23,6 +25,10 @@ def main():
     ap.add_argument("--neurons", type=int, default=30)
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--stride", type=int, default=12, help="patch stride in x and y (patches of 1.5 strides; default 12: the simulator's motion varies over ~10 voxels)")
+    ap.add_argument("--ridge", type=float, default=1e-3, help="pull of init_motion's fit to the identity")
+    ap.add_argument("--lr", type=float, default=1e-6, help="Adam step of the motion update")
+    ap.add_argument("--epochs", type=int, default=2)
+    ap.add_argument("--batch", type=int, default=10)
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -41,8 +47,30 @@ def main():
     print(f"video {tuple(video.shape)}, {len(mc.x_shifts_els[0])} patches; rigid shifts up to "
           f"{np.abs(np.array(mc.shifts_rig)).max():.1f} voxels")
     print(f"mean |x, y error| of the per-frame centres: {err:.2f} voxels with the initialiser, {still:.2f} without")
-    dn = DeformableNMF(sz, K, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
-    print("DeformableNMF accepts the positions:", tuple(dn.fp.A.shape))
+    # the tracks enter the model (init_motion), and come out of it again (positions): one fit from the identity warp and
+    # one from the warp the tracks imply, each judged by where it puts the neurons and by its traces
+    from dnmf_amd.WUtils.Simulator import get_roi_signals
+
+    def median_corr(S):
+        return float(np.median([np.corrcoef(S[k], dataset.traces[k])[0, 1] for k in range(K)]))
+
+    for start in ("identity", "tracks"):
+        torch.manual_seed(1)
+        dn = DeformableNMF(sz, K, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
+        dn.verbose = False
+        if start == "tracks":
+            ok = dn.init_motion(P_T, ridge=a.ridge)
+            print(f"init_motion: {int(ok.sum())} of {T} frames fitted")
+        loader = dataset.loader(a.batch)
+        dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
+        where = dn.positions()
+        dist = float(np.nanmean(np.linalg.norm(where[:, :2, :] - truth[:, :2, :], axis=1)))
+        # the simulator places centres up to half a voxel beyond the last slice: read the box of the nearest voxel inside
+        inside = np.clip(np.nan_to_num(where, nan=-1.0), 0, (sz.numpy() - 1)[None, :, None])
+        roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))
+        print(f"{start} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
+              f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "
+              f"dnmf.positions() {median_corr(np.nan_to_num(roi)):.3f}")
     return err, still
 
 

@@ -443,6 +443,39 @@ int dnmf_nearest_points(const void *points, int points_f64, long ldp, int N, con
                         const float *values, long ldv, int *index_out, long ldi, float *value_out, long ldo, void *workspace,
                         size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K11 / K12 / K13: tracks <-> warp, and the ROI trace read-out ------------------------------------------------------
+ * q_t(x) = basis(x) . beta[:, :, t], basis = [1, x, y, z, x^2, y^2, z^2, xy, xz, yz] (Demix/dNMF.py:46-58), maps a voxel of
+ * frame t to the point of the footprint volume sampled there; a neuron whose footprint is centred at r is seen in frame t at
+ * the x* with q_t(x*) = r.  Coordinates are voxel indices.  Tracks are (K,3,T) contiguous, fp32 or fp64 (tracks_f64 != 0).
+ *
+ * K11 dnmf_fit_quadratic_warp: per frame t the beta_t that sends the tracked positions to `targets` (K,3) fp64 in the least-
+ * squares sense.  A position with a non-finite coordinate is "not tracked in this frame" and skipped.  With u = 2 p / (S - 1)
+ * - 1 per axis (u = 0 on an axis of extent 1), phi = basis(u) restricted to the free rows -- order 0 (translation): {0},
+ * 1 (affine): {0..3}, 2 (quadratic): {0..9}, minus every row that involves an axis of extent 1 -- it minimises
+ *     sum_k |phi(P[k,:,t]) B' - R[k]|^2 + ridge |B' - B'_id|_F^2
+ * over the free rows of B' (B'_id: the identity map in the same coordinates; the other rows, and the output column of an
+ * axis of extent 1, stay at the identity), in float64: normal equations, Gaussian elimination with partial pivoting.  beta is
+ * B' converted back to voxel inputs in float64 and rounded once to fp32: beta (10,3,T), all T columns are written.  ok (T)
+ * bytes: 0 where the system is singular to working precision (a pivot <= 1e-12 of the largest diagonal entry, or fewer
+ * tracked neurons than free rows with ridge == 0); such a frame gets the exact identity.  No NaN is ever written to beta.
+ *
+ * K12 dnmf_invert_quadratic_warp: for every neuron k < K and frame j < B (column times[j] of beta, or j when times is NULL)
+ * the x* with q_t(x*) = targets[k] by Newton's method in float64 on the analytic Jacobian, from start (K,3,B) fp64 (NULL:
+ * the target itself, the solution at the identity), until a step is below tol in every coordinate; 32 steps at most.  out
+ * (K,3,B) fp64; NaN where it did not converge, met |det J| < 1e-12 or left the finite numbers.
+ *
+ * K13 dnmf_roi_signals: WUtils/Simulator.py:230-240 get_roi_signals on frames that live on the device: >= T rows of ldf >=
+ * X Y Z floats, row t = frame t.  out (K,T) fp64 = the mean of the box of 2 window[d] + 1 voxels per axis (window: 3 host
+ * ints >= 0) around the position rounded half to even; voxels of the box outside the volume count as zeros (Utils.py:44-50),
+ * NaN voxels are left out; NaN when the rounded position is outside the volume, not finite, or every voxel is NaN.  A box of
+ * more than 4096 voxels: DNMF_E_UNSUPPORTED. */
+int dnmf_fit_quadratic_warp(const void *tracks, int tracks_f64, int K, int T, const double *targets, int X, int Y, int Z, int order,
+                            double ridge, float *beta, unsigned char *ok, dnmf_stream_t stream);
+int dnmf_invert_quadratic_warp(const float *beta, int T, const int *times, int B, const double *targets, int K, const double *start,
+                               double tol, double *out, dnmf_stream_t stream);
+int dnmf_roi_signals(const float *frames, long ldf, int X, int Y, int Z, const void *tracks, int tracks_f64, int K, int T,
+                     const int *window, double *out, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
