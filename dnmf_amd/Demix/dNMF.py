@@ -34,6 +34,7 @@ device = 'cuda'
 DENSE_RETURN_LIMIT = 1 << 31
 # update_motion keeps the reconstruction images of all T frames resident below this many bytes
 LISTS_BOXFRAC_LIMIT = 6.0   # 'auto' takes K3n below this mean number of footprint boxes per voxel
+LISTS_MAX_K = 256           # neurons the neuron-list kernels (K3n, list reconstruction, list K5 / K6) hold
 RECON_CACHE_LIMIT = 64 << 30
 K2_MAX_FRAMES = 32768       # frames per K2 launch (they ride on gridDim.y)
 STAGE_LIMIT = 96 << 30      # a host loader's frames are staged on the GPU once per pass below this many bytes
@@ -41,6 +42,46 @@ STAGE_LIMIT = 96 << 30      # a host loader's frames are staged on the GPU once 
 
 def _sz_list(sz):
     return [int(s) for s in (sz.tolist() if isinstance(sz, torch.Tensor) else sz)]
+
+
+def lists_verdict(mode, K, boxfrac=None, nslot=None, has_nbr=None):
+    """The one rule for "the neuron-list kernel forms apply", on plain values: None when they do, else the first reason they
+    do not -- 'mode' (the kernel choice is neither 'auto' nor 'lists'), 'K', 'slots' (the pattern of G has too many), 'boxes'
+    (a voxel lies in too many footprint boxes on average; 'lists' forces past this one), 'nbr' (no column lists for K4).
+    ``boxfrac`` / ``nslot`` / ``has_nbr`` describe a layout (``ops.pack_footprints_lists``); one that is None is not tested:
+    a caller passes what its kernels need, and nothing before the layout exists (it is built only for a K that passes)."""
+    if mode not in ('auto', 'lists'):
+        return 'mode'
+    if K > LISTS_MAX_K:
+        return 'K'
+    if nslot is not None and nslot > ops.LISTS_MAX_SLOTS:
+        return 'slots'
+    # the list kernels pay per (voxel, listed neuron) and per listed pair: they win while a voxel lies in few boxes
+    if mode == 'auto' and boxfrac is not None and not boxfrac < LISTS_BOXFRAC_LIMIT:
+        return 'boxes'
+    if has_nbr is not None and not has_nbr:
+        return 'nbr'
+    return None
+
+
+def _pairs(n):
+    """(i, j), i < j < n, in the order every by-pairs-of-groups path walks them."""
+    return [(i, j) for i in range(n) for j in range(i + 1, n)]
+
+
+def _dense_unions(K, group=56):   # K3 holds 127 neurons per launch
+    groups = [list(range(s0, min(K, s0 + group))) for s0 in range(0, K, group)]
+    return [groups[i] + groups[j] for i, j in _pairs(len(groups))]
+
+
+def _gram_by_pairs(G, r, unions, launch):
+    """``launch(u) -> (cols, G_u, r_u)`` on the union ``u`` of every PAIR of neuron groups, scattered into G (B,K,K) and
+    r (B,K) at the neurons ``cols``.  A diagonal block is recomputed by every pair its group belongs to and the last one
+    stays: the order of ``unions`` decides the bits."""
+    for u in unions:
+        cols, Gp, rp = launch(u)
+        G[:, cols[:, None], cols[None, :]] = Gp
+        r[:, cols] = rp
 
 
 class _WarpRecon(torch.autograd.Function):
@@ -110,21 +151,22 @@ class ExponentialFP(nn.Module):
             A[..., k] = torch.exp((-(flow_id - self.pos[k][None, None, None, :].float()) ** 2
                                    / self.sigma[k] ** 2).sum(3))
         self.A = A
-        self._packed = None
-        self._packed_version = None
-        self._sparse = None
-        self._sparse_version = None
-        self._sparse_pairs = None
-        self._sparse_pairs_version = None
-        self._lists = None
-        self._lists_version = None
-        self._lists_exact = None   # (key, layout) of every non-zero value while footprint_floor > 0 (the footprint update's)
+        self.invalidate_layouts()
         self.use_lists = True   # reconstruction image from neuron lists when the footprints are compact
 
     def invalidate_layouts(self):
         """Forget every packed copy of ``A``.  The packed copies are keyed on ``(A.data_ptr(), A._version)``, which a
-        kernel that writes ``A`` through its raw pointer (K6) does not change: such callers say so here."""
-        self._packed = self._sparse = self._sparse_pairs = self._lists = self._lists_exact = None
+        kernel that writes ``A`` through its raw pointer (K6) does not change: such callers say so here.  A NEW dict, so
+        that a shallow copy of the model (MultiChannelDNMF's channels) that calls this has a cache of its own."""
+        self._layouts = {}   # name -> (key, packed copy)
+
+    def _layout(self, name, extra, make):
+        """The packed copy ``name`` of ``A``: the object of the last call while ``A`` and ``extra`` are the same, else ``make()``."""
+        key = (self.A.data_ptr(), self.A._version) + extra
+        hit = self._layouts.get(name)
+        if hit is None or hit[0] != key:
+            hit = self._layouts[name] = (key, make())
+        return hit[1]
 
     @staticmethod
     def quadratic_basis(P):
@@ -134,11 +176,7 @@ class ExponentialFP(nn.Module):
 
     def packed_footprints(self):
         """(P,Kp) zero-padded copy of ``A`` for the MFMA kernels; rebuilt when ``A`` is replaced or edited."""
-        key = (self.A.data_ptr(), self.A._version)
-        if self._packed is None or self._packed_version != key:
-            self._packed = ops.pack_footprints(self.A.contiguous())
-            self._packed_version = key
-        return self._packed
+        return self._layout("packed", (), lambda: ops.pack_footprints(self.A.contiguous()))
 
     def packed_columns(self, cols):
         """Packed copy of the footprints of the neurons ``cols`` only (K > 127 is handled by column groups: the MFMA
@@ -150,16 +188,15 @@ class ExponentialFP(nn.Module):
         """S[b] = A . C[:, times[b]] as (B, >= ops.halo_voxels(sz)) rows in the halo layout K2 gathers from: from the
         neuron lists when the footprints are compact (``use_lists``), else ``dnmf_recon_image`` (fp32 MFMA), by groups
         of 112 neurons when K > 127."""
-        if self.use_lists and self.K <= 256:
-            ly = self.packed_lists()
-            if ly["boxfrac"] < LISTS_BOXFRAC_LIMIT:
-                # zero_state: a one-entry list the owner of a persistent ``out`` keeps -- the layout whose empty tiles are
-                # known to hold zeros in these rows (written by a call without skipping); None after any other writer
-                skip = zero_state is not None and zero_state[0] is ly
-                res = ops.recon_image_lists(ly, self.K, self.sz_list, C, times, out=out, skip_empty=skip)
-                if zero_state is not None:
-                    zero_state[0] = ly
-                return res
+        ly = self.lists_layout() if self.use_lists else None
+        if ly is not None:
+            # zero_state: a one-entry list the owner of a persistent ``out`` keeps -- the layout whose empty tiles are
+            # known to hold zeros in these rows (written by a call without skipping); None after any other writer
+            skip = zero_state is not None and zero_state[0] is ly
+            res = ops.recon_image_lists(ly, self.K, self.sz_list, C, times, out=out, skip_empty=skip)
+            if zero_state is not None:
+                zero_state[0] = ly
+            return res
         if zero_state is not None:
             zero_state[0] = None
         if self.K <= 127:
@@ -199,11 +236,7 @@ class ExponentialFP(nn.Module):
         fraction of 16-neuron blocks that are non-zero per row (``occupancy``).  None if K > 128."""
         if self.K > 128:
             return None
-        key = (self.A.data_ptr(), self.A._version)
-        if self._sparse is None or self._sparse_version != key:
-            self._sparse = self._sparse_layout(self.A.contiguous(), self._zorder())
-            self._sparse_version = key
-        return self._sparse
+        return self._layout("sparse", (), lambda: self._sparse_layout(self.A.contiguous(), self._zorder()))
 
     # Footprint values below ``footprint_floor`` are left out of the neuron lists (K3n, the list reconstruction): 0.0 -- the
     # default -- keeps every non-zero value.  The footprint update (K5 / K6, spatial_step) is not affected: it takes its tile
@@ -218,39 +251,48 @@ class ExponentialFP(nn.Module):
         """Layout of the neuron-list Gram kernel K3n (``ops.pack_footprints_lists``) of the values >= ``floor`` (None:
         ``footprint_floor``), rebuilt when ``A`` changes.  With ``footprint_floor == 0`` every floor of 0 is one layout."""
         floor = float(self.footprint_floor if floor is None else floor)
-        key = (self.A.data_ptr(), self.A._version, floor)
-        own = floor == float(self.footprint_floor)
-        cached = (self._lists_version, self._lists) if own else (self._lists_exact or (None, None))
-        if cached[1] is not None and cached[0] == key:
-            return cached[1]
-        A = self.A.contiguous()
-        if floor > 0:
-            A = torch.where(A < floor, torch.zeros((), dtype=A.dtype, device=A.device), A)
-        ly = ops.pack_footprints_lists(A, self.sz_list)
-        if own:
-            self._lists, self._lists_version = ly, key
-        else:
-            self._lists_exact = (key, ly)
-        return ly
+
+        def make():
+            A = self.A.contiguous()
+            if floor > 0:
+                A = torch.where(A < floor, torch.zeros((), dtype=A.dtype, device=A.device), A)
+            return ops.pack_footprints_lists(A, self.sz_list)
+
+        # two slots: the model's own floor and one other (every non-zero value while footprint_floor > 0, the footprint update's)
+        return self._layout("lists" if floor == float(self.footprint_floor) else "lists_exact", (floor,), make)
+
+    def _lists_verdict(self, mode='auto', floor=None, slots=False, nbr=False):
+        """``(packed_lists(floor), lists_verdict on it)``; ``slots`` / ``nbr``: the caller also needs the slot tables of G /
+        the column lists of K4.  No layout is built when ``mode`` or K rule the lists out."""
+        why = lists_verdict(mode, self.K)
+        if why is not None:
+            return None, why
+        ly = self.packed_lists(floor)
+        return ly, lists_verdict(mode, self.K, ly["boxfrac"], ly["nslot"] if slots else None,
+                                 (ly["nbr"] is not None) if nbr else None)
+
+    def lists_layout(self, forced=False, floor=None):
+        """``packed_lists(floor)`` when the list kernel forms apply (``lists_verdict``; ``forced``: whatever the boxes), else None."""
+        ly, why = self._lists_verdict('lists' if forced else 'auto', floor)
+        return ly if why is None else None
 
     def packed_sparse_pairs(self, group=64):
         """K > 128: the neurons, in Z-order, are cut into groups of ``group`` and every pair of groups gets its own
         K3s layout (a mask byte holds 8 blocks of 16).  Returns ``[(cols (n,) long, layout), ...]``; ``cols`` are
         the original neuron indices of the pair, in the column order of ``layout["Aps"]`` before its own sort."""
-        key = (self.A.data_ptr(), self.A._version, group)
-        if self._sparse_pairs is None or self._sparse_pairs_version != key:
+        def make():
             z = self._zorder().long()
             groups = [z[s0:s0 + group] for s0 in range(0, self.K, group)]
             A2 = self.A.reshape(self.P, self.K)
             pairs = []
-            for i in range(len(groups)):
-                for j in range(i + 1, len(groups)):
-                    cols = torch.cat([groups[i], groups[j]])
-                    sub = A2[:, cols].contiguous()
-                    ident = torch.arange(cols.numel(), dtype=torch.int32, device=device)  # already Z-ordered
-                    pairs.append((cols, self._sparse_layout(sub, ident)))
-            self._sparse_pairs, self._sparse_pairs_version = pairs, key
-        return self._sparse_pairs
+            for i, j in _pairs(len(groups)):
+                cols = torch.cat([groups[i], groups[j]])
+                sub = A2[:, cols].contiguous()
+                ident = torch.arange(cols.numel(), dtype=torch.int32, device=device)  # already Z-ordered
+                pairs.append((cols, self._sparse_layout(sub, ident)))
+            return pairs
+
+        return self._layout("sparse_pairs", (group,), make)
 
     def forward(self, times, C):
         """Returns ``(A_tC (B,X,Y,Z), A_t (B,K,X,Y,Z), grid (X,Y,Z,3,B), reg (B))`` for the frames ``times``."""
@@ -416,25 +458,19 @@ class DeformableNMF:
         frames = torch.from_numpy(np.ascontiguousarray(np.moveaxis(Y, 3, 0).reshape(T, P))).to(dev, torch.float32)
 
         def gram(cols):
-            sub = A_dev if cols is None else A_dev[:, :, cols].contiguous()
+            idx = None if cols is None else torch.as_tensor(cols, device=dev)
+            sub = A_dev if idx is None else A_dev[:, :, idx].contiguous()
             Apk = ops.pack_footprints(sub)                                 # (T*P, Kp)
-            return ops.warp_gram_rhs(Apk, sub.shape[2], (X, Y_, Z), None, list(range(T)), frames,
-                                     a_frame_stride=P * Apk.shape[1])[:2]
+            return (idx,) + ops.warp_gram_rhs(Apk, sub.shape[2], (X, Y_, Z), None, list(range(T)), frames,
+                                              a_frame_stride=P * Apk.shape[1])[:2]
 
         if K <= 127:
-            G, r = gram(None)
+            _, G, r = gram(None)
         else:
-            # one K3 launch holds 127 neurons: groups of 56, every PAIR of groups one launch on their union (both diagonal
-            # blocks and the off-diagonal block of the pair), as DeformableNMF._gram_rhs_grouped does on the fit path
+            # one K3 launch holds 127 neurons: groups of 56 by pairs, as DeformableNMF._gram_rhs_grouped does on the fit path
             G = torch.empty((T, K, K), dtype=torch.float32, device=dev)
             r = torch.empty((T, K), dtype=torch.float32, device=dev)
-            groups = [list(range(s0, min(K, s0 + 56))) for s0 in range(0, K, 56)]
-            for i in range(len(groups)):
-                for j in range(i + 1, len(groups)):
-                    idx = torch.as_tensor(groups[i] + groups[j], device=dev)
-                    Gp, rp = gram(idx)
-                    G[:, idx[:, None], idx[None, :]] = Gp
-                    r[:, idx] = rp
+            _gram_by_pairs(G, r, _dense_unions(K), gram)
         return _mu_temporal(G, r, torch.from_numpy(np.asarray(C, dtype=np.float64)).to(dev), gamma, 1).cpu().numpy()
 
     @staticmethod
@@ -449,12 +485,9 @@ class DeformableNMF:
         Y_dev = torch.from_numpy(np.ascontiguousarray(Y_i.reshape(-1, T).T)).to(dev, torch.float32)
         C_dev = torch.from_numpy(np.ascontiguousarray(C)).to(dev, torch.float32)
         D_dev = None if D is None else torch.from_numpy(np.ascontiguousarray(np.asarray(D).reshape(-1, K))).to(dev, torch.float32)
-        if K <= 128:
-            A1, Cs = ops.spatial_accum(Y_dev, C_dev)
-        else:  # K5 holds 8 trace blocks per wave: columns of A1 by groups; C C^T is tiny
-            A1 = torch.cat([ops.spatial_accum(Y_dev, C_dev[s0:s0 + 128].contiguous())[0] for s0 in range(0, K, 128)], 1)
-            Cs = (C_dev.double() @ C_dev.double().T).float()
-        ops.mu_spatial(A_dev, A1.contiguous(), Cs, D_dev, gamma)
+        A1, Cs = torch.empty_like(A_dev), torch.empty((K, K), dtype=torch.float32, device=dev)
+        DeformableNMF._spatial_accum_dense(Y_dev, C_dev, A1, Cs, None, None)
+        ops.mu_spatial(A_dev, A1, Cs, D_dev, gamma)
         return A_dev.double().cpu().numpy().reshape(A.shape)
 
     def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
@@ -476,14 +509,10 @@ class DeformableNMF:
         n1 = sl["total"] if sl is not None else P * K
         buf = self._spatial_buffer(n1 + K * K)
         Cs = buf[n1:].view(K, K)
-        if sl is not None:
-            A1 = buf[:n1]
-            _, _, self._ws_k5 = ops.spatial_accum_lists(registered, C, sl, fp.sz_list, K, frame_ids=frame_ids, times=times, A1c=A1,
-                                                        Cs=Cs, workspace=getattr(self, "_ws_k5", None))
-        else:
-            A1 = buf[:n1].view(P, K)
-            self._spatial_accum_dense(registered, C, A1, Cs, frame_ids, times)
+        A1 = buf[:n1] if sl is not None else buf[:n1].view(P, K)
+        self._spatial_numerator(registered, C, sl, A1, Cs, frame_ids, times)
         self._allreduce_spatial(buf)
+        self._scale_Cs(Cs)
         A2 = fp.A.reshape(P, K).contiguous()
         Dd = self._device_D(D)
         if sl is not None:
@@ -492,9 +521,25 @@ class DeformableNMF:
         else:
             ops.mu_spatial(A2, A1, Cs, Dd, gamma)
         fp.A = A2.view(*fp.sz_list, K)
-        fp.invalidate_layouts()   # K6 wrote through the raw pointer: the packed copies are stale
-        self._sl = None
+        self._footprints_written()
         return fp.A
+
+    def _spatial_numerator(self, registered, C, sl, A1, Cs, frame_ids, times):
+        """K5 of spatial_step: the numerator into ``A1`` (compact sums at the listed entries when ``sl`` is given, else
+        (P,K)) and ``C C^T`` of the local frames into ``Cs``."""
+        if sl is not None:
+            _, _, self._ws_k5 = ops.spatial_accum_lists(registered, C, sl, self.fp.sz_list, self.fp.K, frame_ids=frame_ids,
+                                                        times=times, A1c=A1, Cs=Cs, workspace=self._ws_k5)
+        else:
+            self._spatial_accum_dense(registered, C, A1, Cs, frame_ids, times)
+
+    def _scale_Cs(self, Cs):
+        """spatial_step's hook on the all-reduced ``C C^T``, in place: nothing to do for one channel."""
+
+    def _footprints_written(self):
+        """K6 wrote ``fp.A`` through its raw pointer: every packed copy and tile list of the old footprints is stale."""
+        self.fp.invalidate_layouts()
+        self._sl = None
 
     def _spatial_buffer(self, n):
         """The one buffer of spatial_step (A1 | C_s: one collective), kept while its size holds."""
@@ -544,13 +589,13 @@ class DeformableNMF:
         the footprints are compact (the rule of the Gram kernel: few boxes per voxel; no tile with more than 32 neurons),
         else None: dense K5 / K6.  The boxes are those of every non-zero value, whatever ``fp.footprint_floor``."""
         fp = self.fp
-        if self.spatial_kernel not in ('auto', 'lists') or fp.K > 256 or fp.P * 32 >= 2 ** 31 or fp.sz_list[1] * fp.sz_list[2] < 4:
+        if fp.P * 32 >= 2 ** 31 or fp.sz_list[1] * fp.sz_list[2] < 4:
             return None
-        ly = fp.packed_lists(floor=0.0)
-        if self.spatial_kernel == 'auto' and ly["boxfrac"] >= LISTS_BOXFRAC_LIMIT:
+        ly, why = fp._lists_verdict(self.spatial_kernel, floor=0.0)
+        if why is not None:
             return None
         # keyed on the layout itself: it is rebuilt whenever A is replaced, edited or invalidated
-        if getattr(self, "_sl", None) is None or self._sl[0] is not ly:
+        if self._sl is None or self._sl[0] is not ly:
             self._sl = (ly, ops.spatial_lists_setup(ly, fp.K, fp.sz_list))
         sl = self._sl[1]
         if sl["total"] <= 0:
@@ -638,15 +683,10 @@ class DeformableNMF:
     def _lists_layout_for_fused_update(self, gamma_c):
         """The K3n layout when update_footprints can run as K3n + K4-on-slots (one channel, no neighbour term, the
         kernel choice allows K3n and the pattern is narrow enough for the per-row lists); else None."""
-        fp = self.fp
-        if not (gamma_c is None or gamma_c == 0) or len(self._channels()) != 1 or fp.K > 256:
+        if not (gamma_c is None or gamma_c == 0) or len(self._channels()) != 1:
             return None
-        if self.gram_kernel not in ('auto', 'lists'):
-            return None
-        ly = fp.packed_lists()
-        if ly["nbr"] is None or ly["nslot"] > ops.LISTS_MAX_SLOTS:
-            return None
-        return ly if (self.gram_kernel == 'lists' or ly["boxfrac"] < LISTS_BOXFRAC_LIMIT) else None
+        ly, why = self.fp._lists_verdict(self.gram_kernel, slots=True, nbr=True)
+        return ly if why is None else None
 
     def _gram_rhs(self, frames, order):
         """Per-frame Gram matrices and right-hand sides under the current warp, summed over the channels."""
@@ -678,27 +718,22 @@ class DeformableNMF:
 
     def _gram_rhs_one(self, fp, frames, order):
         """K3, K3s or K3n on the footprints of ``fp``."""
-        if self.gram_kernel == 'auto':
-            if fp.K > 256:
-                self._note_once("k3n-K", f"gram_kernel='auto': K={fp.K} > 256, the neuron-list kernel K3n does not "
-                                "apply; using K3s / K3 by pairs of neuron groups (several times slower)")
-            else:
-                ly = fp.packed_lists()
-                if ly["nslot"] > ops.LISTS_MAX_SLOTS or ly["boxfrac"] >= LISTS_BOXFRAC_LIMIT:
-                    self._note_once("k3n-shape", f"gram_kernel='auto': footprints too wide for the neuron-list kernel K3n "
-                                    f"(pattern slots {ly['nslot']} vs limit {ops.LISTS_MAX_SLOTS}, mean boxes per voxel "
-                                    f"{ly['boxfrac']:.2f} vs limit {LISTS_BOXFRAC_LIMIT}); using K3s / K3 (6-40x slower)")
-        if self.gram_kernel in ('auto', 'lists') and fp.K <= 256:
-            ly = fp.packed_lists()
-            # K3n pays per (voxel, listed neuron) and per listed pair: it wins while a voxel lies in few boxes
-            if ly["nslot"] <= ops.LISTS_MAX_SLOTS and (self.gram_kernel == 'lists' or ly["boxfrac"] < LISTS_BOXFRAC_LIMIT):
-                G, r, self._ws_k3 = ops.warp_gram_rhs_lists(ly, fp.K, fp.sz_list, fp.beta.detach(), order, frames,
-                                                            workspace=self._ws_k3)
-                self._gram_nbr = ly["nbr"]   # the pattern of this G, for K4
-                return G, r
-            if self.gram_kernel == 'lists':
-                raise ValueError(f"gram_kernel='lists': the pattern of G has {ly['nslot']} slots > "
-                                 f"{ops.LISTS_MAX_SLOTS} (footprints overlap too much)")
+        ly, why = fp._lists_verdict(self.gram_kernel, slots=True)
+        if why is None:
+            G, r, self._ws_k3 = ops.warp_gram_rhs_lists(ly, fp.K, fp.sz_list, fp.beta.detach(), order, frames,
+                                                        workspace=self._ws_k3)
+            self._gram_nbr = ly["nbr"]   # the pattern of this G, for K4
+            return G, r
+        if self.gram_kernel == 'lists' and why == 'slots':
+            raise ValueError(f"gram_kernel='lists': the pattern of G has {ly['nslot']} slots > "
+                             f"{ops.LISTS_MAX_SLOTS} (footprints overlap too much)")
+        if self.gram_kernel == 'auto' and why == 'K':
+            self._note_once("k3n-K", f"gram_kernel='auto': K={fp.K} > {LISTS_MAX_K}, the neuron-list kernel K3n does not "
+                            "apply; using K3s / K3 by pairs of neuron groups (several times slower)")
+        elif self.gram_kernel == 'auto':   # 'slots' or 'boxes'
+            self._note_once("k3n-shape", f"gram_kernel='auto': footprints too wide for the neuron-list kernel K3n "
+                            f"(pattern slots {ly['nslot']} vs limit {ops.LISTS_MAX_SLOTS}, mean boxes per voxel "
+                            f"{ly['boxfrac']:.2f} vs limit {LISTS_BOXFRAC_LIMIT}); using K3s / K3 (6-40x slower)")
         if fp.K > 127:
             return self._gram_rhs_grouped(fp, frames, order)
         sp = fp.packed_sparse() if self.gram_kernel in ('auto', 'sparse') else None
@@ -718,27 +753,23 @@ class DeformableNMF:
         K, B = fp.K, order.numel()
         G = torch.empty((B, K, K), dtype=torch.float32, device=device)
         r = torch.empty((B, K), dtype=torch.float32, device=device)
-        if self.gram_kernel in ('auto', 'sparse'):
-            pairs = fp.packed_sparse_pairs()
-            if self.gram_kernel == 'sparse' or max(sp["occupancy"] for _, sp in pairs) < 0.5:
-                for cols, sp in pairs:
-                    Gp, rp, self._ws_k3 = ops.warp_gram_rhs_sparse(sp["Aps"], cols.numel(), sp["order"], sp["row_mask"],
-                                                                   fp.sz_list, fp.beta.detach(), order, frames,
-                                                                   workspace=self._ws_k3)
-                    G[:, cols[:, None], cols[None, :]] = Gp
-                    r[:, cols] = rp
-                return G, r
-        group = 56
-        groups = [list(range(s0, min(K, s0 + group))) for s0 in range(0, K, group)]
-        for i in range(len(groups)):
-            for j in range(i + 1, len(groups)):
-                cols = groups[i] + groups[j]
-                Gp, rp, self._ws_k3 = ops.warp_gram_rhs(fp.packed_columns(cols), len(cols), fp.sz_list, fp.beta.detach(),
-                                                        order, frames, workspace=self._ws_k3,
-                                                        bf16=self.gram_kernel == 'bf16')
-                idx = torch.as_tensor(cols, device=device)
-                G[:, idx[:, None], idx[None, :]] = Gp
-                r[:, idx] = rp
+
+        def sparse(pair):
+            cols, sp = pair
+            Gp, rp, self._ws_k3 = ops.warp_gram_rhs_sparse(sp["Aps"], cols.numel(), sp["order"], sp["row_mask"], fp.sz_list,
+                                                           fp.beta.detach(), order, frames, workspace=self._ws_k3)
+            return cols, Gp, rp
+
+        def dense(cols):
+            Gp, rp, self._ws_k3 = ops.warp_gram_rhs(fp.packed_columns(cols), len(cols), fp.sz_list, fp.beta.detach(), order,
+                                                    frames, workspace=self._ws_k3, bf16=self.gram_kernel == 'bf16')
+            return torch.as_tensor(cols, device=device), Gp, rp
+
+        pairs = fp.packed_sparse_pairs() if self.gram_kernel in ('auto', 'sparse') else None
+        if pairs is not None and (self.gram_kernel == 'sparse' or max(sp["occupancy"] for _, sp in pairs) < 0.5):
+            _gram_by_pairs(G, r, pairs, sparse)
+        else:
+            _gram_by_pairs(G, r, _dense_unions(K), dense)
         return G, r
 
     def _recon_cache(self):
@@ -1001,11 +1032,9 @@ class DeformableNMF:
     def _motion_lists_layout(self):
         """The K3n layout when the motion gradient can take its reconstruction images from the neuron lists (one
         channel, compact footprints); else None."""
-        fp = self.fp
-        if len(self._channels()) != 1 or not fp.use_lists or fp.K > 256:
+        if len(self._channels()) != 1 or not self.fp.use_lists:
             return None
-        ly = fp.packed_lists()
-        return ly if ly["boxfrac"] < LISTS_BOXFRAC_LIMIT else None
+        return self.fp.lists_layout()
 
     def _motion_epoch(self, plan, frames, rows, optimizer, S_all):
         """One epoch of mini-batch Adam steps: dnmf_adam_epoch phase 0, the gradient of every frame at its coasted
@@ -1093,7 +1122,7 @@ class MultiChannelDNMF(DeformableNMF):
             for c in range(self.colours.shape[0]):
                 f = copy.copy(self.fp)  # shares beta (the caller's optimiser steps one tensor) and the lattice
                 f.A = self.fp.A * self.colours[c]
-                f._packed = f._sparse = f._sparse_pairs = f._lists = f._lists_exact = None
+                f.invalidate_layouts()   # a cache of its own: the copy shares the dict of self.fp
                 self._chan_fp.append((f, slice(c * P, (c + 1) * P)))
             self._chan_key = key
         return self._chan_fp
@@ -1124,42 +1153,30 @@ class MultiChannelDNMF(DeformableNMF):
         per channel (by groups of 128 neurons beyond K = 128).  One all-reduce of the A1 | C_s buffer over ``self.group``
         like the single-channel step.  Not in the reference (no channel axis there): checked against this formula in
         float64 and, for one channel of colour 1, against ``DeformableNMF.spatial_step``."""
-        fp = self.fp
-        P, K = fp.P, fp.K
-        NC = self.colours.shape[0]
+        NC, P = self.colours.shape[0], self.fp.P
         if registered.shape[1] != NC * P:
             raise ValueError(f"MultiChannelDNMF.spatial_step: rows of {registered.shape[1]} floats, expected {NC} x {P}")
-        C = self.C.to(device, torch.float32).contiguous()
-        if times is None:
-            times = frame_ids
-        sl = self._spatial_lists()
-        n1 = sl["total"] if sl is not None else P * K
-        buf = self._spatial_buffer(n1 + K * K)
-        Cs = buf[n1:].view(K, K)
+        return super().spatial_step(registered, D=D, gamma=gamma, frame_ids=frame_ids, times=times)
+
+    def _spatial_numerator(self, registered, C, sl, A1, Cs, frame_ids, times):
+        fp = self.fp
+        P, K = fp.P, fp.K
         if sl is not None:
-            A1 = buf[:n1]
             _, _, self._ws_k5 = ops.spatial_accum_lists_channels(registered, C, self.colours, sl, fp.sz_list, K, frame_ids=frame_ids,
-                                                                 times=times, A1c=A1, Cs=Cs, workspace=getattr(self, "_ws_k5", None))
+                                                                 times=times, A1c=A1, Cs=Cs, workspace=self._ws_k5)
         else:
-            A1 = buf[:n1].view(P, K)
             A1.zero_()
             part = torch.empty((P, K), dtype=torch.float32, device=device)
-            for c in range(NC):
+            for c in range(self.colours.shape[0]):
                 self._spatial_accum_dense(registered[:, c * P:(c + 1) * P], C, part, Cs, frame_ids, times)
                 A1.addcmul_(part, self.colours[c][None, :])
-        self._allreduce_spatial(buf)
+
+    def _scale_Cs(self, Cs):
         Cs.mul_(self.colours.T @ self.colours)
-        A2 = fp.A.reshape(P, K).contiguous()
-        Dd = self._device_D(D)
-        if sl is not None:
-            ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
-        else:
-            ops.mu_spatial(A2, A1, Cs, Dd, gamma)
-        fp.A = A2.view(*fp.sz_list, K)
-        fp.invalidate_layouts()
-        self._sl = None
+
+    def _footprints_written(self):
+        super()._footprints_written()
         self._chan_fp = None
-        return fp.A
 
 
 def _mu_temporal(G, r, C, gamma, iters, group=None, nbr=None):

@@ -3,6 +3,8 @@ the current HIP stream.  torch is plumbing here (device memory, streams); all ar
 libdnmf_hip.so."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -47,6 +49,37 @@ def _i32(t, device) -> torch.Tensor:
 
 def _ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+def _rows(t, fn, name, min_row=0, clause=""):
+    """``t`` as the kernels take rows: float32 CUDA with unit inner stride (any row stride), at least ``min_row`` floats a
+    row (``clause`` says so in the message)."""
+    if t.dtype != torch.float32 or t.stride(-1) != 1 or not t.is_cuda or t.shape[-1] < min_row:
+        raise ValueError(f"{fn}: {name} must be float32 CUDA with unit inner stride{clause}")
+    return t
+
+
+def _ids(frames, frame_ids, times, dev):
+    """``(frame_ids, times, B)``: the two index lists as int32 tensors on ``dev`` (None stays None) and the frames of the
+    call -- as many as ``times``, else as ``frame_ids``, else every row of ``frames``."""
+    fid = _i32(frame_ids, dev) if frame_ids is not None else None
+    tt = _i32(times, dev) if times is not None else None
+    return fid, tt, tt.numel() if tt is not None else (fid.numel() if fid is not None else frames.shape[0])
+
+
+def _nbytes(ws):
+    return 0 if ws is None else ws.numel() * ws.element_size()
+
+
+def _workspace(workspace, need, dev):
+    """``workspace`` while it holds ``need`` bytes, else a new float32 one that does."""
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    return workspace
+
+
+def _int3(v):
+    return (ctypes.c_int * 3)(*[int(x) for x in v])
 
 
 def build_stamp() -> dict:
@@ -152,20 +185,17 @@ def warp_recon_grad(S, s_ids, frames, frame_ids, sz, beta, times, grad=None, gou
     P = X * Y * Z
     dev = beta.device
     _f32(beta, "beta")
-    tt = _i32(times, dev)
-    B = tt.numel()
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
     lib = _lib.load()
     need = lib.dnmf_warp_recon_grad_workspace(X, Y, Z, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    workspace = _workspace(workspace, need, dev)
     recon = torch.empty((B, P), dtype=torch.float32, device=dev) if want_recon else None
     loss = torch.empty((1,), dtype=torch.float32, device=dev) if want_loss else None
     frame_loss = torch.empty((B,), dtype=torch.float32, device=dev) if want_loss else None
     reg = torch.empty((B,), dtype=torch.float32, device=dev) if want_reg else None
     sid = _i32(s_ids, dev) if s_ids is not None else None
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    if frames is not None and (frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda):
-        raise ValueError("warp_recon_grad: frames must be float32 CUDA with unit inner stride")
+    if frames is not None:
+        _rows(frames, "warp_recon_grad", "frames")
     if gout is not None:
         _f32(gout, "gout")
     with _timed("warp_recon_grad"):
@@ -174,7 +204,7 @@ def warp_recon_grad(S, s_ids, frames, frame_ids, sz, beta, times, grad=None, gou
             _ptr(gout), X, Y, Z, beta.data_ptr(), beta.shape[2], tt.data_ptr(), B, int(norm_frames), _ptr(recon),
             _ptr(grad),
             _ptr(loss), _ptr(frame_loss), _ptr(reg), workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), _stream())
+            _nbytes(workspace), _stream())
     _lib.check(rc, "dnmf_warp_recon_grad")
     return {"recon": recon, "loss": loss, "frame_loss": frame_loss, "reg": reg, "workspace": workspace}
 
@@ -186,23 +216,19 @@ def motion_grad_lists(layout, K, sz, C, frames, frame_ids, beta, times, grad, no
     X, Y, Z = (int(s) for s in sz)
     dev = beta.device
     _f32(beta, "beta"), _f32(C, "C"), _f32(grad, "grad")
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("motion_grad_lists: frames must be float32 CUDA with unit inner stride")
-    tt = _i32(times, dev)
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = tt.numel()
+    _rows(frames, "motion_grad_lists", "frames")
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
     lib = _lib.load()
     chunk = max(1, min(int(chunk), B))
     need = lib.dnmf_motion_grad_lists_workspace(X, Y, Z, chunk, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    workspace = _workspace(workspace, need, dev)
     frame_loss = torch.empty((B,), dtype=torch.float32, device=dev) if want else None
     reg = torch.empty((B,), dtype=torch.float32, device=dev) if want else None
     with _timed("motion_grad_lists"):
         rc = lib.dnmf_motion_grad_lists(layout["At"].data_ptr(), layout["bbox"].data_ptr(), K, C.data_ptr(), C.stride(0),
                                         frames.data_ptr(), frames.stride(0), _ptr(fid), X, Y, Z, beta.data_ptr(),
                                         beta.shape[2], tt.data_ptr(), B, int(norm_frames), grad.data_ptr(), _ptr(frame_loss),
-                                        _ptr(reg), chunk, workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                        _ptr(reg), chunk, workspace.data_ptr(), _nbytes(workspace),
                                         _stream())
     _lib.check(rc, "dnmf_motion_grad_lists")
     return {"frame_loss": frame_loss, "reg": reg, "workspace": workspace}
@@ -218,21 +244,17 @@ def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_strid
     if beta is not None:
         _f32(beta, "beta")
     lib = _lib.load()
-    tt = _i32(times, dev) if times is not None else None
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = tt.numel() if tt is not None else (fid.numel() if fid is not None else frames.shape[0])
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("warp_gram_rhs: frames must be float32 CUDA with unit inner stride")
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    _rows(frames, "warp_gram_rhs", "frames")
     need = lib.dnmf_warp_gram_rhs_workspace(P, K, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    workspace = _workspace(workspace, need, dev)
     G = torch.empty((B, K, K), dtype=torch.float32, device=dev)
     r = torch.empty((B, K), dtype=torch.float32, device=dev)
     with _timed("warp_gram_rhs_bf16" if bf16 else "warp_gram_rhs"):
         rc = (lib.dnmf_warp_gram_rhs_bf16 if bf16 else lib.dnmf_warp_gram_rhs)(
             Apk.data_ptr(), Apk.shape[-1], K, a_frame_stride, X, Y, Z, _ptr(beta), B if beta is None else beta.shape[2],
             _ptr(tt), B, frames.data_ptr(), frames.stride(0), _ptr(fid), G.data_ptr(), r.data_ptr(), workspace.data_ptr(),
-            workspace.numel() * workspace.element_size(), _stream())
+            _nbytes(workspace), _stream())
     _lib.check(rc, "dnmf_warp_gram_rhs")
     return G, r, workspace
 
@@ -306,14 +328,9 @@ def adam_epoch(beta, grad, exp_avg, exp_avg_sq, step0, frame_step, nsteps, lr, b
 
 def spatial_accum(Y, C, frame_ids=None, times=None, A1=None, Cs=None, accumulate=False):
     """K5.  Y (>=T, ldy) frames, C (K, ldc) traces -> A1 (P,K) = Y^T C^T over the frames, Cs (K,K) = C C^T."""
-    if Y.dtype != torch.float32 or Y.stride(-1) != 1 or not Y.is_cuda:
-        raise ValueError("spatial_accum: Y must be float32 CUDA with unit inner stride")
-    if C.dtype != torch.float32 or C.stride(-1) != 1 or not C.is_cuda:
-        raise ValueError("spatial_accum: C must be float32 CUDA with unit inner stride")
+    _rows(Y, "spatial_accum", "Y"), _rows(C, "spatial_accum", "C")
     dev = Y.device
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    tt = _i32(times, dev) if times is not None else None
-    T = fid.numel() if fid is not None else (tt.numel() if tt is not None else Y.shape[0])
+    fid, tt, T = _ids(Y, frame_ids, times, dev)
     P, K = Y.shape[1], C.shape[0]
     if A1 is None:
         A1 = torch.empty((P, K), dtype=torch.float32, device=dev)
@@ -356,63 +373,47 @@ def spatial_lists_setup(layout, K, sz):
 
 def spatial_accum_lists(Y, C, sl, sz, K, frame_ids=None, times=None, A1c=None, Cs=None, workspace=None):
     """K5, list form.  Y (>=T, ldy) registered frames, C (K, ldc) -> A1c (total) compact sums, Cs (K,K)."""
-    X, Yd, Z = (int(s) for s in sz)
-    if Y.dtype != torch.float32 or Y.stride(-1) != 1 or not Y.is_cuda:
-        raise ValueError("spatial_accum_lists: Y must be float32 CUDA with unit inner stride")
-    if C.dtype != torch.float32 or C.stride(-1) != 1 or not C.is_cuda:
-        raise ValueError("spatial_accum_lists: C must be float32 CUDA with unit inner stride")
-    dev = Y.device
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    tt = _i32(times, dev) if times is not None else None
-    T = fid.numel() if fid is not None else (tt.numel() if tt is not None else Y.shape[0])
-    total = sl["total"]
-    if A1c is None:
-        A1c = torch.empty((total,), dtype=torch.float32, device=dev)
-        Cs = torch.empty((K, K), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    need = lib.dnmf_spatial_accum_lists_workspace(X, Yd, Z, total, T)
-    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
-    with _timed("spatial_accum_lists"):
-        rc = lib.dnmf_spatial_accum_lists(Y.data_ptr(), Y.stride(0), _ptr(fid), C.data_ptr(), C.stride(0), _ptr(tt), T, X, Yd, Z, K,
-                                          sl["tables"].data_ptr(), total, A1c.data_ptr(), Cs.data_ptr(), _ptr(workspace),
-                                          0 if workspace is None else workspace.numel() * workspace.element_size(), _stream())
-    _lib.check(rc, "dnmf_spatial_accum_lists")
-    return A1c, Cs, workspace
+    return _spatial_accum_lists("spatial_accum_lists", Y, C, None, sl, sz, K, frame_ids, times, A1c, Cs, workspace)
 
 
 def spatial_accum_lists_channels(Y, C, colours, sl, sz, K, frame_ids=None, times=None, A1c=None, Cs=None, workspace=None):
     """K5, list form over colour channels: Y (>=T, ldy) rows of NC channels of P floats, colours (NC,K) ->
     A1c (total) = sum_c colours[c,k] (Y^c C^T) at the listed entries, Cs (K,K) = C C^T."""
+    return _spatial_accum_lists("spatial_accum_lists_channels", Y, C, colours, sl, sz, K, frame_ids, times, A1c, Cs, workspace)
+
+
+def _spatial_accum_lists(fn, Y, C, colours, sl, sz, K, frame_ids, times, A1c, Cs, workspace):
+    """The list-form K5 behind both entry points: ``colours`` None is the single-channel kernel ``dnmf_spatial_accum_lists``."""
     X, Yd, Z = (int(s) for s in sz)
     P = X * Yd * Z
-    _f32(colours, "colours")
-    NC = colours.shape[0]
-    if colours.dim() != 2 or colours.shape[1] != K:
-        raise ValueError(f"spatial_accum_lists_channels: colours must be (NC, K={K}), got {tuple(colours.shape)}")
-    if Y.dtype != torch.float32 or Y.stride(-1) != 1 or not Y.is_cuda or Y.shape[-1] < NC * P:
-        raise ValueError(f"spatial_accum_lists_channels: Y must be float32 CUDA with unit inner stride and rows of {NC} x {P}")
-    if C.dtype != torch.float32 or C.stride(-1) != 1 or not C.is_cuda:
-        raise ValueError("spatial_accum_lists_channels: C must be float32 CUDA with unit inner stride")
+    if colours is None:
+        _rows(Y, fn, "Y")
+    else:
+        _f32(colours, "colours")
+        NC = colours.shape[0]
+        if colours.dim() != 2 or colours.shape[1] != K:
+            raise ValueError(f"{fn}: colours must be (NC, K={K}), got {tuple(colours.shape)}")
+        _rows(Y, fn, "Y", NC * P, f" and rows of {NC} x {P}")
+    _rows(C, fn, "C")
     dev = Y.device
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    tt = _i32(times, dev) if times is not None else None
-    T = fid.numel() if fid is not None else (tt.numel() if tt is not None else Y.shape[0])
+    fid, tt, T = _ids(Y, frame_ids, times, dev)
     total = sl["total"]
     if A1c is None:
         A1c = torch.empty((total,), dtype=torch.float32, device=dev)
         Cs = torch.empty((K, K), dtype=torch.float32, device=dev)
     lib = _lib.load()
     need = lib.dnmf_spatial_accum_lists_workspace(X, Yd, Z, total, T)
-    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    if need:   # 0: these frames go in one pass, no workspace (None is passed on as such)
+        workspace = _workspace(workspace, need, dev)
+    tail = (_ptr(tt), T, X, Yd, Z, K, sl["tables"].data_ptr(), total, A1c.data_ptr(), Cs.data_ptr(), _ptr(workspace),
+            _nbytes(workspace), _stream())
     with _timed("spatial_accum_lists"):
-        rc = lib.dnmf_spatial_accum_lists_channels(Y.data_ptr(), Y.stride(0), P, NC, colours.data_ptr(), _ptr(fid), C.data_ptr(),
-                                                   C.stride(0), _ptr(tt), T, X, Yd, Z, K, sl["tables"].data_ptr(), total,
-                                                   A1c.data_ptr(), Cs.data_ptr(), _ptr(workspace),
-                                                   0 if workspace is None else workspace.numel() * workspace.element_size(),
-                                                   _stream())
-    _lib.check(rc, "dnmf_spatial_accum_lists_channels")
+        if colours is None:
+            rc = lib.dnmf_spatial_accum_lists(Y.data_ptr(), Y.stride(0), _ptr(fid), C.data_ptr(), C.stride(0), *tail)
+        else:
+            rc = lib.dnmf_spatial_accum_lists_channels(Y.data_ptr(), Y.stride(0), P, NC, colours.data_ptr(), _ptr(fid),
+                                                       C.data_ptr(), C.stride(0), *tail)
+    _lib.check(rc, "dnmf_" + fn)
     return A1c, Cs, workspace
 
 
@@ -473,15 +474,11 @@ def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, work
     dev = beta.device
     _f32(beta, "beta")
     lib = _lib.load()
-    tt = _i32(times, dev) if times is not None else None
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = tt.numel() if tt is not None else (fid.numel() if fid is not None else frames.shape[0])
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("warp_gram_rhs_lists: frames must be float32 CUDA with unit inner stride")
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    _rows(frames, "warp_gram_rhs_lists", "frames")
     nslot = layout["nslot"]
     need = lib.dnmf_warp_gram_rhs_lists_workspace(nslot, K, X, Y, Z, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    workspace = _workspace(workspace, need, dev)
     G = torch.empty((B, K, K), dtype=torch.float32, device=dev) if finish else None
     r = torch.empty((B, K), dtype=torch.float32, device=dev) if finish else None
     counters = None
@@ -494,7 +491,7 @@ def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, work
             layout["At"].data_ptr(), layout["bbox"].data_ptr(), layout["pair_slot"].data_ptr(),
             layout["axis_masks"].data_ptr(), nslot, K, X, Y, Z,
             beta.data_ptr(), beta.shape[2], _ptr(tt), B, frames.data_ptr(), frames.stride(0), _ptr(fid), _ptr(G),
-            _ptr(r), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _ptr(counters), _stream())
+            _ptr(r), workspace.data_ptr(), _nbytes(workspace), _ptr(counters), _stream())
     _lib.check(rc, "dnmf_warp_gram_rhs_lists")
     return G, r, workspace
 
@@ -524,7 +521,6 @@ class Communicator:
     one-rank communicator."""
 
     def __init__(self, group=None):
-        import ctypes
         import torch.distributed as dist
         lib = _lib.load()
         multi = dist.is_available() and dist.is_initialized()
@@ -569,14 +565,11 @@ def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, 
     if nchan < 1:
         raise ValueError(f"image_iwarp: nchan={nchan}")
     _f32(beta, "beta")
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("image_iwarp: frames must be float32 CUDA with unit inner stride")
+    _rows(frames, "image_iwarp", "frames")
     if nchan > 1 and frames.shape[-1] < nchan * P:
         raise ValueError(f"image_iwarp: rows of {frames.shape[-1]} floats cannot hold {nchan} channels of {P}")
     dev = frames.device
-    tt = _i32(times, dev)
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = tt.numel()
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
     if out is None:
         out = torch.empty((B, nchan * P), dtype=torch.float32, device=dev)
     if out.shape[0] < B or out.stride(0) < nchan * P or out.stride(1) != 1:
@@ -659,12 +652,10 @@ def nearest_points(points, queries, values=None, out_index=None, out=None, _work
 def patch_grid(sz, strides, overlaps):
     """The patch grid of the reference's ``sliding_window_3d`` (MotionCorrect.py:1190-1221): ``(dims (3,), starts (NP,3))`` as
     numpy int arrays, patches in the reference's order (x outermost)."""
-    import ctypes
-
     import numpy as np
     X, Y, Z = (int(s) for s in sz)
-    st = (ctypes.c_int * 3)(*[int(v) for v in strides])
-    ov = (ctypes.c_int * 3)(*[int(v) for v in overlaps])
+    st = _int3(strides)
+    ov = _int3(overlaps)
     dims = (ctypes.c_int * 3)()
     lib = _lib.load()
     NP = lib.dnmf_register_patches_grid(X, Y, Z, st, ov, dims, None)
@@ -679,17 +670,14 @@ def register_patches(frames, tmpl, sz, strides, overlaps, max_shifts, max_deviat
                      add_to_movie=0.0, frame_ids=None):
     """K8.  frames (>=B, P) fp32 CUDA rows, tmpl (P) -> rigid shifts (B,3) and per-patch shifts (B,NP,3) (signs -x, -y, +z:
     the reference's ``x/y/z_shifts_els``)."""
-    import ctypes
     X, Y, Z = (int(s) for s in sz)
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("register_patches: frames must be float32 CUDA with unit inner stride")
+    _rows(frames, "register_patches", "frames")
     dev = frames.device
     tm = _f32(tmpl.reshape(-1), "tmpl")
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    st = (ctypes.c_int * 3)(*[int(v) for v in strides])
-    ov = (ctypes.c_int * 3)(*[int(v) for v in overlaps])
-    ms = (ctypes.c_int * 3)(*[int(v) for v in max_shifts])
+    fid, _, B = _ids(frames, frame_ids, None, dev)
+    st = _int3(strides)
+    ov = _int3(overlaps)
+    ms = _int3(max_shifts)
     lib = _lib.load()
     NP = lib.dnmf_register_patches_grid(X, Y, Z, st, ov, None, None)
     if NP <= 0:
@@ -714,16 +702,13 @@ def rigid_correct(frames, tmpl, sz, max_shifts, upsample_factor=10, add_to_movie
     """K8, rigid pass.  frames (>=B, P) fp32 CUDA rows, tmpl (P) -> (rigid shifts (B,3) as register_translation_3d returns
     them, corrected frames (B,P) or None, tsum (P) fp32, tcount (P) int32): the per-voxel sums and counts of the finite
     corrected values are ADDED into ``tsum`` / ``tcount`` when given (a video walked in pieces), else start from zero."""
-    import ctypes
     X, Y, Z = (int(s) for s in sz)
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("rigid_correct: frames must be float32 CUDA with unit inner stride")
+    _rows(frames, "rigid_correct", "frames")
     dev = frames.device
     P = X * Y * Z
     tm = _f32(tmpl.reshape(-1), "tmpl")
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    ms = (ctypes.c_int * 3)(*[int(v) for v in max_shifts])
+    fid, _, B = _ids(frames, frame_ids, None, dev)
+    ms = _int3(max_shifts)
     lib = _lib.load()
     ws = torch.empty((lib.dnmf_rigid_correct_workspace(X, Y, Z, B),), dtype=torch.uint8, device=dev)
     rigid = torch.empty((B, 3), dtype=torch.float32, device=dev)
@@ -742,17 +727,14 @@ def apply_pwrigid(frames, patch_shifts, sz, strides, overlaps, add_to_movie=0.0,
     """K9.  frames (>=B, P) fp32 CUDA rows, patch_shifts (B,NP,3) with the signs of x/y/z_shifts_els (-x, -y, +z) -> (the
     piecewise-rigid corrected frames out (B,P) (or (>=B, ldo) given), tsum (P) fp32, tcount (P) int32): the per-voxel sums and
     counts of the finite corrected values are ADDED into ``tsum`` / ``tcount`` when given, else start from zero."""
-    import ctypes
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("apply_pwrigid: frames must be float32 CUDA with unit inner stride")
+    _rows(frames, "apply_pwrigid", "frames")
     dev = frames.device
     sh = _f32(patch_shifts, "patch_shifts")
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    st = (ctypes.c_int * 3)(*[int(v) for v in strides])
-    ov = (ctypes.c_int * 3)(*[int(v) for v in overlaps])
+    fid, _, B = _ids(frames, frame_ids, None, dev)
+    st = _int3(strides)
+    ov = _int3(overlaps)
     lib = _lib.load()
     NP = lib.dnmf_register_patches_grid(X, Y, Z, st, ov, None, None)
     if NP <= 0:
@@ -876,7 +858,6 @@ def roi_signals(frames, sz, P, window=(3, 3, 0)):
     ``device_frames()``), P (K,3,T) fp32 / fp64 CUDA tracks -> (K,T) fp64 CUDA: the reference's ``get_roi_signals`` -- the
     mean of the box of 2 window + 1 voxels per axis around the rounded position, zeros outside the volume, NaN voxels left
     out, NaN for a position outside the volume."""
-    import ctypes
     X, Y, Z = (int(s) for s in sz)
     if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2
             and frames.stride(1) == 1 and frames.stride(0) >= X * Y * Z and frames.shape[1] >= X * Y * Z):
@@ -891,7 +872,7 @@ def roi_signals(frames, sz, P, window=(3, 3, 0)):
     out = torch.empty((K, T), dtype=torch.float64, device=frames.device)
     with _timed("roi_signals"):
         rc = _lib.load().dnmf_roi_signals(frames.data_ptr(), frames.stride(0), X, Y, Z, P.data_ptr(), int(P.dtype == torch.float64),
-                                          K, T, (ctypes.c_int * 3)(*w), out.data_ptr(), _stream())
+                                          K, T, _int3(w), out.data_ptr(), _stream())
     _lib.check(rc, "dnmf_roi_signals")
     return out
 
@@ -928,14 +909,10 @@ def warp_gram_rhs_sparse(Aps, K, order, row_mask, sz, beta, times, frames, frame
     _f32(Aps, "Aps"), _f32(beta, "beta")
     lib = _lib.load()
     od = _i32(order, dev)
-    tt = _i32(times, dev) if times is not None else None
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = tt.numel() if tt is not None else (fid.numel() if fid is not None else frames.shape[0])
-    if frames.dtype != torch.float32 or frames.stride(-1) != 1 or not frames.is_cuda:
-        raise ValueError("warp_gram_rhs_sparse: frames must be float32 CUDA with unit inner stride")
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    _rows(frames, "warp_gram_rhs_sparse", "frames")
     need = (lib.dnmf_warp_gram_rhs_sparse_lt_workspace if lt else lib.dnmf_warp_gram_rhs_sparse_workspace)(P, K, B)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=dev)
+    workspace = _workspace(workspace, need, dev)
     G = torch.empty((B, K, K), dtype=torch.float32, device=dev)
     r = torch.empty((B, K), dtype=torch.float32, device=dev)
     counters = None
@@ -947,6 +924,6 @@ def warp_gram_rhs_sparse(Aps, K, order, row_mask, sz, beta, times, frames, frame
         rc = (lib.dnmf_warp_gram_rhs_sparse_lt if lt else lib.dnmf_warp_gram_rhs_sparse)(
             Aps.data_ptr(), Aps.shape[-1], K, od.data_ptr(), row_mask.data_ptr(), X, Y, Z, beta.data_ptr(),
             beta.shape[2], _ptr(tt), B, frames.data_ptr(), frames.stride(0), _ptr(fid), G.data_ptr(), r.data_ptr(),
-            workspace.data_ptr(), workspace.numel() * workspace.element_size(), _ptr(counters), _stream())
+            workspace.data_ptr(), _nbytes(workspace), _ptr(counters), _stream())
     _lib.check(rc, "dnmf_warp_gram_rhs_sparse")
     return G, r, workspace

@@ -27,7 +27,7 @@ print("update_motion      %.2f ms" % T(lambda: dn.update_motion(train, opt, gamm
 print("update_footprints  %.2f ms" % T(lambda: dn.update_footprints(test, bs, sz, gamma_c=0, iter_c=50, return_dense=False))[0])
 print("  recon cache      %.2f ms" % T(lambda: dn._recon_cache())[0])
 S_all = dn._recon_cache()
-print("  motion epoch     %.2f ms" % T(lambda: dn._motion_epoch(train, opt, S_all))[0])
+print("  motion epoch     %.2f ms" % T(lambda: dn._motion_epoch(train.epoch_plan(), train.frames_2d(), None, opt, S_all))[0])
 print("  epoch_plan       %.2f ms" % T(lambda: train.epoch_plan())[0])
 fr, order = dn._gather_frames(test)
 print("  gram_rhs         %.2f ms" % T(lambda: dn._gram_rhs(fr, order))[0])
