@@ -408,6 +408,10 @@ class DeformableNMF:
         self._S_bufs = None
         self._S_zero = None
         self._gram_nbr = None   # (K,NN) columns of the last Gram matrices that can be non-zero, when K3n made them
+        # after update_footprints(solver='hals'): per frame of that call the largest projected-gradient entry of the
+        # trace problem on the solver's float64 state, before self.C is rounded to float32 (float64 CPU tensor; zero at the
+        # NNLS solution); None after a solver='mu' call
+        self.last_temporal_kkt = None
         # update_motion evaluates a whole epoch per launch when the caller's optimiser is a plain
         # torch.optim.Adam on [fp.beta] and the loader is a ResidentLoader (same result, see _motion_epoch)
         self.fused_motion = True
@@ -445,11 +449,13 @@ class DeformableNMF:
 
     # ---- static NMF updates (numpy in / numpy out like the reference) ---------------------------------
     @staticmethod
-    def update_temporal(A_t, C, Y, gamma=None):
-        """One multiplicative update of ``C`` given explicit warped footprints (reference :139-149).
+    def update_temporal(A_t, C, Y, gamma=None, solver='mu', iters=1):
+        """One multiplicative update of ``C`` given explicit warped footprints (reference :139-149); ``iters`` of them, or
+        with ``solver='hals'`` ``iters`` sweeps of the exact coordinate-descent solver K4h on the same Gram data.
         ``A_t`` (X,Y,Z,K,T), ``C`` (K,T), ``Y`` (X,Y,Z,T) numpy; returns float64 numpy (K,T).  The contraction runs on
         the fp32 matrix cores (K3 without a warp: every voxel's own row of ``A_t``), the update in float64 (K4); more than
         127 neurons go by pairs of neuron groups (one K3 launch holds 127)."""
+        _check_solver(solver)
         A_t, C, Y = np.asarray(A_t), np.asarray(C), np.asarray(Y)
         X, Y_, Z, K, T = A_t.shape
         P = X * Y_ * Z
@@ -471,7 +477,10 @@ class DeformableNMF:
             G = torch.empty((T, K, K), dtype=torch.float32, device=dev)
             r = torch.empty((T, K), dtype=torch.float32, device=dev)
             _gram_by_pairs(G, r, _dense_unions(K), gram)
-        return _mu_temporal(G, r, torch.from_numpy(np.asarray(C, dtype=np.float64)).to(dev), gamma, 1).cpu().numpy()
+        C0 = torch.from_numpy(np.asarray(C, dtype=np.float64)).to(dev)
+        if solver == 'hals':
+            return _hals_temporal(G, r, C0, gamma, iters)[0].cpu().numpy()
+        return _mu_temporal(G, r, C0, gamma, iters).cpu().numpy()
 
     @staticmethod
     def update_spatial(A, C, Y_i, D=None, gamma=None):
@@ -625,8 +634,16 @@ class DeformableNMF:
         return torch.cat(fr, 0).contiguous(), torch.cat(idx, 0)
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
-                          live_spatial=False, iter_a=1):
+                          live_spatial=False, iter_a=1, solver='mu'):
         """Reference :163-179: ``iter_c`` multiplicative updates of ``self.C`` under the current warp.
+
+        ``solver='hals'`` (extension) runs ``iter_c`` sweeps of the exact solver K4h instead, from the same ``self.C``, on
+        the same Gram data: cyclic coordinate descent on the non-negative least-squares problem the multiplicative update
+        only approaches (with ``gamma_c != 0`` red-black over the frames).  ``self.last_temporal_kkt`` then holds, per frame
+        of the call, how far the solver's float64 state was from that problem's solution after the last sweep (largest
+        projected-gradient entry) -- the state BEFORE ``self.C`` is rounded to float32: it falls to ~1e-15 of the gradient's
+        terms with enough sweeps, while the stored float32 traces sit at their rounding floor, ~1e-7
+        (``ops.hals_temporal_kkt`` on ``self.C`` gives that figure).
 
         Returns ``(A_t, Y_i, Y)`` like the reference when the dense float64 ``A_t`` fits
         ``DENSE_RETURN_LIMIT`` (or ``return_dense=True``); otherwise ``(None, None, None)``.
@@ -639,19 +656,34 @@ class DeformableNMF:
         mismatched shapes (:131, :169-176); here the update acts on the footprints the model uses."""
         fp = self.fp
         K, P = fp.K, fp.P
+        _check_solver(solver)
+        hals = solver == 'hals'
+        if hals:
+            _hals_refuse_shards(gamma_c, self.group)
         with torch.no_grad():
             frames, order = self._gather_frames(testloader)
             T_loc = frames.shape[0]
             Csel = self.C.to(device, torch.float32)[:, order.long()].contiguous()
             ly = self._lists_layout_for_fused_update(gamma_c)
+            kkt = None
             if ly is not None:
-                # K3n leaves its slot tables in the workspace and K4 reads them there: no dense (T,K,K) in between
+                # K3n leaves its slot tables in the workspace and K4 / K4h reads them there: no dense (T,K,K) in between
                 _, _, self._ws_k3 = ops.warp_gram_rhs_lists(ly, K, fp.sz_list, fp.beta.detach(), order, frames,
                                                             workspace=self._ws_k3, finish=False)
-                Cnew = ops.mu_temporal_slots(ly, self._ws_k3, fp.sz_list, Csel.clone(), iter_c)
+                if hals:
+                    Cnew, kkt = ops.hals_temporal_slots(ly, self._ws_k3, fp.sz_list, Csel.clone(), iter_c, kkt=True)
+                else:
+                    Cnew = ops.mu_temporal_slots(ly, self._ws_k3, fp.sz_list, Csel.clone(), iter_c)
             else:
                 G, r = self._gram_rhs(frames, order)
-                Cnew = _mu_temporal(G, r, Csel, gamma_c, iter_c, group=self.group, nbr=self._gram_nbr)
+                if hals:
+                    Cnew, kkt = _hals_temporal(G, r, Csel, gamma_c, iter_c, group=self.group, nbr=self._gram_nbr)
+                else:
+                    Cnew = _mu_temporal(G, r, Csel, gamma_c, iter_c, group=self.group, nbr=self._gram_nbr)
+            self.last_temporal_kkt = None if kkt is None else kkt.cpu()
+            if hals and self.verbose:
+                print('Temporal KKT: max %.3e median %.3e' % (float(self.last_temporal_kkt.max()),
+                                                              float(self.last_temporal_kkt.median())))
             C = self.C.to(device, torch.float32).clone()
             C[:, order.long()] = Cnew
             self.C = C
@@ -1083,14 +1115,15 @@ class DeformableNMF:
                 print('Reg: ' + str(out["reg"][j * nf:(j + 1) * nf]))
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
-            spatial=False, gamma_a=1e0):
+            spatial=False, gamma_a=1e0, solver='mu'):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
-        also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``)."""
+        also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
+        that call's (``'hals'``: the exact trace solver K4h)."""
         out = (None, None, None)
         for _ in range(outer):
             self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs)
             out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
-                                         iter_c=iter_c, live_spatial=spatial)
+                                         iter_c=iter_c, live_spatial=spatial, solver=solver)
         return out
 
 
@@ -1131,14 +1164,14 @@ class MultiChannelDNMF(DeformableNMF):
         return self.colours.shape[0]
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=False,
-                          live_spatial=False, iter_a=1):
+                          live_spatial=False, iter_a=1, solver='mu'):
         """As DeformableNMF.update_footprints on the channel sums; the dense ``A_t`` return is not offered.  With
         ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel) and
         ``fp.A`` takes ``iter_a`` steps of ``spatial_step``."""
         if return_dense:
             raise NotImplementedError("MultiChannelDNMF.update_footprints: return_dense")
         return super().update_footprints(testloader, batch_size, sz, gamma_c=gamma_c, gamma_a=gamma_a, iter_c=iter_c,
-                                         return_dense=False, live_spatial=live_spatial, iter_a=iter_a)
+                                         return_dense=False, live_spatial=live_spatial, iter_a=iter_a, solver=solver)
 
     def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
         """One multiplicative update of the (uncoloured) footprints ``fp.A`` from the registered frames of ALL channels
@@ -1206,6 +1239,39 @@ def _mu_temporal(G, r, C, gamma, iters, group=None, nbr=None):
         ops.mu_temporal_step(G, r, a, b, 0.0 if gamma is None else float(gamma), left, right)
         a, b = b, a
     return a.to(C.dtype)
+
+
+SOLVERS = ('mu', 'hals')
+
+
+def _check_solver(solver):
+    if solver not in SOLVERS:
+        raise ValueError(f"solver={solver!r}: expected one of {SOLVERS}")
+
+
+def _hals_refuse_shards(gamma, group):
+    """K4h's red-black order is defined on the whole time axis: the colour of a shard's first frame depends on its
+    global offset and the edges need an exchange per half sweep.  Not built."""
+    if gamma is not None and gamma != 0 and group is not None and torch.distributed.get_world_size(group) > 1:
+        raise NotImplementedError("solver='hals' with gamma_c != 0 on a time axis sharded over ranks is not implemented: "
+                                  "use solver='mu', gamma_c=0, or one rank")
+
+
+def _hals_temporal(G, r, C, gamma, iters, group=None, nbr=None):
+    """``iters`` sweeps of K4h on (T,K,K) / (T,K) Gram data, the counterpart of ``_mu_temporal``: ``(C', kkt)`` with C'
+    of C's dtype and kkt (T) float64, the largest projected-gradient entry per frame after the last sweep.
+
+    ``C`` fp32 and no neighbour term: one launch (fp64 inside, one rounding to fp32 at the end).  ``C`` fp64, or
+    gamma != 0: an fp64 copy takes ``iters`` red-black sweeps of two launches each (even frames, then odd frames)."""
+    _hals_refuse_shards(gamma, group)
+    if C.dtype == torch.float32 and (gamma is None or gamma == 0):
+        return ops.hals_temporal(G, r, C.contiguous().clone(), iters, nbr=nbr, kkt=True)
+    a = C.double().contiguous().clone()
+    g = 0.0 if gamma is None else float(gamma)
+    for _ in range(iters):
+        ops.hals_temporal_step(G, r, a, g, 0, nbr=nbr)
+        ops.hals_temporal_step(G, r, a, g, 1, nbr=nbr)
+    return a.to(C.dtype), ops.hals_temporal_kkt(G, r, a, g, nbr=nbr)
 
 
 class _Prefetch:

@@ -288,6 +288,74 @@ def mu_temporal_step(G, r, Cin, Cout, gamma: float, c_left=None, c_right=None):
     return Cout
 
 
+def _hals_nbr(fn, nbr, K):
+    """``(pointer, NN)`` of an optional (K,NN) int32 neighbour table."""
+    if nbr is None:
+        return 0, 0
+    if not (nbr.is_cuda and nbr.dtype == torch.int32 and nbr.is_contiguous() and nbr.dim() == 2 and nbr.shape[0] == K):
+        raise ValueError(f"{fn}: nbr must be a contiguous int32 CUDA tensor of shape (K={K}, NN)")
+    return nbr.data_ptr(), nbr.shape[1]
+
+
+def _hals_gram(fn, G, r, C):
+    """Shapes of G (T,K,K), r (T,K) against the state C (K,T); returns (K, T)."""
+    _f32(G, "G"), _f32(r, "r")
+    K, T = C.shape
+    if tuple(r.shape) != (T, K) or tuple(G.shape) != (T, K, K):
+        raise ValueError(f"{fn}: G {tuple(G.shape)}, r {tuple(r.shape)} do not match C (K={K}, T={T})")
+    return K, T
+
+
+def hals_temporal(G, r, C, iters: int, nbr=None, kkt=False):
+    """K4h without the neighbour term: ``iters`` sweeps of cyclic coordinate descent (k ascending) on
+    ``1/2 c^T G_t c - r_t^T c, c >= 0`` per frame; C (K,T) fp32 updated in place.  ``nbr`` as for ``mu_temporal``.
+    ``kkt=True``: returns ``(C, kkt)``, kkt (T) float64 = the largest projected-gradient entry per frame after the last
+    sweep (zero at the NNLS solution)."""
+    if not (C.is_cuda and C.dtype == torch.float32 and C.dim() == 2 and C.stride(1) == 1):
+        raise ValueError("hals_temporal: C must be float32 CUDA with unit inner stride")
+    K, T = _hals_gram("hals_temporal", G, r, C)
+    if int(iters) < 0:
+        raise ValueError(f"hals_temporal: iters={iters} < 0")
+    pn, NN = _hals_nbr("hals_temporal", nbr, K)
+    out = torch.empty((T,), dtype=torch.float64, device=C.device) if kkt else None
+    with _timed("hals_temporal"):
+        rc = _lib.load().dnmf_hals_temporal(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T, int(iters), pn, NN,
+                                            _ptr(out), _stream())
+    _lib.check(rc, "dnmf_hals_temporal")
+    return (C, out) if kkt else C
+
+
+def hals_temporal_step(G, r, C, gamma: float, parity: int, nbr=None):
+    """K4h, one half sweep with the neighbour term on the fp64 state C (K,T), in place: the frames ``parity, parity + 2,
+    ...`` are updated.  A sweep is parity 0, then parity 1."""
+    if not (C.is_cuda and C.dtype == torch.float64 and C.dim() == 2 and C.stride(1) == 1):
+        raise ValueError("hals_temporal_step: C must be float64 CUDA with unit inner stride")
+    if parity not in (0, 1):
+        raise ValueError(f"hals_temporal_step: parity={parity!r}, expected 0 or 1")
+    K, T = _hals_gram("hals_temporal_step", G, r, C)
+    pn, NN = _hals_nbr("hals_temporal_step", nbr, K)
+    with _timed("hals_temporal_step"):
+        rc = _lib.load().dnmf_hals_temporal_step(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T, float(gamma),
+                                                 int(parity), pn, NN, _stream())
+    _lib.check(rc, "dnmf_hals_temporal_step")
+    return C
+
+
+def hals_temporal_kkt(G, r, C, gamma: float = 0.0, nbr=None):
+    """(T) float64: the largest projected-gradient entry per frame of the fp64 state C (K,T) under ``gamma`` (the measure
+    ``hals_temporal(..., kkt=True)`` returns, for any state and with the neighbour term)."""
+    if not (C.is_cuda and C.dtype == torch.float64 and C.dim() == 2 and C.stride(1) == 1):
+        raise ValueError("hals_temporal_kkt: C must be float64 CUDA with unit inner stride")
+    K, T = _hals_gram("hals_temporal_kkt", G, r, C)
+    pn, NN = _hals_nbr("hals_temporal_kkt", nbr, K)
+    out = torch.empty((T,), dtype=torch.float64, device=C.device)
+    with _timed("hals_temporal_kkt"):
+        rc = _lib.load().dnmf_hals_temporal_kkt(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T,
+                                                0.0 if gamma is None else float(gamma), pn, NN, out.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_hals_temporal_kkt")
+    return out
+
+
 def render_frames(positions, traces, sz, shape_std, t0=0, T=None, out=None):
     """Simulator render loop on the GPU: frames t0..t0+T-1 of the video as (T,P) fp32."""
     X, Y, Z = (int(s) for s in sz)
@@ -511,6 +579,28 @@ def mu_temporal_slots(layout, workspace, sz, C, iters: int):
                                         int(iters), nbr.data_ptr(), nbr.shape[1], _stream())
     _lib.check(rc, "dnmf_mu_temporal_slots")
     return C
+
+
+def hals_temporal_slots(layout, workspace, sz, C, iters: int, kkt=False):
+    """K4h straight from the slot tables ``warp_gram_rhs_lists(..., finish=False)`` left in ``workspace``; C (K,T) fp32
+    updated in place (T = the frames of that launch).  Needs ``layout["nbr"]``.  ``kkt`` as for ``hals_temporal``."""
+    X, Y, Z = (int(s) for s in sz)
+    if not (C.is_cuda and C.dtype == torch.float32 and C.dim() == 2 and C.stride(1) == 1):
+        raise ValueError("hals_temporal_slots: C must be float32 CUDA with unit inner stride")
+    if int(iters) < 0:
+        raise ValueError(f"hals_temporal_slots: iters={iters} < 0")
+    K, T = C.shape
+    nbr = layout["nbr"]
+    if nbr is None:
+        raise ValueError("hals_temporal_slots: the layout has no neighbour lists (pattern wider than 32 columns)")
+    lib = _lib.load()
+    out = torch.empty((T,), dtype=torch.float64, device=C.device) if kkt else None
+    with _timed("hals_temporal_slots"):
+        rc = lib.dnmf_hals_temporal_slots(workspace.data_ptr(), lib.dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, T),
+                                          layout["nslot"], layout["pair_slot"].data_ptr(), C.data_ptr(), C.stride(0), K, T,
+                                          int(iters), nbr.data_ptr(), nbr.shape[1], _ptr(out), _stream())
+    _lib.check(rc, "dnmf_hals_temporal_slots")
+    return (C, out) if kkt else C
 
 
 class Communicator:

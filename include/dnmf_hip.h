@@ -244,6 +244,45 @@ int dnmf_mu_temporal_step(const float *G, const float *r, const double *Cin, dou
                           int T, double gamma, const double *c_left, const double *c_right,
                           dnmf_stream_t stream);
 
+/* ---- K4h: exact non-negative least-squares traces (HALS / cyclic coordinate descent) -------------------
+ * A second consumer of the G, r that K4 reads.  Per call it descends on
+ *   F(C) = sum_t ( 1/2 c_t^T G_t c_t - r_t^T c_t ) + gamma/2 sum_{t=0..T-2} |c_{t+1} - c_t|^2 ,  C >= 0
+ * (the function whose gradient K4 splits, replicated edges included) one coordinate at a time.  With n_t the number of
+ * real neighbours of frame t (2 inside, 1 at an end, 0 when T = 1) the update of (k,t) is
+ *   d = G_t[k,k] + gamma n_t
+ *   c_k <- d > 0 ? max(0, (r_t[k] - sum_{l != k} G_t[k,l] c_l + gamma (c_{k,t-1} + c_{k,t+1}, real neighbours only)) / d) : 0
+ * No 1e-32 enters; d == 0 (a footprint that is zero everywhere under this warp, gamma = 0) gives 0.  Arithmetic in fp64;
+ * the kernel carries the gradient and applies c_k - grad_k / d, which differs from the formula in fp64 rounding only.
+ * Sweep order (part of the contract: results are deterministic): k = 0 .. K-1 ascending in every frame; with gamma != 0
+ * all even frames first, then all odd frames (red-black in t), each half sweep one launch.
+ *   G (T,K,K) fp32 symmetric, r (T,K) fp32, K <= 256 (DNMF_E_UNSUPPORTED beyond).
+ *   nbr: NULL, or (K,NN) int32, NN in {8,16,32}: per row the columns that can be non-zero, distinct, in [0,K), padded
+ *     with columns that cannot (the lists of K3n's pattern): only those entries of G are read; same result, since a
+ *     column outside the pattern holds an exact zero.  An entry outside [0,K) is skipped (it breaks the contract; nothing is
+ *     read out of bounds for it).  NN is ignored when nbr is NULL.
+ *   kkt: NULL, or (T) fp64: after the last sweep kkt[t] = max_k |pg_k| on the fp64 state, pg_k = grad_k if c_k > 0 else
+ *     min(grad_k, 0), grad = G c - r + gamma (n_t c - neighbours): zero exactly at a solution.  On the fp32 forms this is
+ *     the state BEFORE its rounding to fp32: it says how far the sweeps got (down to ~1e-15 of the gradient's terms), while
+ *     the stored fp32 traces sit at their rounding floor (~1e-7 of them); dnmf_hals_temporal_kkt on the stored traces
+ *     gives that figure.
+ *
+ * dnmf_hals_temporal: gamma = 0, `iters` sweeps in one launch (frames are independent); C (K,T) fp32, row stride ldc,
+ *   in/out, rounded to fp32 once at the end like dnmf_mu_temporal.  iters = 0 leaves C alone and still fills kkt.
+ * dnmf_hals_temporal_slots: the same straight from the slot tables of K3n (arguments as dnmf_mu_temporal_slots): entry
+ *   (k,l) is the ordered sum over the chunks of slot pair_slot[k][l], r[k] that of slot k, the slot nslot-1 a zero.
+ * dnmf_hals_temporal_step: ONE half sweep with the neighbour term on an fp64 state C (K,T), row stride ldc, in place:
+ *   the frames t = parity, parity + 2, ... are updated from their neighbours of the other colour; parity in {0,1}.  A full
+ *   sweep is parity 0, then parity 1.  The frames of the call are the whole time axis (no shard edges).
+ * dnmf_hals_temporal_kkt: kkt (T) as above for an fp64 state C and any gamma (also 0); C is only read. */
+int dnmf_hals_temporal(const float *G, const float *r, float *C, long ldc, int K, int T, int iters, const int *nbr, int NN,
+                       double *kkt, dnmf_stream_t stream);
+int dnmf_hals_temporal_slots(const float *slab, int nchunks, int nslot, const int *pair_slot, float *C, long ldc, int K,
+                             int T, int iters, const int *nbr, int NN, double *kkt, dnmf_stream_t stream);
+int dnmf_hals_temporal_step(const float *G, const float *r, double *C, long ldc, int K, int T, double gamma, int parity,
+                            const int *nbr, int NN, dnmf_stream_t stream);
+int dnmf_hals_temporal_kkt(const float *G, const float *r, const double *C, long ldc, int K, int T, double gamma,
+                           const int *nbr, int NN, double *kkt, dnmf_stream_t stream);
+
 /* ---- K5 / K6: multiplicative update of the footprints -----------------------------------------------
  * DeformableNMF.update_spatial (Demix/dNMF.py:151-160).
  * dnmf_spatial_accum: A1[p,k] = sum_t Y[t,p] C[k,t] (fp32 MFMA, dNMF.py:154) and Cs = C C^T (dNMF.py:153) over
