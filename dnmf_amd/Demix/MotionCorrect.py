@@ -267,6 +267,25 @@ class MotionCorrect(object):
         sh = np.stack([np.stack(self.x_shifts_els[:T]), np.stack(self.y_shifts_els[:T]), np.stack(self.z_shifts_els[:T])], 2)
         return torch.from_numpy(sh.astype(np.float32)).to(device)
 
+    def detect_points(self, K, shape_std=3, **kw):
+        """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
+        made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,
+        ``threshold``, ``background``): the ``points`` ``apply_shifts_points`` takes, float64 numpy, brightest first.  The
+        reference has no counterpart (its real data comes with annotated positions)."""
+        if not self.is3D:
+            raise NotImplementedError("MotionCorrect.detect_points is a 3-D function like apply_shifts_points; register 2-D "
+                                      "videos as (T, X, Y, 1) with is3D=True")
+        tmpl = getattr(self, "total_template_els", None)
+        if tmpl is None:
+            tmpl = getattr(self, "total_template_rig", None)
+        if tmpl is None:
+            raise ValueError("MotionCorrect.detect_points: no template yet, call motion_correct() first")
+        from .dNMF import ExponentialFP
+        tmpl = tmpl if torch.is_tensor(tmpl) else np.asarray(tmpl)
+        pos, _ = ExponentialFP.detect_positions(tmpl, K, shape_std=shape_std, **kw)
+        pos = pos.cpu().numpy() if torch.is_tensor(pos) else pos
+        return pos[np.isfinite(pos).all(1)].astype(np.float64)
+
     def apply_shifts_points(self, video, points):
         """Reference :351-371: ``P_T`` (K, 3, T) float64 numpy -- point k in frame t, moved by the shifts of the patch whose
         centre is nearest to it, relative to frame 0."""

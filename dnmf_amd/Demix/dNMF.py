@@ -385,13 +385,31 @@ class ExponentialFP(nn.Module):
             out = torch.take(flat, idx.reshape(-1).to(device=flat.device, dtype=torch.int64)).reshape(shape)
         return out if on_gpu else out.cpu().numpy()
 
+    @staticmethod
+    def detect_positions(image, K, shape_std=3, **kw):
+        """Where the neurons are in a template volume ``image`` (X,Y,Z) -- a frame, a mean image, ``MotionCorrect``'s
+        template: ``(positions (K,3), amplitudes (K,))`` of up to K blobs exp(-|x - p|^2 / shape_std^2), brightest first, by
+        K14 (``ops.detect_neurons``, whose ``min_distance``, ``threshold`` and ``background`` pass through ``kw``).  Rows
+        beyond the number found are NaN, the "not tracked" of ``init_motion``.  numpy or CPU-torch in, numpy out; a CUDA
+        ``image`` gives CUDA tensors.  The reference has no counterpart: its real data comes with annotated positions."""
+        on_gpu = isinstance(image, torch.Tensor) and image.is_cuda
+        img = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+        if img.dim() != 3:
+            raise ValueError(f"detect_positions: image must be (X,Y,Z), got {tuple(img.shape)}")
+        img = img.to(device, torch.float32).contiguous()
+        pos, amp, _ = ops.detect_neurons(img, img.shape, K, shape_std=shape_std, **kw)
+        return (pos, amp) if on_gpu else (pos.cpu().numpy(), amp.cpu().numpy())
+
 
 class DeformableNMF:
     """Reference ``Demix/dNMF.py:124-194``: owns the spatial model ``fp`` and the traces ``C`` (K,T)."""
 
+    # footprint width the constructor builds ``fp`` with: the reference's 3; from_image sets its own on the instance first
+    _shape_std = 3
+
     def __init__(self, sz, K, T, positions=None):
         self.SpatialModel = ExponentialFP
-        self.fp = self.SpatialModel(sz=sz, K=K, T=T, positions=positions)
+        self.fp = self.SpatialModel(sz=sz, K=K, T=T, positions=positions, shape_std=self._shape_std)
         self.C = torch.rand((K, T)).to(device)
         self.A = torch.rand((K, _sz_list(sz)[0], _sz_list(sz)[1])).to(device)  # unused in the reference too (:131)
         self.verbose = True
@@ -446,6 +464,23 @@ class DeformableNMF:
         self._D_dev = None         # (id(self.D), fp32 device copy of D flattened to (P,K))
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
         self._warned = set()
+
+    @classmethod
+    def from_image(cls, image, K, T, shape_std=3, **kw):
+        """A model on the centres ``ExponentialFP.detect_positions(image, K, shape_std, **kw)`` finds in ``image`` (X,Y,Z): as
+        many neurons as were found (at most K; ValueError when none), footprints of width ``shape_std``, the width the
+        detection matched."""
+        pos, _ = ExponentialFP.detect_positions(image, K, shape_std=shape_std, **kw)
+        pos = torch.as_tensor(pos).to(device)
+        n = int(torch.isfinite(pos).all(1).sum())     # the found rows come first
+        if n == 0:
+            raise ValueError(f"from_image: no neuron found in the image (K={K}, shape_std={shape_std}, {kw})")
+        sz = torch.tensor([int(s) for s in image.shape])
+        positions = pos[:n].float().contiguous()
+        model = cls.__new__(cls)
+        model._shape_std = shape_std                  # read by __init__ where it builds fp
+        model.__init__(sz, n, T, positions=positions)
+        return model
 
     # ---- static NMF updates (numpy in / numpy out like the reference) ---------------------------------
     @staticmethod

@@ -967,6 +967,39 @@ def roi_signals(frames, sz, P, window=(3, 3, 0)):
     return out
 
 
+def detect_neurons(image, sz, K, shape_std=3, min_distance=None, threshold=0.0, background=None, workspace=None):
+    """K14.  image: X Y Z float32 CUDA values (any shape with that many, voxel order of a frame row) -> ``(positions (K,3)
+    fp32, amplitudes (K,) fp32, count (0-dim int32))`` on the device: the centres of up to K blobs exp(-|x - p|^2 /
+    shape_std^2) by a greedy matched-filter pursuit (include/dnmf_hip.h), brightest first; rows from ``count`` on are NaN.
+    ``min_distance`` (None: 2 shape_std): no two centres are closer; a pick must score above ``threshold``; ``background``
+    (None: the image's median) is subtracted first."""
+    X, Y, Z = (int(s) for s in sz)
+    _f32(image, "image")
+    if image.numel() != X * Y * Z:
+        raise ValueError(f"detect_neurons: image of {image.numel()} values for a volume {X}x{Y}x{Z}")
+    sigma, K = float(shape_std), int(K)
+    if not (sigma > 0.0 and sigma != float("inf")):
+        raise ValueError(f"detect_neurons: shape_std={shape_std} must be positive and finite")
+    if K < 1:
+        raise ValueError(f"detect_neurons: K={K} must be at least 1")
+    md = 2.0 * sigma if min_distance is None else float(min_distance)
+    bg = float(image.median()) if background is None else float(background)
+    dev = image.device
+    lib = _lib.load()
+    need = lib.dnmf_detect_neurons_workspace(_int3((X, Y, Z)), K, sigma)
+    if need == 0:
+        raise _lib.DnmfHipError(f"dnmf_detect_neurons_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
+    workspace = _workspace(workspace, need, dev)
+    positions = torch.empty((K, 3), dtype=torch.float32, device=dev)
+    amplitudes = torch.empty((K,), dtype=torch.float32, device=dev)
+    count = torch.empty((), dtype=torch.int32, device=dev)
+    with _timed("detect_neurons"):
+        rc = lib.dnmf_detect_neurons(image.data_ptr(), _int3((X, Y, Z)), K, sigma, md, float(threshold), bg, positions.data_ptr(),
+                                     amplitudes.data_ptr(), count.data_ptr(), workspace.data_ptr(), _nbytes(workspace), _stream())
+    _lib.check(rc, "dnmf_detect_neurons")
+    return positions, amplitudes, count
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

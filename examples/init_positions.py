@@ -5,7 +5,12 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect]
+
+``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
+ground truth of frame 0; the model is built on the detected centres alone, as many neurons as were found.  The simulator's
+centres then serve only to judge the result: a detected centre is matched to the simulated neuron nearest to it in frame 0
+when that is within sigma (one centre per neuron), and the errors and correlations are taken over the matched ones.
 """
 import argparse
 import os
@@ -29,6 +34,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-6, help="Adam step of the motion update")
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=10)
+    ap.add_argument("--detect", action="store_true", help="find the centres in the template instead of taking the simulator's")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -41,9 +47,24 @@ def main():
     mc = MotionCorrect(video, max_shifts=(12, 12, 1), strides=(stride, stride, 1), overlaps=(stride // 2, stride // 2, 1),
                        max_deviation_rigid=3, is3D=True, pw_rigid=True)
     mc.motion_correct()                                              # template=None: rigid pass first
-    P_T = mc.apply_shifts_points(video, truth[:, :, 0])              # (K, 3, T)
-    still = np.abs(truth[:, :2, :] - truth[:, :2, :1]).mean()        # error of "the neurons do not move"
-    err = np.abs(P_T[:, :2, :] - truth[:, :2, :]).mean()
+    # pts: the centres the tracks start from; sel / tr: rows of pts and the simulated neurons they are judged against
+    if a.detect:
+        shape_std = 3.0
+        pts = mc.detect_points(K, shape_std=shape_std)               # (n, 3), brightest first
+        d = np.linalg.norm(pts[:, None, :2] - truth[None, :, :2, 0], axis=2)     # in the plane, like the errors below
+        nearest = d.argmin(1)
+        sel = np.array([j for j in range(len(pts)) if d[j, nearest[j]] <= shape_std and j == d[:, nearest[j]].argmin()], dtype=int)
+        tr = nearest[sel]
+        if len(sel) == 0:
+            raise SystemExit(f"detect_points: {len(pts)} centres, none within {shape_std:g} voxels of a simulated neuron")
+        print(f"detect_points: {len(pts)} centres; {len(sel)} of the simulator's {K} neurons have one within "
+              f"{shape_std:g} voxels, mean distance of those {d[sel, tr].mean():.2f} voxels")
+    else:
+        pts, sel, tr = truth[:, :, 0], np.arange(K), np.arange(K)
+    n = len(pts)
+    P_T = mc.apply_shifts_points(video, pts)                         # (n, 3, T)
+    still = np.abs(truth[tr, :2, :] - truth[tr, :2, :1]).mean()      # error of "the neurons do not move"
+    err = np.abs(P_T[sel, :2, :] - truth[tr, :2, :]).mean()
     print(f"video {tuple(video.shape)}, {len(mc.x_shifts_els[0])} patches; rigid shifts up to "
           f"{np.abs(np.array(mc.shifts_rig)).max():.1f} voxels")
     print(f"mean |x, y error| of the per-frame centres: {err:.2f} voxels with the initialiser, {still:.2f} without")
@@ -52,11 +73,11 @@ def main():
     from dnmf_amd.WUtils.Simulator import get_roi_signals
 
     def median_corr(S):
-        return float(np.median([np.corrcoef(S[k], dataset.traces[k])[0, 1] for k in range(K)]))
+        return float(np.median([np.corrcoef(S[j], dataset.traces[k])[0, 1] for j, k in zip(sel, tr)]))
 
     for start in ("identity", "tracks"):
         torch.manual_seed(1)
-        dn = DeformableNMF(sz, K, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
+        dn = DeformableNMF(sz, n, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
         dn.verbose = False
         if start == "tracks":
             ok = dn.init_motion(P_T, ridge=a.ridge)
@@ -64,7 +85,7 @@ def main():
         loader = dataset.loader(a.batch)
         dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
         where = dn.positions()
-        dist = float(np.nanmean(np.linalg.norm(where[:, :2, :] - truth[:, :2, :], axis=1)))
+        dist = float(np.nanmean(np.linalg.norm(where[sel, :2, :] - truth[tr, :2, :], axis=1)))
         # the simulator places centres up to half a voxel beyond the last slice: read the box of the nearest voxel inside
         inside = np.clip(np.nan_to_num(where, nan=-1.0), 0, (sz.numpy() - 1)[None, :, None])
         roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))

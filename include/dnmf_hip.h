@@ -515,6 +515,35 @@ int dnmf_invert_quadratic_warp(const float *beta, int T, const int *times, int B
 int dnmf_roi_signals(const float *frames, long ldf, int X, int Y, int Z, const void *tracks, int tracks_f64, int K, int T,
                      const int *window, double *out, dnmf_stream_t stream);
 
+/* ---- K14: neuron centres of a template volume ----------------------------------------------------------------------------
+ * A greedy matched-filter pursuit with the footprint model's own Gaussian (Demix/dNMF.py:39-40), g1(d) = exp(-d^2 / sigma^2)
+ * truncated at r = ceil(3 sigma) voxels per axis; the reference has no counterpart (its real data ships with annotated
+ * positions).  tests/detect_restatement.py is the definition in float64; all arithmetic here is fp32.
+ *   filter   R = g (*) (img - background), separable, zero padding;
+ *   score    S(q) = R(q) prod_axis sqrt(nmax / n(q)), n(q) = the sum of the squared taps that fall inside the volume at q, nmax
+ *            its value in the middle of the axis: S = R wherever the window is inside the volume, the same noise level
+ *            everywhere, and the peak of a blob cut by the border stays on its centre;
+ *   pursuit  up to K times: p* = arg-max S (equal scores: the lowest voxel index; NaN scores never win), stop when S(p*) <=
+ *            threshold or is not finite; per axis the peak of the parabola through ln S at p* and its two neighbours (at the
+ *            first / last voxel of an axis of >= 3: p* and the two voxels inward), where those scores are > 0 and the parabola
+ *            is concave, clamped to +-1/2 voxel: between two neighbours delta = (ln m - ln q) / (2 (ln m - 2 ln c + ln q)),
+ *            ln S^ = ln c - sum (ln m - ln q) delta / 4; centre p^ = p* + delta (p^ = p*, S^ = S(p*) when p^ would lie within
+ *            min_distance of an earlier centre); amplitude a = S^ / sqrt(prod_axis nmax sum_x g1(x - p^)^2) over the voxels of
+ *            the volume within r of p*: the least-squares amplitude of the truncated footprint; S(q) -= a prod_axis sqrt(nmax /
+ *            n(q)) sum_x g1(x - q) g1(x - p^) (same x, |x - q| <= r: the score of that footprint); S = -inf where
+ *            |q - p^|_2 <= min_distance.
+ * img: X Y Z floats, voxel p = (x Y + y) Z + z; sz: 3 host ints.  positions (K,3), amplitudes (K) fp32 and count (one int) on
+ * the device; rows from count on are NaN.  One call is four launches (two filter passes, the table of tile maxima, one
+ * workgroup that runs the whole pursuit) and no host synchronisation.  workspace: 4-byte aligned,
+ * dnmf_detect_neurons_workspace(sz, K, sigma) bytes (0 on bad arguments) = two volumes and the table.
+ * DNMF_E_SHAPE: sigma <= 0 or not finite, K < 1, a size < 1, min_distance < 0 or not finite, background not finite, threshold
+ * NaN or +inf;  DNMF_E_UNSUPPORTED: sigma > 32, min_distance > 509, 2^31 voxels or more;  DNMF_E_WORKSPACE: a short or
+ * misaligned workspace (nothing is launched). */
+size_t dnmf_detect_neurons_workspace(const int *sz, int K, double sigma);
+int dnmf_detect_neurons(const float *img, const int *sz, int K, double sigma, double min_distance, double threshold, double background,
+                        float *positions, float *amplitudes, int *count, void *workspace, size_t workspace_bytes,
+                        dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
