@@ -33,8 +33,6 @@ def _stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-# sources that include another source
-EXTRA_DEPS = {"warp_gram_lists_z.hip": ["warp_gram_lists.hip"]}
 # what the last build_library() call did: "compiled" or "reused" (the library was newer than every source)
 LAST_ACTION = None
 # flags of single files (measured per kernel)
@@ -45,12 +43,11 @@ PER_FILE_FLAGS = {
     # K7: the same -- the packed operations come with s_nop wait states between dependent ones
     # (512x512 x 4000 frames: 3.65 ms against 4.14; 512x512x2 x 1000: 5.56 against 7.01)
     "image_iwarp.hip": ["-fno-slp-vectorize"],
-    # K3n for Z >= 2: packed operations want their operands in register pairs -- 200 registers instead of 150, spills
-    # (512x512x2x4000: 19.9 ms against 6.6)
-    "warp_gram_lists_z.hip": ["-fno-slp-vectorize"],
-    # ... and its Z == 1 instantiations: 2.95 ms against 3.01 per 4000 frames of 512x512, K = 100, same box, on the final
-    # code of round 3 (an earlier state of the kernel spilled vector registers without the vectoriser and lost)
+    # K3n, both units (two only so that they compile side by side).  Z >= 2: packed operations want their operands in
+    # register pairs -- 200 registers instead of 150, spills (512x512x2x4000: 19.9 ms against 6.6).  Z == 1: 2.95 ms against
+    # 3.01 per 4000 frames of 512x512, K = 100, same box
     "warp_gram_lists.hip": ["-fno-slp-vectorize"],
+    "warp_gram_lists_z.hip": ["-fno-slp-vectorize"],
 }
 
 
@@ -101,7 +98,7 @@ def build_library(force: bool = False, verbose: bool = True, out: str | None = N
             extra.append(stamp)
         src, obj = os.path.join(CSRC, s), os.path.join(objdir_for(extra), s + ".o")
         objs.append(obj)
-        dep_time = max([os.path.getmtime(src), hdr_time, *[os.path.getmtime(os.path.join(CSRC, d)) for d in EXTRA_DEPS.get(s, [])]])
+        dep_time = max(os.path.getmtime(src), hdr_time)
         if force or not os.path.exists(obj) or os.path.getmtime(obj) < dep_time:
             jobs.append(([hipcc, *cflags, *extra, "-c", src, "-o", obj], s))
     if verbose:

@@ -62,7 +62,7 @@ def main():
         for d in dims[:-1]:
             P *= d
         zm = 1 if len(dims) == 3 else (2 if dims[2] == 2 else 3)
-        lists = ["warp_gram_lists.hip", "common.hpp"] + (["warp_gram_lists_z.hip"] if zm > 1 else [])
+        lists = ["warp_gram_lists.hip", "warp_gram_lists.hpp", "common.hpp"] + (["warp_gram_lists_z.hip"] if zm > 1 else [])
         p1 = kernels(s, [f"warp_gram_lists_kernel<{zm}, "])
         one = {k.rpartition(":")[0] for k in s if k.startswith(f"warp_gram_lists_kernel<{zm}, ")}
         tm = kernels(s, ["lists_tilemask_kernel"])
