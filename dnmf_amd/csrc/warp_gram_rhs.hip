@@ -25,17 +25,14 @@
 // Warp.  Coordinates, floors and corner weights are computed once per voxel by one lane (64 voxels per
 // pass), parked in wave-private LDS and re-read as broadcasts by the 16 lanes that share the voxel.
 // The fp32 sequence for the coordinates is common.hpp's (bit-compatible with the reference's
-// normalise / grid_sample un-normalise round trip).
-#include "common.hpp"
+// normalise / grid_sample un-normalise round trip).  The argument block, voxel_record, wave_fence and the host plan
+// are warp_gram_mfma.hpp's, shared with K3s.
+#include "warp_gram_mfma.hpp"
 
 namespace dnmf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x3 __attribute__((ext_vector_type(3)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int K3_SS = 64;  // voxels per coordinate pass (one per lane)
 
 template <int NB>
 __host__ __device__ constexpr int chan_of(int b, int i) {
@@ -43,8 +40,6 @@ __host__ __device__ constexpr int chan_of(int b, int i) {
     if (b < 4 * NG4) return 64 * (b / 4) + 4 * i + (b % 4);
     return base + R * i + (b - 4 * NG4);
 }
-
-__host__ __device__ constexpr int tile_index(int NB, int bi, int bj) { return bi * NB - bi * (bi - 1) / 2 + (bj - bi); }
 
 // NB fragment values of one footprint row for lane slot i (channel permutation above): NB/4 16-byte loads
 // at byte 256 g + 16 i plus one 4*(NB%4)-byte load at byte 256 (NB/4) + 4 (NB%4) i.
@@ -76,47 +71,8 @@ struct GramParams {
     const float *Apk;
     long a_frame_stride;
     int Kp, K;
-    Volume vol;
-    const float *beta;
-    int T;
-    const int *times;
-    int B;
-    const float *frames;
-    long ldf;
-    const int *frame_ids;
-    float *slab;       // (B, nchunks, NT, 64, 4)
-    int nchunks;
-    long chunk_len;    // passes (patches of 64 voxels) per chunk
-    // a pass is a compact patch of 2^lgx x 2^lgy x 2^lgz = 64 voxels (8x8 for Z == 1): its gathers touch ~80
-    // distinct footprint rows instead of the ~130 of a 64-voxel run, so more of them hit in L1
-    int lgy, lgz, npy, npz;
-    long npatch;
+    GramCommon c;  // c.slab: (B, nchunks, NT, 64, 4)
 };
-
-// Voxel record of the coordinate pass: byte offsets of the NTAP footprint rows, their weights (0 outside the volume,
-// and for a voxel of a patch that sticks out of the volume) and the frame value.
-template <int NTAP>
-__device__ __forceinline__ void voxel_record(const float *bt, const Volume &vol, unsigned row_bytes,
-                                             const float *__restrict__ yb, int x, int y, int z, unsigned (&rows)[NTAP],
-                                             float (&w)[NTAP], float &yv) {
-#pragma unroll
-    for (int c = 0; c < NTAP; ++c) rows[c] = 0u, w[c] = 0.0f;
-    yv = 0.0f;
-    if (x < vol.X && y < vol.Y && z < vol.Z) {
-        unsigned voxs[NTAP];
-        if (bt) {
-            const Sample sm = make_sample_t<(NTAP == 8)>(bt, vol, x, y, z);
-            make_taps<NTAP>(sm, vol, w, voxs);
-        } else {   // no warp (beta == NULL): the footprint row of the voxel itself, weight 1 -- exact on any lattice
-            const unsigned self = (unsigned)((x * vol.Y + y) * vol.Z + z);
-#pragma unroll
-            for (int c = 0; c < NTAP; ++c) voxs[c] = self, w[c] = c == 0 ? 1.0f : 0.0f;
-        }
-#pragma unroll
-        for (int c = 0; c < NTAP; ++c) rows[c] = voxs[c] * row_bytes;
-        yv = yb[((long)x * vol.Y + y) * vol.Z + z];
-    }
-}
 
 // NTAP = 4 (Z == 1, bilinear) or 8 (trilinear).  Tap c: dx = c&1, dy = (c>>1)&1, dz = c>>2 (ATen's corner order).
 //
@@ -130,24 +86,24 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_kernel(GramP
     constexpr int NT = NB * (NB + 1) / 2;
     constexpr int NQ = NTAP / 4;
     constexpr int NG4 = NB / 4, R = NB % 4;
-    __shared__ u32x4 s_row[4][2][NQ][K3_SS];
-    __shared__ f32x4 s_w[4][2][NQ][K3_SS];
-    __shared__ float s_y[4][2][K3_SS];
+    __shared__ u32x4 s_row[4][2][NQ][GRAM_SS];
+    __shared__ f32x4 s_w[4][2][NQ][GRAM_SS];
+    __shared__ float s_y[4][2][GRAM_SS];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long item = (long)blockIdx.x * 4 + wave;  // chunk-major: neighbours share footprint rows in L2
-    if (item >= (long)p.nchunks * p.B) return;      // whole wave leaves; no workgroup barrier below
-    const int chunk = (int)(item / p.B);
-    const int b = (int)(item - (long)chunk * p.B);
-    const int t = p.times ? p.times[b] : b;
+    if (item >= (long)p.c.nchunks * p.c.B) return;    // whole wave leaves; no workgroup barrier below
+    const int chunk = (int)(item / p.c.B);
+    const int b = (int)(item - (long)chunk * p.c.B);
+    const int t = p.c.times ? p.c.times[b] : b;
     const char *__restrict__ Ab = reinterpret_cast<const char *>(p.Apk + (long)b * p.a_frame_stride);
-    const float *__restrict__ yb = p.frames + (long)(p.frame_ids ? p.frame_ids[b] : b) * p.ldf;
-    const Volume vol = p.vol;
+    const float *__restrict__ yb = p.c.frames + (long)(p.c.frame_ids ? p.c.frame_ids[b] : b) * p.c.ldf;
+    const Volume vol = p.c.vol;
     const unsigned row_bytes = (unsigned)p.Kp * 4u;
 
     float bt[30];
-    if (p.beta) load_beta(p.beta, p.T, t, bt);
+    if (p.c.beta) load_beta(p.c.beta, p.c.T, t, bt);
 
     const int ci = lane & 15;   // channel slot
     const int vq = lane >> 4;   // voxel slot inside a k-step
@@ -158,27 +114,26 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_kernel(GramP
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const long q_begin = (long)chunk * p.chunk_len;
-    const long q_end = q_begin + p.chunk_len < p.npatch ? q_begin + p.chunk_len : p.npatch;
+    const long q_begin = (long)chunk * p.c.chunk_len;
+    const long q_end = q_begin + p.c.chunk_len < p.c.npatch ? q_begin + p.c.chunk_len : p.c.npatch;
     const int nss = (int)(q_end - q_begin);
-    const int nk = nss * (K3_SS / 4);
+    const int nk = nss * (GRAM_SS / 4);
     // patch origin of the next coordinate pass (wave-uniform, advanced with carries); lane -> voxel in the patch
-    const int lgy = p.lgy, lgz = p.lgz, lgx = 6 - lgy - lgz;
-    int pz = (int)(q_begin % p.npz), py = (int)((q_begin / p.npz) % p.npy), px = (int)(q_begin / ((long)p.npz * p.npy));
+    const int lgy = p.c.lgy, lgz = p.c.lgz, lgx = 6 - lgy - lgz;
+    int pz = (int)(q_begin % p.c.npz), py = (int)((q_begin / p.c.npz) % p.c.npy), px = (int)(q_begin / ((long)p.c.npz * p.c.npy));
     const int lz = lane & ((1 << lgz) - 1), ly = (lane >> lgz) & ((1 << lgy) - 1), lx = lane >> (lgz + lgy);
-
-    // coordinate pass s (called for s = 0, 1, 2, ... in order): lane -> one voxel of patch q_begin + s, record into
+    // coordinate pass s (called for s = 0, 1, 2, ... in order): lane -> one voxel of the item's next patch, record into
     // LDS buffer s & 1
     auto coord_pass = [&](int s) {
         const int x = (px << lgx) + lx, y = (py << lgy) + ly, z = (pz << lgz) + lz;
-        if (++pz == p.npz) {
+        if (++pz == p.c.npz) {
             pz = 0;
-            if (++py == p.npy) py = 0, ++px;
+            if (++py == p.c.npy) py = 0, ++px;
         }
         unsigned rows[NTAP];
         float w[NTAP];
         float yv;
-        voxel_record<NTAP>(p.beta ? bt : nullptr, vol, row_bytes, yb, x, y, z, rows, w, yv);
+        voxel_record<NTAP>(p.c.beta ? bt : nullptr, vol, row_bytes, yb, x, y, z, rows, w, yv);
         const int buf = s & 1;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -186,12 +141,6 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_kernel(GramP
             s_w[wave][buf][q][lane] = f32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
         }
         s_y[wave][buf][lane] = yv;
-    };
-    // LDS traffic of one wave is processed in order; only the compiler has to be kept from reordering
-    auto wave_fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
 
     struct Stage {
@@ -283,13 +232,13 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_kernel(GramP
         if (s + 1 < nss) coord_pass(s + 1);
         wave_fence();
 #pragma unroll 1
-        for (int kk = s * (K3_SS / 4); kk < (s + 1) * (K3_SS / 4); kk += 2) {
+        for (int kk = s * (GRAM_SS / 4); kk < (s + 1) * (GRAM_SS / 4); kk += 2) {
             step(kk + 2, sa, sb, fb, fa);
             step(kk + 3, sb, sa, fa, fb);
         }
     }
 
-    f32x4 *out = reinterpret_cast<f32x4 *>(p.slab) + (((long)b * p.nchunks + chunk) * NT) * 64 + lane;
+    f32x4 *out = reinterpret_cast<f32x4 *>(p.c.slab) + (((long)b * p.c.nchunks + chunk) * NT) * 64 + lane;
 #pragma unroll
     for (int i = 0; i < NT; ++i) out[(long)i * 64] = acc[i];
 }
@@ -353,24 +302,24 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_bf16_kernel(
     constexpr int NT = NB * (NB + 1) / 2;
     constexpr int NQ = NTAP / 4;
     constexpr int NG4 = NB / 4, R = NB % 4;
-    __shared__ u32x4 s_row[4][2][NQ][K3_SS];
-    __shared__ f32x4 s_w[4][2][NQ][K3_SS];
-    __shared__ float s_y[4][2][K3_SS];
+    __shared__ u32x4 s_row[4][2][NQ][GRAM_SS];
+    __shared__ f32x4 s_w[4][2][NQ][GRAM_SS];
+    __shared__ float s_y[4][2][GRAM_SS];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= (long)p.nchunks * p.B) return;  // whole wave leaves; no workgroup barrier below
-    const int chunk = (int)(item / p.B);
-    const int b = (int)(item - (long)chunk * p.B);
-    const int t = p.times ? p.times[b] : b;
+    const long item = (long)blockIdx.x * 4 + wave;  // chunk-major: neighbours share footprint rows in L2
+    if (item >= (long)p.c.nchunks * p.c.B) return;    // whole wave leaves; no workgroup barrier below
+    const int chunk = (int)(item / p.c.B);
+    const int b = (int)(item - (long)chunk * p.c.B);
+    const int t = p.c.times ? p.c.times[b] : b;
     const char *__restrict__ Ab = reinterpret_cast<const char *>(p.Apk + (long)b * p.a_frame_stride);
-    const float *__restrict__ yb = p.frames + (long)(p.frame_ids ? p.frame_ids[b] : b) * p.ldf;
-    const Volume vol = p.vol;
+    const float *__restrict__ yb = p.c.frames + (long)(p.c.frame_ids ? p.c.frame_ids[b] : b) * p.c.ldf;
+    const Volume vol = p.c.vol;
     const unsigned row_bytes = (unsigned)p.Kp * 4u;
 
     float bt[30];
-    if (p.beta) load_beta(p.beta, p.T, t, bt);
+    if (p.c.beta) load_beta(p.c.beta, p.c.T, t, bt);
 
     const int ci = lane & 15;  // channel slot
     const int kq = lane >> 4;  // which eight voxels of a group of 32
@@ -381,23 +330,25 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_bf16_kernel(
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const long q_begin = (long)chunk * p.chunk_len;
-    const long q_end = q_begin + p.chunk_len < p.npatch ? q_begin + p.chunk_len : p.npatch;
+    const long q_begin = (long)chunk * p.c.chunk_len;
+    const long q_end = q_begin + p.c.chunk_len < p.c.npatch ? q_begin + p.c.chunk_len : p.c.npatch;
     const int nss = (int)(q_end - q_begin);
-    const int lgy = p.lgy, lgz = p.lgz, lgx = 6 - lgy - lgz;
-    int pz = (int)(q_begin % p.npz), py = (int)((q_begin / p.npz) % p.npy), px = (int)(q_begin / ((long)p.npz * p.npy));
+    // patch origin of the next coordinate pass (wave-uniform, advanced with carries); lane -> voxel in the patch
+    const int lgy = p.c.lgy, lgz = p.c.lgz, lgx = 6 - lgy - lgz;
+    int pz = (int)(q_begin % p.c.npz), py = (int)((q_begin / p.c.npz) % p.c.npy), px = (int)(q_begin / ((long)p.c.npz * p.c.npy));
     const int lz = lane & ((1 << lgz) - 1), ly = (lane >> lgz) & ((1 << lgy) - 1), lx = lane >> (lgz + lgy);
-
+    // coordinate pass s (called for s = 0, 1, 2, ... in order): lane -> one voxel of the item's next patch, record into
+    // LDS buffer s & 1
     auto coord_pass = [&](int s) {
         const int x = (px << lgx) + lx, y = (py << lgy) + ly, z = (pz << lgz) + lz;
-        if (++pz == p.npz) {
+        if (++pz == p.c.npz) {
             pz = 0;
-            if (++py == p.npy) py = 0, ++px;
+            if (++py == p.c.npy) py = 0, ++px;
         }
         unsigned rows[NTAP];
         float w[NTAP];
         float yv;
-        voxel_record<NTAP>(p.beta ? bt : nullptr, vol, row_bytes, yb, x, y, z, rows, w, yv);
+        voxel_record<NTAP>(p.c.beta ? bt : nullptr, vol, row_bytes, yb, x, y, z, rows, w, yv);
         const int buf = s & 1;
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
@@ -405,11 +356,6 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_bf16_kernel(
             s_w[wave][buf][q][lane] = f32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
         }
         s_y[wave][buf][lane] = yv;
-    };
-    auto wave_fence = [&]() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
 
     struct Stage {
@@ -484,44 +430,24 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_bf16_kernel(
         }
     }
 
-    f32x4 *out = reinterpret_cast<f32x4 *>(p.slab) + (((long)b * p.nchunks + chunk) * NT) * 64 + lane;
+    f32x4 *out = reinterpret_cast<f32x4 *>(p.c.slab) + (((long)b * p.c.nchunks + chunk) * NT) * 64 + lane;
 #pragma unroll
     for (int i = 0; i < NT; ++i) out[(long)i * 64] = acc[i];
 }
 
-static void patch_shape(const Volume &vol, int &lgy, int &lgz, int &npy, int &npz, long &npatch) {
-    lgz = vol.Z == 1 ? 0 : (vol.Z == 2 ? 1 : 2);
-    lgy = vol.Z <= 2 ? 3 : 2;
-    const int lgx = 6 - lgy - lgz;
-    npz = (vol.Z + (1 << lgz) - 1) >> lgz;
-    npy = (vol.Y + (1 << lgy) - 1) >> lgy;
-    npatch = (long)((vol.X + (1 << lgx) - 1) >> lgx) * npy * npz;
-}
-
-static void choose_chunks(long npatch, int B, int &nchunks, long &chunk_len) {
-    const long nss = npatch;  // coordinate passes per frame
-    long want = (4096 + B - 1) / B;            // aim for >= 4096 wave-sized work items
-    if (want < 1) want = 1;
-    if (want > 64) want = 64;
-    if (want > nss) want = nss;
-    const long ss_per_chunk = (nss + want - 1) / want;
-    chunk_len = ss_per_chunk;
-    nchunks = (int)((npatch + chunk_len - 1) / chunk_len);
-}
-
 template <int NB>
 static int launch_gram(GramParams p, float *G, float *r, bool bf16, hipStream_t st) {
-    const long nitems = (long)p.nchunks * p.B;
+    const long nitems = (long)p.c.nchunks * p.c.B;
     const unsigned nwg = (unsigned)((nitems + 3) / 4);
-    if (bf16 && p.vol.Z > 1)
+    if (bf16 && p.c.vol.Z > 1)
         hipLaunchKernelGGL((warp_gram_bf16_kernel<NB, 8>), dim3(nwg), dim3(256), 0, st, p);
     else if (bf16)
         hipLaunchKernelGGL((warp_gram_bf16_kernel<NB, 4>), dim3(nwg), dim3(256), 0, st, p);
-    else if (p.vol.Z > 1)
+    else if (p.c.vol.Z > 1)
         hipLaunchKernelGGL((warp_gram_kernel<NB, 8>), dim3(nwg), dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL((warp_gram_kernel<NB, 4>), dim3(nwg), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((gram_finish_kernel<NB>), dim3((unsigned)p.B), dim3(256), 0, st, p.slab, p.nchunks, p.K, G, r);
+    hipLaunchKernelGGL((gram_finish_kernel<NB>), dim3((unsigned)p.c.B), dim3(256), 0, st, p.c.slab, p.c.nchunks, p.K, G, r);
     return check_launch("dnmf_warp_gram_rhs");
 }
 
@@ -532,10 +458,7 @@ extern "C" {
 size_t dnmf_warp_gram_rhs_workspace(long P, int K, int B) {
     if (P <= 0 || K <= 0 || B <= 0) return 0;
     const int NB = dnmf_padded_k(K) / 16;
-    long want = (4096 + B - 1) / B;  // upper bound of the chunk count chosen at launch (it depends on the shape)
-    if (want < 1) want = 1;
-    if (want > 64) want = 64;
-    return (size_t)B * (size_t)(want + 1) * (NB * (NB + 1) / 2) * 256 * sizeof(float);
+    return (size_t)B * (size_t)(dnmf::max_chunks(B, dnmf::GRAM_ITEMS_DENSE) + 1) * (NB * (NB + 1) / 2) * 256 * sizeof(float);
 }
 
 static int gram_entry(bool bf16, const float *Apk, int Kp, int K, long a_frame_stride, int X, int Y, int Z,
@@ -543,40 +466,19 @@ static int gram_entry(bool bf16, const float *Apk, int Kp, int K, long a_frame_s
                       const int *frame_ids, float *G, float *r, void *workspace, size_t workspace_bytes,
                       dnmf_stream_t stream) {
     using namespace dnmf;
-    DNMF_REQUIRE(Apk && frames && G && r && workspace, DNMF_E_NULL, "dnmf_warp_gram_rhs: NULL buffer");
-    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && K > 0 && T > 0 && B > 0 && Kp == dnmf_padded_k(K), DNMF_E_SHAPE,
-                 "dnmf_warp_gram_rhs: X=%d Y=%d Z=%d K=%d Kp=%d T=%d B=%d", X, Y, Z, K, Kp, T, B);
     GramParams p;
-    p.vol = make_volume(X, Y, Z);
-    DNMF_REQUIRE(ldf >= p.vol.P && a_frame_stride >= 0, DNMF_E_SHAPE, "dnmf_warp_gram_rhs: ldf=%ld < P=%ld", ldf,
-                 p.vol.P);
-    DNMF_REQUIRE(p.vol.P * Kp < (1L << 30), DNMF_E_UNSUPPORTED,
-                 "dnmf_warp_gram_rhs: P*Kp=%ld does not fit 32-bit byte offsets", p.vol.P * Kp);
-    DNMF_REQUIRE((reinterpret_cast<size_t>(Apk) & 15) == 0 && (a_frame_stride % 4) == 0 &&
-                     (reinterpret_cast<size_t>(workspace) & 15) == 0,
-                 DNMF_E_SHAPE, "dnmf_warp_gram_rhs: Apk / workspace must be 16-byte aligned");
-    DNMF_REQUIRE(workspace_bytes >= dnmf_warp_gram_rhs_workspace(p.vol.P, K, B), DNMF_E_WORKSPACE,
+    if (const int rc = gram_common_args(bf16 ? "dnmf_warp_gram_rhs_bf16" : "dnmf_warp_gram_rhs", "Kp", p.c, Apk, Kp,
+                                        dnmf_padded_k(K), 0, true, a_frame_stride, K, X, Y, Z, beta, T, times, B, frames,
+                                        ldf, frame_ids, G, r, workspace, GRAM_ITEMS_DENSE))
+        return rc;
+    DNMF_REQUIRE(workspace_bytes >= dnmf_warp_gram_rhs_workspace(p.c.vol.P, K, B), DNMF_E_WORKSPACE,
                  "dnmf_warp_gram_rhs: workspace %zu < %zu bytes", workspace_bytes,
-                 dnmf_warp_gram_rhs_workspace(p.vol.P, K, B));
+                 dnmf_warp_gram_rhs_workspace(p.c.vol.P, K, B));
     p.Apk = Apk, p.a_frame_stride = a_frame_stride, p.Kp = Kp, p.K = K;
-    p.beta = beta, p.T = T, p.times = times, p.B = B;
-    p.frames = frames, p.ldf = ldf, p.frame_ids = frame_ids;
-    p.slab = static_cast<float *>(workspace);
-    patch_shape(p.vol, p.lgy, p.lgz, p.npy, p.npz, p.npatch);
-    choose_chunks(p.npatch, B, p.nchunks, p.chunk_len);
-    hipStream_t st = (hipStream_t)stream;
-    switch (Kp / 16) {
-        case 1: return launch_gram<1>(p, G, r, bf16, st);
-        case 2: return launch_gram<2>(p, G, r, bf16, st);
-        case 3: return launch_gram<3>(p, G, r, bf16, st);
-        case 4: return launch_gram<4>(p, G, r, bf16, st);
-        case 5: return launch_gram<5>(p, G, r, bf16, st);
-        case 6: return launch_gram<6>(p, G, r, bf16, st);
-        case 7: return launch_gram<7>(p, G, r, bf16, st);
-        case 8: return launch_gram<8>(p, G, r, bf16, st);
-        default:
-            return fail(DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs: K=%d needs Kp=%d > 128 (not built yet)", K, Kp);
-    }
+    int rc;
+    if (dispatch_nb(Kp / 16, rc, [&](auto nb) { return launch_gram<decltype(nb)::value>(p, G, r, bf16, (hipStream_t)stream); }))
+        return rc;
+    return fail(DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs: K=%d needs Kp=%d > 128 (not built yet)", K, Kp);
 }
 
 int dnmf_warp_gram_rhs(const float *Apk, int Kp, int K, long a_frame_stride, int X, int Y, int Z, const float *beta,

@@ -11,20 +11,15 @@
 // for the 8 k-steps of each half pass (one set per half), and issues the MFMAs of tile (bi,bj) only if both
 // blocks are in S; a half pass with S empty costs its share of the coordinate pass and nothing else.  Accumulators stay statically indexed: the skips are
 // scalar branches around fully unrolled code.  The right-hand side is accumulated on the vector ALU.
-#include "common.hpp"
-
-#include <type_traits>
+//
+// The argument block, wave_fence, tile_index and the host plan are warp_gram_mfma.hpp's, shared with K3 / K3b.  The
+// work-item prologue, the patch walk and the coordinate pass are this file's own copies (see the note in that header).
+#include "warp_gram_mfma.hpp"
 
 namespace dnmf {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KS_SS = 64;          // voxels per pass
-constexpr int KS_NKS = KS_SS / 4;  // k-steps per pass
+constexpr int KS_NKS = GRAM_SS / 4;  // k-steps per pass
 constexpr int KS_HALF = KS_NKS / 2;  // k-steps per half pass (block sets are per half)
-
-__host__ __device__ constexpr int sp_tile_index(int NB, int bi, int bj) { return bi * NB - bi * (bi - 1) / 2 + (bj - bi); }
 
 // Aps[p][c] = c < K ? A[p][order[c]] : 0 ;  row_mask[p] bit b = any(Aps[p][16b .. 16b+15] != 0)
 __global__ __launch_bounds__(256) void pack_sparse_kernel(const float *__restrict__ A, long P, int K,
@@ -52,21 +47,7 @@ struct SparseParams {
     const float *Aps;
     const unsigned char *row_mask;
     int Ks, K;
-    Volume vol;
-    const float *beta;
-    int T;
-    const int *times;
-    int B;
-    const float *frames;
-    long ldf;
-    const int *frame_ids;
-    float *slab;  // (B, nchunks, NT*256 + 128)
-    int nchunks;
-    long chunk_len;    // passes (patches of 64 voxels) per chunk
-    // a pass is a compact patch of 2^lgx x 2^lgy x 2^lgz = 64 voxels (8x8 for Z == 1), not a run of 64 voxels: fewer
-    // footprints reach into a compact patch, so fewer blocks and tiles are active per pass
-    int lgy, lgz, npy, npz;
-    long npatch;
+    GramCommon c;  // c.slab: (B, nchunks, NT*256 + 128) static, (B, nchunks, NB*NB*256 + 128) table
     unsigned long long *counters;  // optional: [0] += MFMAs issued, [1] += (active block, k-step) blends
 };
 
@@ -75,24 +56,24 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_sparse_kerne
     constexpr int NT = NB * (NB + 1) / 2;
     constexpr int NQ = NTAP / 4;
     constexpr int SLAB = NT * 256 + 128;
-    __shared__ u32x4 s_row[4][NQ][KS_SS];
-    __shared__ f32x4 s_w[4][NQ][KS_SS];
-    __shared__ float s_y[4][KS_SS];
+    __shared__ u32x4 s_row[4][NQ][GRAM_SS];
+    __shared__ f32x4 s_w[4][NQ][GRAM_SS];
+    __shared__ float s_y[4][GRAM_SS];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= (long)p.nchunks * p.B) return;
-    const int chunk = (int)(item / p.B);
-    const int b = (int)(item - (long)chunk * p.B);
-    const int t = p.times ? p.times[b] : b;
+    if (item >= (long)p.c.nchunks * p.c.B) return;
+    const int chunk = (int)(item / p.c.B);
+    const int b = (int)(item - (long)chunk * p.c.B);
+    const int t = p.c.times ? p.c.times[b] : b;
     const char *__restrict__ Ab = reinterpret_cast<const char *>(p.Aps);
-    const float *__restrict__ yb = p.frames + (long)(p.frame_ids ? p.frame_ids[b] : b) * p.ldf;
-    const Volume vol = p.vol;
+    const float *__restrict__ yb = p.c.frames + (long)(p.c.frame_ids ? p.c.frame_ids[b] : b) * p.c.ldf;
+    const Volume vol = p.c.vol;
     const unsigned row_bytes = (unsigned)p.Ks * 4u;
 
     float bt[30];
-    load_beta(p.beta, p.T, t, bt);
+    load_beta(p.c.beta, p.c.T, t, bt);
     const int ci = lane & 15, vq = lane >> 4;
     const unsigned lane_off = 4u * ci;
 
@@ -103,12 +84,12 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_sparse_kerne
 #pragma unroll
     for (int i = 0; i < NB; ++i) racc[i] = 0.0f;
 
-    const long q_begin = (long)chunk * p.chunk_len;
-    const long q_end = q_begin + p.chunk_len < p.npatch ? q_begin + p.chunk_len : p.npatch;
+    const long q_begin = (long)chunk * p.c.chunk_len;
+    const long q_end = q_begin + p.c.chunk_len < p.c.npatch ? q_begin + p.c.chunk_len : p.c.npatch;
     const int nss = (int)(q_end - q_begin);
     // patch origin of the first pass (wave-uniform), advanced with carries; lane -> voxel inside the patch
-    const int lgy = p.lgy, lgz = p.lgz;
-    int pz = (int)(q_begin % p.npz), py = (int)((q_begin / p.npz) % p.npy), px = (int)(q_begin / ((long)p.npz * p.npy));
+    const int lgy = p.c.lgy, lgz = p.c.lgz;
+    int pz = (int)(q_begin % p.c.npz), py = (int)((q_begin / p.c.npz) % p.c.npy), px = (int)(q_begin / ((long)p.c.npz * p.c.npy));
     const int lz = lane & ((1 << lgz) - 1), ly = (lane >> lgz) & ((1 << lgy) - 1), lx = lane >> (lgz + lgy);
     const int lgx = 6 - lgy - lgz;
     unsigned n_tiles = 0, n_blocks = 0;  // (tile, half pass) and (block, half pass) pairs executed
@@ -151,9 +132,7 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_sparse_kerne
             S2[0] |= ((unsigned)(bal & 0xffffffffull) != 0u ? 1u : 0u) << bb;
             S2[1] |= ((unsigned)(bal >> 32) != 0u ? 1u : 0u) << bb;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_fence();
 
 #pragma unroll 1
         for (int h = 0; h < 2; ++h) {
@@ -192,7 +171,7 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_sparse_kerne
 #pragma unroll
                     for (int bj = bi; bj < NB; ++bj) {
                         if ((S >> bj) & 1u) {
-                            const int idx = sp_tile_index(NB, bi, bj);
+                            const int idx = tile_index(NB, bi, bj);
 #pragma unroll
                             for (int ks = 0; ks < KS_HALF; ++ks)
                                 acc[idx] = __builtin_amdgcn_mfma_f32_16x16x4f32(frag[bi][ks], frag[bj][ks], acc[idx], 0, 0, 0);
@@ -201,21 +180,19 @@ __global__ __launch_bounds__(256, NTAP == 4 ? 2 : 1) void warp_gram_sparse_kerne
                 }
             }
         }
-        if (++pz == p.npz) {
+        if (++pz == p.c.npz) {
             pz = 0;
-            if (++py == p.npy) py = 0, ++px;
+            if (++py == p.c.npy) py = 0, ++px;
         }
         // the next coordinate pass overwrites the records: keep it behind this pass's reads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_fence();
     }
 
     if (p.counters && lane == 0) {
         atomicAdd(p.counters + 0, (unsigned long long)n_tiles * KS_HALF);
         atomicAdd(p.counters + 1, (unsigned long long)n_blocks * KS_HALF);
     }
-    float *out = p.slab + ((long)b * p.nchunks + chunk) * SLAB;
+    float *out = p.c.slab + ((long)b * p.c.nchunks + chunk) * SLAB;
     f32x4 *out4 = reinterpret_cast<f32x4 *>(out) + lane;
 #pragma unroll
     for (int i = 0; i < NT; ++i) out4[(long)i * 64] = acc[i];
@@ -246,26 +223,26 @@ __global__ __launch_bounds__(256, 3) void warp_gram_lt_kernel(SparseParams p) {
     constexpr int KP = 8;            // k-steps per part: block sets are formed per half pass (32 voxels)
     constexpr int NPART = KS_NKS / KP;
     static_assert(NPART == 2, "the block sets are formed for lanes 0-31 / 32-63");
-    __shared__ u32x4 s_row[4][NQ][KS_SS];
-    __shared__ f32x4 s_w[4][NQ][KS_SS];
-    __shared__ float s_y[4][KS_SS];
+    __shared__ u32x4 s_row[4][NQ][GRAM_SS];
+    __shared__ f32x4 s_w[4][NQ][GRAM_SS];
+    __shared__ float s_y[4][GRAM_SS];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const long item = (long)blockIdx.x * 4 + wave;
-    if (item >= (long)p.nchunks * p.B) return;
-    const int chunk = (int)(item / p.B);
-    const int b = (int)(item - (long)chunk * p.B);
-    const int t = p.times ? p.times[b] : b;
+    if (item >= (long)p.c.nchunks * p.c.B) return;
+    const int chunk = (int)(item / p.c.B);
+    const int b = (int)(item - (long)chunk * p.c.B);
+    const int t = p.c.times ? p.c.times[b] : b;
     const char *__restrict__ Ab = reinterpret_cast<const char *>(p.Aps);
-    const float *__restrict__ yb = p.frames + (long)(p.frame_ids ? p.frame_ids[b] : b) * p.ldf;
-    const Volume vol = p.vol;
+    const float *__restrict__ yb = p.c.frames + (long)(p.c.frame_ids ? p.c.frame_ids[b] : b) * p.c.ldf;
+    const Volume vol = p.c.vol;
     const unsigned row_bytes = (unsigned)p.Ks * 4u;
-    float *slab = p.slab + ((long)b * p.nchunks + chunk) * SLAB;  // zeroed by the launch function
+    float *slab = p.c.slab + ((long)b * p.c.nchunks + chunk) * SLAB;  // zeroed by the launch function
     f32x4 *slab4 = reinterpret_cast<f32x4 *>(slab);
 
     float bt[30];
-    load_beta(p.beta, p.T, t, bt);
+    load_beta(p.c.beta, p.c.T, t, bt);
     const int ci = lane & 15, vq = lane >> 4;
     const unsigned lane_off = 4u * ci;
 
@@ -371,11 +348,11 @@ __global__ __launch_bounds__(256, 3) void warp_gram_lt_kernel(SparseParams p) {
         return tm;
     };
 
-    const long q_begin = (long)chunk * p.chunk_len;
-    const long q_end = q_begin + p.chunk_len < p.npatch ? q_begin + p.chunk_len : p.npatch;
+    const long q_begin = (long)chunk * p.c.chunk_len;
+    const long q_end = q_begin + p.c.chunk_len < p.c.npatch ? q_begin + p.c.chunk_len : p.c.npatch;
     const int nss = (int)(q_end - q_begin);
-    const int lgy = p.lgy, lgz = p.lgz;
-    int pz = (int)(q_begin % p.npz), py = (int)((q_begin / p.npz) % p.npy), px = (int)(q_begin / ((long)p.npz * p.npy));
+    const int lgy = p.c.lgy, lgz = p.c.lgz;
+    int pz = (int)(q_begin % p.c.npz), py = (int)((q_begin / p.c.npz) % p.c.npy), px = (int)(q_begin / ((long)p.c.npz * p.c.npy));
     const int lz = lane & ((1 << lgz) - 1), ly = (lane >> lgz) & ((1 << lgy) - 1), lx = lane >> (lgz + lgy);
     const int lgx = 6 - lgy - lgz;
 
@@ -420,9 +397,7 @@ __global__ __launch_bounds__(256, 3) void warp_gram_lt_kernel(SparseParams p) {
             v |= __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, true);  // row_bcast:15 into rows 1 and 3
             Sw = (unsigned)__builtin_amdgcn_readlane(v, 31) | ((unsigned)__builtin_amdgcn_readlane(v, 63) << 8);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_fence();
 
 #pragma unroll 1
         for (int h = 0; h < NPART; ++h) {
@@ -497,13 +472,11 @@ __global__ __launch_bounds__(256, 3) void warp_gram_lt_kernel(SparseParams p) {
                 }
             }
         }
-        if (++pz == p.npz) {
+        if (++pz == p.c.npz) {
             pz = 0;
-            if (++py == p.npy) py = 0, ++px;
+            if (++py == p.c.npy) py = 0, ++px;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_fence();
     }
     flush_all();
     if (p.counters && lane == 0) {
@@ -566,7 +539,7 @@ __global__ __launch_bounds__(256) void gram_sparse_finish_kernel(const float *__
     for (int bi = 0; bi < NB; ++bi) {
 #pragma unroll
         for (int bj = bi; bj < NB; ++bj) {
-            const float *src = base + sp_tile_index(NB, bi, bj) * 256 + e;
+            const float *src = base + tile_index(NB, bi, bj) * 256 + e;
             float s = 0.0f;
             for (int c = 0; c < nchunks; ++c) s += src[(long)c * SLAB];
             const int ck = 16 * bi + i, cl = 16 * bj + j;
@@ -584,109 +557,85 @@ __global__ __launch_bounds__(256) void gram_sparse_finish_kernel(const float *__
     }
 }
 
-static void sp_patch_shape(const Volume &vol, int &lgy, int &lgz, int &npy, int &npz, long &npatch) {
-    lgz = vol.Z == 1 ? 0 : (vol.Z == 2 ? 1 : 2);
-    lgy = vol.Z <= 2 ? 3 : 2;
-    const int lgx = 6 - lgy - lgz;
-    npz = (vol.Z + (1 << lgz) - 1) >> lgz;
-    npy = (vol.Y + (1 << lgy) - 1) >> lgy;
-    npatch = (long)((vol.X + (1 << lgx) - 1) >> lgx) * npy * npz;
-}
-
-static void sp_choose_chunks(long npatch, int B, int &nchunks, long &chunk_len) {
-    const long nss = npatch;
-    long want = (8192 + B - 1) / B;  // passes differ a lot in cost: more, smaller work items than the dense kernel
-    if (want < 1) want = 1;
-    if (want > 64) want = 64;
-    if (want > nss) want = nss;
-    const long ss_per_chunk = (nss + want - 1) / want;
-    chunk_len = ss_per_chunk;
-    nchunks = (int)((npatch + chunk_len - 1) / chunk_len);
-}
-
 template <int NB>
-static int launch_sparse(SparseParams p, const int *order, float *G, float *r, hipStream_t st) {
-    const long nitems = (long)p.nchunks * p.B;
-    const unsigned nwg = (unsigned)((nitems + 3) / 4);
-    if (p.vol.Z > 1)
-        hipLaunchKernelGGL((warp_gram_sparse_kernel<NB, 8>), dim3(nwg), dim3(256), 0, st, p);
+static int launch_sparse(bool table, SparseParams p, const int *order, float *G, float *r, hipStream_t st) {
+    const long nitems = (long)p.c.nchunks * p.c.B;
+    const dim3 nwg((unsigned)((nitems + 3) / 4)), nb((unsigned)p.c.B);
+    if (table) {
+        const size_t bytes = (size_t)nitems * ((size_t)NB * NB * 256 + 128) * sizeof(float);
+        hipError_t e = hipMemsetAsync(p.c.slab, 0, bytes, st);  // the kernel adds into its slab region
+        if (e != hipSuccess) return fail((int)e, "dnmf_warp_gram_rhs_sparse_lt: memset: %s", hipGetErrorString(e));
+        if (p.c.vol.Z > 1)
+            hipLaunchKernelGGL((warp_gram_lt_kernel<NB, 8>), nwg, dim3(256), 0, st, p);
+        else
+            hipLaunchKernelGGL((warp_gram_lt_kernel<NB, 4>), nwg, dim3(256), 0, st, p);
+        hipLaunchKernelGGL((gram_lt_finish_kernel<NB>), nb, dim3(256), 0, st, p.c.slab, p.c.nchunks, p.K, order, G, r);
+        return check_launch("dnmf_warp_gram_rhs_sparse_lt");
+    }
+    if (p.c.vol.Z > 1)
+        hipLaunchKernelGGL((warp_gram_sparse_kernel<NB, 8>), nwg, dim3(256), 0, st, p);
     else
-        hipLaunchKernelGGL((warp_gram_sparse_kernel<NB, 4>), dim3(nwg), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((gram_sparse_finish_kernel<NB>), dim3((unsigned)p.B), dim3(256), 0, st, p.slab, p.nchunks, p.K,
-                       order, G, r);
+        hipLaunchKernelGGL((warp_gram_sparse_kernel<NB, 4>), nwg, dim3(256), 0, st, p);
+    hipLaunchKernelGGL((gram_sparse_finish_kernel<NB>), nb, dim3(256), 0, st, p.c.slab, p.c.nchunks, p.K, order, G, r);
     return check_launch("dnmf_warp_gram_rhs_sparse");
 }
 
-template <int NB>
-static int launch_sparse_lt(SparseParams p, const int *order, float *G, float *r, hipStream_t st) {
-    const long nitems = (long)p.nchunks * p.B;
-    const unsigned nwg = (unsigned)((nitems + 3) / 4);
-    const size_t bytes = (size_t)nitems * ((size_t)NB * NB * 256 + 128) * sizeof(float);
-    hipError_t e = hipMemsetAsync(p.slab, 0, bytes, st);  // the kernel adds into its slab region
-    if (e != hipSuccess) return fail((int)e, "dnmf_warp_gram_rhs_sparse_lt: memset: %s", hipGetErrorString(e));
-    if (p.vol.Z > 1)
-        hipLaunchKernelGGL((warp_gram_lt_kernel<NB, 8>), dim3(nwg), dim3(256), 0, st, p);
-    else
-        hipLaunchKernelGGL((warp_gram_lt_kernel<NB, 4>), dim3(nwg), dim3(256), 0, st, p);
-    hipLaunchKernelGGL((gram_lt_finish_kernel<NB>), dim3((unsigned)p.B), dim3(256), 0, st, p.slab, p.nchunks, p.K, order, G,
-                       r);
-    return check_launch("dnmf_warp_gram_rhs_sparse_lt");
+// floats of one work item's slab region: the upper-triangle tiles (static) or the full grid (table), 128 for r
+static size_t sparse_item_floats(bool table, int NB) { return (size_t)(table ? NB * NB : NB * (NB + 1) / 2) * 256 + 128; }
+
+static size_t sparse_workspace(bool table, long P, int K, int B) {
+    if (P <= 0 || K <= 0 || B <= 0) return 0;
+    return (size_t)B * (size_t)(max_chunks(B, GRAM_ITEMS_SPARSE) + 1) * sparse_item_floats(table, (K + 15) / 16) * sizeof(float);
+}
+
+static int sparse_entry(bool table, const float *Aps, int Ks, int K, const int *order, const unsigned char *row_mask, int X,
+                        int Y, int Z, const float *beta, int T, const int *times, int B, const float *frames, long ldf,
+                        const int *frame_ids, float *G, float *r, void *workspace, size_t workspace_bytes,
+                        unsigned long long *counters, dnmf_stream_t stream) {
+    const char *who = table ? "dnmf_warp_gram_rhs_sparse_lt" : "dnmf_warp_gram_rhs_sparse";
+    DNMF_REQUIRE(order && row_mask && beta, DNMF_E_NULL, "%s: NULL buffer", who);
+    SparseParams p;
+    if (const int rc = gram_common_args(who, "Ks", p.c, Aps, Ks, dnmf_sparse_k(K), 128, false, 0, K, X, Y, Z, beta, T, times,
+                                        B, frames, ldf, frame_ids, G, r, workspace, GRAM_ITEMS_SPARSE))
+        return rc;
+    // the static variant asks for its whole documented workspace, both for what this plan uses
+    if (!table)
+        DNMF_REQUIRE(workspace_bytes >= sparse_workspace(false, p.c.vol.P, K, B), DNMF_E_WORKSPACE,
+                     "%s: workspace %zu < %zu bytes", who, workspace_bytes, sparse_workspace(false, p.c.vol.P, K, B));
+    DNMF_REQUIRE(workspace_bytes >= (size_t)B * p.c.nchunks * sparse_item_floats(table, Ks / 16) * sizeof(float),
+                 DNMF_E_WORKSPACE, "%s: workspace too small for %d chunks", who, p.c.nchunks);
+    p.Aps = Aps, p.row_mask = row_mask, p.Ks = Ks, p.K = K;
+    p.counters = counters;
+    int rc = DNMF_E_UNSUPPORTED;  // Ks <= 128 was checked: every NB is built
+    dispatch_nb(Ks / 16, rc, [&](auto nb) { return launch_sparse<decltype(nb)::value>(table, p, order, G, r, (hipStream_t)stream); });
+    return rc;
 }
 
 }  // namespace dnmf
 
 extern "C" {
 
-size_t dnmf_warp_gram_rhs_sparse_lt_workspace(long P, int K, int B) {
-    if (P <= 0 || K <= 0 || B <= 0) return 0;
-    const int NB = (K + 15) / 16;
-    long want = (8192 + B - 1) / B;
-    if (want < 1) want = 1;
-    if (want > 64) want = 64;
-    return (size_t)B * (size_t)(want + 1) * ((size_t)NB * NB * 256 + 128) * sizeof(float);
+int dnmf_sparse_k(int K) { return K < 1 ? 0 : 16 * ((K + 15) / 16); }
+
+size_t dnmf_warp_gram_rhs_sparse_workspace(long P, int K, int B) { return dnmf::sparse_workspace(false, P, K, B); }
+
+size_t dnmf_warp_gram_rhs_sparse_lt_workspace(long P, int K, int B) { return dnmf::sparse_workspace(true, P, K, B); }
+
+int dnmf_warp_gram_rhs_sparse(const float *Aps, int Ks, int K, const int *order, const unsigned char *row_mask, int X,
+                              int Y, int Z, const float *beta, int T, const int *times, int B, const float *frames,
+                              long ldf, const int *frame_ids, float *G, float *r, void *workspace,
+                              size_t workspace_bytes, unsigned long long *counters, dnmf_stream_t stream) {
+    return dnmf::sparse_entry(false, Aps, Ks, K, order, row_mask, X, Y, Z, beta, T, times, B, frames, ldf, frame_ids, G, r,
+                              workspace, workspace_bytes, counters, stream);
 }
 
 int dnmf_warp_gram_rhs_sparse_lt(const float *Aps, int Ks, int K, const int *order, const unsigned char *row_mask, int X,
                                  int Y, int Z, const float *beta, int T, const int *times, int B, const float *frames,
                                  long ldf, const int *frame_ids, float *G, float *r, void *workspace,
                                  size_t workspace_bytes, unsigned long long *counters, dnmf_stream_t stream) {
-    using namespace dnmf;
-    DNMF_REQUIRE(Aps && order && row_mask && beta && frames && G && r && workspace, DNMF_E_NULL,
-                 "dnmf_warp_gram_rhs_sparse_lt: NULL buffer");
-    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && K > 0 && T > 0 && B > 0 && Ks == 16 * ((K + 15) / 16), DNMF_E_SHAPE,
-                 "dnmf_warp_gram_rhs_sparse_lt: X=%d Y=%d Z=%d K=%d Ks=%d T=%d B=%d", X, Y, Z, K, Ks, T, B);
-    DNMF_REQUIRE(Ks <= 128, DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs_sparse_lt: K=%d > 128", K);
-    SparseParams p;
-    p.vol = make_volume(X, Y, Z);
-    DNMF_REQUIRE(ldf >= p.vol.P, DNMF_E_SHAPE, "dnmf_warp_gram_rhs_sparse_lt: ldf=%ld < P=%ld", ldf, p.vol.P);
-    DNMF_REQUIRE(p.vol.P * Ks < (1L << 30), DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs_sparse_lt: P*Ks=%ld too large",
-                 p.vol.P * Ks);
-    DNMF_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, DNMF_E_SHAPE,
-                 "dnmf_warp_gram_rhs_sparse_lt: workspace must be 16-byte aligned");
-    p.Aps = Aps, p.row_mask = row_mask, p.Ks = Ks, p.K = K;
-    p.beta = beta, p.T = T, p.times = times, p.B = B;
-    p.frames = frames, p.ldf = ldf, p.frame_ids = frame_ids;
-    p.slab = static_cast<float *>(workspace);
-    p.counters = counters;
-    sp_patch_shape(p.vol, p.lgy, p.lgz, p.npy, p.npz, p.npatch);
-    sp_choose_chunks(p.npatch, B, p.nchunks, p.chunk_len);
-    const int NB = Ks / 16;
-    DNMF_REQUIRE(workspace_bytes >= (size_t)B * p.nchunks * ((size_t)NB * NB * 256 + 128) * sizeof(float), DNMF_E_WORKSPACE,
-                 "dnmf_warp_gram_rhs_sparse_lt: workspace too small for %d chunks", p.nchunks);
-    hipStream_t st = (hipStream_t)stream;
-    switch (NB) {
-        case 1: return launch_sparse_lt<1>(p, order, G, r, st);
-        case 2: return launch_sparse_lt<2>(p, order, G, r, st);
-        case 3: return launch_sparse_lt<3>(p, order, G, r, st);
-        case 4: return launch_sparse_lt<4>(p, order, G, r, st);
-        case 5: return launch_sparse_lt<5>(p, order, G, r, st);
-        case 6: return launch_sparse_lt<6>(p, order, G, r, st);
-        case 7: return launch_sparse_lt<7>(p, order, G, r, st);
-        default: return launch_sparse_lt<8>(p, order, G, r, st);
-    }
+    return dnmf::sparse_entry(true, Aps, Ks, K, order, row_mask, X, Y, Z, beta, T, times, B, frames, ldf, frame_ids, G, r,
+                              workspace, workspace_bytes, counters, stream);
 }
-
-int dnmf_sparse_k(int K) { return K < 1 ? 0 : 16 * ((K + 15) / 16); }
 
 int dnmf_pack_footprints_sparse(const float *A, long P, int K, const int *order, float *Aps, int Ks,
                                 unsigned char *row_mask, dnmf_stream_t stream) {
@@ -699,62 +648,6 @@ int dnmf_pack_footprints_sparse(const float *A, long P, int K, const int *order,
     hipLaunchKernelGGL(pack_sparse_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A,
                        P, K, order, Aps, Ks, row_mask);
     return check_launch("dnmf_pack_footprints_sparse");
-}
-
-size_t dnmf_warp_gram_rhs_sparse_workspace(long P, int K, int B) {
-    if (P <= 0 || K <= 0 || B <= 0) return 0;
-    const int NB = dnmf_sparse_k(K) / 16;
-    // the patch count depends on the volume shape, not only on P: bound it by the worst shape (all three
-    // axes one voxel past a patch boundary cannot exceed 8x the voxel count / 64)
-    const long npatch_max = P / 8 + 64;
-    const long per_item = (long)(NB * (NB + 1) / 2) * 256 + 128;
-    long want = (8192 + B - 1) / B;
-    if (want < 1) want = 1;
-    if (want > 64) want = 64;
-    (void)npatch_max;
-    return (size_t)B * (size_t)(want + 1) * per_item * sizeof(float);
-}
-
-int dnmf_warp_gram_rhs_sparse(const float *Aps, int Ks, int K, const int *order, const unsigned char *row_mask, int X,
-                              int Y, int Z, const float *beta, int T, const int *times, int B, const float *frames,
-                              long ldf, const int *frame_ids, float *G, float *r, void *workspace,
-                              size_t workspace_bytes, unsigned long long *counters, dnmf_stream_t stream) {
-    using namespace dnmf;
-    DNMF_REQUIRE(Aps && order && row_mask && beta && frames && G && r && workspace, DNMF_E_NULL,
-                 "dnmf_warp_gram_rhs_sparse: NULL buffer");
-    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && K > 0 && T > 0 && B > 0 && Ks == dnmf_sparse_k(K), DNMF_E_SHAPE,
-                 "dnmf_warp_gram_rhs_sparse: X=%d Y=%d Z=%d K=%d Ks=%d T=%d B=%d", X, Y, Z, K, Ks, T, B);
-    DNMF_REQUIRE(Ks <= 128, DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs_sparse: K=%d > 128", K);
-    SparseParams p;
-    p.vol = make_volume(X, Y, Z);
-    DNMF_REQUIRE(ldf >= p.vol.P, DNMF_E_SHAPE, "dnmf_warp_gram_rhs_sparse: ldf=%ld < P=%ld", ldf, p.vol.P);
-    DNMF_REQUIRE(p.vol.P * Ks < (1L << 30), DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs_sparse: P*Ks=%ld too large",
-                 p.vol.P * Ks);
-    DNMF_REQUIRE((reinterpret_cast<size_t>(workspace) & 15) == 0, DNMF_E_SHAPE,
-                 "dnmf_warp_gram_rhs_sparse: workspace must be 16-byte aligned");
-    DNMF_REQUIRE(workspace_bytes >= dnmf_warp_gram_rhs_sparse_workspace(p.vol.P, K, B), DNMF_E_WORKSPACE,
-                 "dnmf_warp_gram_rhs_sparse: workspace %zu < %zu bytes", workspace_bytes,
-                 dnmf_warp_gram_rhs_sparse_workspace(p.vol.P, K, B));
-    p.Aps = Aps, p.row_mask = row_mask, p.Ks = Ks, p.K = K;
-    p.beta = beta, p.T = T, p.times = times, p.B = B;
-    p.frames = frames, p.ldf = ldf, p.frame_ids = frame_ids;
-    p.slab = static_cast<float *>(workspace);
-    p.counters = counters;
-    sp_patch_shape(p.vol, p.lgy, p.lgz, p.npy, p.npz, p.npatch);
-    sp_choose_chunks(p.npatch, B, p.nchunks, p.chunk_len);
-    DNMF_REQUIRE(workspace_bytes >= (size_t)B * p.nchunks * ((size_t)(Ks / 16 * (Ks / 16 + 1) / 2) * 256 + 128) * sizeof(float),
-                 DNMF_E_WORKSPACE, "dnmf_warp_gram_rhs_sparse: workspace too small for %d chunks", p.nchunks);
-    hipStream_t st = (hipStream_t)stream;
-    switch (Ks / 16) {
-        case 1: return launch_sparse<1>(p, order, G, r, st);
-        case 2: return launch_sparse<2>(p, order, G, r, st);
-        case 3: return launch_sparse<3>(p, order, G, r, st);
-        case 4: return launch_sparse<4>(p, order, G, r, st);
-        case 5: return launch_sparse<5>(p, order, G, r, st);
-        case 6: return launch_sparse<6>(p, order, G, r, st);
-        case 7: return launch_sparse<7>(p, order, G, r, st);
-        default: return launch_sparse<8>(p, order, G, r, st);
-    }
 }
 
 }  // extern "C"

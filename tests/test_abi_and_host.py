@@ -86,6 +86,26 @@ def test_argument_errors_are_reported_without_a_gpu(lib):
     assert lib.dnmf_comm_destroy(None) == 0
 
 
+def test_gram_workspace_values(lib):
+    """What the workspace functions of K3 / K3b and of both K3s variants return, pinned: B * (max chunks + 1) work-item
+    regions, max chunks = min(64, ceil(target / B)) with target 4096 (K3) or 8192 (K3s); a K3 item holds the NT =
+    NB(NB+1)/2 upper-triangle tiles of 256 floats, a K3s item NT tiles (static) or the NB x NB grid (table) plus 128
+    floats of right-hand side."""
+    assert lib.dnmf_warp_gram_rhs_workspace(262144, 100, 4000) == 4000 * 3 * 28 * 256 * 4
+    assert lib.dnmf_warp_gram_rhs_workspace(262144, 100, 1) == 65 * 28 * 256 * 4
+    for (P, K, B), static, table in (((262144, 100, 4000), 466944000, 811008000), ((262144, 100, 1), 1896960, 3294720),
+                                     ((1024, 16, 100), 9984000, 9984000)):
+        NB = (K + 15) // 16
+        chunks = min(64, -(-8192 // B)) + 1
+        assert static == B * chunks * (NB * (NB + 1) // 2 * 256 + 128) * 4 and table == B * chunks * (NB * NB * 256 + 128) * 4
+        assert lib.dnmf_warp_gram_rhs_sparse_workspace(P, K, B) == static
+        assert lib.dnmf_warp_gram_rhs_sparse_lt_workspace(P, K, B) == table
+    for fn in (lib.dnmf_warp_gram_rhs_workspace, lib.dnmf_warp_gram_rhs_sparse_workspace,
+               lib.dnmf_warp_gram_rhs_sparse_lt_workspace):
+        for args in ((0, 100, 4), (-1, 100, 4), (1024, 0, 4), (1024, -3, 4), (1024, 100, 0), (1024, 100, -1)):
+            assert fn(*args) == 0, (fn, args)
+
+
 def test_product_has_no_cpu_fallback():
     """The classes need the HIP library and a GPU; on a CPU box construction raises instead of computing."""
     if torch.cuda.is_available():

@@ -938,6 +938,47 @@ def test_sparse_gram_equals_dense(M, O, sz, K, T, sigma, variant):
     np.testing.assert_allclose(rs.cpu().numpy(), rref.T, rtol=2e-5, atol=2e-5 * np.abs(rref).max())
 
 
+@pytest.mark.parametrize("sz,K", [([33, 47, 1], 20), ([21, 19, 2], 10)])
+def test_mfma_gram_kernels_read_frames_through_frame_ids(M, O, sz, K):
+    """The work-item prologue K3, K3b and both K3s variants share: frames picked by `frame_ids` out of a buffer with
+    more rows and a row stride above P, `times` not monotone.  Against the same call on a contiguous copy of the chosen
+    rows (frame_ids=None) every G and r is bitwise equal: same B, hence the same chunk plan, and every work item does
+    the same arithmetic on the same values -- only the row a frame is read from differs.  The 3-D shape has ragged
+    patches on all three axes (21 x 19 x 2 under 4 x 8 x 2 patches is ragged in x and y, [33, 47, 1] under 8 x 8)."""
+    from dnmf_amd import ops
+    T, P = 6, int(np.prod(sz))
+    rng = np.random.RandomState(K)
+    pos = rng.rand(K, 3) * np.array(sz)
+    A = O.gaussian_footprints(sz, pos, np.full(K, 1.0))
+    beta = O.identity_beta(T)
+    beta += (rng.randn(10, 3, T) * np.array([1.5, 1e-2, 1e-2, 1e-2, 2e-4, 2e-4, 2e-4, 2e-4, 2e-4, 2e-4])[:, None, None]
+             ).astype(np.float32)
+    if sz[2] == 1:
+        beta[:, 2] = O.identity_beta(T)[:, 2]
+    fp = make_fp(M, sz, K, T, pos, beta=beta, A=A)
+    buf = dev(rng.rand(T + 2, P + 5).astype(np.float32))
+    frames = buf[:, :P]
+    assert frames.stride(0) == P + 5
+    frame_ids, times = [6, 1, 7, 3], [4, 0, 5, 2]
+    picked = frames[frame_ids].contiguous()
+    assert picked.shape == (4, P) and picked.stride(0) == P
+    b, Apk, sp = fp.beta.detach(), fp.packed_footprints(), fp.packed_sparse()
+    calls = {
+        "K3": lambda fr, ids: ops.warp_gram_rhs(Apk, K, sz, b, times, fr, frame_ids=ids),
+        "K3b": lambda fr, ids: ops.warp_gram_rhs(Apk, K, sz, b, times, fr, frame_ids=ids, bf16=True),
+        "K3s table": lambda fr, ids: ops.warp_gram_rhs_sparse(sp["Aps"], K, sp["order"], sp["row_mask"], sz, b, times, fr,
+                                                              frame_ids=ids, variant="table"),
+        "K3s static": lambda fr, ids: ops.warp_gram_rhs_sparse(sp["Aps"], K, sp["order"], sp["row_mask"], sz, b, times, fr,
+                                                               frame_ids=ids, variant="static"),
+    }
+    for name, call in calls.items():
+        G, r = call(frames, frame_ids)[:2]
+        Gref, rref = call(picked, None)[:2]
+        assert G.shape == (4, K, K) and float(Gref.abs().max()) > 0 and float(rref.abs().max()) > 0, name
+        assert torch.equal(G, Gref), name
+        assert torch.equal(r, rref), name
+
+
 def test_sparse_gram_full_size(M):
     """512x512, K=100, the bench geometry: K3s == K3 on every frame."""
     from dnmf_amd import ops

@@ -37,7 +37,7 @@ def main():
             for (int e = 0; e < 4; ++e) load_row<NB>(st.raw[4 * q + e], Ab, rc.rr[q][e] + lane_a, rc.rr[q][e] + lane_b);
 #endif''')
     open(os.path.join(ROOT, "tools", "abl_warp_gram_rhs.hip"), "w").write(
-        s.replace('#include "common.hpp"', '#include "../dnmf_amd/csrc/common.hpp"'))
+        must_replace(s, '#include "warp_gram_mfma.hpp"', '#include "../dnmf_amd/csrc/warp_gram_mfma.hpp"'))
 
     s = open(os.path.join(CSRC, "warp_gram_sparse.hip")).read()
     i = s.index('    auto process = [&](int ks0, unsigned Lg, unsigned Lr, unsigned tm) {')
@@ -47,7 +47,7 @@ def main():
                        '((rr[e] + boff) & 1020u)), ww[e], v);')
     s = s[:i] + blk + s[j:]
     open(os.path.join(ROOT, "tools", "abl_warp_gram_sparse.hip"), "w").write(
-        s.replace('#include "common.hpp"', '#include "../dnmf_amd/csrc/common.hpp"'))
+        must_replace(s, '#include "warp_gram_mfma.hpp"', '#include "../dnmf_amd/csrc/warp_gram_mfma.hpp"'))
 
 
 if __name__ == "__main__":

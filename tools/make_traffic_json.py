@@ -86,8 +86,8 @@ def main():
         if rl:
             entries[geom + "_recon_lists"] = {"value": hbm_bytes(rl), "files": ["recon_lists.hip", "common.hpp"],
                                              "what": "HBM bytes per list-reconstruction launch"}
-        for kern, key, files in (("warp_gram_kernel<", name, ["warp_gram_rhs.hip", "common.hpp"]),
-                                 ("warp_gram_lt_kernel<", name + "_sparse", ["warp_gram_sparse.hip", "common.hpp"])):
+        for kern, key, files in (("warp_gram_kernel<", name, ["warp_gram_rhs.hip", "warp_gram_mfma.hpp", "common.hpp"]),
+                                 ("warp_gram_lt_kernel<", name + "_sparse", ["warp_gram_sparse.hip", "warp_gram_mfma.hpp", "common.hpp"])):
             c = kernels(s, [kern])
             if c and "FETCH_SIZE" in c:
                 entries[key] = {"value": hbm_bytes(c), "files": files, "what": "HBM bytes per launch of " + kern.rstrip("<")}
