@@ -299,6 +299,24 @@ class MotionCorrect(object):
         out = ops.apply_shifts_points(pts, self._shift_table(T), centers)
         return out.double().cpu().numpy()
 
+    def track_points(self, video, points, search=None, shape_std=3, **kw):
+        """``points`` (K,3) followed through ``video`` (T, X, Y, Z) by ``ExponentialFP.track_positions`` (K15): ``(P_T (K,3,T)
+        float64, amplitudes (K,T))``, numpy.  The search of every frame is centred on ``apply_shifts_points(video, points)``
+        when piecewise shifts are stored -- the patch grid's coarse track, refined per neuron -- else on the points
+        themselves; ``search`` defaults to ``max_shifts``; ``kw``: ``threshold``, ``background``.  A neuron within about 2
+        shape_std of a brighter one can be captured by it: ``search`` is the guard.  The reference has no counterpart."""
+        if not self.is3D:
+            raise NotImplementedError("MotionCorrect.track_points is a 3-D function like apply_shifts_points; register 2-D "
+                                      "videos as (T, X, Y, 1) with is3D=True")
+        from .dNMF import ExponentialFP
+        pts = np.asarray(points.cpu() if torch.is_tensor(points) else points, dtype=np.float64)
+        predict = self.apply_shifts_points(video, pts) if getattr(self, "x_shifts_els", None) else None
+        search = self.max_shifts if search is None else search
+        pos, amp = ExponentialFP.track_positions(video, pts, shape_std=shape_std, search=search, predict=predict, **kw)
+        if torch.is_tensor(pos):
+            pos, amp = pos.cpu().numpy(), amp.cpu().numpy()
+        return pos, amp
+
     def apply_shifts_frame(self, video, points, t):
         """Reference :330-349: the points moved by frame t's shifts (no reference frame, all three signs +)."""
         if not self.is3D:

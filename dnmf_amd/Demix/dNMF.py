@@ -400,6 +400,49 @@ class ExponentialFP(nn.Module):
         pos, amp, _ = ops.detect_neurons(img, img.shape, K, shape_std=shape_std, **kw)
         return (pos, amp) if on_gpu else (pos.cpu().numpy(), amp.cpu().numpy())
 
+    @staticmethod
+    def _video_rows(video, name):
+        """(rows (T, ld) fp32 CUDA, [X, Y, Z], rows came from the GPU) of a video given as (T, X, Y, Z) values (numpy / torch), as
+        resident rows with their volume ``(rows (T, P), sz)``, or as a ``ResidentLoader``."""
+        if hasattr(video, "frames_2d"):
+            return video.frames_2d(), _sz_list(video.sz), True
+        if isinstance(video, (tuple, list)) and len(video) == 2 and getattr(video[0], "ndim", 0) == 2:
+            rows, sz = video
+            on_gpu = isinstance(rows, torch.Tensor) and rows.is_cuda
+            rows = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows))
+            rows = rows.to(device, torch.float32)
+            return (rows if rows.stride(1) == 1 else rows.contiguous()), _sz_list(sz), on_gpu
+        on_gpu = isinstance(video, torch.Tensor) and video.is_cuda
+        v = video if isinstance(video, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(video))
+        if v.dim() != 4:
+            raise ValueError(f"{name}: a video is (T, X, Y, Z), (rows (T, P), sz) or a ResidentLoader, got {tuple(v.shape)}")
+        return v.to(device, torch.float32).reshape(v.shape[0], -1).contiguous(), [int(n) for n in v.shape[1:]], on_gpu
+
+    @staticmethod
+    def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None):
+        """Where the neurons are in every frame of ``video`` -- (T, X, Y, Z) values, or frames that already live on the GPU as
+        ``(rows (T, P), sz)`` or a ``ResidentLoader``: ``(P_T (K,3,T) float64, amplitudes (K,T))`` by K15
+        (``ops.track_neurons``): per neuron and frame the sub-voxel peak of the frame's matched-filter score (K14's, with
+        exp(-|x - p|^2 / shape_std^2)) within ``search`` voxels per axis of the rounded prediction, and its least-squares
+        amplitude.  ``points`` (K,3): the centres in one frame, annotated or detected (``detect_positions``); ``predict``
+        (K,3,T) or (K,3): where to look in every frame (None: at ``points``) -- it carries any prior, frame t is not chained
+        on frame t - 1.  NaN = not found (the "not tracked" of ``init_motion``): the prediction is not finite, the window
+        misses the volume, or the peak is not above ``threshold``.  ``background``: None (0), a number or T values taken off
+        the frames.  The searches are independent and neighbouring neurons are not removed from the score: a neuron within
+        about 2 shape_std of a brighter one can be captured by it, and ``search`` is the guard against that.  numpy or
+        CPU-torch in, numpy out; a CUDA ``video`` gives CUDA tensors.  The reference has no counterpart."""
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "track_positions")
+        pred = points if predict is None else predict
+        pred = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred))
+        if pred.dtype not in (torch.float32, torch.float64):
+            pred = pred.double()
+        pred = pred.to(device)
+        K = len(points)
+        if pred.dim() not in (2, 3) or pred.shape[0] != K or pred.shape[1] != 3:
+            raise ValueError(f"track_positions: predict must be ({K}, 3, T) or ({K}, 3), got {tuple(pred.shape)}")
+        pos, amp, _ = ops.track_neurons(rows, sz, pred, shape_std=shape_std, search=search, threshold=threshold, background=background)
+        return (pos, amp) if on_gpu else (pos.cpu().numpy(), amp.cpu().numpy())
+
 
 class DeformableNMF:
     """Reference ``Demix/dNMF.py:124-194``: owns the spatial model ``fp`` and the traces ``C`` (K,T)."""
@@ -923,6 +966,19 @@ class DeformableNMF:
             self.fp.beta.copy_(torch.where(ok[None, None, :], beta, self.fp.beta))
         self.fp.beta.grad = None
         return ok
+
+    def track(self, frames, search=(6, 6, 1), predict=None, **kw):
+        """The model's neurons followed through ``frames`` (what ``ExponentialFP.track_positions`` takes as ``video``) with
+        the model's own centres ``fp.pos`` and width ``fp.sigma`` (K15): ``(P_T (K,3,T) float64, amplitudes (K,T))``, tracks
+        that feed ``init_motion`` unchanged.  ``predict``: None looks around ``fp.pos`` in every frame, ``'model'`` around
+        ``self.positions()`` -- tracking around the current warp -- and a (K,3,T) or (K,3) array around itself; ``kw``:
+        ``threshold``, ``background``.  Neighbouring neurons are not removed from the score, so a neuron within about
+        2 sigma of a brighter one can be captured by it: ``search`` is the guard."""
+        if isinstance(predict, str):
+            if predict != 'model':
+                raise ValueError(f"track: predict must be None, 'model' or positions, got {predict!r}")
+            predict = self.positions()
+        return ExponentialFP.track_positions(frames, self.fp.pos, shape_std=float(self.fp.sigma[0]), search=search, predict=predict, **kw)
 
     def positions(self, points=None, times=None, start=None, tol=1e-6):
         """``fp.positions``: where the fitted warp puts the neurons in every frame, (K,3,T) float64 numpy."""

@@ -18,12 +18,12 @@
 //            filter's response to that footprint through per-axis tables h_axis in LDS, exclusion (-inf) of the voxels within
 //            min_distance, and the new maxima of the tiles the window touched.  The steps are separated by __syncthreads; R
 //            and the table live in the caller's workspace and are only touched by this workgroup.
-#include "common.hpp"
+#include "matched_filter.hpp"
 
 namespace dnmf {
 namespace {
 
-constexpr int DT_R_MAX = 96;      // taps per side: sigma <= 32
+constexpr int DT_R_MAX = MF_R_MAX; // taps per side: sigma <= 32
 constexpr int DT_WR_MAX = 511;    // half-width of the pursuit's window: max(2 r, what min_distance reaches)
 constexpr int DT_TX = 16, DT_TY = 16, DT_TZ = 4;   // a tile of the table
 constexpr int DT_TILE_OUT = 1024; // outputs of a filter block
@@ -38,35 +38,6 @@ struct DetectGeom {
     float md2;        // min_distance^2
     float threshold;
 };
-
-// sum of the squared taps inside an axis of S voxels at voxel s, from c2[k] = tap[0]^2 + ... + tap[k]^2
-__device__ __forceinline__ float axis_norm(const float *c2, int r, int s, int S) { return c2[min(r, s)] + c2[min(r, S - 1 - s)] - c2[0]; }
-// sqrt(nmax / n(s)): 1 where the window is inside the volume
-__device__ __forceinline__ float axis_weight(const float *c2, int r, int s, int S) {
-    return sqrtf(axis_norm(c2, r, (S - 1) / 2, S) / axis_norm(c2, r, s, S));
-}
-
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-// (largest value, lowest index among equals) over the wave, valid in lane 63: the fixed tree of wave_sum_last with the
-// lanes that have no partner keeping their own pair
-template <int CTRL, int RMASK>
-__device__ __forceinline__ void argmax_step(float &v, int &i) {
-    const int vb = __builtin_bit_cast(int, v);
-    const float ov = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(vb, vb, CTRL, RMASK, 0xf, false));
-    const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, RMASK, 0xf, false);
-    const bool take = better(ov, oi, v, i);
-    v = take ? ov : v, i = take ? oi : i;
-}
-
-__device__ __forceinline__ void wave_argmax_last(float &v, int &i) {
-    argmax_step<0x111, 0xf>(v, i);  // row_shr:1
-    argmax_step<0x112, 0xf>(v, i);  // row_shr:2
-    argmax_step<0x114, 0xf>(v, i);  // row_shr:4
-    argmax_step<0x118, 0xf>(v, i);  // row_shr:8 -> lane 15 of a row holds the row's pair
-    argmax_step<0x142, 0xa>(v, i);  // row_bcast:15 into rows 1 and 3
-    argmax_step<0x143, 0xc>(v, i);  // row_bcast:31 into rows 2 and 3
-}
 
 // One wave: the pair of tile `t` of the table, valid in lane 63.  NaN scores never win: a tile of nothing but NaN reports
 // (-inf, INT_MAX), a tile of excluded voxels (-inf, its lowest voxel).
@@ -99,15 +70,7 @@ __global__ __launch_bounds__(256) void filter_axis_kernel(const float *__restric
     float *c2 = lds + ((r + 4) & ~3);       // r + 1 running sums of tap^2
     float *tile = lds + 2 * ((r + 4) & ~3); // (rows + 2 r) x bw
     const int tid = threadIdx.x;
-    for (int i = tid; i <= r; i += 256) {
-        tap[i] = expf(-(float)(i * i) * inv_s2);
-        float acc = 0.0f;
-        for (int j = 0; j <= i; ++j) {
-            const float t = expf(-(float)(j * j) * inv_s2);
-            acc += t * t;
-        }
-        c2[i] = acc;
-    }
+    fill_taps(tap, c2, r, inv_s2, tid, 256);
     const int bb = blockIdx.x % nbb, sb = (blockIdx.x / nbb) % nsb, a = blockIdx.x / (nbb * nsb);
     const int s0 = sb * ts, b0 = bb * tbw;
     const int rows = min(ts, S - s0), bw = min(tbw, B - b0);
@@ -168,15 +131,7 @@ __global__ __launch_bounds__(DT_THREADS) void pursuit_kernel(float *R, float *tm
     const int S[3] = {g.X, g.Y, g.Z};
     const int r = g.r, wr = g.wr;
     const float ninf = -__builtin_inff();
-    for (int i = tid; i <= r; i += DT_THREADS) {
-        s_tap[i] = expf(-(float)(i * i) * g.inv_s2);
-        float acc = 0.0f;
-        for (int j = 0; j <= i; ++j) {
-            const float t = expf(-(float)(j * j) * g.inv_s2);
-            acc += t * t;
-        }
-        s_c2[i] = acc;
-    }
+    fill_taps(s_tap, s_c2, r, g.inv_s2, tid, DT_THREADS);
     __syncthreads();
     int found = 0;
     for (int k = 0; k < K; ++k) {
@@ -213,17 +168,7 @@ __global__ __launch_bounds__(DT_THREADS) void pursuit_kernel(float *R, float *tm
             if (bv > 0.0f && (two || one)) {
                 const int in = p[d] == 0 ? stride : -stride;
                 const float m = R[two ? bi - stride : bi + in], q = R[two ? bi + stride : bi + 2 * in];
-                if (m > 0.0f && q > 0.0f) {
-                    const float lm = logf(m), lc = logf(bv), lq = logf(q);
-                    // f(t) = lc + b t + a2 t^2
-                    const float a2 = two ? 0.5f * (lm - 2.0f * lc + lq) : 0.5f * (lc - 2.0f * lm + lq);
-                    const float b = two ? 0.5f * (lq - lm) : (lm - lc) - a2;
-                    if (a2 < 0.0f) {
-                        const float t = fminf(0.5f, fmaxf(-0.5f, -b / (2.0f * a2)));
-                        adj = b * t + a2 * t * t;
-                        dl = two || p[d] == 0 ? t : -t;
-                    }
-                }
+                refine_axis(bv, m, q, two, p[d] == 0, dl, adj);
             }
             s_f[d] = dl, s_f[4 + d] = adj;
         }
@@ -243,12 +188,11 @@ __global__ __launch_bounds__(DT_THREADS) void pursuit_kernel(float *R, float *tm
             dl[d] = keep ? s_f[d] : 0.0f;
             ph[d] = (float)p[d] + dl[d];
         }
-        const float rhat = keep ? bv * expf((s_f[4] + s_f[5]) + s_f[6]) : bv;
+        const float rhat = keep ? refined_score(bv, s_f[4], s_f[5], s_f[6]) : bv;
         // the footprint along each axis: x = p* + o, o in [-r, r]
         for (int i = tid; i < 3 * (2 * r + 1); i += DT_THREADS) {
             const int d = i / (2 * r + 1), o = i - d * (2 * r + 1) - r;
-            const float t = (float)o - dl[d];
-            s_e[d][o + r] = in_range(p[d] + o, S[d]) ? expf(-(t * t) * g.inv_s2) : 0.0f;
+            s_e[d][o + r] = footprint_tap(p[d], o, dl[d], S[d], g.inv_s2);
         }
         __syncthreads();
         // h(q) = sum_x g1(x - q) e(x) over |x - q| <= r, q = p* + j, j in [-wr, wr]; and the norms sum e^2
@@ -267,8 +211,7 @@ __global__ __launch_bounds__(DT_THREADS) void pursuit_kernel(float *R, float *tm
         }
         __syncthreads();
         // S^ = a sqrt(prod nmax) sqrt(prod sum e^2) for the footprint a e_x e_y e_z
-        const float amp = rhat / sqrtf(((s_f[8] * axis_norm(s_c2, r, (S[0] - 1) / 2, S[0])) * (s_f[9] * axis_norm(s_c2, r, (S[1] - 1) / 2, S[1]))) *
-                                       (s_f[10] * axis_norm(s_c2, r, (S[2] - 1) / 2, S[2])));
+        const float amp = footprint_amplitude(rhat, s_c2, r, S, s_f[8], s_f[9], s_f[10]);
         // subtract and exclude over the window
         int lo[3], ext[3];
 #pragma unroll

@@ -1000,6 +1000,64 @@ def detect_neurons(image, sz, K, shape_std=3, min_distance=None, threshold=0.0, 
     return positions, amplitudes, count
 
 
+def track_neurons(frames, sz, predict, shape_std=3, search=(6, 6, 1), threshold=0.0, background=None, times=None):
+    """K15.  frames (rows, ld >= X Y Z) fp32 CUDA rows (``ResidentLoader.frames_2d()`` / ``device_frames()``), predict (K,3,T)
+    or (K,3) (used for every frame) fp32 / fp64 CUDA -> ``(positions (K,3,T) fp64, amplitudes (K,T) fp32, peaks (K,T) fp32)``
+    on the device: for every neuron and every frame of ``times`` (None: rows 0..T-1; T = the frames of ``predict``, else every
+    row) the sub-voxel peak of the frame's K14 score -- the matched filter with exp(-|x - p|^2 / shape_std^2), noise-normalised
+    -- inside the window of ``search`` voxels per axis around the rounded prediction, its least-squares amplitude and the score
+    at the picked voxel (include/dnmf_hip.h).  NaN where the prediction is not finite, the window misses the volume or the
+    peak is not above ``threshold``.  ``background``: None (0), a number, or T values taken off the frames first.  The K T
+    searches are independent and nothing is subtracted: a neuron within about 2 shape_std of a brighter one can be captured
+    by it; ``search`` is the guard."""
+    X, Y, Z = (int(s) for s in sz)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2
+            and frames.stride(1) == 1 and frames.stride(0) >= X * Y * Z and frames.shape[1] >= X * Y * Z):
+        raise ValueError("track_neurons: frames must be float32 CUDA (T, ld) rows with unit inner stride and ld >= X Y Z")
+    dev = frames.device
+    per_frame = isinstance(predict, torch.Tensor) and predict.dim() == 3
+    if per_frame:
+        predict = _tracks(predict, "track_neurons")
+    elif not (isinstance(predict, torch.Tensor) and predict.is_cuda and predict.dtype in (torch.float32, torch.float64)
+              and predict.dim() == 2 and predict.shape[1] == 3 and predict.shape[0] >= 1):
+        raise ValueError("track_neurons: predict must be a (K,3,T) or (K,3) float32 or float64 CUDA tensor with K >= 1")
+    predict = predict.contiguous()
+    K = predict.shape[0]
+    tt = None
+    if times is not None:
+        tt = _i32(times, dev)
+        if tt.numel() < 1 or int(tt.min()) < 0 or int(tt.max()) >= frames.shape[0]:
+            raise ValueError(f"track_neurons: times must be at least one row index in [0, {frames.shape[0]})")
+    T = tt.numel() if tt is not None else (predict.shape[2] if per_frame else frames.shape[0])
+    if per_frame and predict.shape[2] != T:
+        raise ValueError(f"track_neurons: predict of {predict.shape[2]} frames for {T} frames")
+    if tt is None and frames.shape[0] < T:
+        raise ValueError(f"track_neurons: {frames.shape[0]} frames for a prediction of {T} frames")
+    w = [int(v) for v in search]
+    if len(w) != 3 or min(w) < 0:
+        raise ValueError(f"track_neurons: search must be three integers >= 0, got {search}")
+    sigma = float(shape_std)
+    if not (sigma > 0.0 and sigma != float("inf")):
+        raise ValueError(f"track_neurons: shape_std={shape_std} must be positive and finite")
+    bg = None
+    if background is not None:
+        if isinstance(background, torch.Tensor) or hasattr(background, "__len__"):
+            bg = torch.as_tensor(background).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if bg.numel() != T:
+                raise ValueError(f"track_neurons: background of {bg.numel()} values for {T} frames")
+        else:
+            bg = torch.full((T,), float(background), dtype=torch.float32, device=dev)
+    positions = torch.empty((K, 3, T), dtype=torch.float64, device=dev)
+    amplitudes = torch.empty((K, T), dtype=torch.float32, device=dev)
+    peaks = torch.empty((K, T), dtype=torch.float32, device=dev)
+    with _timed("track_neurons"):
+        rc = _lib.load().dnmf_track_neurons(frames.data_ptr(), frames.stride(0), _int3((X, Y, Z)), T, _ptr(tt), predict.data_ptr(),
+                                            int(predict.dtype == torch.float64), int(per_frame), K, sigma, _int3(w), float(threshold),
+                                            _ptr(bg), positions.data_ptr(), amplitudes.data_ptr(), peaks.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_track_neurons")
+    return positions, amplitudes, peaks
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -5,12 +5,16 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
 ground truth of frame 0; the model is built on the detected centres alone, as many neurons as were found.  The simulator's
 centres then serve only to judge the result: a detected centre is matched to the simulated neuron nearest to it in frame 0
 when that is within sigma (one centre per neuron), and the errors and correlations are taken over the matched ones.
+
+``--track``: the initialiser's tracks are refined per neuron and frame by the tracker (``MotionCorrect.track_points``, K15: the
+peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
+printed for both sets of tracks.
 """
 import argparse
 import os
@@ -35,6 +39,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--detect", action="store_true", help="find the centres in the template instead of taking the simulator's")
+    ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
+    ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -75,12 +81,20 @@ def main():
     def median_corr(S):
         return float(np.median([np.corrcoef(S[j], dataset.traces[k])[0, 1] for j, k in zip(sel, tr)]))
 
-    for start in ("identity", "tracks"):
+    starts = {"identity": None, "tracks": P_T}
+    if a.track:
+        refined, _ = mc.track_points(video, pts, search=(a.search, a.search, 1), shape_std=3)
+        lost = np.isnan(refined).any(1)
+        print(f"track_points: {int((~lost).sum())} of {lost.size} (neuron, frame) pairs found; mean |x, y error| of the per-frame "
+              f"centres {np.nanmean(np.abs(refined[sel, :2, :] - truth[tr, :2, :])):.2f} voxels with the tracker, {err:.2f} with "
+              f"the initialiser alone")
+        starts["tracker"] = refined
+    for start, tracks in starts.items():
         torch.manual_seed(1)
         dn = DeformableNMF(sz, n, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
         dn.verbose = False
-        if start == "tracks":
-            ok = dn.init_motion(P_T, ridge=a.ridge)
+        if tracks is not None:
+            ok = dn.init_motion(tracks, ridge=a.ridge)
             print(f"init_motion: {int(ok.sum())} of {T} frames fitted")
         loader = dataset.loader(a.batch)
         dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)

@@ -544,6 +544,34 @@ int dnmf_detect_neurons(const float *img, const int *sz, int K, double sigma, do
                         float *positions, float *amplitudes, int *count, void *workspace, size_t workspace_bytes,
                         dnmf_stream_t stream);
 
+/* ---- K15: per-frame neuron tracking by a local matched filter ------------------------------------------------------------
+ * For every neuron k < K and frame j < T the peak of K14's score volume of that frame inside a search window around a
+ * predicted position.  tests/track_restatement.py is the definition in float64; all arithmetic here is fp32 and the positions
+ * are widened where they are stored.
+ *   score    S_j = K14's score of frame j: taps g1(d) = exp(-d^2 / sigma^2) truncated at r = ceil(3 sigma), zero padding,
+ *            background[j] taken off first, per-axis weight sqrt(nmax / n(q));
+ *   window   c = predict[k, :, j] rounded half to even; the voxels q of the volume with |q_d - c_d| <= search[d] on every axis;
+ *   pick     p* = arg-max of S_j over the window (equal scores: the lowest voxel index (x Y + y) Z + z; NaN scores never win);
+ *   refine   K14's rule unchanged: per axis the log-parabola through S_j at p* and its two neighbours (at the first / last voxel
+ *            of an axis of >= 3: p* and the two voxels inward), where those scores are > 0 and the parabola is concave, clamped
+ *            to +-1/2 voxel; the neighbours are voxels of the volume and may lie outside the window; p^ = p* + delta;
+ *   amplitude a = S^ / sqrt(prod_axis nmax sum_x g1(x - p^)^2) over the voxels of the volume within r of p*, as K14.
+ * A row is NaN when the prediction is not finite, the window has no voxel inside the volume, S_j(p*) is not finite or
+ * S_j(p*) <= threshold.  Nothing is subtracted and nothing excluded: the K T searches are independent, so a neuron within about
+ * 2 sigma of a brighter one can be captured by it -- the search window is the guard.  Frame j does not depend on frame j - 1:
+ * predict carries any prior.
+ * frames: >= max row + 1 rows of ldf >= X Y Z floats, voxel p = (x Y + y) Z + z; sz, search: 3 host ints; times: T device row
+ * indices (NULL: 0..T-1); predict: (K,3,T) when predict_per_frame, else (K,3) used for every frame, fp64 when predict_f64 else
+ * fp32; background: T device floats (NULL: 0).  positions (K,3,T) fp64, the layout K11 / K12 / K13 read; amplitudes and peaks
+ * (= S_j(p*)) (K,T) fp32, either may be NULL.  One launch, one workgroup per (k, j), which stages the region of at most
+ * prod_axis min(S, 2 (search + 1 + r) + 1) voxels in LDS; no host synchronisation, no workspace.
+ * DNMF_E_NULL: frames, sz, predict, search or positions NULL;  DNMF_E_SHAPE: sigma <= 0 or not finite, K or T < 1, a size < 1, a
+ * negative search entry, threshold NaN or +inf, ldf < X Y Z;  DNMF_E_UNSUPPORTED: sigma > 32, 2^31 voxels or K T searches or
+ * more, a region that needs more than 48 KiB of LDS (the message names its size).  Nothing is launched on an error. */
+int dnmf_track_neurons(const float *frames, long ldf, const int *sz, int T, const int *times, const void *predict, int predict_f64,
+                       int predict_per_frame, int K, double sigma, const int *search, double threshold, const float *background,
+                       double *positions, float *amplitudes, float *peaks, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
