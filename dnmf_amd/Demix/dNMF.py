@@ -38,6 +38,7 @@ LISTS_MAX_K = 256           # neurons the neuron-list kernels (K3n, list reconst
 RECON_CACHE_LIMIT = 64 << 30
 K2_MAX_FRAMES = 32768       # frames per K2 launch (they ride on gridDim.y)
 STAGE_LIMIT = 96 << 30      # a host loader's frames are staged on the GPU once per pass below this many bytes
+GN_CHUNK_BYTES = 1 << 30    # update_motion(solver='gn') builds the reconstruction images of this many bytes of frames at a time
 
 
 def _sz_list(sz):
@@ -503,6 +504,8 @@ class DeformableNMF:
         # images that stay in the Infinity Cache did not materialise), so it is a memory option; 0 = all frames at once
         self.motion_chunk = 0
         self._stage_buf = None     # device copy of the frames a host loader served in its last pass
+        # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam (CUDA tensors, (T,)); else None
+        self.last_motion_gn = None
         self._reg_buf = None       # registered frames (K7) of the last update_footprints(live_spatial=True)
         self._D_dev = None         # (id(self.D), fp32 device copy of D flattened to (P,K))
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
@@ -984,14 +987,22 @@ class DeformableNMF:
         """``fp.positions``: where the fitted warp puts the neurons in every frame, (K,3,T) float64 numpy."""
         return self.fp.positions(points=points, times=times, start=start, tol=tol)
 
-    def update_motion(self, dataloader, optimizer, gamma=0, epochs=20):
+    def update_motion(self, dataloader, optimizer, gamma=0, epochs=20, solver='adam', iters=None, damping=1e-3):
         """Reference :181-194: mini-batch steps of the caller's optimiser on ``fp.beta`` against
         ``mse(A_tC, frames) + gamma*mean(reg)`` (the reg term is gradient-free in the reference, :60-61).
+
+        ``solver='gn'`` (not in the reference) fits every frame's warp by damped Gauss-Newton steps instead
+        (``_update_motion_gn``: K16 + ``dnmf_lm_step``): no learning rate, ``optimizer`` may be None and is left untouched,
+        ``iters`` (default ``epochs``) Levenberg-Marquardt iterations per frame starting at the damping ``damping``; ``gamma``
+        is ignored, as the reference's gradient-free reg term is.
 
         A ``ResidentLoader`` hands over rows that already live on the GPU.  Any other loader (the stock
         ``torch.utils.data.DataLoader`` of demo.py:33-35) is iterated once per epoch by a background thread while this
         thread copies the mini-batches into a device buffer (``_stage_epoch``); the epoch then runs from that buffer --
         as four launches when the optimiser is the demo's plain Adam (``_motion_epoch``), else step by step."""
+        _check_motion_solver(solver, "update_motion")
+        if solver == 'gn':
+            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma)
         fp = self.fp
         beta = fp.beta
         # reconstruction images of all frames (C is constant inside this call): built when first needed -- the fused
@@ -1051,6 +1062,89 @@ class DeformableNMF:
                 if want:
                     print('Recon: ' + str(out["loss"][0]))
                     print('Reg: ' + str(out["reg"]))
+
+    def _update_motion_gn(self, dataloader, iters, damping, gamma=0):
+        """``update_motion(solver='gn')``: Levenberg-Marquardt on the 30 (12 at Z = 1) coefficients of every frame.
+
+        The loss is a sum over frames and frame t only sees ``beta[:, :, t]``, so the frames are independent small dense
+        least-squares problems.  Chunk-outer, iteration-inner: for each chunk of frames the reconstruction images are built
+        once (``fp.recon_image``: from the neuron lists when the footprints are compact; C is constant here), then ``iters``
+        pairs of K16 (``ops.warp_normal_eqs``: H = J^T J, g = J^T r, sse at the trial coefficients, summed over the colour
+        channels) and ``ops.lm_step`` (accept or reject the trial, next trial) run without a host synchronisation, and a last
+        K16 + accept-only step leaves the best ACCEPTED coefficients in ``fp.beta`` -- never an untested trial.  The images of
+        the whole video are never needed; a chunk is ``motion_chunk`` frames when that is set, else what fits
+        ``GN_CHUNK_BYTES``.  A ``ResidentLoader`` and a stageable loader are served from their device rows in one pass (frame
+        order is irrelevant); any other loader batch by batch, each mini-batch getting its iterations when it arrives.
+
+        ``fp.beta`` is updated in place (``requires_grad`` kept, ``.grad`` left alone).  Afterwards ``last_motion_gn`` holds,
+        per frame of the model (NaN / 0 for frames the loader did not serve), ``sse0`` and ``sse`` (squared error at the
+        start and at the result), ``accepted`` / ``rejected`` step counts and the final damping ``lam``.  With the T axis
+        sharded over ranks every rank fits its own frames: there is no collective and nothing to exchange."""
+        fp = self.fp
+        iters = int(iters)
+        if iters < 0:
+            raise ValueError(f"update_motion(solver='gn'): iters={iters}")
+        if self.verbose and gamma:
+            print(f"update_motion(solver='gn'): gamma={gamma} ignored (the reg term is gradient-free in the reference)")
+        chans = self._channels()
+        row = sum(f.P for f, _ in chans)
+        lds = ops.halo_voxels(fp.sz_list)
+        chunk = int(self.motion_chunk) if self.motion_chunk > 0 else max(1, GN_CHUNK_BYTES // (4 * lds * len(chans)))
+        chunk = min(chunk, K2_MAX_FRAMES)
+        Cdev = self.C.to(device, torch.float32).contiguous()
+        beta = fp.beta.detach()          # the same storage: the kernels read and write the leaf's columns
+        stats = {"sse0": torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device),
+                 "sse": torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device),
+                 "accepted": torch.zeros((fp.T,), dtype=torch.int32, device=device),
+                 "rejected": torch.zeros((fp.T,), dtype=torch.int32, device=device),
+                 "lam": torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)}
+        bufs = {}
+
+        def fit(frames, fid, times):
+            """All iterations of the frames ``times`` (distinct; frame ``times[i]`` in row ``fid[i]``, None: row i)."""
+            for s0 in range(0, times.numel(), chunk):
+                tt = times[s0:s0 + chunk].contiguous()
+                n = tt.numel()
+                ff = None if fid is None else fid[s0:s0 + chunk].contiguous()
+                fr = frames if fid is not None else frames[s0:s0 + n]
+                if "S" not in bufs or bufs["S"][0].shape[0] < n:
+                    bufs["S"] = [torch.empty((n, lds), dtype=torch.float32, device=device) for _ in chans]
+                S = [f.recon_image(Cdev, tt, out=buf[:n]) for (f, _), buf in zip(chans, bufs["S"])]
+                state = ops.lm_state(n, device)
+                eqs = None
+                for it in range(iters + 1):
+                    for c, ((f, cols), Sc) in enumerate(zip(chans, S)):
+                        eqs = ops.warp_normal_eqs(Sc, None, fr if cols is None else fr[:, cols], ff, fp.sz_list, beta, tt,
+                                                  out=eqs, accumulate=c > 0, workspace=bufs.get("ws"))
+                        bufs["ws"] = eqs["workspace"]
+                    ops.lm_step(state, eqs, fp.sz_list, beta, tt, lam0=damping, accept_only=it == iters)
+                idx = tt.long()
+                stats["sse0"][idx], stats["sse"][idx], stats["lam"][idx] = state["sse0"], state["sse"], state["lam"]
+                stats["accepted"][idx], stats["rejected"][idx] = state["counts"][:, 0], state["counts"][:, 1]
+                if self.verbose:
+                    print(f"GN frames {int(tt[0])}..: sse {float(state['sse0'].sum()):.6g} -> {float(state['sse'].sum()):.6g}")
+
+        with torch.no_grad():
+            staged = None
+            if isinstance(dataloader, ResidentLoader):
+                staged = (dataloader.frames_2d(), [dataloader.order_tensor().tolist()], True)
+            elif self.stream_loader:
+                staged = self._stage_epoch(dataloader)
+            if staged is not None:
+                frames, batch_times, by_frame = staged
+                flat = torch.tensor([t for b in batch_times for t in b], dtype=torch.int64)
+                if frames.shape[1] != row:
+                    raise ValueError(f"a frame has {frames.shape[1]} values, the model expects {row}")
+                # frame t in row t, or in the (last) row of the staging buffer it arrived in
+                rows = torch.zeros(fp.T, dtype=torch.int64)
+                rows[flat] = flat if by_frame else torch.arange(flat.numel(), dtype=torch.int64)
+                times = torch.unique(flat)
+                fit(frames, rows[times].to(device, torch.int32), times.to(device, torch.int32))
+            else:
+                for data in dataloader:
+                    times = torch.as_tensor(data[1]).to(device, torch.int32).reshape(-1)
+                    fit(data[0].to(device, torch.float32).reshape(times.numel(), -1), None, times)
+        self.last_motion_gn = stats
 
     def _motion_epoch_from_host(self, dataloader, optimizer, S_all, Cdev):
         """One epoch with every mini-batch copied from the host when it is needed (loaders that cannot be staged)."""
@@ -1206,13 +1300,15 @@ class DeformableNMF:
                 print('Reg: ' + str(out["reg"][j * nf:(j + 1) * nf]))
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
-            spatial=False, gamma_a=1e0, solver='mu'):
+            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam'):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
-        that call's (``'hals'``: the exact trace solver K4h)."""
+        that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
+        Gauss-Newton, ``optimizer`` may then be None)."""
+        _check_motion_solver(motion_solver, "fit")
         out = (None, None, None)
         for _ in range(outer):
-            self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs)
+            self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
             out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
                                          iter_c=iter_c, live_spatial=spatial, solver=solver)
         return out
@@ -1338,6 +1434,11 @@ SOLVERS = ('mu', 'hals')
 def _check_solver(solver):
     if solver not in SOLVERS:
         raise ValueError(f"solver={solver!r}: expected one of {SOLVERS}")
+
+
+def _check_motion_solver(solver, who):
+    if solver not in ('adam', 'gn'):
+        raise ValueError(f"{who}: motion solver must be 'adam' or 'gn', got {solver!r}")
 
 
 def _hals_refuse_shards(gamma, group):

@@ -1,0 +1,535 @@
+// K16 -- the per-frame normal equations of the motion fit, and the Levenberg-Marquardt step that uses them.
+//
+// The motion loss sum_t sum_v (A_tC(v) - y_t(v))^2 is a sum over frames, and frame t only sees beta[:, :, t]: 30 unknowns
+// (12 at Z = 1) against P residuals.  With r(v) = A_tC(v) - y(v), g_d(v) = d A_tC / d q_d (v) -- both exactly K2's, same
+// warp, same normalise / un-normalise round trip, same taps from the halo layout -- and the CENTRED quadratic basis
+//   phi(v) = quadratic_basis(u(v)),   u_d = 2 x_d / (S_d - 1) - 1   (u_d = 0 on an axis of one voxel)
+// the Jacobian row of voxel v is J(v)[a,d] = phi_a(v) g_d(v), and per frame
+//   H = sum_v J^T J (30,30),   g = sum_v J^T r (30),   sse = sum_v r^2,        parameter index a*3 + d.
+// Centred coordinates keep every monomial in [-1, 1]: in voxel monomials H has entries up to 511^4 beside entries of
+// order 1 and is useless in fp32.  tests/gn_restatement.py is the definition in float64.
+//
+// Kernel shape: K2's work layout -- a lane owns one position of the (y,z) plane (both slices of it at Z == 2) and walks
+// down K16_ROWS consecutive x.  u_y and u_z are constant along the walk, so a thread only accumulates moments over x:
+// sum g_d g_e u_x^m (m = 0..4) and sum r g_d u_x^m (m = 0..2): 15 + 6 + 1 sums at Z = 1, 30 + 9 + 1 per slice at Z > 1.
+// phi_a phi_b is a monomial of degree <= 4 in u, so the DISTINCT sums behind H are (monomials of degree <= 4) x (pairs
+// d <= e): 15 x 3 = 45 at Z = 1, 35 x 6 = 210 at Z > 1; behind g (degree <= 2) x d: 12 / 30.  A thread expands its moments
+// into those (a product with powers of its u_y, u_z), the block reduces them (DPP tree per wave, four waves through
+// LDS) and writes one row of partial sums; the finish kernel adds the rows of a frame in float64 and only there
+// spreads them into the full symmetric matrix.
+#include "common.hpp"
+
+namespace dnmf {
+
+typedef float gn_f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
+typedef float gn_f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+
+constexpr int K16_ROWS = 32;    // voxels per lane along x (K2's)
+constexpr int K16_COLS = 256;   // positions of the (y,z) plane per block
+
+// monomials u_x^i u_y^j u_z^k of degree <= DEG in NDIM variables, numbered i outermost, k innermost
+template <int NDIM, int DEG>
+__host__ __device__ constexpr int mono_count() {
+    int n = 0;
+    for (int i = 0; i <= DEG; ++i)
+        for (int j = 0; j <= DEG - i; ++j)
+            for (int k = 0; k <= (NDIM == 3 ? DEG - i - j : 0); ++k) ++n;
+    return n;
+}
+template <int NDIM, int DEG>
+__host__ __device__ constexpr int mono_index(int ei, int ej, int ek) {
+    int n = 0;
+    for (int i = 0; i <= DEG; ++i)
+        for (int j = 0; j <= DEG - i; ++j)
+            for (int k = 0; k <= (NDIM == 3 ? DEG - i - j : 0); ++k) {
+                if (i == ei && j == ej && k == ek) return n;
+                ++n;
+            }
+    return -1;
+}
+
+// layout of one row of sums: [pair (d <= e)][monomial of degree <= 4], then [d][monomial of degree <= 2], then sse
+template <int NDIM>
+struct GnSums {
+    static constexpr int ND = NDIM;
+    static constexpr int NP = NDIM * (NDIM + 1) / 2;
+    static constexpr int NM4 = mono_count<NDIM, 4>();
+    static constexpr int NM2 = mono_count<NDIM, 2>();
+    static constexpr int G0 = NP * NM4;
+    static constexpr int SSE = G0 + NDIM * NM2;
+    static constexpr int NS = SSE + 1;
+    __host__ __device__ static constexpr int pair(int d, int e) { return d * NDIM - d * (d - 1) / 2 + (e - d); }   // d <= e
+};
+static_assert(GnSums<2>::NS == 45 + 12 + 1 && GnSums<3>::NS == 210 + 30 + 1, "the sums a block reduces");
+static_assert(GnSums<3>::NS <= K16_COLS, "one thread per sum writes the block's row");
+
+// u = coordinate * s + o per axis: s = 2 / (S - 1), o = -1 (s = o = 0 on an axis of one voxel)
+struct Centre {
+    float s[3], o[3];
+};
+
+// (x, x*x, u_x, u_x^2) for every x of the volume (scalar loads in the main kernel)
+__global__ void k16_xtab_kernel(float4 *__restrict__ xtab, int X) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < X) {
+        const float xf = (float)x;
+        const float u = X > 1 ? (float)(2.0 * (double)x / (double)(X - 1) - 1.0) : 0.0f;
+        xtab[x] = make_float4(xf, __fmul_rn(xf, xf), u, u * u);
+    }
+}
+
+// ZM = 1: Z == 1 (two coordinates, four taps, the z terms left out); 2: Z == 2 (a lane owns both slices, their z-pairs
+// are one 16-byte gather per x-corner); 3: Z > 2.  The sample and its derivative are K2's (warp_recon_grad.hip), operation
+// for operation.
+template <int ZM>
+__global__ __launch_bounds__(256) void warp_normal_eqs_kernel(const float *__restrict__ S, long lds, const int *__restrict__ s_ids,
+                                                              const float *__restrict__ frames, long ldf,
+                                                              const int *__restrict__ frame_ids, Volume vol, HaloLayout hl,
+                                                              Centre cen, const float *__restrict__ beta, int T,
+                                                              const int *__restrict__ times, float *__restrict__ partial,
+                                                              const float4 *__restrict__ xtab, int nub) {
+    constexpr bool HASZ = ZM > 1;
+    constexpr bool ZPAIR = ZM == 2;
+    constexpr int NV = ZPAIR ? 2 : 1;
+    using L = GnSums<HASZ ? 3 : 2>;
+    constexpr int ND = L::ND, NP = L::NP;
+    const int b = blockIdx.y;
+    float *__restrict__ prow = partial + ((long)b * gridDim.x + blockIdx.x) * L::NS;
+    float bt[30];
+    load_beta(beta, T, times[b], bt);
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 30; ++i) finite = finite && bt[i] - bt[i] == 0.0f;   // false for NaN and +-inf
+    if (!finite) {   // block-uniform: nothing is gathered; H and g get zeros, sse a NaN
+        if ((int)threadIdx.x < L::NS) prow[threadIdx.x] = (int)threadIdx.x == L::SSE ? __builtin_nanf("") : 0.0f;
+        return;
+    }
+    const char *__restrict__ s = reinterpret_cast<const char *>(S + (long)(s_ids ? s_ids[b] : b) * lds);
+    const float *__restrict__ y = frames + (long)(frame_ids ? frame_ids[b] : b) * ldf;
+
+    float hm[NV][NP][5], gm[NV][ND][3];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+            for (int m = 0; m < 5; ++m) hm[v][p][m] = 0.0f;
+#pragma unroll
+        for (int d = 0; d < ND; ++d)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) gm[v][d][m] = 0.0f;
+    }
+    float sq = 0.0f;
+    const int YZ = vol.Y * vol.Z;
+    const int plane = ZPAIR ? vol.Y : YZ;
+    const int bu = blockIdx.x % nub, bx = blockIdx.x / nub;
+    const int u = bu * K16_COLS + threadIdx.x;        // position in the (y,z) plane; Z == 2: y
+    const int yy = ZM == 3 ? div_small(u, vol.Z, vol.rcp_z) : u;
+    const int z = ZM == 3 ? u - yy * vol.Z : 0;
+    const float yf = (float)yy, zf = (float)z;
+
+    if (u < plane) {
+        float b2[30];
+        double_beta(bt, b2);
+        const int x_first = bx * K16_ROWS;
+        const int nrow = min(K16_ROWS, vol.X - x_first);
+        const unsigned u4 = (unsigned)u * (4u * NV);
+        for (int i = 0; i < nrow; ++i) {
+            const float4 xt = xtab[x_first + i];
+            const float ux = xt.z, ux2 = xt.w, ux3 = ux2 * ux, ux4 = ux2 * ux2;
+            const char *op = reinterpret_cast<const char *>(y + (long)(x_first + i) * YZ) + u4;
+            float other[NV];
+            if constexpr (ZPAIR) {
+                const float2 o2 = *reinterpret_cast<const float2 *>(op);   // (x, y, 0), (x, y, 1)
+                other[0] = o2.x, other[NV - 1] = o2.y;
+            } else {
+                other[0] = *reinterpret_cast<const float *>(op);
+            }
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const float zv = ZPAIR ? (float)v : zf;
+                float a[3] = {0.0f, 0.0f, 0.0f};
+                if constexpr (HASZ) {
+                    const Monomials<true> m = {xt.x, yf, zv, xt.y, __fmul_rn(yf, yf), __fmul_rn(zv, zv), __fmul_rn(xt.x, yf),
+                                               __fmul_rn(xt.x, zv), __fmul_rn(yf, zv)};
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) a[d] = poly_a<true>(b2, d, m);
+                } else {
+                    const Monomials<false> m = {xt.x, yf, 0.0f, xt.y, __fmul_rn(yf, yf), 0.0f, __fmul_rn(xt.x, yf), 0.0f, 0.0f};
+#pragma unroll
+                    for (int d = 0; d < 2; ++d) a[d] = poly_a<false>(b2, d, m);
+                }
+                float fx, fy, w0, wx1, wy1;
+                axis_taps_halo(unnormalise(normalise_axis<-1>(a[0], vol, 0), vol.hx1), hl.xhi, fx, w0, wx1);
+                axis_taps_halo(unnormalise(normalise_axis<-1>(a[1], vol, 1), vol.hy1), hl.yhi, fy, w0, wy1);
+                unsigned olo = halo_offset<false>(fx, fy, hl, hl.origin4, hl.origin4f);   // base corner, slice 0
+                float wzm[2] = {1.0f, 0.0f}, vz[2] = {0.0f, 0.0f};
+                if constexpr (HASZ) {
+                    const float uz = unnormalise(normalise_axis<-1>(a[2], vol, 2), vol.hz1);
+                    if constexpr (ZM == 2) {   // the pair is (0, 1): see K2 for the weights and their derivatives
+                        const float uc = z_pair_weights(uz, wzm[0], wzm[1]);
+                        const float c0 = fmaf(2.0f, floorf(uc), 1.0f), c1 = c0 - 2.0f;
+                        vz[0] = fabsf(c0) == 1.0f ? -c0 : 0.0f;
+                        vz[1] = fabsf(c1) == 1.0f ? -c1 : 0.0f;
+                    } else {                   // the pair (izc, izc + 1) inside the volume that holds every in-range z-tap
+                        int iz;
+                        float wz[2];
+                        axis_weights(uz, iz, wz[0], wz[1]);
+                        const int izc = clamp_index(iz, vol.Z - 1);
+                        const bool same = iz == izc, below = iz + 1 == izc, above = iz == izc + 1;
+                        wzm[0] = same ? wz[0] : (below ? wz[1] : 0.0f);
+                        wzm[1] = same ? wz[1] : (above ? wz[0] : 0.0f);
+                        vz[0] = same ? -1.0f : (below ? 1.0f : 0.0f);
+                        vz[1] = same ? 1.0f : (above ? -1.0f : 0.0f);
+                        olo += (unsigned)izc * 4u;
+                    }
+                }
+                // taps sv[dz][dy][dx]: the x-corner rows olo and olo + row4
+                float sv[HASZ ? 2 : 1][2][2];
+#pragma unroll
+                for (int dx = 0; dx < 2; ++dx) {
+                    const char *t = s + (olo + (unsigned)(dx * hl.row4));
+                    if constexpr (ZM == 2) {          // (y, z0), (y, z1), (y + 1, z0), (y + 1, z1)
+                        const gn_f32x4_a8 r = *reinterpret_cast<const gn_f32x4_a8 *>(t);
+                        sv[0][0][dx] = r.x, sv[1][0][dx] = r.y, sv[0][1][dx] = r.z, sv[1][1][dx] = r.w;
+                    } else if constexpr (ZM == 3) {   // the z-pair of corner y, then of corner y + 1
+                        const gn_f32x2_a4 r0 = *reinterpret_cast<const gn_f32x2_a4 *>(t);
+                        const gn_f32x2_a4 r1 = *reinterpret_cast<const gn_f32x2_a4 *>(t + hl.col4);
+                        sv[0][0][dx] = r0.x, sv[1][0][dx] = r0.y, sv[0][1][dx] = r1.x, sv[1][1][dx] = r1.y;
+                    } else {
+                        sv[0][0][dx] = *reinterpret_cast<const float *>(t);
+                        sv[0][1][dx] = *reinterpret_cast<const float *>(t + 4);
+                    }
+                }
+                float rec = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int dz = 0; dz < (HASZ ? 2 : 1); ++dz) {   // K2's blends
+                    const float d0 = sv[dz][0][1] - sv[dz][0][0];
+                    const float d1 = sv[dz][1][1] - sv[dz][1][0];
+                    const float a0 = fmaf(wx1, d0, sv[dz][0][0]);
+                    const float a1 = fmaf(wx1, d1, sv[dz][1][0]);
+                    const float gy2 = a1 - a0;
+                    const float r2 = fmaf(wy1, gy2, a0);
+                    const float gx2 = fmaf(wy1, d1 - d0, d0);
+                    if (HASZ) {
+                        rec = fmaf(wzm[dz], r2, rec);
+                        g[0] = fmaf(wzm[dz], gx2, g[0]);
+                        g[1] = fmaf(wzm[dz], gy2, g[1]);
+                        g[2] = fmaf(vz[dz], r2, g[2]);
+                    } else {
+                        rec = r2, g[0] = gx2, g[1] = gy2;
+                    }
+                }
+                const float resid = rec - other[v];
+                sq = fmaf(resid, resid, sq);
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    const float rg = resid * g[d];
+                    gm[v][d][0] += rg;
+                    gm[v][d][1] = fmaf(ux, rg, gm[v][d][1]);
+                    gm[v][d][2] = fmaf(ux2, rg, gm[v][d][2]);
+#pragma unroll
+                    for (int e = d; e < ND; ++e) {
+                        const float gg = g[d] * g[e];
+                        float(&h)[5] = hm[v][L::pair(d, e)];
+                        h[0] += gg;
+                        h[1] = fmaf(ux, gg, h[1]);
+                        h[2] = fmaf(ux2, gg, h[2]);
+                        h[3] = fmaf(ux3, gg, h[3]);
+                        h[4] = fmaf(ux4, gg, h[4]);
+                    }
+                }
+            }
+        }
+    }
+
+    // a thread's share of every distinct sum: its x-moments times powers of its u_y, u_z; then the block reduction
+    // (wave_sum_last: a DPP tree, total in lane 63; the four waves' totals through LDS)
+    __shared__ float red[4][L::NS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float py[5], pz[NV][5];
+    {
+        const float uy = fmaf(yf, cen.s[1], cen.o[1]);
+        py[0] = 1.0f;
+#pragma unroll
+        for (int j = 1; j < 5; ++j) py[j] = py[j - 1] * uy;
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            const float uz = HASZ ? fmaf(ZPAIR ? (float)v : zf, cen.s[2], cen.o[2]) : 0.0f;
+            pz[v][0] = 1.0f;
+#pragma unroll
+            for (int k = 1; k < 5; ++k) pz[v][k] = pz[v][k - 1] * uz;
+        }
+    }
+    {
+        int n = 0;
+#pragma unroll
+        for (int i = 0; i <= 4; ++i)
+#pragma unroll
+            for (int j = 0; j <= 4 - i; ++j)
+#pragma unroll
+                for (int k = 0; k <= (HASZ ? 4 - i - j : 0); ++k) {
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) {
+                        float val = 0.0f;
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) val = fmaf(py[j] * pz[v][k], hm[v][p][i], val);
+                        val = wave_sum_last(val);
+                        if (lane == 63) red[wave][p * L::NM4 + n] = val;
+                    }
+                    ++n;
+                }
+        n = 0;
+#pragma unroll
+        for (int i = 0; i <= 2; ++i)
+#pragma unroll
+            for (int j = 0; j <= 2 - i; ++j)
+#pragma unroll
+                for (int k = 0; k <= (HASZ ? 2 - i - j : 0); ++k) {
+#pragma unroll
+                    for (int d = 0; d < ND; ++d) {
+                        float val = 0.0f;
+#pragma unroll
+                        for (int v = 0; v < NV; ++v) val = fmaf(py[j] * pz[v][k], gm[v][d][i], val);
+                        val = wave_sum_last(val);
+                        if (lane == 63) red[wave][L::G0 + d * L::NM2 + n] = val;
+                    }
+                    ++n;
+                }
+        const float v = wave_sum_last(sq);
+        if (lane == 63) red[wave][L::SSE] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < L::NS)
+        prow[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// exponents of the quadratic basis [1, x, y, z, x^2, y^2, z^2, xy, xz, yz]
+__device__ constexpr int GN_EX[10] = {0, 1, 0, 0, 2, 0, 0, 1, 1, 0};
+__device__ constexpr int GN_EY[10] = {0, 0, 1, 0, 0, 2, 0, 1, 0, 1};
+__device__ constexpr int GN_EZ[10] = {0, 0, 0, 1, 0, 0, 2, 0, 1, 1};
+
+// One block per frame: the block rows of the frame added in float64 (fixed order), then spread into H (30,30), g (30), sse.
+// NDIM = 2 (Z == 1): entries of an unknown with z in its basis term or d == 2 are exact zeros.
+template <int NDIM>
+__global__ __launch_bounds__(256) void warp_normal_eqs_finish_kernel(const float *__restrict__ partial, int nblk,
+                                                                     double *__restrict__ H, double *__restrict__ g,
+                                                                     double *__restrict__ sse, int accumulate) {
+    using L = GnSums<NDIM>;
+    __shared__ double tot[L::NS];
+    const int b = blockIdx.x, j = threadIdx.x;
+    if (j < L::NS) {
+        const float *src = partial + (long)b * nblk * L::NS + j;
+        double s0 = 0.0;
+        for (int k = 0; k < nblk; ++k) s0 += (double)src[(long)k * L::NS];
+        tot[j] = s0;
+    }
+    __syncthreads();
+    auto active = [](int a, int d) { return NDIM == 3 || (GN_EZ[a] == 0 && d < 2); };
+    for (int idx = j; idx < 900; idx += 256) {
+        const int r = idx / 30, c = idx - r * 30;
+        const int a = r / 3, d = r - a * 3, a2 = c / 3, e = c - a2 * 3;
+        double val = 0.0;
+        if (active(a, d) && active(a2, e)) {
+            const int m = mono_index<NDIM, 4>(GN_EX[a] + GN_EX[a2], GN_EY[a] + GN_EY[a2], GN_EZ[a] + GN_EZ[a2]);
+            val = tot[L::pair(d < e ? d : e, d < e ? e : d) * L::NM4 + m];
+        }
+        double *dst = H + (long)b * 900 + idx;
+        *dst = accumulate ? *dst + val : val;
+    }
+    if (j < 30) {
+        const int a = j / 3, d = j - a * 3;
+        const double val = active(a, d) ? tot[L::G0 + d * L::NM2 + mono_index<NDIM, 2>(GN_EX[a], GN_EY[a], GN_EZ[a])] : 0.0;
+        g[(long)b * 30 + j] = accumulate ? g[(long)b * 30 + j] + val : val;
+    }
+    if (j == 32) sse[b] = accumulate ? sse[b] + tot[L::SSE] : tot[L::SSE];
+}
+
+// ---- the Levenberg-Marquardt step ----------------------------------------------------------------------------------
+// One wave per frame, float64, everything on the device.  State of frame b: the accepted coefficients beta_acc (30 floats,
+// [a*3+d]), their H / g / sse, the damping lam, sse0 (the first evaluation) and counts = (accepted, rejected, initialised).
+// The trial coefficients live in beta (10,3,T) at column times[b], where K16 reads them.
+__global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ H, const double *__restrict__ g,
+                                                     const double *__restrict__ sse, int nact, const double *__restrict__ M,
+                                                     float *__restrict__ beta, int T, const int *__restrict__ times,
+                                                     double *__restrict__ Hacc, double *__restrict__ gacc,
+                                                     double *__restrict__ sse_acc, double *__restrict__ sse0,
+                                                     double *__restrict__ lam, float *__restrict__ beta_acc,
+                                                     int *__restrict__ counts, double nu, double lam0, double lam_min,
+                                                     double lam_max, int accept_only) {
+    __shared__ double A[30][31];
+    __shared__ double rhs[30], sc[30], dl[30];
+    __shared__ int okflag;
+    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
+    const bool first = counts[b * 3 + 2] == 0;
+    const double st = sse[b], sa = sse_acc[b];
+    const bool accept = first || (st - st == 0.0 && st < sa);   // finite and below
+    double l = first ? lam0 : lam[b];
+    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
+    __syncthreads();   // every thread has read the state before it changes
+    if (accept) {
+        for (int i = j; i < 900; i += 64) Hacc[(long)b * 900 + i] = H[(long)b * 900 + i];
+        if (j < 30) {
+            gacc[b * 30 + j] = g[b * 30 + j];
+            beta_acc[b * 30 + j] = beta[(long)j * T + t];
+        }
+    }
+    if (j == 0) {
+        lam[b] = l;
+        if (accept) sse_acc[b] = st;
+        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
+        else counts[b * 3 + (accept ? 0 : 1)] += 1;
+    }
+    __syncthreads();
+    if (accept_only) {
+        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+        return;
+    }
+    // active unknowns: all 30, or at Z == 1 the 12 without z: act(i) = parameter index of the i-th
+    auto act = [nact](int i) {
+        if (nact == 30) return i;
+        constexpr int AZ[6] = {0, 1, 2, 4, 5, 7};
+        return AZ[i >> 1] * 3 + (i & 1);
+    };
+    const double *Ha = Hacc + (long)b * 900;
+    if (j == 0) okflag = 1;
+    double hmax = 0.0;
+    for (int i = 0; i < nact; ++i) hmax = fmax(hmax, Ha[act(i) * 31]);
+    const double tiny = 1e-12 * hmax + 1e-30;
+    // (H + lam diag(H) + tiny I) delta = -g, scaled to a unit diagonal: sc = 1 / sqrt(diagonal)
+    if (j < nact) {
+        const double dd = Ha[act(j) * 31] * (1.0 + l) + tiny;
+        sc[j] = 1.0 / sqrt(dd);
+    }
+    __syncthreads();
+    if (j < nact) {
+        for (int c = 0; c < nact; ++c) {
+            double v = Ha[act(j) * 30 + act(c)];
+            if (c == j) v = v * (1.0 + l) + tiny;
+            A[j][c] = v * sc[j] * sc[c];
+        }
+        rhs[j] = -gacc[b * 30 + act(j)] * sc[j];
+    }
+    __syncthreads();
+    // Cholesky A = L L^T in place (lower triangle), row j owned by thread j
+    for (int k = 0; k < nact; ++k) {
+        if (j == 0) {
+            const double piv = A[k][k];
+            if (!(piv > 0.0) || !(piv - piv == 0.0)) okflag = 0;
+            A[k][k] = sqrt(piv);
+        }
+        __syncthreads();
+        if (!okflag) break;
+        if (j > k && j < nact) A[j][k] /= A[k][k];
+        __syncthreads();
+        if (j > k && j < nact)
+            for (int c = k + 1; c <= j; ++c) A[j][c] -= A[j][k] * A[c][k];
+        __syncthreads();
+    }
+    if (j == 0) {
+        if (okflag) {
+            for (int i = 0; i < nact; ++i) {       // L w = rhs
+                double v = rhs[i];
+                for (int c = 0; c < i; ++c) v -= A[i][c] * rhs[c];
+                rhs[i] = v / A[i][i];
+            }
+            for (int i = nact - 1; i >= 0; --i) {  // L^T y = w
+                double v = rhs[i];
+                for (int c = i + 1; c < nact; ++c) v -= A[c][i] * rhs[c];
+                rhs[i] = v / A[i][i];
+            }
+        }
+        for (int i = 0; i < 30; ++i) dl[i] = 0.0;
+        if (okflag)
+            for (int i = 0; i < nact; ++i) dl[act(i)] = rhs[i] * sc[i];
+    }
+    __syncthreads();
+    if (j < 30) {   // delta (centred basis) -> d beta = M delta, per coordinate d
+        const int a = j / 3, d = j - a * 3;
+        double db = 0.0;
+        for (int c = 0; c < 10; ++c) db += M[a * 10 + c] * dl[c * 3 + d];
+        beta[(long)j * T + t] = (float)((double)beta_acc[b * 30 + j] + db);
+    }
+}
+
+}  // namespace dnmf
+
+extern "C" {
+
+static long k16_blocks(int X, int Y, int Z, int *nub_out) {
+    const long nub = ((long)Y * (Z == 2 ? 1 : Z) + dnmf::K16_COLS - 1) / dnmf::K16_COLS;
+    if (nub_out) *nub_out = (int)nub;
+    return nub * ((X + dnmf::K16_ROWS - 1) / dnmf::K16_ROWS);
+}
+
+static size_t k16_xtab_bytes(int X) { return ((size_t)X * sizeof(float4) + 255) / 256 * 256; }
+
+static int k16_sums(int Z) { return Z > 1 ? dnmf::GnSums<3>::NS : dnmf::GnSums<2>::NS; }
+
+size_t dnmf_warp_normal_eqs_workspace(int X, int Y, int Z, int B) {
+    if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0) return 0;
+    return k16_xtab_bytes(X) + (size_t)B * k16_blocks(X, Y, Z, nullptr) * k16_sums(Z) * sizeof(float);
+}
+
+int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float *frames, long ldf, const int *frame_ids,
+                         int X, int Y, int Z, const float *beta, int T, const int *times, int B, double *H, double *g,
+                         double *sse, int accumulate, void *workspace, size_t workspace_bytes, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(S && frames && beta && times && H && g && sse && workspace, DNMF_E_NULL, "dnmf_warp_normal_eqs: NULL buffer");
+    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && T > 0 && B > 0 && B <= 65535, DNMF_E_SHAPE,
+                 "dnmf_warp_normal_eqs: X=%d Y=%d Z=%d T=%d B=%d", X, Y, Z, T, B);
+    const Volume vol = make_volume(X, Y, Z);
+    const HaloLayout hl = make_halo_layout(X, Y, Z);
+    // 32-bit byte offsets into an image; 24-bit multiplies for the tap offsets (K2's limits)
+    DNMF_REQUIRE(hl.Pp < (1L << 29) && hl.row4 < (1 << 23) && hl.Xp < (1 << 23), DNMF_E_UNSUPPORTED,
+                 "dnmf_warp_normal_eqs: volume %dx%dx%d too large for 32-bit tap offsets", X, Y, Z);
+    int nub = 0;
+    const long nblk = k16_blocks(X, Y, Z, &nub);
+    DNMF_REQUIRE(nblk < (1L << 31), DNMF_E_UNSUPPORTED, "dnmf_warp_normal_eqs: %ld blocks per frame", nblk);
+    DNMF_REQUIRE(lds >= hl.Pp && ldf >= vol.P, DNMF_E_SHAPE, "dnmf_warp_normal_eqs: lds=%ld < %ld (halo layout) or ldf=%ld < P=%ld",
+                 lds, hl.Pp, ldf, vol.P);
+    DNMF_REQUIRE(workspace_bytes >= dnmf_warp_normal_eqs_workspace(X, Y, Z, B), DNMF_E_WORKSPACE,
+                 "dnmf_warp_normal_eqs: workspace %zu < %zu bytes", workspace_bytes, dnmf_warp_normal_eqs_workspace(X, Y, Z, B));
+    Centre cen;
+    const int dims[3] = {X, Y, Z};
+    for (int d = 0; d < 3; ++d) {
+        cen.s[d] = dims[d] > 1 ? (float)(2.0 / (double)(dims[d] - 1)) : 0.0f;
+        cen.o[d] = dims[d] > 1 ? -1.0f : 0.0f;
+    }
+    float4 *xtab = static_cast<float4 *>(workspace);
+    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + k16_xtab_bytes(X));
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k16_xtab_kernel, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, st, xtab, X);
+    const dim3 grid((unsigned)nblk, (unsigned)B);
+#define DNMF_K16_LAUNCH(ZM)                                                                                                   \
+    hipLaunchKernelGGL((warp_normal_eqs_kernel<ZM>), grid, dim3(256), 0, st, S, lds, s_ids, frames, ldf, frame_ids, vol, hl, cen, \
+                       beta, T, times, partial, xtab, nub)
+    if (Z > 2) DNMF_K16_LAUNCH(3);
+    else if (Z == 2) DNMF_K16_LAUNCH(2);
+    else DNMF_K16_LAUNCH(1);
+#undef DNMF_K16_LAUNCH
+    if (Z > 1)
+        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<3>), dim3((unsigned)B), dim3(256), 0, st, partial, (int)nblk, H, g, sse,
+                           accumulate);
+    else
+        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<2>), dim3((unsigned)B), dim3(256), 0, st, partial, (int)nblk, H, g, sse,
+                           accumulate);
+    return check_launch("dnmf_warp_normal_eqs");
+}
+
+int dnmf_lm_step(const double *H, const double *g, const double *sse, int B, int Z, const double *M, float *beta, int T,
+                 const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0, double *lam, float *beta_acc,
+                 int *counts, double nu, double lam0, double lam_min, double lam_max, int accept_only, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(H && g && sse && M && beta && times && H_acc && g_acc && sse_acc && sse0 && lam && beta_acc && counts,
+                 DNMF_E_NULL, "dnmf_lm_step: NULL buffer");
+    DNMF_REQUIRE(B > 0 && Z > 0 && T > 0, DNMF_E_SHAPE, "dnmf_lm_step: B=%d Z=%d T=%d", B, Z, T);
+    DNMF_REQUIRE(nu > 1.0 && lam0 > 0.0 && lam_min > 0.0 && lam_max >= lam_min, DNMF_E_SHAPE,
+                 "dnmf_lm_step: nu=%g lam0=%g lam_min=%g lam_max=%g (want nu > 1, 0 < lam_min <= lam_max, lam0 > 0)", nu, lam0,
+                 lam_min, lam_max);
+    hipLaunchKernelGGL(lm_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, H, g, sse, Z > 1 ? 30 : 12, M, beta, T,
+                       times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max, accept_only);
+    return check_launch("dnmf_lm_step");
+}
+
+}  // extern "C"

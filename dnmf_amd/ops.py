@@ -234,6 +234,98 @@ def motion_grad_lists(layout, K, sz, C, frames, frame_ids, beta, times, grad, no
     return {"frame_loss": frame_loss, "reg": reg, "workspace": workspace}
 
 
+def warp_normal_eqs(S, s_ids, frames, frame_ids, sz, beta, times, out=None, accumulate=False, workspace=None):
+    """K16.  The per-frame normal equations of the motion fit at ``beta[:, :, times]`` in the centred quadratic basis
+    (``include/dnmf_hip.h``): ``S`` / ``s_ids`` / ``frames`` / ``frame_ids`` as ``warp_recon_grad`` takes them.  Returns
+    dict(H (B,30,30), g (B,30), sse (B), workspace), float64, parameter index a*3+d; ``out``: an earlier result to write into,
+    ``accumulate``: add to it instead (colour channels)."""
+    X, Y, Z = (int(s) for s in sz)
+    dev = beta.device
+    _f32(beta, "beta")
+    _rows(frames, "warp_normal_eqs", "frames")
+    _rows(S, "warp_normal_eqs", "S")
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    if tt is None:
+        raise ValueError("warp_normal_eqs: times is required")
+    if accumulate and out is None:
+        raise ValueError("warp_normal_eqs: accumulate=True needs the earlier result as out")
+    lib = _lib.load()
+    workspace = _workspace(workspace, lib.dnmf_warp_normal_eqs_workspace(X, Y, Z, B), dev)
+    if out is None:
+        out = {"H": torch.empty((B, 30, 30), dtype=torch.float64, device=dev),
+               "g": torch.empty((B, 30), dtype=torch.float64, device=dev),
+               "sse": torch.empty((B,), dtype=torch.float64, device=dev)}
+    H, g, sse = out["H"], out["g"], out["sse"]
+    for t, shape in ((H, (30, 30)), (g, (30,)), (sse, ())):
+        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.shape[0] < B or tuple(t.shape[1:]) != shape:
+            raise ValueError("warp_normal_eqs: out must hold contiguous float64 CUDA H (>=B,30,30), g (>=B,30), sse (>=B)")
+    sid = _i32(s_ids, dev) if s_ids is not None else None
+    with _timed("warp_normal_eqs"):
+        rc = lib.dnmf_warp_normal_eqs(S.data_ptr(), S.stride(0), _ptr(sid), frames.data_ptr(), frames.stride(0), _ptr(fid),
+                                      X, Y, Z, beta.data_ptr(), beta.shape[2], tt.data_ptr(), B, H.data_ptr(), g.data_ptr(),
+                                      sse.data_ptr(), 1 if accumulate else 0, workspace.data_ptr(), _nbytes(workspace),
+                                      _stream())
+    _lib.check(rc, "dnmf_warp_normal_eqs")
+    return {"H": H, "g": g, "sse": sse, "workspace": workspace}
+
+
+def centred_basis_matrix(sz):
+    """M (10,10) float64 numpy with ``basis(u(v)) . gamma == basis(v) . (M gamma)`` for every voxel v, where
+    ``u_d = 2 x_d / (S_d - 1) - 1`` (0 on an axis of one voxel) and ``basis`` is the reference's
+    [1, x, y, z, x^2, y^2, z^2, xy, xz, yz]: coefficients of the centred basis (K16's unknowns) -> coefficients ``beta``."""
+    import numpy as np
+    s = [2.0 / (int(n) - 1) if int(n) > 1 else 0.0 for n in sz]
+    o = [-1.0 if int(n) > 1 else 0.0 for n in sz]
+    M = np.zeros((10, 10), dtype=np.float64)
+    M[0, 0] = 1.0
+    for d in range(3):                       # u_d and u_d^2
+        M[0, 1 + d], M[1 + d, 1 + d] = o[d], s[d]
+        M[0, 4 + d], M[1 + d, 4 + d], M[4 + d, 4 + d] = o[d] * o[d], 2.0 * s[d] * o[d], s[d] * s[d]
+    for c, (p, q) in ((7, (0, 1)), (8, (0, 2)), (9, (1, 2))):   # u_p u_q
+        M[0, c], M[1 + p, c], M[1 + q, c], M[c, c] = o[p] * o[q], s[p] * o[q], o[p] * s[q], s[p] * s[q]
+    return M
+
+
+def lm_state(B: int, dev):
+    """The per-frame state ``lm_step`` keeps for ``B`` frames (``include/dnmf_hip.h``); only ``counts`` needs its zeros."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    return {"H": torch.empty((B, 30, 30), **f64), "g": torch.empty((B, 30), **f64), "sse": torch.empty((B,), **f64),
+            "sse0": torch.empty((B,), **f64), "lam": torch.empty((B,), **f64),
+            "beta": torch.empty((B, 30), dtype=torch.float32, device=dev),
+            "counts": torch.zeros((B, 3), dtype=torch.int32, device=dev)}
+
+
+_CENTRED_M = {}
+
+
+def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_max=1e9, accept_only=False):
+    """One Levenberg-Marquardt step per frame on the device (``dnmf_lm_step``).  ``eqs``: ``warp_normal_eqs``' result at the
+    trial coefficients ``beta[:, :, times]``; ``state``: ``lm_state(B, device)``.  The trial is accepted when its sse is finite
+    and below the accepted one (always on a frame's first call), ``beta[:, :, times]`` then receives the next trial -- or, with
+    ``accept_only``, the best accepted coefficients.  Returns ``state``."""
+    dev = beta.device
+    _f32(beta, "beta")
+    tt = _i32(times, dev)
+    B = tt.numel()
+    H, g, sse = eqs["H"], eqs["g"], eqs["sse"]
+    if min(H.shape[0], g.shape[0], sse.shape[0], *(state[k].shape[0] for k in ("H", "g", "sse", "sse0", "lam", "beta", "counts"))) < B:
+        raise ValueError(f"lm_step: {B} frames, but the normal equations or the state hold fewer")
+    for name, t in (("H", H), ("g", g), ("sse", sse)):
+        if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"lm_step: {name} must be a contiguous float64 CUDA tensor")
+    key = (tuple(int(s) for s in sz), str(dev))
+    if key not in _CENTRED_M:
+        _CENTRED_M[key] = torch.from_numpy(centred_basis_matrix(sz)).to(dev)
+    M = _CENTRED_M[key]
+    rc = _lib.load().dnmf_lm_step(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), beta.data_ptr(),
+                                  beta.shape[2], tt.data_ptr(), state["H"].data_ptr(), state["g"].data_ptr(),
+                                  state["sse"].data_ptr(), state["sse0"].data_ptr(), state["lam"].data_ptr(),
+                                  state["beta"].data_ptr(), state["counts"].data_ptr(), float(nu), float(lam0), float(lam_min),
+                                  float(lam_max), 1 if accept_only else 0, _stream())
+    _lib.check(rc, "dnmf_lm_step")
+    return state
+
+
 def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_stride=0, workspace=None, bf16=False):
     """K3 (``bf16=True``: K3b, operands rounded to bf16, fp32 accumulate).  Returns G (B,K,K), r (B,K) for the
     frames listed.  ``beta`` None: no warp (each voxel's own footprint row, weight 1)."""

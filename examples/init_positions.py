@@ -5,7 +5,7 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track] [--gn]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
 ground truth of frame 0; the model is built on the detected centres alone, as many neurons as were found.  The simulator's
@@ -15,6 +15,9 @@ when that is within sigma (one centre per neuron), and the errors and correlatio
 ``--track``: the initialiser's tracks are refined per neuron and frame by the tracker (``MotionCorrect.track_points``, K15: the
 peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
 printed for both sets of tracks.
+
+``--gn``: every fit is repeated with the Gauss-Newton motion solver (``fit(..., motion_solver='gn')``: K16 + Levenberg-Marquardt
+steps per frame, ``--gn-iters`` of them, no learning rate) and its three numbers are printed beside Adam's.
 """
 import argparse
 import os
@@ -40,6 +43,8 @@ def main():
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--detect", action="store_true", help="find the centres in the template instead of taking the simulator's")
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
+    ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
+    ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
     ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
     torch.manual_seed(0)
@@ -90,22 +95,27 @@ def main():
               f"the initialiser alone")
         starts["tracker"] = refined
     for start, tracks in starts.items():
-        torch.manual_seed(1)
-        dn = DeformableNMF(sz, n, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
-        dn.verbose = False
-        if tracks is not None:
-            ok = dn.init_motion(tracks, ridge=a.ridge)
-            print(f"init_motion: {int(ok.sum())} of {T} frames fitted")
-        loader = dataset.loader(a.batch)
-        dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
-        where = dn.positions()
-        dist = float(np.nanmean(np.linalg.norm(where[sel, :2, :] - truth[tr, :2, :], axis=1)))
-        # the simulator places centres up to half a voxel beyond the last slice: read the box of the nearest voxel inside
-        inside = np.clip(np.nan_to_num(where, nan=-1.0), 0, (sz.numpy() - 1)[None, :, None])
-        roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))
-        print(f"{start} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
-              f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "
-              f"dnmf.positions() {median_corr(np.nan_to_num(roi)):.3f}")
+        for solver in ("adam", "gn") if a.gn else ("adam",):
+            torch.manual_seed(1)
+            dn = DeformableNMF(sz, n, T, positions=torch.from_numpy(P_T[:, :, 0]).float())
+            dn.verbose = False
+            if tracks is not None:
+                ok = dn.init_motion(tracks, ridge=a.ridge)
+                print(f"init_motion: {int(ok.sum())} of {T} frames fitted")
+            loader = dataset.loader(a.batch)
+            if solver == "gn":
+                dn.fit(loader, loader, None, a.batch, outer=1, epochs=a.gn_iters, gamma_c=0, iter_c=30, motion_solver='gn')
+            else:
+                dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
+            where = dn.positions()
+            dist = float(np.nanmean(np.linalg.norm(where[sel, :2, :] - truth[tr, :2, :], axis=1)))
+            # the simulator places centres up to half a voxel beyond the last slice: read the box of the nearest voxel inside
+            inside = np.clip(np.nan_to_num(where, nan=-1.0), 0, (sz.numpy() - 1)[None, :, None])
+            roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))
+            label = start if solver == "adam" else f"{start} (gn, {a.gn_iters} iterations)"
+            print(f"{label} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
+                  f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "
+                  f"dnmf.positions() {median_corr(np.nan_to_num(roi)):.3f}")
     return err, still
 
 

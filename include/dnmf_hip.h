@@ -572,6 +572,46 @@ int dnmf_track_neurons(const float *frames, long ldf, const int *sz, int T, cons
                        int predict_per_frame, int K, double sigma, const int *search, double threshold, const float *background,
                        double *positions, float *amplitudes, float *peaks, dnmf_stream_t stream);
 
+/* ---- K16: per-frame normal equations of the motion fit, and the Levenberg-Marquardt step -----------------------------------
+ * The motion loss is a sum over frames and frame t only sees beta[:, :, t]: 30 unknowns (12 at Z == 1) against P residuals.
+ * With r(v) = A_tC(v) - y(v) and g_d(v) = d A_tC / d q_d (v) exactly as K2 forms them (same warp, same taps, out-of-bounds
+ * corners add zeros) and the CENTRED basis phi(v) = quadratic_basis(u(v)), u_d = 2 x_d / (S_d - 1) - 1 (0 on an axis of one
+ * voxel), the Jacobian row of voxel v is J(v)[a,d] = phi_a(v) g_d(v) and, per frame b, with the parameter index a*3 + d:
+ *   H (B,30,30) = sum_v J^T J    float64, symmetric, both triangles written
+ *   g (B,30)    = sum_v J^T r    float64
+ *   sse (B)     = sum_v r^2      float64
+ * Sums run in fp32 inside a block and in float64 across the blocks of a frame.  At Z == 1 the unknowns with z in their basis
+ * term or d == 2 get exact zeros.  accumulate != 0 adds to H, g, sse instead of overwriting them (colour channels are extra
+ * voxels that share beta).  A frame whose beta has a non-finite entry is skipped: H and g get 0, sse NaN, nothing is gathered.
+ * tests/gn_restatement.py is the definition in float64.
+ *   S, lds, s_ids, frames, ldf, frame_ids, beta, T, times: as K2's (times must not contain duplicates; B <= 65535)
+ *   workspace: dnmf_warp_normal_eqs_workspace(X,Y,Z,B) bytes
+ * DNMF_E_NULL: a NULL buffer;  DNMF_E_SHAPE: a size, T or B < 1, B > 65535, lds or ldf below a row;  DNMF_E_UNSUPPORTED: a
+ * volume beyond K2's 32-bit tap offsets;  DNMF_E_WORKSPACE: a short workspace. */
+size_t dnmf_warp_normal_eqs_workspace(int X, int Y, int Z, int B);
+int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float *frames, long ldf, const int *frame_ids,
+                         int X, int Y, int Z, const float *beta, int T, const int *times, int B, double *H, double *g,
+                         double *sse, int accumulate, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
+
+/* One damped Gauss-Newton step per frame from K16's output at the trial coefficients, one wave per frame, float64, no host
+ * synchronisation.  The trial coefficients of frame b are column times[b] of beta (10,3,T); the state of frame b is H_acc
+ * (B,30,30), g_acc (B,30), sse_acc (B): the normal equations at the accepted coefficients beta_acc (B,30) ([a*3+d], fp32), the
+ * damping lam (B), sse0 (B) (the first evaluation) and counts (B,3) = accepted steps, rejected steps, initialised; counts must
+ * be zero before the first call, nothing else needs initialising.
+ *   first call of a frame (counts[b,2] == 0): the trial is accepted unconditionally, lam = lam0, sse0 = sse;
+ *   later: sse finite and < sse_acc -> accept (trial becomes the accepted state, lam = max(lam / nu, lam_min)),
+ *          else reject (lam = min(lam nu, lam_max));
+ *   then  (H_acc + lam diag(H_acc) + tiny I) delta = -g_acc on the active unknowns (all 30, at Z == 1 the 12 without z) with
+ *          tiny = 1e-12 max_i H_ii + 1e-30, by a Cholesky factorisation of the system scaled to a unit diagonal (a pivot that is
+ *          not positive and finite: delta = 0);  d beta[a,d] = sum_c M[a,c] delta[c,d] with M (10,10) row-major float64, the
+ *          change of basis basis(u(v)) . gamma = basis(v) . (M gamma);  beta[:, :, times[b]] = fp32(beta_acc + d beta).
+ *   accept_only != 0: the accept / reject bookkeeping, then beta[:, :, times[b]] = beta_acc (the best accepted coefficients).
+ * H == 0 gives delta = 0; a NaN frame stays NaN and touches nothing else.
+ * DNMF_E_NULL: a NULL buffer;  DNMF_E_SHAPE: B, Z or T < 1, nu <= 1, lam0 or lam_min <= 0, lam_max < lam_min. */
+int dnmf_lm_step(const double *H, const double *g, const double *sse, int B, int Z, const double *M, float *beta, int T,
+                 const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0, double *lam, float *beta_acc,
+                 int *counts, double nu, double lam0, double lam_min, double lam_max, int accept_only, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

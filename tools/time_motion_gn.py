@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""Times of the Gauss-Newton motion solver beside the Adam path, 512x512x1 and 512x512x2, K = 100, T = 4000, warp about a voxel
+off the identity (bench.py's ``displaced_beta``):
+
+  kernels    K16 (``ops.warp_normal_eqs``) alone beside K2 (``ops.warp_recon_grad``) alone on the same frames and images:
+             both read exactly the same bytes, so the ratio is the cost of K16's extra sums
+  iteration  one Levenberg-Marquardt iteration (K16 + ``ops.lm_step``; from ``update_motion(solver='gn')`` with 5 and with 1
+             iterations) beside one Adam epoch of ``update_motion`` (reconstruction + K2 + ``adam_epoch``)
+
+    python tools/time_motion_gn.py [--frames 4000] [--neurons 100]
+
+Every measurement is a process of its own under a time limit; the first one that fails ends the script.  One JSON line each.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def median_ms(fn, warm=2, reps=5):
+    import torch
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return sorted(ts)[len(ts) // 2]
+
+
+def setup(Z, K, T):
+    import torch
+    from bench import displaced_beta
+    from dnmf_amd.Demix import dNMF
+    torch.manual_seed(0)
+    sz = [512, 512, Z]
+    pos = torch.rand(K, 3) * torch.tensor([511.0, 511.0, float(Z - 1)])
+    model = dNMF.DeformableNMF(torch.tensor(sz), K, T, positions=pos)
+    model.verbose = False
+    with torch.no_grad():
+        model.fp.beta.copy_(displaced_beta(T, sz, "cuda"))
+    frames = torch.rand((T, 512 * 512 * Z), device="cuda")
+    return dNMF, model, sz, frames
+
+
+def step_kernels(Z, K, T):
+    import torch
+    from dnmf_amd import ops
+    _, model, sz, frames = setup(Z, K, T)
+    S = model._recon_cache()[0]
+    times = torch.arange(T, dtype=torch.int32, device="cuda")
+    beta = model.fp.beta.detach()
+    grad = torch.zeros_like(beta)
+    ws = {}
+
+    def k2():
+        ws["k2"] = ops.warp_recon_grad(S, times, frames, None, sz, beta, times, grad=grad, want_loss=False, want_reg=False,
+                                       workspace=ws.get("k2"))["workspace"]
+
+    def k16():
+        ws["eq"] = ops.warp_normal_eqs(S, times, frames, None, sz, beta, times, out=ws.get("eq"), workspace=ws.get("k16"))
+        ws["k16"] = ws["eq"]["workspace"]
+
+    t2, t16 = median_ms(k2), median_ms(k16)
+    return {"step": "kernels", "Z": Z, "K": K, "T": T, "k2_ms": t2, "k16_ms": t16, "ratio": t16 / t2}
+
+
+def step_iteration(Z, K, T):
+    import torch
+    dNMF, model, sz, frames = setup(Z, K, T)
+    loader = dNMF.ResidentLoader(frames, sz, 100)
+    start = model.fp.beta.detach().clone()
+    opt = torch.optim.Adam([model.fp.beta], lr=1e-5 * (50 / 512) ** 2)
+
+    def reset():
+        with torch.no_grad():
+            model.fp.beta.copy_(start)
+
+    def wall(fn, reps=3):
+        ts = []
+        for _ in range(reps + 1):
+            reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return sorted(ts[1:])[len(ts[1:]) // 2]     # the first run warms up
+
+    adam = wall(lambda: model.update_motion(loader, opt, epochs=1))
+    gn1 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=1))
+    gn5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
+    return {"step": "iteration", "Z": Z, "K": K, "T": T, "adam_epoch_ms": adam, "gn_iters1_ms": gn1, "gn_iters5_ms": gn5,
+            "lm_iteration_ms": (gn5 - gn1) / 4}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=4000)
+    ap.add_argument("--neurons", type=int, default=100)
+    ap.add_argument("--step", choices=["kernels", "iteration"])
+    ap.add_argument("--z", type=int, default=1)
+    ap.add_argument("--limit", type=int, default=240, help="seconds a measurement may take")
+    a = ap.parse_args()
+    if a.step:
+        fn = step_kernels if a.step == "kernels" else step_iteration
+        print(json.dumps(fn(a.z, a.neurons, a.frames)), flush=True)
+        return 0
+    for z in (1, 2):
+        for step in ("kernels", "iteration"):
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--step", step, "--z", str(z),
+                   "--frames", str(a.frames), "--neurons", str(a.neurons)]
+            rc = subprocess.run(cmd, cwd=ROOT).returncode
+            if rc != 0:
+                print(f"time_motion_gn: {step} at Z={z} ended with status {rc}; stopping", flush=True)
+                return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
