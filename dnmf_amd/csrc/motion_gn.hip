@@ -9,23 +9,17 @@
 // Centred coordinates keep every monomial in [-1, 1]: in voxel monomials H has entries up to 511^4 beside entries of
 // order 1 and is useless in fp32.  tests/gn_restatement.py is the definition in float64.
 //
-// Kernel shape: K2's work layout -- a lane owns one position of the (y,z) plane (both slices of it at Z == 2) and walks
-// down K16_ROWS consecutive x.  u_y and u_z are constant along the walk, so a thread only accumulates moments over x:
+// Kernel shape: K2's work layout (warp_taps.hpp) -- a lane owns one position of the (y,z) plane (both slices of it at
+// Z == 2) and walks down PLANE_ROWS consecutive x.  u_y and u_z are constant along the walk, so a thread only accumulates moments over x:
 // sum g_d g_e u_x^m (m = 0..4) and sum r g_d u_x^m (m = 0..2): 15 + 6 + 1 sums at Z = 1, 30 + 9 + 1 per slice at Z > 1.
 // phi_a phi_b is a monomial of degree <= 4 in u, so the DISTINCT sums behind H are (monomials of degree <= 4) x (pairs
 // d <= e): 15 x 3 = 45 at Z = 1, 35 x 6 = 210 at Z > 1; behind g (degree <= 2) x d: 12 / 30.  A thread expands its moments
 // into those (a product with powers of its u_y, u_z), the block reduces them (DPP tree per wave, four waves through
 // LDS) and writes one row of partial sums; the finish kernel adds the rows of a frame in float64 and only there
 // spreads them into the full symmetric matrix.
-#include "common.hpp"
+#include "warp_taps.hpp"
 
 namespace dnmf {
-
-typedef float gn_f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float gn_f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
-constexpr int K16_ROWS = 32;    // voxels per lane along x (K2's)
-constexpr int K16_COLS = 256;   // positions of the (y,z) plane per block
 
 // monomials u_x^i u_y^j u_z^k of degree <= DEG in NDIM variables, numbered i outermost, k innermost
 template <int NDIM, int DEG>
@@ -61,7 +55,7 @@ struct GnSums {
     __host__ __device__ static constexpr int pair(int d, int e) { return d * NDIM - d * (d - 1) / 2 + (e - d); }   // d <= e
 };
 static_assert(GnSums<2>::NS == 45 + 12 + 1 && GnSums<3>::NS == 210 + 30 + 1, "the sums a block reduces");
-static_assert(GnSums<3>::NS <= K16_COLS, "one thread per sum writes the block's row");
+static_assert(GnSums<3>::NS <= PLANE_COLS, "one thread per sum writes the block's row");
 
 // u = coordinate * s + o per axis: s = 2 / (S - 1), o = -1 (s = o = 0 on an axis of one voxel)
 struct Centre {
@@ -79,8 +73,8 @@ __global__ void k16_xtab_kernel(float4 *__restrict__ xtab, int X) {
 }
 
 // ZM = 1: Z == 1 (two coordinates, four taps, the z terms left out); 2: Z == 2 (a lane owns both slices, their z-pairs
-// are one 16-byte gather per x-corner); 3: Z > 2.  The sample and its derivative are K2's (warp_recon_grad.hip), operation
-// for operation.
+// are one 16-byte gather per x-corner); 3: Z > 2.  The sample and its derivative are the code K2 calls (warp_taps.hpp), with
+// the wave-uniform choice of the division shortcut and the integer tap offsets.
 template <int ZM>
 __global__ __launch_bounds__(256) void warp_normal_eqs_kernel(const float *__restrict__ S, long lds, const int *__restrict__ s_ids,
                                                               const float *__restrict__ frames, long ldf,
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(256) void warp_normal_eqs_kernel(const float *__res
     const int YZ = vol.Y * vol.Z;
     const int plane = ZPAIR ? vol.Y : YZ;
     const int bu = blockIdx.x % nub, bx = blockIdx.x / nub;
-    const int u = bu * K16_COLS + threadIdx.x;        // position in the (y,z) plane; Z == 2: y
+    const int u = bu * PLANE_COLS + threadIdx.x;        // position in the (y,z) plane; Z == 2: y
     const int yy = ZM == 3 ? div_small(u, vol.Z, vol.rcp_z) : u;
     const int z = ZM == 3 ? u - yy * vol.Z : 0;
     const float yf = (float)yy, zf = (float)z;
@@ -131,12 +125,16 @@ __global__ __launch_bounds__(256) void warp_normal_eqs_kernel(const float *__res
     if (u < plane) {
         float b2[30];
         double_beta(bt, b2);
-        const int x_first = bx * K16_ROWS;
-        const int nrow = min(K16_ROWS, vol.X - x_first);
+        Monomials<true> mono[NV];   // y, z, y^2, z^2, yz of the lane's voxels: fixed along the rows
+#pragma unroll
+        for (int v = 0; v < NV; ++v) mono[v] = monomials<true>(0.0f, yf, ZPAIR ? (float)v : zf);
+        const int x_first = bx * PLANE_ROWS;
+        const int nrow = min(PLANE_ROWS, vol.X - x_first);
         const unsigned u4 = (unsigned)u * (4u * NV);
         for (int i = 0; i < nrow; ++i) {
             const float4 xt = xtab[x_first + i];
             const float ux = xt.z, ux2 = xt.w, ux3 = ux2 * ux, ux4 = ux2 * ux2;
+            const float xy = __fmul_rn(xt.x, yf);
             const char *op = reinterpret_cast<const char *>(y + (long)(x_first + i) * YZ) + u4;
             float other[NV];
             if constexpr (ZPAIR) {
@@ -147,79 +145,12 @@ __global__ __launch_bounds__(256) void warp_normal_eqs_kernel(const float *__res
             }
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
-                const float zv = ZPAIR ? (float)v : zf;
-                float a[3] = {0.0f, 0.0f, 0.0f};
-                if constexpr (HASZ) {
-                    const Monomials<true> m = {xt.x, yf, zv, xt.y, __fmul_rn(yf, yf), __fmul_rn(zv, zv), __fmul_rn(xt.x, yf),
-                                               __fmul_rn(xt.x, zv), __fmul_rn(yf, zv)};
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) a[d] = poly_a<true>(b2, d, m);
-                } else {
-                    const Monomials<false> m = {xt.x, yf, 0.0f, xt.y, __fmul_rn(yf, yf), 0.0f, __fmul_rn(xt.x, yf), 0.0f, 0.0f};
-#pragma unroll
-                    for (int d = 0; d < 2; ++d) a[d] = poly_a<false>(b2, d, m);
-                }
-                float fx, fy, w0, wx1, wy1;
-                axis_taps_halo(unnormalise(normalise_axis<-1>(a[0], vol, 0), vol.hx1), hl.xhi, fx, w0, wx1);
-                axis_taps_halo(unnormalise(normalise_axis<-1>(a[1], vol, 1), vol.hy1), hl.yhi, fy, w0, wy1);
-                unsigned olo = halo_offset<false>(fx, fy, hl, hl.origin4, hl.origin4f);   // base corner, slice 0
-                float wzm[2] = {1.0f, 0.0f}, vz[2] = {0.0f, 0.0f};
-                if constexpr (HASZ) {
-                    const float uz = unnormalise(normalise_axis<-1>(a[2], vol, 2), vol.hz1);
-                    if constexpr (ZM == 2) {   // the pair is (0, 1): see K2 for the weights and their derivatives
-                        const float uc = z_pair_weights(uz, wzm[0], wzm[1]);
-                        const float c0 = fmaf(2.0f, floorf(uc), 1.0f), c1 = c0 - 2.0f;
-                        vz[0] = fabsf(c0) == 1.0f ? -c0 : 0.0f;
-                        vz[1] = fabsf(c1) == 1.0f ? -c1 : 0.0f;
-                    } else {                   // the pair (izc, izc + 1) inside the volume that holds every in-range z-tap
-                        int iz;
-                        float wz[2];
-                        axis_weights(uz, iz, wz[0], wz[1]);
-                        const int izc = clamp_index(iz, vol.Z - 1);
-                        const bool same = iz == izc, below = iz + 1 == izc, above = iz == izc + 1;
-                        wzm[0] = same ? wz[0] : (below ? wz[1] : 0.0f);
-                        wzm[1] = same ? wz[1] : (above ? wz[0] : 0.0f);
-                        vz[0] = same ? -1.0f : (below ? 1.0f : 0.0f);
-                        vz[1] = same ? 1.0f : (above ? -1.0f : 0.0f);
-                        olo += (unsigned)izc * 4u;
-                    }
-                }
-                // taps sv[dz][dy][dx]: the x-corner rows olo and olo + row4
-                float sv[HASZ ? 2 : 1][2][2];
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx) {
-                    const char *t = s + (olo + (unsigned)(dx * hl.row4));
-                    if constexpr (ZM == 2) {          // (y, z0), (y, z1), (y + 1, z0), (y + 1, z1)
-                        const gn_f32x4_a8 r = *reinterpret_cast<const gn_f32x4_a8 *>(t);
-                        sv[0][0][dx] = r.x, sv[1][0][dx] = r.y, sv[0][1][dx] = r.z, sv[1][1][dx] = r.w;
-                    } else if constexpr (ZM == 3) {   // the z-pair of corner y, then of corner y + 1
-                        const gn_f32x2_a4 r0 = *reinterpret_cast<const gn_f32x2_a4 *>(t);
-                        const gn_f32x2_a4 r1 = *reinterpret_cast<const gn_f32x2_a4 *>(t + hl.col4);
-                        sv[0][0][dx] = r0.x, sv[1][0][dx] = r0.y, sv[0][1][dx] = r1.x, sv[1][1][dx] = r1.y;
-                    } else {
-                        sv[0][0][dx] = *reinterpret_cast<const float *>(t);
-                        sv[0][1][dx] = *reinterpret_cast<const float *>(t + 4);
-                    }
-                }
-                float rec = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int dz = 0; dz < (HASZ ? 2 : 1); ++dz) {   // K2's blends
-                    const float d0 = sv[dz][0][1] - sv[dz][0][0];
-                    const float d1 = sv[dz][1][1] - sv[dz][1][0];
-                    const float a0 = fmaf(wx1, d0, sv[dz][0][0]);
-                    const float a1 = fmaf(wx1, d1, sv[dz][1][0]);
-                    const float gy2 = a1 - a0;
-                    const float r2 = fmaf(wy1, gy2, a0);
-                    const float gx2 = fmaf(wy1, d1 - d0, d0);
-                    if (HASZ) {
-                        rec = fmaf(wzm[dz], r2, rec);
-                        g[0] = fmaf(wzm[dz], gx2, g[0]);
-                        g[1] = fmaf(wzm[dz], gy2, g[1]);
-                        g[2] = fmaf(vz[dz], r2, g[2]);
-                    } else {
-                        rec = r2, g[0] = gx2, g[1] = gy2;
-                    }
-                }
+                WarpTaps<HASZ> q;
+                const unsigned olo = warp_taps_front<ZM, -1, false>(b2, mono[v], xt.x, xt.y, xy, vol, hl, q);
+                gather_tap_row<ZM>(s, olo, hl, q.t[0]);
+                gather_tap_row<ZM>(s, olo + (unsigned)hl.row4, hl, q.t[1]);
+                float rec, g[3];
+                blend_taps<HASZ>(q, rec, g);
                 const float resid = rec - other[v];
                 sq = fmaf(resid, resid, sq);
 #pragma unroll
@@ -456,19 +387,11 @@ __global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ 
 
 extern "C" {
 
-static long k16_blocks(int X, int Y, int Z, int *nub_out) {
-    const long nub = ((long)Y * (Z == 2 ? 1 : Z) + dnmf::K16_COLS - 1) / dnmf::K16_COLS;
-    if (nub_out) *nub_out = (int)nub;
-    return nub * ((X + dnmf::K16_ROWS - 1) / dnmf::K16_ROWS);
-}
-
-static size_t k16_xtab_bytes(int X) { return ((size_t)X * sizeof(float4) + 255) / 256 * 256; }
-
 static int k16_sums(int Z) { return Z > 1 ? dnmf::GnSums<3>::NS : dnmf::GnSums<2>::NS; }
 
 size_t dnmf_warp_normal_eqs_workspace(int X, int Y, int Z, int B) {
     if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0) return 0;
-    return k16_xtab_bytes(X) + (size_t)B * k16_blocks(X, Y, Z, nullptr) * k16_sums(Z) * sizeof(float);
+    return dnmf::plane_walk_xtab_bytes<float4>(X) + (size_t)B * dnmf::plane_walk_blocks(X, Y, Z, nullptr) * k16_sums(Z) * sizeof(float);
 }
 
 int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float *frames, long ldf, const int *frame_ids,
@@ -478,14 +401,11 @@ int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float
     DNMF_REQUIRE(S && frames && beta && times && H && g && sse && workspace, DNMF_E_NULL, "dnmf_warp_normal_eqs: NULL buffer");
     DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && T > 0 && B > 0 && B <= 65535, DNMF_E_SHAPE,
                  "dnmf_warp_normal_eqs: X=%d Y=%d Z=%d T=%d B=%d", X, Y, Z, T, B);
-    const Volume vol = make_volume(X, Y, Z);
-    const HaloLayout hl = make_halo_layout(X, Y, Z);
-    // 32-bit byte offsets into an image; 24-bit multiplies for the tap offsets (K2's limits)
-    DNMF_REQUIRE(hl.Pp < (1L << 29) && hl.row4 < (1 << 23) && hl.Xp < (1 << 23), DNMF_E_UNSUPPORTED,
-                 "dnmf_warp_normal_eqs: volume %dx%dx%d too large for 32-bit tap offsets", X, Y, Z);
-    int nub = 0;
-    const long nblk = k16_blocks(X, Y, Z, &nub);
-    DNMF_REQUIRE(nblk < (1L << 31), DNMF_E_UNSUPPORTED, "dnmf_warp_normal_eqs: %ld blocks per frame", nblk);
+    Volume vol;
+    HaloLayout hl;
+    int nblk = 0, nub = 0;
+    const int rc = plane_walk_geometry("dnmf_warp_normal_eqs", X, Y, Z, vol, hl, nblk, nub);
+    if (rc != 0) return rc;
     DNMF_REQUIRE(lds >= hl.Pp && ldf >= vol.P, DNMF_E_SHAPE, "dnmf_warp_normal_eqs: lds=%ld < %ld (halo layout) or ldf=%ld < P=%ld",
                  lds, hl.Pp, ldf, vol.P);
     DNMF_REQUIRE(workspace_bytes >= dnmf_warp_normal_eqs_workspace(X, Y, Z, B), DNMF_E_WORKSPACE,
@@ -497,7 +417,7 @@ int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float
         cen.o[d] = dims[d] > 1 ? -1.0f : 0.0f;
     }
     float4 *xtab = static_cast<float4 *>(workspace);
-    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + k16_xtab_bytes(X));
+    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + plane_walk_xtab_bytes<float4>(X));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k16_xtab_kernel, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, st, xtab, X);
     const dim3 grid((unsigned)nblk, (unsigned)B);
@@ -509,10 +429,10 @@ int dnmf_warp_normal_eqs(const float *S, long lds, const int *s_ids, const float
     else DNMF_K16_LAUNCH(1);
 #undef DNMF_K16_LAUNCH
     if (Z > 1)
-        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<3>), dim3((unsigned)B), dim3(256), 0, st, partial, (int)nblk, H, g, sse,
+        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<3>), dim3((unsigned)B), dim3(256), 0, st, partial, nblk, H, g, sse,
                            accumulate);
     else
-        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<2>), dim3((unsigned)B), dim3(256), 0, st, partial, (int)nblk, H, g, sse,
+        hipLaunchKernelGGL((warp_normal_eqs_finish_kernel<2>), dim3((unsigned)B), dim3(256), 0, st, partial, nblk, H, g, sse,
                            accumulate);
     return check_launch("dnmf_warp_normal_eqs");
 }

@@ -4,13 +4,11 @@
 #include <mutex>
 #include <type_traits>
 
-#include "common.hpp"
+#include "warp_taps.hpp"
 
 namespace dnmf {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));   // four floats at an 8-byte aligned address
-typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
 
 // The coordinates of a voxel's taps are the reference's fp32 sequence -- the ten-term FMA chain, n = 2q/(S-1) - 1,
 // u = ((n+1)/2)(S-1) -- which is what decides floor() at lattice coincidences and what K2, K1 and the dense kernels
@@ -389,19 +387,7 @@ __global__ __launch_bounds__(256, (ZM == 1 ? LISTS_WAVES : (ZM == 2 ? (PASS == 2
                 const bool in = FULL || (yz_in && x < vol.X);   // a voxel beyond the volume: weights 0, frame value 0
                 if constexpr (HASZ) {
                     float wzm[2];
-                    unsigned zo = 0u;
-                    if (ZM == 2) {   // the pair (0, 1): common.hpp, z_pair_weights
-                        z_pair_weights(uz, wzm[0], wzm[1]);
-                    } else {
-                        int iz;
-                        float wz[2];
-                        axis_weights(uz, iz, wz[0], wz[1]);
-                        const int izc = clamp_index(iz, vol.Z - 1);   // the pair (izc, izc + 1) inside the volume
-                        const bool same = iz == izc;
-                        wzm[0] = same ? wz[0] : (iz + 1 == izc ? wz[1] : 0.0f);
-                        wzm[1] = same ? wz[1] : (iz == izc + 1 ? wz[0] : 0.0f);
-                        zo = (unsigned)izc * 4u;
-                    }
+                    const unsigned zo = z_pair_members<ZM, false>(uz, vol, wzm, nullptr);   // no derivatives here
                     // (a voxel beyond the volume is not covered by the tile's region: it reads the region's first floats,
                     // times zero)
                     off[v][0] = staged ? (in ? (unsigned)fmaf(fx, (float)(4 * LISTS_RC), fmaf(fy, 8.0f, lds_origin)) : 0u) : o0 + zo;
@@ -442,19 +428,8 @@ __global__ __launch_bounds__(256, (ZM == 1 ? LISTS_WAVES : (ZM == 2 ? (PASS == 2
                 if constexpr (HASZ) {
                     float q[2][4];
 #pragma unroll
-                    for (int dx = 0; dx < 2; ++dx) {
-                        unsigned o = off[v][0] + (dx ? (unsigned)hl.row4 : 0u);
-                        asm("" : "+v"(o));
-                        const char *src = Ak + o;
-                        if constexpr (ZM == 2) {
-                            const f32x4_a8 t = *reinterpret_cast<const f32x4_a8 *>(src);
-                            q[dx][0] = t.x, q[dx][1] = t.y, q[dx][2] = t.z, q[dx][3] = t.w;
-                        } else {
-                            const f32x2_a4 t0 = *reinterpret_cast<const f32x2_a4 *>(src);
-                            const f32x2_a4 t1 = *reinterpret_cast<const f32x2_a4 *>(src + hl.col4);
-                            q[dx][0] = t0.x, q[dx][1] = t0.y, q[dx][2] = t1.x, q[dx][3] = t1.y;
-                        }
-                    }
+                    for (int dx = 0; dx < 2; ++dx)
+                        gather_tap_row<ZM>(Ak, off[v][0] + (dx ? (unsigned)hl.row4 : 0u), hl, q[dx]);
                     a[v] = blend8(q[0], q[1], w[v]);
                 } else {
                     float s = 0.0f;

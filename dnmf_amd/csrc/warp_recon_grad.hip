@@ -10,32 +10,14 @@
 // The factor (S-1)/2 of grid_sample's backward and the 2/(S-1) of the normalisation cancel.
 #include <type_traits>
 
-#include "common.hpp"
+#include "warp_taps.hpp"
 
 namespace dnmf {
 
-typedef float f32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));   // four floats at an 8-byte aligned address
-typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
-
-constexpr int K2_ROWS = 32;           // voxels per lane: consecutive x (the block reduction is paid once per K2_ROWS voxels)
-constexpr int K2_COLS = 256;          // positions of the (y,z) plane per block: 64 lanes x 4 waves
 constexpr int K2_NACC = 32;           // 30 gradient sums + squared error + pad
-#ifndef DNMF_K2_UNROLL
-#define DNMF_K2_UNROLL 2
-#endif
-#ifndef DNMF_K2_UNROLL_Z
-#define DNMF_K2_UNROLL_Z 1
-#endif
-#ifndef DNMF_K2_REUSE
-#define DNMF_K2_REUSE 1   // the lower tap row from the last voxel's upper one when the whole wave steps by one row
-#endif
-constexpr bool K2_REUSE = DNMF_K2_REUSE != 0;
-#ifndef DNMF_K2_WAVES_Z
-#define DNMF_K2_WAVES_Z 1
-#endif
-constexpr int K2_UNROLL = DNMF_K2_UNROLL;      // rows requested together (Z == 1)
-constexpr int K2_UNROLL_Z = DNMF_K2_UNROLL_Z;  // the same for Z >= 2
-static_assert(K2_ROWS % K2_UNROLL == 0 && K2_ROWS % K2_UNROLL_Z == 0, "the row loop takes K2_UNROLL rows at a time");
+constexpr int K2_UNROLL = 2;          // rows requested together (Z == 1)
+constexpr int K2_UNROLL_Z = 1;        // the same for Z >= 2
+static_assert(PLANE_ROWS % K2_UNROLL == 0 && PLANE_ROWS % K2_UNROLL_Z == 0, "the row loop takes K2_UNROLL rows at a time");
 
 // (sum_loss_kernel only; the main kernel reduces with DPP adds, common.hpp: wave_sum_last)
 __device__ __forceinline__ float wave_sum(float v) {
@@ -44,7 +26,7 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// Work layout: a block owns K2_ROWS x-rows by 256 consecutive positions of the (y,z) plane (lane = position, so the frame
+// Work layout: a block owns PLANE_ROWS x-rows by 256 consecutive positions of the (y,z) plane (lane = position, so the frame
 // and the reconstruction image are read in 256-byte runs and the taps of neighbouring lanes share cache lines); a
 // thread walks down its rows with (y,z) fixed: the monomials without x are per-thread constants, and x, x^2 are the
 // same for the whole block: they come from a table (scalar loads).  The polynomial itself is the reference's chain of
@@ -59,23 +41,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 // (the other 18 gradient sums are identically zero and are written as such).  PLAIN = the fit step's call (frames
 // given, no upstream gradient, A_tC not wanted): the row loop then has no branches.
 //
-// Z >= 2 (ZM = 2: Z == 2, ZM = 3: Z > 2).  The two z-taps of a corner are adjacent floats of a halo row
-// ((y + HALO) Z + z): they are fetched as ONE pair (izc, izc + 1) with izc = the base slice clamped into [0, Z - 2], i.e.
-// the pair inside the volume that holds every in-range z-tap of the sample; a tap outside [0, Z) has no partner in the
-// pair and its weight is dropped -- what grid_sample's per-corner bounds test does -- by giving each member of the pair
-// the weight of the tap it stands for (or 0).  For Z == 2 the pair is always (0, 1) and the pairs of the corners y and
-// y + 1 are 16 contiguous bytes: a voxel is TWO sixteen-byte gathers (one per x-corner; round 2 issued eight four-byte
-// ones, 8.1 ms per 4000 frames at 512x512x2); for Z > 2 four eight-byte ones.
+// Z >= 2 (ZM = 2: Z == 2, ZM = 3: Z > 2): the two z-taps of a corner are fetched as one pair (warp_taps.hpp).
 template <int ZM, int FAST, bool F32OFF, bool PLAIN>
-__global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_recon_grad_kernel(const float *__restrict__ S, long lds,
-                                                              const int *__restrict__ s_ids,
-                                                              const float *__restrict__ frames, long ldf,
-                                                              const int *__restrict__ frame_ids,
-                                                              const float *__restrict__ gout, Volume vol, HaloLayout hl,
-                                                              const float *__restrict__ beta, int T,
-                                                              const int *__restrict__ times,
-                                                              float *__restrict__ recon, float *__restrict__ partial,
-                                                              const float2 *__restrict__ xtab, int nub) {
+__global__ __launch_bounds__(256, 1) void warp_recon_grad_kernel(const float *__restrict__ S, long lds,
+                                                                 const int *__restrict__ s_ids,
+                                                                 const float *__restrict__ frames, long ldf,
+                                                                 const int *__restrict__ frame_ids,
+                                                                 const float *__restrict__ gout, Volume vol, HaloLayout hl,
+                                                                 const float *__restrict__ beta, int T,
+                                                                 const int *__restrict__ times,
+                                                                 float *__restrict__ recon, float *__restrict__ partial,
+                                                                 const float2 *__restrict__ xtab, int nub) {
     constexpr bool HASZ = ZM > 1;
     constexpr bool ZPAIR = ZM == 2;                  // a thread owns BOTH slices of its (x, y) columns
     constexpr int NV = ZPAIR ? 2 : 1;                // voxels per thread and row
@@ -103,7 +79,7 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
     const int YZ = vol.Y * vol.Z;
     const int plane = ZPAIR ? vol.Y : YZ;              // positions the lanes of a frame's blocks run over
     const int bu = blockIdx.x % nub, bx = blockIdx.x / nub;
-    const int u = bu * K2_COLS + threadIdx.x;          // position in the (y,z) plane; Z == 2: y
+    const int u = bu * PLANE_COLS + threadIdx.x;          // position in the (y,z) plane; Z == 2: y
     const int yy = (HASZ && !ZPAIR) ? div_small(u, vol.Z, vol.rcp_z) : u;
     const int z = (HASZ && !ZPAIR) ? u - yy * vol.Z : 0;
     const float yf = (float)yy, zf = (float)z;
@@ -112,15 +88,13 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
         float b2[30];
         double_beta(bt, b2);
         const Monomials<true> mono = monomials<true>(0.0f, yf, zf);   // y, z, y^2, z^2, yz: fixed along the rows
-        const int x_first = bx * K2_ROWS;
-        const int nrow = min(K2_ROWS, vol.X - x_first);
+        const int x_first = bx * PLANE_ROWS;
+        const int nrow = min(PLANE_ROWS, vol.X - x_first);
 
         // A row is handled in two steps so that the loop below can keep the taps of the next rows in flight while
         // it blends the current ones: request() = coordinates, weights, tap offsets, loads; consume() = the blends,
         // the residual and the moment sums.
-        struct Vox {
-            float sv[HASZ ? 2 : 1][2][2];  // [dz][dy][dx]
-            float wx1, wy1, wzm[2], vz[2];
+        struct Vox : WarpTaps<HASZ> {
             float other;                  // frame value, or the caller's upstream gradient
         };
         struct Req {
@@ -129,62 +103,15 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
             Vox v[NV];
         };
         unsigned u4 = (unsigned)u * (4u * NV);
-        // ZC: the voxel's slice when it is known at compile time (Z == 2: 0 or 1), else -1.  z == 0: the four terms with z
-        // add an exact zero each (the Z == 1 chain); z == 1: their monomials are 1, 1, x, y.
+        constexpr int NT = HASZ ? 4 : 2;
         unsigned prev_o[NV];
-        float prev_v[NV][HASZ ? 4 : 2];
+        float prev_v[NV][NT];
 #pragma unroll
         for (int v = 0; v < NV; ++v) prev_o[v] = 0xffffffffu;
+        // zc: the voxel's slice when it is known at compile time (warp_taps.hpp: ZC)
         auto taps = [&](const float2 xv, float xy, auto zc, int slot, Vox &q) {
-            constexpr int ZC = decltype(zc)::value;
-            float a[3] = {0.0f, 0.0f, 0.0f};
-            if constexpr (ZC == 0) {
-                Monomials<false> m;
-                m.x = xv.x, m.y = yf, m.z = 0.0f, m.xx = xv.y, m.yy = mono.yy, m.zz = 0.0f, m.xy = xy, m.xz = 0.0f, m.yz = 0.0f;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) a[d] = poly_a<false>(b2, d, m);
-            } else {
-                Monomials<true> m = mono;
-                m.x = xv.x, m.xx = xv.y, m.xy = xy;
-                if constexpr (ZC == 1) {
-                    m.z = 1.0f, m.zz = 1.0f, m.xz = xv.x, m.yz = yf;
-                } else if (HASZ) {
-                    m.xz = __fmul_rn(xv.x, zf);
-                }
-#pragma unroll
-                for (int d = 0; d < ND; ++d) a[d] = HASZ ? poly_a<true>(b2, d, m) : poly_a<false>(b2, d, Monomials<false>{m.x, m.y, 0.0f, m.xx, m.yy, 0.0f, m.xy, 0.0f, 0.0f});
-            }
-            float fx, fy, w0;
-            axis_taps_halo(unnormalise(normalise_axis<FAST>(a[0], vol, 0), vol.hx1), hl.xhi, fx, w0, q.wx1);
-            axis_taps_halo(unnormalise(normalise_axis<FAST>(a[1], vol, 1), vol.hy1), hl.yhi, fy, w0, q.wy1);
-            const unsigned o0 = halo_offset<F32OFF>(fx, fy, hl, hl.origin4, hl.origin4f);   // base corner, slice 0
-            unsigned zo = 0u;
-            if (HASZ) {
-                const float uz = unnormalise(normalise_axis<FAST>(a[2], vol, 2), vol.hz1);
-                if (ZM == 2) {
-                    // the pair is (0, 1): weights of its members by common.hpp: z_pair_weights.  d weight / d u of
-                    // member 0 is +1 for f = floor(u) = -1 and -1 for f = 0, of member 1 +1 for f = 0 and -1 for f = 1,
-                    // else 0: with c = 2 f + 1 (c - 2) that is -c where |c| = 1.
-                    const float uc = z_pair_weights(uz, q.wzm[0], q.wzm[1]);
-                    const float c0 = fmaf(2.0f, floorf(uc), 1.0f), c1 = c0 - 2.0f;
-                    q.vz[0] = fabsf(c0) == 1.0f ? -c0 : 0.0f;
-                    q.vz[1] = fabsf(c1) == 1.0f ? -c1 : 0.0f;
-                } else {
-                    int iz;
-                    float wz[2];
-                    axis_weights(uz, iz, wz[0], wz[1]);
-                    // member 0 / 1 of the pair (izc, izc + 1) stands for tap iz / iz + 1 when iz == izc, member 0 for tap
-                    // iz + 1 when iz == izc - 1 (tap iz = -1 is outside), member 1 for tap iz when iz == izc + 1 (tap
-                    // iz + 1 = Z is outside); vz = d weight / d u_z of the tap a member stands for
-                    const int izc = clamp_index(iz, vol.Z - 1);
-                    const bool same = iz == izc, below = iz + 1 == izc, above = iz == izc + 1;
-                    q.wzm[0] = same ? wz[0] : (below ? wz[1] : 0.0f);
-                    q.wzm[1] = same ? wz[1] : (above ? wz[0] : 0.0f);
-                    q.vz[0] = same ? -1.0f : (below ? 1.0f : 0.0f);
-                    q.vz[1] = same ? 1.0f : (above ? -1.0f : 0.0f);
-                    zo = (unsigned)izc * 4u;
-                }
-            }
+            const unsigned olo = warp_taps_front<ZM, FAST, F32OFF, decltype(zc)::value>(b2, mono, xv.x, xv.y, xy, vol, hl, q);
+            const unsigned ohi = olo + (unsigned)hl.row4;
             // The tap row dx = 0 of this voxel is the tap row dx = 1 of the thread's last voxel whenever the warp moves the
             // base corner by exactly one row between consecutive x (every near-identity warp): when that holds for all lanes of
             // the wave the values are still in registers and only the upper row is gathered -- the kernel is bound by the
@@ -192,40 +119,16 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
             // wave-instruction), this halves its load for such warps: Z = 1 1.95 -> 1.72 ms per 4000 frames at 512x512 in the
             // bench, 4.6 TB/s -> 5.05 TB/s = what a device copy reaches.  Z >= 2 is bound by instruction issue instead: the
             // test and the moves cost it 8 % (4.66 -> 5.05 ms), so it is Z == 1 only.  Same bytes either way.
-            constexpr int NT = HASZ ? 4 : 2;
-            const unsigned olo = o0 + (ZM == 3 ? zo : 0u), ohi = olo + (unsigned)hl.row4;
-            auto gather = [&](unsigned o, float (&v)[NT]) {
-                asm("" : "+v"(o));
-                const char *t = s + o;   // (scalar base + 32-bit offset) loads
-                if constexpr (ZM == 2) {          // (y, z0), (y, z1), (y + 1, z0), (y + 1, z1): one load, 8-byte aligned
-                    const f32x4_a8 r = *reinterpret_cast<const f32x4_a8 *>(t);
-                    v[0] = r.x, v[1] = r.y, v[2] = r.z, v[3] = r.w;
-                } else if constexpr (ZM == 3) {   // the z-pair of corner y, then of corner y + 1
-                    const f32x2_a4 r0 = *reinterpret_cast<const f32x2_a4 *>(t);
-                    const f32x2_a4 r1 = *reinterpret_cast<const f32x2_a4 *>(t + hl.col4);
-                    v[0] = r0.x, v[1] = r0.y, v[2] = r1.x, v[3] = r1.y;
-                } else {
-                    v[0] = *reinterpret_cast<const float *>(t);
-                    v[1] = *reinterpret_cast<const float *>(t + 4);
-                }
-            };
-            float lo[NT], hi[NT];
-            if (K2_REUSE && (ZM == 1 || DNMF_K2_REUSE > 1) && __ballot(olo != prev_o[slot]) == 0) {   // wave-uniform
+            if (ZM == 1 && __ballot(olo != prev_o[slot]) == 0) {   // wave-uniform
 #pragma unroll
-                for (int i = 0; i < NT; ++i) lo[i] = prev_v[slot][i];
+                for (int i = 0; i < NT; ++i) q.t[0][i] = prev_v[slot][i];
             } else {
-                gather(olo, lo);
+                gather_tap_row<ZM>(s, olo, hl, q.t[0]);
             }
-            gather(ohi, hi);
+            gather_tap_row<ZM>(s, ohi, hl, q.t[1]);
             prev_o[slot] = ohi;
 #pragma unroll
-            for (int i = 0; i < NT; ++i) prev_v[slot][i] = hi[i];
-            if constexpr (HASZ) {
-                q.sv[0][0][0] = lo[0], q.sv[1][0][0] = lo[1], q.sv[0][1][0] = lo[2], q.sv[1][1][0] = lo[3];
-                q.sv[0][0][1] = hi[0], q.sv[1][0][1] = hi[1], q.sv[0][1][1] = hi[2], q.sv[1][1][1] = hi[3];
-            } else {
-                q.sv[0][0][0] = lo[0], q.sv[0][1][0] = lo[1], q.sv[0][0][1] = hi[0], q.sv[0][1][1] = hi[1];
-            }
+            for (int i = 0; i < NT; ++i) prev_v[slot][i] = q.t[1][i];
         };
         auto request = [&](int x, Req &q) {
             q.xv = xtab[x];                   // a scalar load
@@ -248,28 +151,8 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
                 const Vox &q = rq.v[v];
-                float rec = 0.0f, g[3] = {0.0f, 0.0f, 0.0f};
-#pragma unroll
-                for (int dz = 0; dz < (HASZ ? 2 : 1); ++dz) {
-                    // x- and y-blends as s0 + w1 (s1 - s0): the weights of an axis add up to exactly 1 (u - f and
-                    // (f + 1) - u are exact), the differences are the gradient's anyway -- one operation less per blend
-                    // than w0 s0 + w1 s1
-                    const float d0 = q.sv[dz][0][1] - q.sv[dz][0][0];                          // x-differences of the rows
-                    const float d1 = q.sv[dz][1][1] - q.sv[dz][1][0];
-                    const float a0 = fmaf(q.wx1, d0, q.sv[dz][0][0]);                          // x-interpolated rows y0, y1
-                    const float a1 = fmaf(q.wx1, d1, q.sv[dz][1][0]);
-                    const float gy2 = a1 - a0;
-                    const float r2 = fmaf(q.wy1, gy2, a0);                                     // value of this z-slice
-                    const float gx2 = fmaf(q.wy1, d1 - d0, d0);
-                    if (HASZ) {
-                        rec = fmaf(q.wzm[dz], r2, rec);
-                        g[0] = fmaf(q.wzm[dz], gx2, g[0]);
-                        g[1] = fmaf(q.wzm[dz], gy2, g[1]);
-                        g[2] = fmaf(q.vz[dz], r2, g[2]);
-                    } else {
-                        rec = r2, g[0] = gx2, g[1] = gy2;
-                    }
-                }
+                float rec, g[3];
+                blend_taps<HASZ>(q, rec, g);
                 recs[v] = rec;
                 // upstream gradient: the mse residual (scaled by 2/(B P) in the finish kernel) or the caller's
                 const float resid = !PLAIN && go ? q.other : rec - q.other;
@@ -290,12 +173,12 @@ __global__ __launch_bounds__(256, (ZM > 1 ? DNMF_K2_WAVES_Z : 1)) void warp_reco
                     *reinterpret_cast<float *>(dst) = recs[0];
             }
         };
-        if (nrow == K2_ROWS) {
+        if (nrow == PLANE_ROWS) {
             // K2_UNROLL rows at a time: their taps are requested together, then blended (keeping the next rows' taps in
             // flight behind the blends of the current ones did not pay: 2.07 against 1.99 ms, tools/time_k2.py)
             constexpr int UR = HASZ ? K2_UNROLL_Z : K2_UNROLL;
 #pragma unroll 1
-            for (int i = 0; i < K2_ROWS; i += UR) {
+            for (int i = 0; i < PLANE_ROWS; i += UR) {
                 Req q[UR];
 #pragma unroll
                 for (int j = 0; j < UR; ++j) request(x_first + i + j, q[j]);
@@ -427,18 +310,10 @@ __global__ __launch_bounds__(64) void sum_loss_kernel(const float *__restrict__ 
 
 extern "C" {
 
-static long k2_blocks(int X, int Y, int Z, int *nub_out) {
-    const long nub = ((long)Y * (Z == 2 ? 1 : Z) + dnmf::K2_COLS - 1) / dnmf::K2_COLS;   // Z == 2: a lane owns both slices
-    if (nub_out) *nub_out = (int)nub;
-    return nub * ((X + dnmf::K2_ROWS - 1) / dnmf::K2_ROWS);
-}
-
-static size_t k2_xtab_bytes(int X) { return ((size_t)X * sizeof(float2) + 255) / 256 * 256; }
-
 size_t dnmf_warp_recon_grad_workspace(int X, int Y, int Z, int B) {
     if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0) return 0;
-    return k2_xtab_bytes(X) + (size_t)B * k2_blocks(X, Y, Z, nullptr) * dnmf::K2_NACC * sizeof(float) +
-           (size_t)B * sizeof(float);
+    return dnmf::plane_walk_xtab_bytes<float2>(X) +
+           (size_t)B * dnmf::plane_walk_blocks(X, Y, Z, nullptr) * dnmf::K2_NACC * sizeof(float) + (size_t)B * sizeof(float);
 }
 
 long dnmf_halo_voxels(int X, int Y, int Z) {
@@ -477,20 +352,6 @@ static void k2_launch_main(const float *S, long lds, const int *s_ids, const flo
 #undef DNMF_K2_LAUNCH
 }
 
-// argument checks shared by the two entry points; fills vol / hl / nblk / nub
-static int k2_geometry(const char *who, int X, int Y, int Z, dnmf::Volume &vol, dnmf::HaloLayout &hl, int &nblk, int &nub) {
-    using namespace dnmf;
-    vol = make_volume(X, Y, Z);
-    hl = make_halo_layout(X, Y, Z);
-    // 32-bit byte offsets into an image; 24-bit multiplies for the tap offsets
-    DNMF_REQUIRE(hl.Pp < (1L << 29) && hl.row4 < (1 << 23) && hl.Xp < (1 << 23), DNMF_E_UNSUPPORTED,
-                 "%s: volume %dx%dx%d too large for 32-bit tap offsets", who, X, Y, Z);
-    const long nblk_l = k2_blocks(X, Y, Z, &nub);
-    DNMF_REQUIRE(nblk_l < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld blocks per frame", who, nblk_l);
-    nblk = (int)nblk_l;
-    return DNMF_OK;
-}
-
 int dnmf_warp_recon_grad(const float *S, long lds, const int *s_ids, const float *frames, long ldf,
                          const int *frame_ids, const float *gout, int X, int Y, int Z, const float *beta, int T,
                          const int *times, int B, int norm_frames, float *recon, float *grad, float *loss, float *frame_loss, float *reg,
@@ -503,7 +364,7 @@ int dnmf_warp_recon_grad(const float *S, long lds, const int *s_ids, const float
     Volume vol;
     HaloLayout hl;
     int nblk = 0, nub = 0;
-    const int rc = k2_geometry("dnmf_warp_recon_grad", X, Y, Z, vol, hl, nblk, nub);
+    const int rc = plane_walk_geometry("dnmf_warp_recon_grad", X, Y, Z, vol, hl, nblk, nub);
     if (rc != 0) return rc;
     DNMF_REQUIRE(lds >= hl.Pp && (!frames || ldf >= vol.P), DNMF_E_SHAPE,
                  "dnmf_warp_recon_grad: lds=%ld < %ld (halo layout) or ldf=%ld < P=%ld", lds, hl.Pp, ldf, vol.P);
@@ -511,7 +372,7 @@ int dnmf_warp_recon_grad(const float *S, long lds, const int *s_ids, const float
                  "dnmf_warp_recon_grad: workspace %zu < %zu bytes", workspace_bytes,
                  dnmf_warp_recon_grad_workspace(X, Y, Z, B));
     float2 *xtab = static_cast<float2 *>(workspace);
-    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + k2_xtab_bytes(X));
+    float *partial = reinterpret_cast<float *>(static_cast<char *>(workspace) + plane_walk_xtab_bytes<float2>(X));
     float *fl = frame_loss ? frame_loss : partial + (size_t)B * nblk * K2_NACC;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k2_xtab_kernel, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, st, xtab, X);
@@ -537,8 +398,8 @@ static size_t motion_images_bytes(int X, int Y, int Z, int chunk) {
 
 size_t dnmf_motion_grad_lists_workspace(int X, int Y, int Z, int chunk, int B) {
     if (X <= 0 || Y <= 0 || Z <= 0 || chunk <= 0 || B <= 0) return 0;
-    return motion_images_bytes(X, Y, Z, chunk) + k2_xtab_bytes(X) +
-           (size_t)B * k2_blocks(X, Y, Z, nullptr) * dnmf::K2_NACC * sizeof(float) + (size_t)B * sizeof(float);
+    return motion_images_bytes(X, Y, Z, chunk) + dnmf::plane_walk_xtab_bytes<float2>(X) +
+           (size_t)B * dnmf::plane_walk_blocks(X, Y, Z, nullptr) * dnmf::K2_NACC * sizeof(float) + (size_t)B * sizeof(float);
 }
 
 int dnmf_motion_grad_lists(const float *At, const int *bbox, int K, const float *C, long ldc, const float *frames, long ldf,
@@ -554,7 +415,7 @@ int dnmf_motion_grad_lists(const float *At, const int *bbox, int K, const float 
     Volume vol;
     HaloLayout hl;
     int nblk = 0, nub = 0;
-    int rc = k2_geometry("dnmf_motion_grad_lists", X, Y, Z, vol, hl, nblk, nub);
+    int rc = plane_walk_geometry("dnmf_motion_grad_lists", X, Y, Z, vol, hl, nblk, nub);
     if (rc != 0) return rc;
     DNMF_REQUIRE(ldf >= vol.P, DNMF_E_SHAPE, "dnmf_motion_grad_lists: ldf=%ld < P=%ld", ldf, vol.P);
     DNMF_REQUIRE(workspace_bytes >= dnmf_motion_grad_lists_workspace(X, Y, Z, chunk, B), DNMF_E_WORKSPACE,
@@ -563,7 +424,7 @@ int dnmf_motion_grad_lists(const float *At, const int *bbox, int K, const float 
     float *S = static_cast<float *>(workspace);
     char *at = static_cast<char *>(workspace) + motion_images_bytes(X, Y, Z, chunk);
     float2 *xtab = reinterpret_cast<float2 *>(at);
-    float *partial = reinterpret_cast<float *>(at + k2_xtab_bytes(X));
+    float *partial = reinterpret_cast<float *>(at + plane_walk_xtab_bytes<float2>(X));
     float *fl = frame_loss ? frame_loss : partial + (size_t)B * nblk * K2_NACC;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k2_xtab_kernel, dim3((unsigned)((X + 255) / 256)), dim3(256), 0, st, xtab, X);

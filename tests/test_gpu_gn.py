@@ -142,6 +142,32 @@ def test_k16_gradient_is_the_references_and_k2s(M):
         np.testing.assert_allclose(float(eq["sse"].sum()) / (B * P), g[label + "_loss"], rtol=1e-5)
 
 
+@pytest.mark.parametrize("sz", SHAPES[:3])
+def test_k2_and_k16_see_the_same_sample_bit_for_bit(M, sz):
+    """K2 and K16 call one warped sample (csrc/warp_taps.hpp) and reduce a block the same way, and these shapes are one block
+    per frame: K2's finish kernel then adds a single partial sum and K16's float64 finish converts a single fp32 one.  So on the
+    same images, frames and coefficients K2's per-frame loss is K16's sse and K2's gradient of the constant term is K16's g of
+    it, up to the one fp32 scaling K2's finish kernel applies -- exactly."""
+    from dnmf_amd import ops
+    c = k16_case(sz)
+    times = [0, 1, 2, 3, 4]                     # the finite frames; frame 4's first rows sample outside the volume
+    B, P = len(times), int(np.prod(sz))
+    eq = k16(c, times)
+    tt = torch.tensor(times, dtype=torch.int32, device="cuda")
+    grad = torch.zeros_like(dev(c["beta"]))
+    k2 = ops.warp_recon_grad(halo_images(c["S32"], c["sz"]), tt, dev(c["buf"]), dev(c["rows"][times], torch.int32), c["sz"],
+                             dev(c["beta"]), tt, grad=grad)
+    torch.cuda.synchronize()
+    sse, g = eq["sse"].cpu().numpy(), eq["g"].cpu().numpy()
+    loss, grad = k2["frame_loss"].cpu().numpy(), grad.cpu().numpy()
+    n = np.float32(B) * np.float32(P)
+    assert np.isfinite(sse).all() and g[1:].any()
+    np.testing.assert_array_equal(sse.astype(np.float32).astype(np.float64), sse)
+    np.testing.assert_array_equal(loss, sse.astype(np.float32) * (np.float32(1) / n))
+    for d in range(3 if sz[2] > 1 else 2):
+        np.testing.assert_array_equal(grad[0, d, times], (np.float32(2) / n) * g[:, d].astype(np.float32))
+
+
 def lm_inputs(sz, B, seed):
     rng = np.random.default_rng(seed)
     J = rng.normal(size=(B, 60, 30)) * rng.uniform(0.1, 10, (1, 1, 30))

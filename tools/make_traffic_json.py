@@ -62,7 +62,7 @@ def main():
         for d in dims[:-1]:
             P *= d
         zm = 1 if len(dims) == 3 else (2 if dims[2] == 2 else 3)
-        lists = ["warp_gram_lists.hip", "warp_gram_lists.hpp", "common.hpp"] + (["warp_gram_lists_z.hip"] if zm > 1 else [])
+        lists = ["warp_gram_lists.hip", "warp_gram_lists.hpp", "warp_taps.hpp", "common.hpp"] + (["warp_gram_lists_z.hip"] if zm > 1 else [])
         p1 = kernels(s, [f"warp_gram_lists_kernel<{zm}, "])
         one = {k.rpartition(":")[0] for k in s if k.startswith(f"warp_gram_lists_kernel<{zm}, ")}
         tm = kernels(s, ["lists_tilemask_kernel"])
@@ -80,7 +80,7 @@ def main():
             entries[name + "_lists_valu"] = {"value": valu, "files": lists}
         k2 = kernels(s, ["warp_recon_grad_kernel<"])
         if k2:
-            entries[geom + "_K2"] = {"value": hbm_bytes(k2), "files": ["warp_recon_grad.hip", "common.hpp"],
+            entries[geom + "_K2"] = {"value": hbm_bytes(k2), "files": ["warp_recon_grad.hip", "warp_taps.hpp", "common.hpp"],
                                      "what": "HBM bytes per K2 launch", "issue": issue(k2, T * P / 64.0)}
         rl = kernels(s, ["recon_lists_kernel<"])
         if rl:
