@@ -368,6 +368,8 @@ int dnmf_warp_recon_grad(const float *S, long lds, const int *s_ids, const float
     if (rc != 0) return rc;
     DNMF_REQUIRE(lds >= hl.Pp && (!frames || ldf >= vol.P), DNMF_E_SHAPE,
                  "dnmf_warp_recon_grad: lds=%ld < %ld (halo layout) or ldf=%ld < P=%ld", lds, hl.Pp, ldf, vol.P);
+    // Z == 2: (x, y, 0), (x, y, 1) of a frame are one eight-byte load at row * ldf + an even offset
+    DNMF_REQUIRE(Z != 2 || !frames || ldf % 2 == 0, DNMF_E_SHAPE, "dnmf_warp_recon_grad: Z == 2 needs an even ldf, got %ld", ldf);
     DNMF_REQUIRE(workspace_bytes >= dnmf_warp_recon_grad_workspace(X, Y, Z, B), DNMF_E_WORKSPACE,
                  "dnmf_warp_recon_grad: workspace %zu < %zu bytes", workspace_bytes,
                  dnmf_warp_recon_grad_workspace(X, Y, Z, B));
@@ -418,6 +420,7 @@ int dnmf_motion_grad_lists(const float *At, const int *bbox, int K, const float 
     int rc = plane_walk_geometry("dnmf_motion_grad_lists", X, Y, Z, vol, hl, nblk, nub);
     if (rc != 0) return rc;
     DNMF_REQUIRE(ldf >= vol.P, DNMF_E_SHAPE, "dnmf_motion_grad_lists: ldf=%ld < P=%ld", ldf, vol.P);
+    DNMF_REQUIRE(Z != 2 || ldf % 2 == 0, DNMF_E_SHAPE, "dnmf_motion_grad_lists: Z == 2 needs an even ldf, got %ld", ldf);
     DNMF_REQUIRE(workspace_bytes >= dnmf_motion_grad_lists_workspace(X, Y, Z, chunk, B), DNMF_E_WORKSPACE,
                  "dnmf_motion_grad_lists: workspace %zu < %zu bytes", workspace_bytes,
                  dnmf_motion_grad_lists_workspace(X, Y, Z, chunk, B));

@@ -90,7 +90,8 @@ int dnmf_recon_image(const float *Apk, int X, int Y, int Z, int K, int Kp, const
  * (dNMF.py:188, mean over B*P) and its autograd gradient w.r.t. beta[:,:,times]; also reg of
  * dNMF.py:60-61 (gradient-free in the reference).
  *   S       recon images in the halo layout (zero border), frame b at S + s_ids[b]*lds (s_ids NULL -> b)
- *   frames  video frames, frame b at frames + frame_ids[b]*ldf (frame_ids NULL -> b)
+ *   frames  video frames, frame b at frames + frame_ids[b]*ldf (frame_ids NULL -> b).  Z == 2: ldf must be even (the two
+ *           slices of a column are read as one aligned pair of floats; an odd ldf is DNMF_E_SHAPE)
  *   gout    NULL, or (B,P) upstream gradient d L / d A_tC of an arbitrary loss: then grad receives
  *           its chain through the warp unscaled, `frames` may be NULL and loss / frame_loss are
  *           meaningless (this is the backward of the autograd node the Python surface exposes)
@@ -209,7 +210,7 @@ int dnmf_recon_image_lists_ex(const float *At, const int *bbox, int K, int X, in
  * arguments, no upstream gradient, A_tC not returned) alternate over pieces of `chunk` frames that share ONE buffer of
  * `chunk` images, so S_t = A.C_t never makes the round trip through HBM (Demix/dNMF.py:58 + 186-190 for B frames).
  * Same kernels and sums as the two calls on all B frames (K2's finish kernel runs once at the end).  norm_frames > 0 is
- * required; B may exceed 65535; workspace: dnmf_motion_grad_lists_workspace(X,Y,Z,chunk,B) bytes. */
+ * required; B may exceed 65535; Z == 2: ldf even, as K2 asks; workspace: dnmf_motion_grad_lists_workspace(X,Y,Z,chunk,B) bytes. */
 size_t dnmf_motion_grad_lists_workspace(int X, int Y, int Z, int chunk, int B);
 int dnmf_motion_grad_lists(const float *At, const int *bbox, int K, const float *C, long ldc, const float *frames, long ldf,
                            const int *frame_ids, int X, int Y, int Z, const float *beta, int T, const int *times, int B,

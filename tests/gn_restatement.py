@@ -82,17 +82,18 @@ def source_coords(beta_t, sz, exact=False):
 
 def sample(s, u):
     """Zero-padded trilinear sample of the image s (X,Y,Z) at u (X,Y,Z,3) and its derivative w.r.t. u: (rec, dq (3,X,Y,Z)),
-    in-bounds corners only (ATen grid_sampler_3d forward / backward)."""
+    in-bounds corners only (ATen grid_sampler_3d forward / backward).  u may cover any block of voxels (..., 3): rec and dq
+    then have its shape."""
     dims = s.shape
     f = np.floor(u)
-    rec = np.zeros(dims)
-    dq = np.zeros((3,) + dims)
+    rec = np.zeros(u.shape[:-1])
+    dq = np.zeros((3,) + u.shape[:-1])
     for dz in (0, 1):
         for dy in (0, 1):
             for dx in (0, 1):
                 off = (dx, dy, dz)
                 c = [f[..., d] + off[d] for d in range(3)]
-                ok = np.ones(dims, bool)
+                ok = np.ones(u.shape[:-1], bool)
                 for d in range(3):
                     ok &= (c[d] >= 0) & (c[d] <= dims[d] - 1)
                 ci = [np.clip(c[d], 0, dims[d] - 1).astype(np.int64) for d in range(3)]

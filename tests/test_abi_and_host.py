@@ -77,6 +77,17 @@ def test_argument_errors_are_reported_without_a_gpu(lib):
     assert lib.dnmf_adam_epoch_workspace(1000) == 16000
     assert lib.dnmf_adam_epoch(addr, None, addr, addr, 4, 0, addr, None, 10, 1e-3, 0.9, 0.999, 1e-8, 0, addr, 8, None) == -4
     assert lib.dnmf_warp_recon_grad_workspace(512, 512, 1, 4000) == 512 * 8 + 4000 * 32 * 32 * 4 + 4000 * 4
+    # K2 at Z == 2 reads a column's two slices as one aligned pair: an odd frame stride is refused (lds = 8 x 32, P = 32)
+    k2 = lambda ldf, ws: lib.dnmf_warp_recon_grad(addr, 256, None, addr, ldf, None, None, 4, 4, 2, addr, 1, addr, 1, 0, None, addr,
+                                                  None, None, None, addr, ws, None)
+    assert k2(33, 1 << 20) == -2 and b"even ldf" in lib.dnmf_last_error()
+    assert k2(34, 8) == -4                                            # an even one goes on to the workspace check
+    assert lib.dnmf_warp_recon_grad(addr, 256, None, addr, 17, None, None, 4, 4, 1, addr, 1, addr, 1, 0, None, addr, None, None,
+                                    None, addr, 8, None) == -4        # Z == 1: any stride
+    mg = lambda ldf: lib.dnmf_motion_grad_lists(addr, addr, 3, addr, 1, addr, ldf, None, 4, 4, 2, addr, 1, addr, 1, 1, addr, None,
+                                                None, 1, addr, 8, None)
+    assert mg(33) == -2 and b"even ldf" in lib.dnmf_last_error()
+    assert mg(34) == -4
     # C1: arguments are checked before RCCL is looked up
     assert lib.dnmf_comm_unique_id(None) == -1
     assert lib.dnmf_comm_init(None, addr, 2, 0) == -1

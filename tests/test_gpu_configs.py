@@ -739,6 +739,35 @@ def test_motion_grad_in_pieces_is_the_same_gradient(M):
     assert torch.equal(res[0], res[1])
 
 
+@pytest.mark.parametrize("sz", [[65, 300, 2], [34, 90, 3]])
+def test_motion_grad_in_pieces_is_the_same_gradient_with_slices(M, sz):
+    """The same bit-for-bit comparison of dnmf_motion_grad_lists with dnmf_recon_image_lists + dnmf_warp_recon_grad at Z == 2 and
+    Z > 2 (two shapes of tests/test_gpu_k2_float64.py: several blocks per frame), the warp also along z; piece sizes that do
+    not divide the 23 frames, row ids, norm_frames != B."""
+    from dnmf_amd import ops
+    torch.manual_seed(3)
+    K, T = 9, 23
+    pos = torch.rand(K, 3) * torch.tensor([float(s) for s in sz])
+    fp = M.ExponentialFP(torch.tensor(sz), K, T, positions=pos)
+    with torch.no_grad():
+        fp.beta += 1e-2 * torch.randn_like(fp.beta) * torch.tensor([50, 1, 1, 1, 1e-3, 1e-3, 1e-3, 1e-3, 1e-3, 1e-3], device="cuda")[:, None, None]
+    C = torch.rand(K, T, device="cuda")
+    frames = torch.rand(T + 5, fp.P, device="cuda")
+    rows = torch.randperm(T + 5)[:T].to(torch.int32).cuda()
+    times = torch.randperm(T).to(torch.int32).cuda()
+    ly = fp.packed_lists()
+    beta = fp.beta.detach()
+    S = ops.recon_image_lists(ly, K, sz, C, times)
+    g0 = torch.zeros_like(beta)
+    ref = ops.warp_recon_grad(S, None, frames, rows, sz, beta, times, grad=g0, norm_frames=4)
+    assert bool(g0[:, 2].abs().sum() > 0) and bool(g0[3].abs().sum() > 0)          # the z entries are there
+    for chunk in (1, 5, 8, 23, 64):
+        g = torch.zeros_like(beta)
+        out = ops.motion_grad_lists(ly, K, sz, C, frames, rows, beta, times, g, 4, chunk, want=True)
+        assert torch.equal(g, g0), chunk
+        assert torch.equal(out["frame_loss"], ref["frame_loss"]) and torch.equal(out["reg"], ref["reg"])
+
+
 @pytest.mark.parametrize("sz", [[64, 48, 2], [37, 30, 1], [21, 9, 3]])
 def test_list_form_of_the_footprint_update(M, O, sz):
     """K5 / K6 in their list form (sums only for the (tile, listed neuron) pairs whose box meets the tile) against the dense
