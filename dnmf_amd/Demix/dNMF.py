@@ -154,6 +154,7 @@ class ExponentialFP(nn.Module):
         self.A = A
         self.invalidate_layouts()
         self.use_lists = True   # reconstruction image from neuron lists when the footprints are compact
+        self.last_registered_bad = None   # registered_video('linear'): int64[1] CUDA, lattice points without a solution
 
     def invalidate_layouts(self):
         """Forget every packed copy of ``A``.  The packed copies are keyed on ``(A.data_ptr(), A._version)``, which a
@@ -355,6 +356,48 @@ class ExponentialFP(nn.Module):
             Yi_list.append(Yi.view(len(times), X, Y_, Z).permute(1, 2, 3, 0).double().cpu().numpy())
         return np.concatenate(A_list, 4), np.concatenate(Yi_list, 3), np.concatenate(Y_list, 3)
 
+    def registered_video(self, frames, times=None, interpolation='linear', fill=None, nchan=1):
+        """The motion-corrected movie under the current ``beta``: frame b registered to the footprint volume with the warp of
+        frame ``times[b]`` (None: b).  CUDA rows (B, nchan*P) in give CUDA rows (B, nchan*P) out (``nchan`` channels of a row
+        share the warp); numpy or CPU-torch ``(X, Y, Z, B)`` in gives float64 numpy ``(X, Y, Z, B)`` out, the layout
+        ``update_footprints`` returns ``Y_i`` in.
+
+        ``interpolation='linear'`` (K17, ``ops.warp_pullback``): for every lattice point u the x with q_t(x) = u, and the frame
+        sampled trilinearly there with zero padding -- the model's own forward read backwards, smooth in the warp.  It works in
+        true voxel coordinates and does NOT carry the ``sz``-for-``sz - 1`` un-normalisation quirk that ``spatial_pushforward``
+        keeps from the reference: an extension, not a parity path.  ``fill``: None = zero padding and 0 where the warp has no
+        solution Newton finds; a float (NaN, say) marks every point that comes from outside the frame, and those.
+        ``self.last_registered_bad`` then holds the number of lattice points without a solution (an int64 CUDA tensor).
+        ``interpolation='nearest'``: the reference's nearest-neighbour registration (K7, ``ops.image_iwarp``), which has no
+        ``fill``."""
+        if interpolation not in ('linear', 'nearest'):
+            raise ValueError(f"registered_video: interpolation must be 'linear' or 'nearest', got {interpolation!r}")
+        if interpolation == 'nearest' and fill is not None:
+            raise ValueError("registered_video: fill applies to interpolation='linear' only")
+        X, Y, Z = self.sz_list
+        on_gpu = isinstance(frames, torch.Tensor) and frames.is_cuda
+        if on_gpu:
+            if frames.dim() != 2:
+                raise ValueError(f"registered_video: CUDA frames are rows (B, nchan*P), got {tuple(frames.shape)}")
+            rows = frames
+        else:
+            v = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
+            if v.dim() != 4 or list(v.shape[:3]) != [X, Y, Z] or nchan != 1:
+                raise ValueError(f"registered_video: host frames are ({X}, {Y}, {Z}, B) with one channel, got {tuple(v.shape)}")
+            rows = v.to(device, torch.float32).permute(3, 0, 1, 2).reshape(v.shape[3], -1).contiguous()
+        if times is None:
+            times = torch.arange(rows.shape[0], dtype=torch.int32, device=device)
+        beta = self.beta.detach()
+        if interpolation == 'linear':
+            self.last_registered_bad = torch.zeros(1, dtype=torch.int64, device=device)
+            out = ops.warp_pullback(rows, None, self.sz_list, beta, times, nchan=nchan, fill=fill, count=self.last_registered_bad)
+        else:
+            self.last_registered_bad = None
+            out = ops.image_iwarp(rows, None, self.sz_list, beta, times, nchan=nchan)
+        if on_gpu:
+            return out
+        return out.view(-1, X, Y, Z).permute(1, 2, 3, 0).double().cpu().numpy()
+
     @staticmethod
     def image_iwarp(im, flow, grid):
         """Reference :95-103: the value of ``im`` at the flow point nearest to each query of ``grid`` (scipy's
@@ -506,7 +549,8 @@ class DeformableNMF:
         self._stage_buf = None     # device copy of the frames a host loader served in its last pass
         # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam (CUDA tensors, (T,)); else None
         self.last_motion_gn = None
-        self._reg_buf = None       # registered frames (K7) of the last update_footprints(live_spatial=True)
+        self._reg_buf = None       # registered frames (K7 / K17) of the last update_footprints(live_spatial=True)
+        self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
         self._D_dev = None         # (id(self.D), fp32 device copy of D flattened to (P,K))
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
         self._warned = set()
@@ -714,8 +758,20 @@ class DeformableNMF:
             idx.append(torch.as_tensor(data[1]).to(device, torch.int32).reshape(-1))
         return torch.cat(fr, 0).contiguous(), torch.cat(idx, 0)
 
+    def registered_video(self, loader, interpolation='linear', fill=None):
+        """The motion-corrected movie of every frame ``loader`` serves, under the current ``fp.beta``: (T_loc, nchan*P) fp32
+        CUDA rows in the loader's order (``ExponentialFP.registered_video``: ``'linear'`` = K17, trilinear in true voxel
+        coordinates, an extension without the reference's ``sz``-for-``sz - 1`` quirk; ``'nearest'`` = K7, the reference's).
+        ``self.last_registered_bad``: the number of lattice points the warp had no solution for (None for ``'nearest'``)."""
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            out = self.fp.registered_video(frames, times=order, interpolation=interpolation, fill=fill, nchan=self._nchan())
+        bad = self.fp.last_registered_bad
+        self.last_registered_bad = None if bad is None else int(bad)
+        return out
+
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
-                          live_spatial=False, iter_a=1, solver='mu'):
+                          live_spatial=False, iter_a=1, solver='mu', registered='nearest'):
         """Reference :163-179: ``iter_c`` multiplicative updates of ``self.C`` under the current warp.
 
         ``solver='hals'`` (extension) runs ``iter_c`` sweeps of the exact solver K4h instead, from the same ``self.C``, on
@@ -728,16 +784,21 @@ class DeformableNMF:
 
         Returns ``(A_t, Y_i, Y)`` like the reference when the dense float64 ``A_t`` fits
         ``DENSE_RETURN_LIMIT`` (or ``return_dense=True``); otherwise ``(None, None, None)``.
-        ``Y_i`` comes from the nearest-neighbour search K7 (``dnmf_image_iwarp``).
+        ``Y_i`` comes from the nearest-neighbour search K7 (``dnmf_image_iwarp``) unless ``registered='linear'``.
         ``gamma_a`` is unused unless ``live_spatial`` is set, as in the reference (its footprint update is commented
         out, :174).  ``live_spatial=True`` (extension) wires that update: after the temporal updates the frames are
         registered (K7) and ``fp.A`` takes ``iter_a`` multiplicative updates ``A * (Y_i C^T) / (A C C^T + gamma_a D +
         1e-32)`` (``spatial_step``: K5, one all-reduce over ``self.group``, K6) with the ``D`` of the constructor
         flattened over the voxels -- the reference's commented lines update an unrelated random ``self.A`` with
-        mismatched shapes (:131, :169-176); here the update acts on the footprints the model uses."""
+        mismatched shapes (:131, :169-176); here the update acts on the footprints the model uses.
+
+        ``registered='linear'`` (extension) registers with K17 (``ops.warp_pullback``: trilinear, true voxel coordinates,
+        without the reference's ``sz``-for-``sz - 1`` quirk -- not a parity path) instead of K7, both for the ``live_spatial``
+        input of ``spatial_step`` and for the returned ``Y_i``; the default ``'nearest'`` is the reference's."""
         fp = self.fp
         K, P = fp.K, fp.P
         _check_solver(solver)
+        _check_registered(registered, "update_footprints")
         hals = solver == 'hals'
         if hals:
             _hals_refuse_shards(gamma_c, self.group)
@@ -773,7 +834,10 @@ class DeformableNMF:
                 if self._reg_buf is None or self._reg_buf.shape != (T_loc, nch * P):
                     self._reg_buf = None
                     self._reg_buf = torch.empty((T_loc, nch * P), dtype=torch.float32, device=device)
-                ops.image_iwarp(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
+                if registered == 'linear':
+                    ops.warp_pullback(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
+                else:
+                    ops.image_iwarp(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
                 for _ in range(iter_a):
                     self.spatial_step(self._reg_buf, D=self.D, gamma=gamma_a, times=order)
             if return_dense is None:
@@ -789,7 +853,10 @@ class DeformableNMF:
             Yv = frames.view(T_loc, X, Y_, Z).permute(1, 2, 3, 0).double().cpu().numpy()
             Yi = np.empty_like(Yv)
             for s in range(0, T_loc, 256):
-                yi = ops.image_iwarp(frames, order[s:s + 256], fp.sz_list, fp.beta.detach(), order[s:s + 256])
+                if registered == 'linear':
+                    yi = ops.warp_pullback(frames[s:s + 256], None, fp.sz_list, fp.beta.detach(), order[s:s + 256])
+                else:
+                    yi = ops.image_iwarp(frames, order[s:s + 256], fp.sz_list, fp.beta.detach(), order[s:s + 256])
                 Yi[..., s:s + 256] = yi.view(-1, X, Y_, Z).permute(1, 2, 3, 0).double().cpu().numpy()
             return A_t, Yi, Yv
 
@@ -1300,17 +1367,18 @@ class DeformableNMF:
                 print('Reg: ' + str(out["reg"][j * nf:(j + 1) * nf]))
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
-            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam'):
+            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest'):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
-        Gauss-Newton, ``optimizer`` may then be None)."""
+        Gauss-Newton, ``optimizer`` may then be None); ``registered`` is ``update_footprints``' (``'linear'``: K17)."""
         _check_motion_solver(motion_solver, "fit")
+        _check_registered(registered, "fit")
         out = (None, None, None)
         for _ in range(outer):
             self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
             out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
-                                         iter_c=iter_c, live_spatial=spatial, solver=solver)
+                                         iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
         return out
 
 
@@ -1351,14 +1419,16 @@ class MultiChannelDNMF(DeformableNMF):
         return self.colours.shape[0]
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=False,
-                          live_spatial=False, iter_a=1, solver='mu'):
+                          live_spatial=False, iter_a=1, solver='mu', registered='nearest'):
         """As DeformableNMF.update_footprints on the channel sums; the dense ``A_t`` return is not offered.  With
-        ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel) and
-        ``fp.A`` takes ``iter_a`` steps of ``spatial_step``."""
+        ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel;
+        ``registered='linear'``: one K17 call, one solve per lattice point) and ``fp.A`` takes ``iter_a`` steps of
+        ``spatial_step``."""
         if return_dense:
             raise NotImplementedError("MultiChannelDNMF.update_footprints: return_dense")
         return super().update_footprints(testloader, batch_size, sz, gamma_c=gamma_c, gamma_a=gamma_a, iter_c=iter_c,
-                                         return_dense=False, live_spatial=live_spatial, iter_a=iter_a, solver=solver)
+                                         return_dense=False, live_spatial=live_spatial, iter_a=iter_a, solver=solver,
+                                         registered=registered)
 
     def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
         """One multiplicative update of the (uncoloured) footprints ``fp.A`` from the registered frames of ALL channels
@@ -1434,6 +1504,11 @@ SOLVERS = ('mu', 'hals')
 def _check_solver(solver):
     if solver not in SOLVERS:
         raise ValueError(f"solver={solver!r}: expected one of {SOLVERS}")
+
+
+def _check_registered(registered, who):
+    if registered not in ('nearest', 'linear'):
+        raise ValueError(f"{who}: registered must be 'nearest' (K7) or 'linear' (K17), got {registered!r}")
 
 
 def _check_motion_solver(solver, who):

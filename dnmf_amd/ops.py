@@ -779,6 +779,56 @@ def image_iwarp(frames, frame_ids, sz, beta, times, out=None, exhaustive=False, 
     return out
 
 
+PULLBACK_MAX_FRAMES = 32768   # frames per K17 launch (they ride on gridDim.y)
+
+
+def warp_pullback(frames, frame_ids, sz, beta, times, out=None, nchan=1, fill=None, coords=None, count=None):
+    """K17.  Registered frames (B, nchan*P): for every lattice point u of the volume the x with q_t(x) = u under
+    beta[:, :, times] (Newton from u), and the frame sampled trilinearly there (zero padding, the model's own forward).  True
+    voxel coordinates: none of the reference's ``sz``-for-``sz - 1`` scaling that K7 (``image_iwarp``) keeps -- an extension,
+    not a parity path.  ``frames`` / ``frame_ids`` / ``times`` / ``out`` / ``nchan`` as ``image_iwarp`` (``times`` None:
+    column b of beta for frame b).  ``fill``: None = zero padding, points without a solution get 0; a float (NaN, say) is
+    written to every point whose x lies outside the volume and to points without a solution.  ``coords``: a (B,P,3) fp32 CUDA
+    tensor that receives x (NaN where there is no solution); ``count``: int64[1] CUDA tensor incremented by the lattice
+    points without a solution."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    nchan = int(nchan)
+    if nchan < 1:
+        raise ValueError(f"warp_pullback: nchan={nchan}")
+    _f32(beta, "beta")
+    if beta.dim() != 3 or tuple(beta.shape[:2]) != (10, 3):
+        raise ValueError(f"warp_pullback: beta must be (10,3,T), got {tuple(beta.shape)}")
+    _rows(frames, "warp_pullback", "frames", nchan * P, f" and rows of {nchan} x {P} floats")
+    dev = frames.device
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    if out is None:
+        out = torch.empty((B, nchan * P), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or not out.is_cuda or out.dim() != 2 or out.shape[0] < B or out.stride(0) < nchan * P or out.stride(1) != 1:
+        raise ValueError(f"warp_pullback: out must be float32 CUDA (>=B, ld) with ld >= {nchan} x P")
+    if coords is not None and (coords.dtype != torch.float32 or not coords.is_cuda or not coords.is_contiguous()
+                               or tuple(coords.shape) != (B, P, 3)):
+        raise ValueError(f"warp_pullback: coords must be a contiguous float32 CUDA tensor of shape ({B}, {P}, 3)")
+    if count is not None and (count.dtype != torch.int64 or not count.is_cuda or count.numel() < 1):
+        raise ValueError("warp_pullback: count must be an int64 CUDA tensor")
+    if tt is None:
+        tt = torch.arange(B, dtype=torch.int32, device=dev)
+    # the row stride of a single row means nothing (a view through numpy's newaxis has 0)
+    ldf = frames.stride(0) if frames.shape[0] != 1 else max(frames.stride(0), nchan * P)
+    lib = _lib.load()
+    for s in range(0, B, PULLBACK_MAX_FRAMES):
+        n = min(PULLBACK_MAX_FRAMES, B - s)
+        src = frames if fid is not None else frames[s:]   # without ids, frame b of a launch is its row b
+        with _timed("warp_pullback"):
+            rc = lib.dnmf_warp_pullback(src.data_ptr(), ldf, P, nchan, 0 if fid is None else fid[s:].data_ptr(), X, Y, Z,
+                                        beta.data_ptr(), beta.shape[2], tt[s:].data_ptr(), n, out[s:].data_ptr(), out.stride(0), P,
+                                        0 if fill is None else 1,
+                                        0.0 if fill is None else float(fill), 0 if coords is None else coords[s:].data_ptr(),
+                                        _ptr(count), _stream())
+        _lib.check(rc, "dnmf_warp_pullback")
+    return out
+
+
 def nearest_points(points, queries, values=None, out_index=None, out=None, _workspace_bytes=None):
     """K10.  points (B,N,3) fp32 or fp64 CUDA, queries (Q,3) (one set for every frame) or (B,Q,3), converted to float64 ->
     ``index`` (B,Q) int32: per frame and query the point of the smallest float64 (d2, index), exact, ties to the lowest index;

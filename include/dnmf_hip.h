@@ -613,6 +613,33 @@ int dnmf_lm_step(const double *H, const double *g, const double *sse, int B, int
                  const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0, double *lam, float *beta_acc,
                  int *counts, double nu, double lam0, double lam_min, double lam_max, int accept_only, dnmf_stream_t stream);
 
+/* ---- K17: the trilinear registered movie under the fitted warp ----------------------------------------------------------------
+ * For every frame j < B (column t = times[j] of beta, or j when times is NULL; row frame_ids[j] of frames, or j) and every lattice
+ * point u = (i, j, k) of the footprint volume: the x with q_t(x) = u, and the frame sampled trilinearly at x.  Conventions as K11 /
+ * K12: q_t(x) = basis(x) . beta[:, :, t] in voxel indices, the true Jacobian.  tests/pullback_restatement.py is the definition in
+ * float64.  An EXTENSION, not a parity path: true voxel coordinates throughout, none of the sz-for-(sz - 1) scaling K7 keeps from
+ * the reference's spatial_pushforward.
+ *   solve    Newton from x = u; an axis of extent 1 is inactive (its coordinate stays 0, its equation is dropped: K2's Z == 1).
+ *            The definition stops at a step below 1e-6 in every coordinate, 32 steps at most; the kernel iterates in fp32 on the
+ *            displacement x - u and stops at a step below 1e-4 (relative to |x - u| beyond 32 voxels).  Contract: x is within 1e-3
+ *            voxel of the definition's wherever that converges with |det J| >= 0.5, at extents up to 512.  A point is BAD when
+ *            |det J| < 1e-12, an iterate is not finite or the steps run out; so is every point of a frame whose t is outside [0, T).
+ *   sample   sum over the 8 taps (4 at Z == 1) of w Y[tap], weights from floor(x) and x - floor(x); a tap outside the volume
+ *            contributes 0 (grid_sample, zeros, align_corners=True: the model's own forward), NaN voxels propagate as IEEE gives
+ *            them.  At the identity and at an integer translation inside the volume the output equals the input bit for bit.
+ *   fill     fill_mode 0: the zero padding above, bad points 0;  1: fill_value (NaN, say) at every point whose x lies outside
+ *            [0, S_d - 1] on an active axis, and at bad points.
+ * Frame row b holds nchan channels that share the warp, channel c at frames[row + c ldc_in] and at out[b ldo + c ldc_out]: one
+ * solve per lattice point serves them all (nchan == 1: ldc_in, ldc_out unused).  coords: NULL or (B,P,3) fp32, the x of every
+ * point (NaN where bad).  bad_count: NULL or one int64 INCREMENTED by the bad points of the call (per lattice point, not per
+ * channel).  One launch, no workspace, no host synchronisation.
+ * DNMF_E_NULL: frames, beta or out NULL;  DNMF_E_SHAPE: a size or T < 1, B < 0, B > T without times, nchan < 1, fill_mode not 0 / 1,
+ * ldc_in or ldc_out < P, ldf < (nchan-1) ldc_in + P, ldo < (nchan-1) ldc_out + P;  DNMF_E_UNSUPPORTED: 2^31 voxels or more, B > 65535
+ * (frames ride on gridDim.y: split the call). */
+int dnmf_warp_pullback(const float *frames, long ldf, long ldc_in, int nchan, const int *frame_ids, int X, int Y, int Z,
+                       const float *beta, int T, const int *times, int B, float *out, long ldo, long ldc_out, int fill_mode,
+                       float fill_value, float *coords, long long *bad_count, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
