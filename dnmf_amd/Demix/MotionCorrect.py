@@ -267,20 +267,67 @@ class MotionCorrect(object):
         sh = np.stack([np.stack(self.x_shifts_els[:T]), np.stack(self.y_shifts_els[:T]), np.stack(self.z_shifts_els[:T])], 2)
         return torch.from_numpy(sh.astype(np.float32)).to(device)
 
+    def summary_images(self, video=None, neighbours='full'):
+        """The summary images (K18, ``ExponentialFP.summary_images``) of a (T, X, Y, Z) ``video`` or, without one, of the stored
+        corrected movie -- ``mc_els`` when the piecewise pass kept one, else ``mc`` (``save_corrected=True``; several videos
+        count as one movie): a dict ``mean / std / max / corr`` of (X, Y, Z) float64 numpy images (CUDA tensors for a CUDA
+        ``video``).  The stored movie goes to the GPU in pieces of at most 1 GiB.  Voxels the correction left NaN in some
+        frame are NaN."""
+        from .dNMF import ExponentialFP
+        if video is not None:
+            return ExponentialFP.summary_images(video, neighbours=neighbours)
+        movies = getattr(self, "mc_els", None) or getattr(self, "mc", None)
+        if not movies:
+            raise ValueError("MotionCorrect.summary_images: no video given and no corrected movie stored; construct with "
+                             "save_corrected=True and call motion_correct() first")
+        sz = [int(n) for n in movies[0].shape[:3]]
+        P = sz[0] * sz[1] * sz[2]
+        limit = max(1, (1 << 30) // (4 * P))
+        pieces = [(m, s, min(m.shape[3], s + limit)) for m in movies for s in range(0, m.shape[3], limit)]
+        state = ops.summary_images_state(sz, max(e - s for _, s, e in pieces), neighbours=neighbours, device=device)
+        for n, (m, s, e) in enumerate(pieces):
+            rows = torch.from_numpy(np.ascontiguousarray(np.moveaxis(m[..., s:e], 3, 0))).to(device, torch.float32).reshape(e - s, P)
+            images, state = ops.summary_images(rows, sz, neighbours=neighbours, state=state, first=n == 0, finish=n == len(pieces) - 1)
+        return {k: v.cpu().numpy() for k, v in images.items()}
+
     def detect_points(self, K, shape_std=3, **kw):
         """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
         made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,
         ``threshold``, ``background``): the ``points`` ``apply_shifts_points`` takes, float64 numpy, brightest first.  The
-        reference has no counterpart (its real data comes with annotated positions)."""
+        reference has no counterpart (its real data comes with annotated positions).
+
+        ``image`` (keyword, default ``'template'``: the above, unchanged): ``'corr'``, ``'max'`` or ``'std'`` search that summary
+        image of the stored corrected movie (``summary_images()``, K18; needs ``save_corrected=True``) -- the template averages
+        over time and hides neurons that are dim on average but active; an (X, Y, Z) array is searched as given.  NaNs (the
+        border strips the correction leaves, voxels without a valid neighbour) are replaced by the image's finite minimum,
+        as the template's are."""
         if not self.is3D:
             raise NotImplementedError("MotionCorrect.detect_points is a 3-D function like apply_shifts_points; register 2-D "
                                       "videos as (T, X, Y, 1) with is3D=True")
+        image = kw.pop("image", "template")
+        from .dNMF import ExponentialFP
+        if not isinstance(image, str) or image != "template":
+            if isinstance(image, str):
+                if image not in ("corr", "max", "std"):
+                    raise ValueError(f"MotionCorrect.detect_points: image must be 'template', 'corr', 'max', 'std' or an (X, Y, Z) "
+                                     f"array, got {image!r}")
+                img = self.summary_images()[image]
+            else:
+                img = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
+                if img.ndim != 3:
+                    raise ValueError(f"MotionCorrect.detect_points: an image is (X, Y, Z), got {img.shape}")
+            img = np.array(img, dtype=np.float64)
+            finite = np.isfinite(img)
+            if not finite.any():
+                raise ValueError("MotionCorrect.detect_points: the image has no finite voxel")
+            img[~finite] = img[finite].min()
+            pos, _ = ExponentialFP.detect_positions(img, K, shape_std=shape_std, **kw)
+            return pos[np.isfinite(pos).all(1)].astype(np.float64)
         tmpl = getattr(self, "total_template_els", None)
         if tmpl is None:
             tmpl = getattr(self, "total_template_rig", None)
         if tmpl is None:
             raise ValueError("MotionCorrect.detect_points: no template yet, call motion_correct() first")
-        from .dNMF import ExponentialFP
         tmpl = tmpl if torch.is_tensor(tmpl) else np.asarray(tmpl)
         pos, _ = ExponentialFP.detect_positions(tmpl, K, shape_std=shape_std, **kw)
         pos = pos.cpu().numpy() if torch.is_tensor(pos) else pos

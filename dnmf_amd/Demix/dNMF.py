@@ -463,6 +463,19 @@ class ExponentialFP(nn.Module):
         return v.to(device, torch.float32).reshape(v.shape[0], -1).contiguous(), [int(n) for n in v.shape[1:]], on_gpu
 
     @staticmethod
+    def summary_images(video, neighbours='full'):
+        """The summary images of ``video`` -- (T, X, Y, Z) values, ``(rows (T, P), sz)`` or a ``ResidentLoader``, as
+        ``track_positions`` takes it: a dict ``mean / std / max / corr`` of (X, Y, Z) float64 images by K18
+        (``ops.summary_images``): per voxel the mean, the population std and the max over time, and the local correlation
+        image, the mean Pearson correlation of the voxel with its ``neighbours`` ('full': 26, 8 at Z = 1; 'face': 6 / 4).
+        The max, std and correlation images show neurons that are dim on average but active, which a mean image hides: the
+        usual seeds for ``detect_positions``.  A voxel without a neighbour of non-zero variance has corr = NaN; a voxel with
+        a sample that is not finite is NaN in all four.  numpy or CPU-torch in, numpy out; CUDA frames give CUDA tensors."""
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "summary_images")
+        images, _ = ops.summary_images(rows, sz, neighbours=neighbours)
+        return images if on_gpu else {k: v.cpu().numpy() for k, v in images.items()}
+
+    @staticmethod
     def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None):
         """Where the neurons are in every frame of ``video`` -- (T, X, Y, Z) values, or frames that already live on the GPU as
         ``(rows (T, P), sz)`` or a ``ResidentLoader``: ``(P_T (K,3,T) float64, amplitudes (K,T))`` by K15
@@ -769,6 +782,41 @@ class DeformableNMF:
         bad = self.fp.last_registered_bad
         self.last_registered_bad = None if bad is None else int(bad)
         return out
+
+    def summary_images(self, loader, source='video', registered=None, neighbours='full'):
+        """The summary images (``ExponentialFP.summary_images``, K18) of every frame ``loader`` serves: a dict ``mean / std /
+        max / corr`` of (X, Y, Z) float64 CUDA images.  ``source='residual'``: of Y - S_t with the model's reconstruction
+        S_t = A C_t (``fp.recon_image``) -- where a neuron the model has no component for shows, which is how one sees that
+        ``K`` was chosen too small; the kernel subtracts as it reads, no subtracted movie is made.  S_t lives in the
+        coordinates of the footprints: with ``registered='linear'`` (K17) or ``'nearest'`` (K7) the frames are first
+        registered to the footprint volume under the current ``fp.beta``, and the images are in the coordinates ``fp.A`` and
+        ``detect_positions`` use; with ``registered=None`` the frames are taken as they are, which for the residual is right
+        only where the warp is the identity.  The frames go through in pieces of at most 1 GiB."""
+        if source not in ('video', 'residual'):
+            raise ValueError(f"summary_images: source must be 'video' or 'residual', got {source!r}")
+        if registered is not None:
+            _check_registered(registered, "summary_images")
+        if self._nchan() != 1:
+            raise NotImplementedError("summary_images: one channel only")
+        fp = self.fp
+        sz = fp.sz_list
+        P = sz[0] * sz[1] * sz[2]
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            T = frames.shape[0]
+            step = max(1, min(T, (1 << 30) // (4 * P)))
+            C = self.C.to(device, torch.float32).contiguous() if source == 'residual' else None
+            state = images = None
+            for s in range(0, T, step):
+                fr, tt = frames[s:s + step], order[s:s + step]
+                sub = None
+                if C is not None:
+                    sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
+                if registered is not None:
+                    fr = fp.registered_video(fr, times=tt, interpolation=registered)
+                images, state = ops.summary_images(fr, sz, sub=sub, neighbours=neighbours, state=state, first=s == 0,
+                                                   finish=s + step >= T)
+        return images
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
                           live_spatial=False, iter_a=1, solver='mu', registered='nearest'):

@@ -96,6 +96,8 @@ SIGNATURES = {
     "dnmf_warp_normal_eqs": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "dnmf_lm_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp]),
     "dnmf_warp_pullback": (_i, [_vp, _l, _l, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _l, _i, C.c_float, _vp, _vp, _vp]),
+    "dnmf_summary_images_workspace": (_sz, [_vp, _i, _i, _i]),
+    "dnmf_summary_images": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

@@ -1200,6 +1200,70 @@ def track_neurons(frames, sz, predict, shape_std=3, search=(6, 6, 1), threshold=
     return positions, amplitudes, peaks
 
 
+NEIGHBOURS = {"face": 0, "full": 1}   # DNMF_NEIGHBOURS_* of include/dnmf_hip.h
+
+
+def summary_images_state(sz, B, neighbours='full', segment=0, device="cuda"):
+    """An empty state for ``summary_images`` calls of up to ``B`` frames each (a movie fed in pieces whose first is not the
+    largest); pass it with ``first=True``."""
+    if neighbours not in NEIGHBOURS:
+        raise ValueError(f"summary_images_state: neighbours must be 'face' or 'full', got {neighbours!r}")
+    lib = _lib.load()
+    need = lib.dnmf_summary_images_workspace(_int3(sz), NEIGHBOURS[neighbours], int(B), int(segment))
+    if need == 0:
+        raise _lib.DnmfHipError(f"dnmf_summary_images_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
+    return _workspace(None, need, device)
+
+
+def summary_images(frames, sz, sub=None, frame_ids=None, neighbours='full', state=None, first=True, finish=True, segment=0):
+    """K18.  frames (rows, ld >= X Y Z) fp32 CUDA rows -> ``(images, state)``: the summary images of the frames seen since
+    the state was reset -- ``images`` a dict ``mean / std / max / corr`` of float64 CUDA tensors (X, Y, Z) (None with
+    ``finish=False``): per voxel the mean, the population std and the max over time, and the local correlation image, the
+    mean Pearson correlation with the ``neighbours`` ('face': 6, 'full': 26; 4 / 8 at Z = 1) that exist, are finite in
+    every frame and have a variance > 0 (NaN without one; a voxel with a sample that is not finite is NaN in all four).
+    ``sub`` (B, ld >= X Y Z) fp32 CUDA rows: the images of ``frames - sub`` (row j of ``sub`` for the j-th frame of the call),
+    bit for bit those of the subtracted rows.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order).  A movie
+    larger than one buffer goes in several calls: ``first=True`` resets ``state`` (None: a new one), later calls pass the
+    returned ``state`` with ``first=False``, the last one ``finish=True``; a later call may not be larger than the first.
+    One pass, float64 sums, no atomics: the same input gives the same bits.  ``segment``: frames per workgroup (0: the
+    kernel's choice)."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if neighbours not in NEIGHBOURS:
+        raise ValueError(f"summary_images: neighbours must be 'face' or 'full', got {neighbours!r}")
+    _rows(frames, "summary_images", "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"summary_images: frames are rows (T, ld), got {tuple(frames.shape)}")
+    dev = frames.device
+    fid = _i32(frame_ids, dev) if frame_ids is not None else None
+    B = fid.numel() if fid is not None else frames.shape[0]
+    if sub is not None:
+        _rows(sub, "summary_images", "sub", P, f" and rows of {P} floats")
+        if sub.dim() != 2 or sub.shape[0] < B:
+            raise ValueError(f"summary_images: sub must hold one row for each of the {B} frames, got {tuple(sub.shape)}")
+    lib = _lib.load()
+    need = lib.dnmf_summary_images_workspace(_int3((X, Y, Z)), NEIGHBOURS[neighbours], B, int(segment))
+    if need == 0:
+        raise _lib.DnmfHipError(f"dnmf_summary_images_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
+    if first:
+        state = _workspace(state, need, dev)
+    elif state is None or _nbytes(state) < need:
+        raise ValueError(f"summary_images: first=False needs the state of the earlier calls, and one of at least {need} bytes "
+                         "(a later call may not be larger than the first)")
+    images = torch.empty((4, X, Y, Z), dtype=torch.float64, device=dev) if finish else None
+    # the row stride of a single row means nothing (a view through numpy's newaxis has 0)
+    ldf = frames.stride(0) if frames.shape[0] != 1 else max(frames.stride(0), P)
+    lds = 0 if sub is None else (sub.stride(0) if sub.shape[0] != 1 else max(sub.stride(0), P))
+    with _timed("summary_images"):
+        rc = lib.dnmf_summary_images(frames.data_ptr(), ldf, _ptr(sub), lds, _ptr(fid), _int3((X, Y, Z)), B, NEIGHBOURS[neighbours],
+                                     1 if first else 0, 1 if finish else 0, int(segment), state.data_ptr(), _nbytes(state),
+                                     _ptr(images), _stream())
+    _lib.check(rc, "dnmf_summary_images")
+    if not finish:
+        return None, state
+    return dict(mean=images[0], std=images[1], max=images[2], corr=images[3]), state
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -6,11 +6,16 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 MI355X.
 
     python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track] [--gn]
+                                      [--detect-image {template,corr,max,std}]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
 ground truth of frame 0; the model is built on the detected centres alone, as many neurons as were found.  The simulator's
 centres then serve only to judge the result: a detected centre is matched to the simulated neuron nearest to it in frame 0
 when that is within sigma (one centre per neuron), and the errors and correlations are taken over the matched ones.
+
+``--detect-image corr | max | std`` (implies ``--detect``): the centres come from that summary image of the corrected movie
+(``MotionCorrect.summary_images``, K18; the registration then keeps its movie, ``save_corrected=True``) instead of the template,
+which averages over time.  The same three numbers are printed for the chosen image.
 
 ``--track``: the initialiser's tracks are refined per neuron and frame by the tracker (``MotionCorrect.track_points``, K15: the
 peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
@@ -42,11 +47,15 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--detect", action="store_true", help="find the centres in the template instead of taking the simulator's")
+    ap.add_argument("--detect-image", choices=("template", "corr", "max", "std"), default=None,
+                    help="--detect on this image: the registration template or a summary image (K18) of the corrected movie")
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
     ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
     ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
+    a.detect = a.detect or a.detect_image is not None
+    image = a.detect_image or "template"
     torch.manual_seed(0)
     np.random.seed(0)
     K, T, sz = a.neurons, a.frames, torch.tensor([a.size, a.size, 2])
@@ -56,19 +65,19 @@ def main():
     truth = np.asarray(dataset.positions)                            # (K, 3, T)
     stride = a.stride
     mc = MotionCorrect(video, max_shifts=(12, 12, 1), strides=(stride, stride, 1), overlaps=(stride // 2, stride // 2, 1),
-                       max_deviation_rigid=3, is3D=True, pw_rigid=True)
+                       max_deviation_rigid=3, is3D=True, pw_rigid=True, save_corrected=image != "template")
     mc.motion_correct()                                              # template=None: rigid pass first
     # pts: the centres the tracks start from; sel / tr: rows of pts and the simulated neurons they are judged against
     if a.detect:
         shape_std = 3.0
-        pts = mc.detect_points(K, shape_std=shape_std)               # (n, 3), brightest first
+        pts = mc.detect_points(K, shape_std=shape_std, image=image)  # (n, 3), brightest first
         d = np.linalg.norm(pts[:, None, :2] - truth[None, :, :2, 0], axis=2)     # in the plane, like the errors below
         nearest = d.argmin(1)
         sel = np.array([j for j in range(len(pts)) if d[j, nearest[j]] <= shape_std and j == d[:, nearest[j]].argmin()], dtype=int)
         tr = nearest[sel]
         if len(sel) == 0:
-            raise SystemExit(f"detect_points: {len(pts)} centres, none within {shape_std:g} voxels of a simulated neuron")
-        print(f"detect_points: {len(pts)} centres; {len(sel)} of the simulator's {K} neurons have one within "
+            raise SystemExit(f"detect_points (image={image!r}): {len(pts)} centres, none within {shape_std:g} voxels of a simulated neuron")
+        print(f"detect_points (image={image!r}): {len(pts)} centres; {len(sel)} of the simulator's {K} neurons have one within "
               f"{shape_std:g} voxels, mean distance of those {d[sel, tr].mean():.2f} voxels")
     else:
         pts, sel, tr = truth[:, :, 0], np.arange(K), np.arange(K)

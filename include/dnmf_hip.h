@@ -640,6 +640,38 @@ int dnmf_warp_pullback(const float *frames, long ldf, long ldc_in, int nchan, co
                        const float *beta, int T, const int *times, int B, float *out, long ldo, long ldc_out, int fill_mode,
                        float fill_value, float *coords, long long *bad_count, dnmf_stream_t stream);
 
+/* ---- K18: summary images of a video: mean, std, max over time and the local correlation image -----------------------------
+ * For B frames x[t, p] of a volume (X, Y, Z) (rows of ldf >= P floats, voxel p = (x Y + y) Z + z; row frame_ids[j] of frames, or j,
+ * for the j-th frame of the call) and, with sub, x = frames - sub rounded to fp32 (row j of sub, lds >= P floats: the result equals,
+ * bit for bit, the call on explicitly subtracted rows).  tests/summary_restatement.py is the definition in float64.  Per voxel,
+ * over every frame since the state was reset:
+ *   mean, std (population, ddof = 0), max;
+ *   corr     the mean, over the valid neighbours q of p, of the Pearson correlation of the two time series.  DNMF_NEIGHBOURS_FACE:
+ *            the voxels that differ by 1 on one axis (6; 4 at Z == 1), DNMF_NEIGHBOURS_FULL: by at most 1 on every axis (26; 8).
+ *            No padding and no wrap: a neighbour outside the volume does not exist, an axis of one voxel has none.  A pair is valid
+ *            when both voxels are finite in every frame and both variances are > 0; a voxel without a valid pair gets NaN.
+ *   A voxel with a sample that is not finite is NaN in all four images and is nobody's neighbour.
+ * One pass in float64 on d = x - x0, x0 the voxel's value in the first frame after the reset (exact in float64, so a constant voxel
+ * has a variance of exactly 0): sum d, sum d^2 and sum d_p d_q for the half-set of directions (13 full, 3 face; 4 and 2 at Z == 1);
+ * var = max(0, (sum d^2 - (sum d)^2 / T) / T).  A workgroup owns a tile of voxels (staged with a one-voxel halo in LDS) and a
+ * segment of frames (segment > 0: that many frames each; 0: the kernel's choice, enough segments to fill the machine); a second
+ * launch adds the segments to the state in a fixed order -- no floating-point atomics, the same input gives the same bits.
+ *   state    caller-owned, 8-byte aligned, dnmf_summary_images_workspace(sz, neighbours, B, segment) bytes (0 on bad arguments; it
+ *            does not decrease with B, so the size for the largest call serves every call): the frame count, the sums, the max, the
+ *            pivot x0, and the partial sums of the segments of one call.  first != 0 resets it; a movie larger than one buffer is
+ *            fed in several calls with the same sz and neighbours.
+ *   finish   != 0: a third launch writes images (4, P) float64: mean, std, max, corr.
+ * No host synchronisation: the frame count lives in the state.
+ * DNMF_E_NULL: frames, sz or state NULL, images NULL with finish;  DNMF_E_SHAPE: a size or B < 1, an unknown neighbourhood,
+ * segment < 0, ldf or lds < P;  DNMF_E_UNSUPPORTED: 2^31 voxels or more, Z > 137 (LDS), more than 65535 segments;
+ * DNMF_E_WORKSPACE: a short or misaligned state.  Nothing is launched on an error. */
+#define DNMF_NEIGHBOURS_FACE 0
+#define DNMF_NEIGHBOURS_FULL 1
+size_t dnmf_summary_images_workspace(const int *sz, int neighbours, int B, int segment);
+int dnmf_summary_images(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const int *sz, int B,
+                        int neighbours, int first, int finish, int segment, void *state, size_t state_bytes, double *images,
+                        dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
