@@ -559,8 +559,13 @@ class DeformableNMF:
         # 512x512x4000): same results bit for bit, same speed within 2 % from 128 frames on (the hoped-for gain from
         # images that stay in the Infinity Cache did not materialise), so it is a memory option; 0 = all frames at once
         self.motion_chunk = 0
+        # weight of the temporal smoothness prior of update_motion(solver='gn') (K16s, see _update_motion_gn): mean squared
+        # error per squared voxel of frame-to-frame change of a warp coefficient.  0 = none, every frame fitted on its own.  An
+        # attribute like motion_chunk, not a parameter: update_motion keeps the parameter list it had
+        self.motion_smooth = 0.0
         self._stage_buf = None     # device copy of the frames a host loader served in its last pass
-        # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam (CUDA tensors, (T,)); else None
+        # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam -- and prior when smooth > 0 -- (CUDA
+        # tensors, (T,)); else None
         self.last_motion_gn = None
         self._reg_buf = None       # registered frames (K7 / K17) of the last update_footprints(live_spatial=True)
         self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
@@ -1109,15 +1114,19 @@ class DeformableNMF:
         ``solver='gn'`` (not in the reference) fits every frame's warp by damped Gauss-Newton steps instead
         (``_update_motion_gn``: K16 + ``dnmf_lm_step``): no learning rate, ``optimizer`` may be None and is left untouched,
         ``iters`` (default ``epochs``) Levenberg-Marquardt iterations per frame starting at the damping ``damping``; ``gamma``
-        is ignored, as the reference's gradient-free reg term is.
+        is ignored, as the reference's gradient-free reg term is.  ``self.motion_smooth`` > 0 (``solver='gn'`` only; with any
+        other solver, or negative or not finite, a ValueError) adds the temporal prior ``motion_smooth`` * sum_t |theta_t -
+        theta_{t+1}|^2 to the mean squared error (K16s, see ``_update_motion_gn``): a frame whose neurons are dark is then
+        carried by its neighbours in time instead of keeping its start.
 
         A ``ResidentLoader`` hands over rows that already live on the GPU.  Any other loader (the stock
         ``torch.utils.data.DataLoader`` of demo.py:33-35) is iterated once per epoch by a background thread while this
         thread copies the mini-batches into a device buffer (``_stage_epoch``); the epoch then runs from that buffer --
         as four launches when the optimiser is the demo's plain Adam (``_motion_epoch``), else step by step."""
         _check_motion_solver(solver, "update_motion")
+        smooth = _check_motion_smooth(self.motion_smooth, solver, "update_motion")
         if solver == 'gn':
-            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma)
+            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma, smooth)
         fp = self.fp
         beta = fp.beta
         # reconstruction images of all frames (C is constant inside this call): built when first needed -- the fused
@@ -1178,7 +1187,7 @@ class DeformableNMF:
                     print('Recon: ' + str(out["loss"][0]))
                     print('Reg: ' + str(out["reg"]))
 
-    def _update_motion_gn(self, dataloader, iters, damping, gamma=0):
+    def _update_motion_gn(self, dataloader, iters, damping, gamma=0, smooth=0.0):
         """``update_motion(solver='gn')``: Levenberg-Marquardt on the 30 (12 at Z = 1) coefficients of every frame.
 
         The loss is a sum over frames and frame t only sees ``beta[:, :, t]``, so the frames are independent small dense
@@ -1194,7 +1203,36 @@ class DeformableNMF:
         ``fp.beta`` is updated in place (``requires_grad`` kept, ``.grad`` left alone).  Afterwards ``last_motion_gn`` holds,
         per frame of the model (NaN / 0 for frames the loader did not serve), ``sse0`` and ``sse`` (squared error at the
         start and at the result), ``accepted`` / ``rejected`` step counts and the final damping ``lam``.  With the T axis
-        sharded over ranks every rank fits its own frames: there is no collective and nothing to exchange."""
+        sharded over ranks every rank fits its own frames: there is no collective and nothing to exchange.
+
+        ``smooth`` (the model's ``motion_smooth``) > 0 (K16s, ``dnmf_lm_step_smooth``; tests/gn_smooth_restatement.py is the
+        definition).  With theta_t the 30 (12) coefficients of frame t in K16's centred basis -- its monomials are O(1) over the
+        volume, so theta is in voxels -- n the residuals of a frame (voxels x colour channels) and m = ``smooth`` n, the
+        objective becomes
+            F(beta) = sum_t sse_t + m sum_t |theta_t - theta_{t+1}|^2,
+        F / n = mse + ``smooth`` * roughness: ``smooth`` is the mean squared error one is willing to pay per squared voxel of
+        frame-to-frame change of a coefficient.  It is lowered by red-black block coordinate descent: ``beta_ref``, a copy of
+        ``fp.beta`` made at entry, holds every frame's ACCEPTED coefficients; inside an iteration the chunk's frames of even t
+        take K16 + step, then those of odd t, each reading its neighbours t +- 1 from ``beta_ref`` (never from ``fp.beta``,
+        which holds untested trials between steps).  Same-colour frames do not interact, so every accepted step lowers F.
+        The work per iteration is the same in twice the launches; a chunk's images are still built once.  A frame with
+        H = 0 (dark neurons) takes a damped step to its neighbours' mean.  ``last_motion_gn`` gains ``prior``: per frame m
+        sum_s |theta_t - theta_s|^2 of the result against its neighbours (NaN for frames not served); ``sse0`` / ``sse``
+        stay the data term alone.
+        * A chunk's boundary frames see what the neighbouring chunk currently holds in ``beta_ref`` -- its start values if
+          that chunk comes later -- so ONE CALL carries information across a chunk boundary only once, and only forward;
+          a mini-batch of a non-stageable loader is a chunk in this sense.  Call again (or raise ``motion_chunk``) when
+          dark stretches span chunk boundaries.
+        * With T sharded over ranks a shard's first and last frame treat the off-shard neighbour as absent; there is still
+          no collective.
+        * BIAS.  The prior is first order: it pulls a warp that moves linearly in time toward a constant one.  Float64
+          definition, 7 frames, true warp linear in t, C[:, 3] = 0, identity start, 8 iterations, largest distance (voxels)
+          between fitted and true warp per frame t = 0 .. 6:
+              24x20x1  smooth 0     0      0      0      0.512  0      0      0
+              24x20x1  smooth 1e-4  0.007  0.006  0.012  0.027  0.015  0.011  0.010
+              24x20x2  smooth 0     0      0      0      0.402  0      0      0
+              24x20x2  smooth 1e-4  0.017  0.013  0.017  0.030  0.028  0.024  0.023
+          (0: below 5e-5).  At ``smooth`` = 1e-3 / 1e-2 every frame is 0.04 - 0.12 / 0.14 - 0.26 voxel off."""
         fp = self.fp
         iters = int(iters)
         if iters < 0:
@@ -1213,10 +1251,15 @@ class DeformableNMF:
                  "accepted": torch.zeros((fp.T,), dtype=torch.int32, device=device),
                  "rejected": torch.zeros((fp.T,), dtype=torch.int32, device=device),
                  "lam": torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)}
+        beta_ref = None
+        if smooth:
+            stats["prior"] = torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)
+            beta_ref = beta.clone()      # every frame's accepted coefficients: the neighbours a step reads
         bufs = {}
 
-        def fit(frames, fid, times):
-            """All iterations of the frames ``times`` (distinct; frame ``times[i]`` in row ``fid[i]``, None: row i)."""
+        def fit(frames, fid, times, host_times):
+            """All iterations of the frames ``times`` (distinct; frame ``times[i]`` in row ``fid[i]``, None: row i);
+            ``host_times``: the same list on the CPU (the colours are split there: no synchronisation)."""
             for s0 in range(0, times.numel(), chunk):
                 tt = times[s0:s0 + chunk].contiguous()
                 n = tt.numel()
@@ -1225,19 +1268,36 @@ class DeformableNMF:
                 if "S" not in bufs or bufs["S"][0].shape[0] < n:
                     bufs["S"] = [torch.empty((n, lds), dtype=torch.float32, device=device) for _ in chans]
                 S = [f.recon_image(Cdev, tt, out=buf[:n]) for (f, _), buf in zip(chans, bufs["S"])]
-                state = ops.lm_state(n, device)
-                eqs = None
+                # colours: [rows of S, rows of fr, model times, state, normal equations]; one colour of all frames without the
+                # prior, else the frames of even t and those of odd t (each a launch of pairwise non-adjacent frames)
+                colours = [[None, ff, tt, ops.lm_state(n, device), None]]
+                if smooth:
+                    colours = []
+                    th = host_times[s0:s0 + chunk]
+                    for parity in (0, 1):
+                        pick = torch.nonzero(th % 2 == parity).reshape(-1)          # CPU
+                        if pick.numel():
+                            sel, pick = pick.to(device, torch.int32), pick.to(device)
+                            colours.append([sel, sel if ff is None else ff[pick].contiguous(), tt[pick].contiguous(),
+                                            ops.lm_state(pick.numel(), device), None])
                 for it in range(iters + 1):
-                    for c, ((f, cols), Sc) in enumerate(zip(chans, S)):
-                        eqs = ops.warp_normal_eqs(Sc, None, fr if cols is None else fr[:, cols], ff, fp.sz_list, beta, tt,
-                                                  out=eqs, accumulate=c > 0, workspace=bufs.get("ws"))
-                        bufs["ws"] = eqs["workspace"]
-                    ops.lm_step(state, eqs, fp.sz_list, beta, tt, lam0=damping, accept_only=it == iters)
-                idx = tt.long()
-                stats["sse0"][idx], stats["sse"][idx], stats["lam"][idx] = state["sse0"], state["sse"], state["lam"]
-                stats["accepted"][idx], stats["rejected"][idx] = state["counts"][:, 0], state["counts"][:, 1]
-                if self.verbose:
-                    print(f"GN frames {int(tt[0])}..: sse {float(state['sse0'].sum()):.6g} -> {float(state['sse'].sum()):.6g}")
+                    for col in colours:
+                        sel, cf, ct, state, eqs = col
+                        for c, ((f, cols), Sc) in enumerate(zip(chans, S)):
+                            eqs = ops.warp_normal_eqs(Sc, sel, fr if cols is None else fr[:, cols], cf, fp.sz_list, beta, ct,
+                                                      out=eqs, accumulate=c > 0, workspace=bufs.get("ws"))
+                            bufs["ws"] = eqs["workspace"]
+                        col[4] = eqs
+                        ops.lm_step(state, eqs, fp.sz_list, beta, ct, lam0=damping, accept_only=it == iters, smooth=smooth,
+                                    n_residuals=row, beta_ref=beta_ref)
+                for _, _, ct, state, _ in colours:
+                    idx = ct.long()
+                    stats["sse0"][idx], stats["sse"][idx], stats["lam"][idx] = state["sse0"], state["sse"], state["lam"]
+                    stats["accepted"][idx], stats["rejected"][idx] = state["counts"][:, 0], state["counts"][:, 1]
+                    if smooth:
+                        stats["prior"][idx] = state["prior"]
+                    if self.verbose:
+                        print(f"GN frames {int(ct[0])}..: sse {float(state['sse0'].sum()):.6g} -> {float(state['sse'].sum()):.6g}")
 
         with torch.no_grad():
             staged = None
@@ -1254,11 +1314,12 @@ class DeformableNMF:
                 rows = torch.zeros(fp.T, dtype=torch.int64)
                 rows[flat] = flat if by_frame else torch.arange(flat.numel(), dtype=torch.int64)
                 times = torch.unique(flat)
-                fit(frames, rows[times].to(device, torch.int32), times.to(device, torch.int32))
+                fit(frames, rows[times].to(device, torch.int32), times.to(device, torch.int32), times)
             else:
                 for data in dataloader:
                     times = torch.as_tensor(data[1]).to(device, torch.int32).reshape(-1)
-                    fit(data[0].to(device, torch.float32).reshape(times.numel(), -1), None, times)
+                    fit(data[0].to(device, torch.float32).reshape(times.numel(), -1), None, times,
+                        torch.as_tensor(data[1]).reshape(-1).to("cpu", torch.int64) if smooth else None)
         self.last_motion_gn = stats
 
     def _motion_epoch_from_host(self, dataloader, optimizer, S_all, Cdev):
@@ -1415,18 +1476,26 @@ class DeformableNMF:
                 print('Reg: ' + str(out["reg"][j * nf:(j + 1) * nf]))
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
-            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest'):
+            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
-        Gauss-Newton, ``optimizer`` may then be None); ``registered`` is ``update_footprints``' (``'linear'``: K17)."""
+        Gauss-Newton, ``optimizer`` may then be None) and ``motion_smooth`` the temporal prior's weight for the calls made
+        here (``'gn'`` only; None: the model's ``motion_smooth``, 0 unless set; the attribute is put back afterwards);
+        ``registered`` is ``update_footprints``' (``'linear'``: K17)."""
         _check_motion_solver(motion_solver, "fit")
+        kept = self.motion_smooth
+        motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
         _check_registered(registered, "fit")
         out = (None, None, None)
-        for _ in range(outer):
-            self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
-            out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
-                                         iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
+        self.motion_smooth = motion_smooth
+        try:
+            for _ in range(outer):
+                self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
+                out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
+                                             iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
+        finally:
+            self.motion_smooth = kept
         return out
 
 
@@ -1562,6 +1631,17 @@ def _check_registered(registered, who):
 def _check_motion_solver(solver, who):
     if solver not in ('adam', 'gn'):
         raise ValueError(f"{who}: motion solver must be 'adam' or 'gn', got {solver!r}")
+
+
+def _check_motion_smooth(smooth, solver, who):
+    """The temporal prior's weight as a float: finite, >= 0, and non-zero only with the Gauss-Newton solver."""
+    smooth = float(smooth)
+    if not 0.0 <= smooth < float('inf'):
+        raise ValueError(f"{who}: motion_smooth={smooth}: the temporal prior's weight must be finite and >= 0")
+    if smooth and solver != 'gn':
+        raise ValueError(f"{who}: motion_smooth={smooth} is supported by the motion solver 'gn' only (got {solver!r}); "
+                         "Adam steps on the reference's loss, which has no temporal term")
+    return smooth
 
 
 def _hals_refuse_shards(gamma, group):

@@ -277,69 +277,50 @@ __global__ __launch_bounds__(256) void warp_normal_eqs_finish_kernel(const float
 }
 
 // ---- the Levenberg-Marquardt step ----------------------------------------------------------------------------------
-// One wave per frame, float64, everything on the device.  State of frame b: the accepted coefficients beta_acc (30 floats,
-// [a*3+d]), their H / g / sse, the damping lam, sse0 (the first evaluation) and counts = (accepted, rejected, initialised).
-// The trial coefficients live in beta (10,3,T) at column times[b], where K16 reads them.
-__global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ H, const double *__restrict__ g,
-                                                     const double *__restrict__ sse, int nact, const double *__restrict__ M,
-                                                     float *__restrict__ beta, int T, const int *__restrict__ times,
-                                                     double *__restrict__ Hacc, double *__restrict__ gacc,
-                                                     double *__restrict__ sse_acc, double *__restrict__ sse0,
-                                                     double *__restrict__ lam, float *__restrict__ beta_acc,
-                                                     int *__restrict__ counts, double nu, double lam0, double lam_min,
-                                                     double lam_max, int accept_only) {
+// active unknowns: all 30, or at Z == 1 the 12 without z: lm_act(nact, i) = parameter index of the i-th
+__device__ __forceinline__ int lm_act(int nact, int i) {
+    if (nact == 30) return i;
+    constexpr int AZ[6] = {0, 1, 2, 4, 5, 7};
+    return AZ[i >> 1] * 3 + (i & 1);
+}
+
+// The damped solve both step kernels end with, by the one wave of the block (all 64 threads call it, after a barrier that
+// follows the last write of Ha / ga / bacc):  (H' + l diag(H') + tiny I) delta = -g' on the active unknowns, scaled to a unit
+// diagonal, float64 Cholesky, two triangular solves, d beta = M delta, beta[:, :, t] = fp32(bacc + d beta).  H' = Ha, g' = ga;
+// with PRIOR, H' = Ha + hadd I and g' = ga + gadd (gadd: 30 doubles in LDS by parameter index) on the active unknowns.
+// Ha, ga and bacc are the state the calling kernel has just written: plain pointers, nothing here may be read as invariant.
+template <bool PRIOR>
+__device__ void lm_damped_solve(const double *Ha, const double *ga, double l, int nact, const double *__restrict__ M,
+                                const float *bacc, float *beta, int T, int t, double hadd, const double *gadd) {
     __shared__ double A[30][31];
     __shared__ double rhs[30], sc[30], dl[30];
     __shared__ int okflag;
-    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
-    const bool first = counts[b * 3 + 2] == 0;
-    const double st = sse[b], sa = sse_acc[b];
-    const bool accept = first || (st - st == 0.0 && st < sa);   // finite and below
-    double l = first ? lam0 : lam[b];
-    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
-    __syncthreads();   // every thread has read the state before it changes
-    if (accept) {
-        for (int i = j; i < 900; i += 64) Hacc[(long)b * 900 + i] = H[(long)b * 900 + i];
-        if (j < 30) {
-            gacc[b * 30 + j] = g[b * 30 + j];
-            beta_acc[b * 30 + j] = beta[(long)j * T + t];
-        }
-    }
-    if (j == 0) {
-        lam[b] = l;
-        if (accept) sse_acc[b] = st;
-        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
-        else counts[b * 3 + (accept ? 0 : 1)] += 1;
-    }
-    __syncthreads();
-    if (accept_only) {
-        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
-        return;
-    }
-    // active unknowns: all 30, or at Z == 1 the 12 without z: act(i) = parameter index of the i-th
-    auto act = [nact](int i) {
-        if (nact == 30) return i;
-        constexpr int AZ[6] = {0, 1, 2, 4, 5, 7};
-        return AZ[i >> 1] * 3 + (i & 1);
+    const int j = threadIdx.x;
+    auto act = [nact](int i) { return lm_act(nact, i); };
+    auto diag = [&](int i) {
+        if constexpr (PRIOR) return Ha[act(i) * 31] + hadd;
+        else return Ha[act(i) * 31];
     };
-    const double *Ha = Hacc + (long)b * 900;
     if (j == 0) okflag = 1;
     double hmax = 0.0;
-    for (int i = 0; i < nact; ++i) hmax = fmax(hmax, Ha[act(i) * 31]);
+    for (int i = 0; i < nact; ++i) hmax = fmax(hmax, diag(i));
     const double tiny = 1e-12 * hmax + 1e-30;
     // (H + lam diag(H) + tiny I) delta = -g, scaled to a unit diagonal: sc = 1 / sqrt(diagonal)
     if (j < nact) {
-        const double dd = Ha[act(j) * 31] * (1.0 + l) + tiny;
+        const double dd = diag(j) * (1.0 + l) + tiny;
         sc[j] = 1.0 / sqrt(dd);
     }
     __syncthreads();
     if (j < nact) {
         for (int c = 0; c < nact; ++c) {
             double v = Ha[act(j) * 30 + act(c)];
+            if constexpr (PRIOR)
+                if (c == j) v += hadd;
             if (c == j) v = v * (1.0 + l) + tiny;
             A[j][c] = v * sc[j] * sc[c];
         }
-        rhs[j] = -gacc[b * 30 + act(j)] * sc[j];
+        if constexpr (PRIOR) rhs[j] = -(ga[act(j)] + gadd[act(j)]) * sc[j];
+        else rhs[j] = -ga[act(j)] * sc[j];
     }
     __syncthreads();
     // Cholesky A = L L^T in place (lower triangle), row j owned by thread j
@@ -379,8 +360,140 @@ __global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ 
         const int a = j / 3, d = j - a * 3;
         double db = 0.0;
         for (int c = 0; c < 10; ++c) db += M[a * 10 + c] * dl[c * 3 + d];
-        beta[(long)j * T + t] = (float)((double)beta_acc[b * 30 + j] + db);
+        beta[(long)j * T + t] = (float)((double)bacc[j] + db);
     }
+}
+
+// One wave per frame, float64, everything on the device.  State of frame b: the accepted coefficients beta_acc (30 floats,
+// [a*3+d]), their H / g / sse, the damping lam, sse0 (the first evaluation) and counts = (accepted, rejected, initialised).
+// The trial coefficients live in beta (10,3,T) at column times[b], where K16 reads them.
+__global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ H, const double *__restrict__ g,
+                                                     const double *__restrict__ sse, int nact, const double *__restrict__ M,
+                                                     float *__restrict__ beta, int T, const int *__restrict__ times,
+                                                     double *__restrict__ Hacc, double *__restrict__ gacc,
+                                                     double *__restrict__ sse_acc, double *__restrict__ sse0,
+                                                     double *__restrict__ lam, float *__restrict__ beta_acc,
+                                                     int *__restrict__ counts, double nu, double lam0, double lam_min,
+                                                     double lam_max, int accept_only) {
+    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
+    const bool first = counts[b * 3 + 2] == 0;
+    const double st = sse[b], sa = sse_acc[b];
+    const bool accept = first || (st - st == 0.0 && st < sa);   // finite and below
+    double l = first ? lam0 : lam[b];
+    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
+    __syncthreads();   // every thread has read the state before it changes
+    if (accept) {
+        for (int i = j; i < 900; i += 64) Hacc[(long)b * 900 + i] = H[(long)b * 900 + i];
+        if (j < 30) {
+            gacc[b * 30 + j] = g[b * 30 + j];
+            beta_acc[b * 30 + j] = beta[(long)j * T + t];
+        }
+    }
+    if (j == 0) {
+        lam[b] = l;
+        if (accept) sse_acc[b] = st;
+        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
+        else counts[b * 3 + (accept ? 0 : 1)] += 1;
+    }
+    __syncthreads();
+    if (accept_only) {
+        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+        return;
+    }
+    lm_damped_solve<false>(Hacc + (long)b * 900, gacc + b * 30, l, nact, M, beta_acc + b * 30, beta, T, t, 0.0, nullptr);
+}
+
+// K16s: the step with the temporal prior m sum_{s in N_t} |theta_t - theta_s|^2, theta = Minv beta per coordinate on the active
+// unknowns, N_t = the frames t +- 1 inside [0, T) whose column of beta_ref (every frame's ACCEPTED coefficients) is finite.
+// Both sides of the accept test carry their prior against the CURRENT beta_ref; on accept the trial's column goes to beta_ref.
+// A neighbour's theta is 10 x 10 x (2 or 3) FMAs from its fp32 column: computed here, kept in LDS, never stored.  The frames of
+// a launch are pairwise non-adjacent (the caller's contract): no block reads a column another block writes.
+__global__ __launch_bounds__(64) void lm_step_smooth_kernel(const double *__restrict__ H, const double *__restrict__ g,
+                                                            const double *__restrict__ sse, int nact,
+                                                            const double *__restrict__ M, const double *__restrict__ Minv,
+                                                            float *__restrict__ beta, int T, const int *__restrict__ times,
+                                                            double *__restrict__ Hacc, double *__restrict__ gacc,
+                                                            double *__restrict__ sse_acc, double *__restrict__ sse0,
+                                                            double *__restrict__ lam, float *__restrict__ beta_acc,
+                                                            int *__restrict__ counts, double nu, double lam0, double lam_min,
+                                                            double lam_max, int accept_only, float *beta_ref, double m,
+                                                            double *__restrict__ prior) {
+    __shared__ double thn[2][30];       // theta of the neighbours in use
+    __shared__ double sq[2][30];        // squared distances to them: [0] of the trial, [1] of the accepted point
+    __shared__ double gadd[30];
+    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
+    const int a = j / 3, d = j - a * 3;
+    const bool unknown = j < 30 && (nact == 30 || (GN_EZ[a] == 0 && d < 2));
+    const bool first = counts[b * 3 + 2] == 0;
+    // theta of a column held with stride ld between its 30 entries; exact zero on an inactive unknown
+    auto theta = [&](const float *col, long ld) {
+        double v = 0.0;
+        if (unknown)
+            for (int c = 0; c < 10; ++c) v = fma(Minv[a * 10 + c], (double)col[(long)(c * 3 + d) * ld], v);
+        return v;
+    };
+    int nn = 0;                         // block-uniform
+    if (m != 0.0) {
+        for (int side = -1; side <= 1; side += 2) {
+            const int s = t + side;
+            if (s < 0 || s >= T) continue;
+            const float v = j < 30 ? beta_ref[(long)j * T + s] : 0.0f;
+            if (!__all(v - v == 0.0f)) continue;    // a column with a NaN or an inf is no neighbour
+            if (j < 30) thn[nn][j] = theta(beta_ref + s, T);
+            ++nn;
+        }
+    }
+    const double th_trial = theta(beta + t, T);
+    const double th_old = first ? 0.0 : theta(beta_acc + b * 30, 1);
+    __syncthreads();
+    if (j < 30) {
+        double qt = 0.0, qa = 0.0;
+        for (int i = 0; i < nn; ++i) {
+            const double dt = th_trial - thn[i][j], da = th_old - thn[i][j];
+            qt += dt * dt, qa += da * da;
+        }
+        sq[0][j] = qt, sq[1][j] = qa;
+    }
+    __syncthreads();
+    double p_trial = 0.0, p_acc = 0.0;
+    if (nn > 0) {                       // every thread adds the 30 terms in the same order: one value in the whole wave
+        for (int i = 0; i < 30; ++i) p_trial += sq[0][i], p_acc += sq[1][i];
+        p_trial *= m, p_acc *= m;
+    }
+    const double st = sse[b], sa = sse_acc[b];
+    const double ft = st + p_trial, fa = sa + p_acc;
+    const bool accept = first || (ft - ft == 0.0 && ft < fa);   // finite and below
+    double l = first ? lam0 : lam[b];
+    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
+    __syncthreads();   // every thread has read the state before it changes
+    if (accept) {
+        for (int i = j; i < 900; i += 64) Hacc[(long)b * 900 + i] = H[(long)b * 900 + i];
+        if (j < 30) {
+            const float bt = beta[(long)j * T + t];
+            gacc[b * 30 + j] = g[b * 30 + j];
+            beta_acc[b * 30 + j] = bt;
+            beta_ref[(long)j * T + t] = bt;
+        }
+    }
+    if (j < 30) {
+        const double th = accept ? th_trial : th_old;
+        double ga = 0.0;
+        for (int i = 0; i < nn; ++i) ga += th - thn[i][j];
+        gadd[j] = m * ga;
+    }
+    if (j == 0) {
+        lam[b] = l;
+        prior[b] = accept ? p_trial : p_acc;
+        if (accept) sse_acc[b] = st;
+        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
+        else counts[b * 3 + (accept ? 0 : 1)] += 1;
+    }
+    __syncthreads();
+    if (accept_only) {
+        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+        return;
+    }
+    lm_damped_solve<true>(Hacc + (long)b * 900, gacc + b * 30, l, nact, M, beta_acc + b * 30, beta, T, t, m * (double)nn, gadd);
 }
 
 }  // namespace dnmf
@@ -450,6 +563,26 @@ int dnmf_lm_step(const double *H, const double *g, const double *sse, int B, int
     hipLaunchKernelGGL(lm_step_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, H, g, sse, Z > 1 ? 30 : 12, M, beta, T,
                        times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max, accept_only);
     return check_launch("dnmf_lm_step");
+}
+
+int dnmf_lm_step_smooth(const double *H, const double *g, const double *sse, int B, int Z, const double *M, const double *Minv,
+                        float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0,
+                        double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min, double lam_max,
+                        int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(H && g && sse && M && Minv && beta && times && H_acc && g_acc && sse_acc && sse0 && lam && beta_acc && counts &&
+                     beta_ref && prior,
+                 DNMF_E_NULL, "dnmf_lm_step_smooth: NULL buffer");
+    DNMF_REQUIRE(B > 0 && Z > 0 && T > 0, DNMF_E_SHAPE, "dnmf_lm_step_smooth: B=%d Z=%d T=%d", B, Z, T);
+    DNMF_REQUIRE(nu > 1.0 && lam0 > 0.0 && lam_min > 0.0 && lam_max >= lam_min, DNMF_E_SHAPE,
+                 "dnmf_lm_step_smooth: nu=%g lam0=%g lam_min=%g lam_max=%g (want nu > 1, 0 < lam_min <= lam_max, lam0 > 0)", nu,
+                 lam0, lam_min, lam_max);
+    DNMF_REQUIRE(m >= 0.0 && m - m == 0.0, DNMF_E_SHAPE, "dnmf_lm_step_smooth: m=%g (want a finite weight >= 0)", m);
+    DNMF_REQUIRE(beta_ref != beta, DNMF_E_SHAPE, "dnmf_lm_step_smooth: beta_ref must not be beta (it holds accepted points only)");
+    hipLaunchKernelGGL(lm_step_smooth_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, H, g, sse, Z > 1 ? 30 : 12, M,
+                       Minv, beta, T, times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max,
+                       accept_only, beta_ref, m, prior);
+    return check_launch("dnmf_lm_step_smooth");
 }
 
 }  // extern "C"

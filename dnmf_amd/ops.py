@@ -286,6 +286,17 @@ def centred_basis_matrix(sz):
     return M
 
 
+def centred_basis_inverse(sz):
+    """Minv (10,10) float64 numpy: the inverse of ``centred_basis_matrix(sz)`` on the active monomials (all 10; the 6 without z
+    at Z = 1, where M itself is singular), zeros elsewhere: coefficients ``beta`` -> coefficients of the centred basis."""
+    import numpy as np
+    M = centred_basis_matrix(sz)
+    rows = [a for a in range(10) if int(sz[2]) > 1 or a not in (3, 6, 8, 9)]
+    Minv = np.zeros((10, 10), dtype=np.float64)
+    Minv[np.ix_(rows, rows)] = np.linalg.inv(M[np.ix_(rows, rows)])
+    return Minv
+
+
 def lm_state(B: int, dev):
     """The per-frame state ``lm_step`` keeps for ``B`` frames (``include/dnmf_hip.h``); only ``counts`` needs its zeros."""
     f64 = dict(dtype=torch.float64, device=dev)
@@ -298,13 +309,39 @@ def lm_state(B: int, dev):
 _CENTRED_M = {}
 
 
-def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_max=1e9, accept_only=False):
+def _centred(sz, dev):
+    """(M, Minv) of the volume on ``dev``, made once."""
+    key = (tuple(int(s) for s in sz), str(dev))
+    if key not in _CENTRED_M:
+        _CENTRED_M[key] = (torch.from_numpy(centred_basis_matrix(sz)).to(dev), torch.from_numpy(centred_basis_inverse(sz)).to(dev))
+    return _CENTRED_M[key]
+
+
+def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_max=1e9, accept_only=False, smooth=0.0,
+            n_residuals=None, beta_ref=None):
     """One Levenberg-Marquardt step per frame on the device (``dnmf_lm_step``).  ``eqs``: ``warp_normal_eqs``' result at the
     trial coefficients ``beta[:, :, times]``; ``state``: ``lm_state(B, device)``.  The trial is accepted when its sse is finite
     and below the accepted one (always on a frame's first call), ``beta[:, :, times]`` then receives the next trial -- or, with
-    ``accept_only``, the best accepted coefficients.  Returns ``state``."""
+    ``accept_only``, the best accepted coefficients.  Returns ``state``.
+
+    ``smooth`` != 0: the step with the temporal prior (``dnmf_lm_step_smooth``), weight m = ``smooth`` * ``n_residuals`` (default:
+    the voxels of ``sz``; pass voxels x colour channels).  ``beta_ref`` (10,3,T) fp32 holds every frame's accepted coefficients:
+    read at t +- 1, written at t on accept, never ``beta`` itself.  ``state`` gains ``prior`` (B) float64.  The frames of one call
+    must be pairwise non-adjacent; a ``times`` given as a host sequence is checked, a device tensor is the caller's word."""
     dev = beta.device
     _f32(beta, "beta")
+    smooth = float(smooth)
+    if smooth != 0.0:
+        if not (smooth > 0.0 and smooth != float("inf")):
+            raise ValueError(f"lm_step: smooth={smooth}: expected a finite weight >= 0")
+        if not isinstance(times, torch.Tensor):
+            host = sorted(int(t) for t in times)
+            if any(b - a == 1 for a, b in zip(host, host[1:])):
+                raise ValueError("lm_step: smooth != 0 needs pairwise non-adjacent frames in one call (one parity of t at a "
+                                 f"time), got times={list(times)}")
+        if beta_ref is None or beta_ref.shape != beta.shape or beta_ref.data_ptr() == beta.data_ptr():
+            raise ValueError("lm_step: smooth != 0 needs beta_ref, a float32 CUDA tensor shaped like beta and not beta itself")
+        _f32(beta_ref, "beta_ref")
     tt = _i32(times, dev)
     B = tt.numel()
     H, g, sse = eqs["H"], eqs["g"], eqs["sse"]
@@ -313,16 +350,25 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
     for name, t in (("H", H), ("g", g), ("sse", sse)):
         if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"lm_step: {name} must be a contiguous float64 CUDA tensor")
-    key = (tuple(int(s) for s in sz), str(dev))
-    if key not in _CENTRED_M:
-        _CENTRED_M[key] = torch.from_numpy(centred_basis_matrix(sz)).to(dev)
-    M = _CENTRED_M[key]
-    rc = _lib.load().dnmf_lm_step(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), beta.data_ptr(),
-                                  beta.shape[2], tt.data_ptr(), state["H"].data_ptr(), state["g"].data_ptr(),
-                                  state["sse"].data_ptr(), state["sse0"].data_ptr(), state["lam"].data_ptr(),
-                                  state["beta"].data_ptr(), state["counts"].data_ptr(), float(nu), float(lam0), float(lam_min),
-                                  float(lam_max), 1 if accept_only else 0, _stream())
-    _lib.check(rc, "dnmf_lm_step")
+    M, Minv = _centred(sz, dev)
+    if smooth == 0.0:
+        rc = _lib.load().dnmf_lm_step(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), beta.data_ptr(),
+                                      beta.shape[2], tt.data_ptr(), state["H"].data_ptr(), state["g"].data_ptr(),
+                                      state["sse"].data_ptr(), state["sse0"].data_ptr(), state["lam"].data_ptr(),
+                                      state["beta"].data_ptr(), state["counts"].data_ptr(), float(nu), float(lam0), float(lam_min),
+                                      float(lam_max), 1 if accept_only else 0, _stream())
+        _lib.check(rc, "dnmf_lm_step")
+        return state
+    if "prior" not in state or state["prior"].shape[0] < B:
+        state["prior"] = torch.zeros((state["counts"].shape[0],), dtype=torch.float64, device=dev)
+    n = int(sz[0]) * int(sz[1]) * int(sz[2]) if n_residuals is None else int(n_residuals)
+    rc = _lib.load().dnmf_lm_step_smooth(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), Minv.data_ptr(),
+                                         beta.data_ptr(), beta.shape[2], tt.data_ptr(), state["H"].data_ptr(),
+                                         state["g"].data_ptr(), state["sse"].data_ptr(), state["sse0"].data_ptr(),
+                                         state["lam"].data_ptr(), state["beta"].data_ptr(), state["counts"].data_ptr(), float(nu),
+                                         float(lam0), float(lam_min), float(lam_max), 1 if accept_only else 0, beta_ref.data_ptr(),
+                                         smooth * n, state["prior"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_lm_step_smooth")
     return state
 
 

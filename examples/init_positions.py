@@ -5,7 +5,8 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track] [--gn]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track]
+                                      [--gn [--motion-smooth S]]
                                       [--detect-image {template,corr,max,std}]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
@@ -22,7 +23,9 @@ peak of the matched-filter score within 3 voxels of the patch grid's track) befo
 printed for both sets of tracks.
 
 ``--gn``: every fit is repeated with the Gauss-Newton motion solver (``fit(..., motion_solver='gn')``: K16 + Levenberg-Marquardt
-steps per frame, ``--gn-iters`` of them, no learning rate) and its three numbers are printed beside Adam's.
+steps per frame, ``--gn-iters`` of them, no learning rate) and its three numbers are printed beside Adam's.  ``--motion-smooth S``
+gives that fit the temporal prior (``fit(..., motion_smooth=S)``, K16s: S in mean squared error per squared voxel of
+frame-to-frame change of a warp coefficient); the numbers with it are unmeasured.
 """
 import argparse
 import os
@@ -52,9 +55,12 @@ def main():
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
     ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
+    ap.add_argument("--motion-smooth", type=float, default=0.0, help="--gn: weight of the temporal smoothness prior (0: none)")
     ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
     a.detect = a.detect or a.detect_image is not None
+    if a.motion_smooth and not a.gn:
+        ap.error("--motion-smooth needs --gn (the Adam fit has no temporal term)")
     image = a.detect_image or "template"
     torch.manual_seed(0)
     np.random.seed(0)
@@ -113,7 +119,8 @@ def main():
                 print(f"init_motion: {int(ok.sum())} of {T} frames fitted")
             loader = dataset.loader(a.batch)
             if solver == "gn":
-                dn.fit(loader, loader, None, a.batch, outer=1, epochs=a.gn_iters, gamma_c=0, iter_c=30, motion_solver='gn')
+                dn.fit(loader, loader, None, a.batch, outer=1, epochs=a.gn_iters, gamma_c=0, iter_c=30, motion_solver='gn',
+                       motion_smooth=a.motion_smooth)
             else:
                 dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
             where = dn.positions()
@@ -121,7 +128,9 @@ def main():
             # the simulator places centres up to half a voxel beyond the last slice: read the box of the nearest voxel inside
             inside = np.clip(np.nan_to_num(where, nan=-1.0), 0, (sz.numpy() - 1)[None, :, None])
             roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))
-            label = start if solver == "adam" else f"{start} (gn, {a.gn_iters} iterations)"
+            label = start
+            if solver == "gn":
+                label += f" (gn, {a.gn_iters} iterations" + (f", smooth {a.motion_smooth:g})" if a.motion_smooth else ")")
             print(f"{label} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
                   f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "
                   f"dnmf.positions() {median_corr(np.nan_to_num(roi)):.3f}")

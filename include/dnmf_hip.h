@@ -613,6 +613,29 @@ int dnmf_lm_step(const double *H, const double *g, const double *sse, int B, int
                  const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0, double *lam, float *beta_acc,
                  int *counts, double nu, double lam0, double lam_min, double lam_max, int accept_only, dnmf_stream_t stream);
 
+/* K16s: dnmf_lm_step with a temporal smoothness prior.  theta_t (30, [a*3+d]) are frame t's coefficients in the centred basis on
+ * the active unknowns (beta[:, :, t] = M theta_t per coordinate; theta = Minv beta, Minv (10,10) row-major float64 = the inverse
+ * of M on the active monomials, zeros on the others), and frame t minimises
+ *   f_t(theta) = sse_t(theta) + m sum_{s in N_t} |theta - theta_s|^2,
+ * N_t = the frames t - 1, t + 1 inside [0, T) whose column of beta_ref is finite.  beta_ref (10,3,T) fp32 holds every frame's
+ * ACCEPTED coefficients; it is read at t +- 1, written at t on accept, and must not be beta (which holds untested trials).
+ *   accept   first call: always.  Later: f_t(trial) finite and < f_t(accepted), both priors against the current beta_ref.
+ *            On accept the trial's column is also written to beta_ref.  lam, sse0 and counts as dnmf_lm_step.
+ *   step     H' = H_acc + m |N_t| I, g' = g_acc + m sum_s (theta_acc - theta_s) on the active unknowns, then dnmf_lm_step's
+ *            damped solve of (H' + lam diag H' + tiny I) delta = -g' (the same device function) and d beta = M delta.
+ *            H_acc == 0 gives a damped step to the neighbours' mean, not delta = 0.
+ *   prior    (B) float64 out: m sum_s |theta_acc - theta_s|^2 of the accepted point after this call.  sse_acc and sse0 stay
+ *            the data term alone.
+ * m == 0, or a frame without a neighbour, is dnmf_lm_step exactly.  tests/gn_smooth_restatement.py is the definition.
+ * CONTRACT: the frames of one launch are pairwise non-adjacent (|times[i] - times[j]| != 1; all of one parity is enough): a
+ * block reads beta_ref[t +- 1] while the block of another frame may write its own column.  Nothing checks this on the device.
+ * One wave per frame, float64, no host synchronisation, no workspace.
+ * DNMF_E_NULL: a NULL buffer;  DNMF_E_SHAPE: as dnmf_lm_step, or m < 0 or not finite, or beta_ref == beta. */
+int dnmf_lm_step_smooth(const double *H, const double *g, const double *sse, int B, int Z, const double *M, const double *Minv,
+                        float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc, double *sse0,
+                        double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min, double lam_max,
+                        int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream);
+
 /* ---- K17: the trilinear registered movie under the fitted warp ----------------------------------------------------------------
  * For every frame j < B (column t = times[j] of beta, or j when times is NULL; row frame_ids[j] of frames, or j) and every lattice
  * point u = (i, j, k) of the footprint volume: the x with q_t(x) = u, and the frame sampled trilinearly at x.  Conventions as K11 /

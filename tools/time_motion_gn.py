@@ -7,7 +7,10 @@ off the identity (bench.py's ``displaced_beta``):
   iteration  one Levenberg-Marquardt iteration (K16 + ``ops.lm_step``; from ``update_motion(solver='gn')`` with 5 and with 1
              iterations) beside one Adam epoch of ``update_motion`` (reconstruction + K2 + ``adam_epoch``)
 
-    python tools/time_motion_gn.py [--frames 4000] [--neurons 100]
+  --smooth S an LM iteration with the temporal prior (``model.motion_smooth = S``, ``update_motion(solver='gn')``: the same
+             work in twice the launches, ``dnmf_lm_step_smooth``) beside the one without, in the ``iteration`` line
+
+    python tools/time_motion_gn.py [--frames 4000] [--neurons 100] [--smooth 1e-4]
 
 Every measurement is a process of its own under a time limit; the first one that fails ends the script.  One JSON line each.
 """
@@ -74,7 +77,7 @@ def step_kernels(Z, K, T):
     return {"step": "kernels", "Z": Z, "K": K, "T": T, "k2_ms": t2, "k16_ms": t16, "ratio": t16 / t2}
 
 
-def step_iteration(Z, K, T):
+def step_iteration(Z, K, T, smooth=0.0):
     import torch
     dNMF, model, sz, frames = setup(Z, K, T)
     loader = dNMF.ResidentLoader(frames, sz, 100)
@@ -99,8 +102,15 @@ def step_iteration(Z, K, T):
     adam = wall(lambda: model.update_motion(loader, opt, epochs=1))
     gn1 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=1))
     gn5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
-    return {"step": "iteration", "Z": Z, "K": K, "T": T, "adam_epoch_ms": adam, "gn_iters1_ms": gn1, "gn_iters5_ms": gn5,
-            "lm_iteration_ms": (gn5 - gn1) / 4}
+    out = {"step": "iteration", "Z": Z, "K": K, "T": T, "adam_epoch_ms": adam, "gn_iters1_ms": gn1, "gn_iters5_ms": gn5,
+           "lm_iteration_ms": (gn5 - gn1) / 4}
+    if smooth:
+        model.motion_smooth = smooth
+        s1 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=1))
+        s5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
+        model.motion_smooth = 0.0
+        out.update(smooth=smooth, gn_smooth_iters1_ms=s1, gn_smooth_iters5_ms=s5, lm_smooth_iteration_ms=(s5 - s1) / 4)
+    return out
 
 
 def main():
@@ -109,16 +119,17 @@ def main():
     ap.add_argument("--neurons", type=int, default=100)
     ap.add_argument("--step", choices=["kernels", "iteration"])
     ap.add_argument("--z", type=int, default=1)
+    ap.add_argument("--smooth", type=float, default=0.0, help="also time an LM iteration with this temporal prior weight")
     ap.add_argument("--limit", type=int, default=240, help="seconds a measurement may take")
     a = ap.parse_args()
     if a.step:
-        fn = step_kernels if a.step == "kernels" else step_iteration
-        print(json.dumps(fn(a.z, a.neurons, a.frames)), flush=True)
+        out = step_kernels(a.z, a.neurons, a.frames) if a.step == "kernels" else step_iteration(a.z, a.neurons, a.frames, a.smooth)
+        print(json.dumps(out), flush=True)
         return 0
     for z in (1, 2):
         for step in ("kernels", "iteration"):
             cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--step", step, "--z", str(z),
-                   "--frames", str(a.frames), "--neurons", str(a.neurons)]
+                   "--frames", str(a.frames), "--neurons", str(a.neurons), "--smooth", str(a.smooth)]
             rc = subprocess.run(cmd, cwd=ROOT).returncode
             if rc != 0:
                 print(f"time_motion_gn: {step} at Z={z} ended with status {rc}; stopping", flush=True)
