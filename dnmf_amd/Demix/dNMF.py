@@ -476,6 +476,17 @@ class ExponentialFP(nn.Module):
         return images if on_gpu else {k: v.cpu().numpy() for k, v in images.items()}
 
     @staticmethod
+    def background(video, iters=3):
+        """The rank-1 background of ``video`` as it is (K19, ``ops.background_fit``): ``(b (X, Y, Z), f (T,))`` fp32, both >= 0
+        with mean(f) = 1, after ``iters`` alternations of the two exact coordinate steps of ``min |video - b f|^2`` from b = 1.
+        ``video``: (T, X, Y, Z) values, ``(rows (T, P), sz)`` or a ``ResidentLoader``, as ``summary_images`` takes it.  On a
+        movie that also shows neurons, b holds their time-averaged light as well: ``DeformableNMF.update_background`` fits the
+        background on what the model leaves.  numpy or CPU-torch in, numpy out; CUDA frames give CUDA tensors."""
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "background")
+        b, f = ops.background_fit(rows, sz, iters)
+        return (b, f) if on_gpu else (b.cpu().numpy(), f.cpu().numpy())
+
+    @staticmethod
     def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None):
         """Where the neurons are in every frame of ``video`` -- (T, X, Y, Z) values, or frames that already live on the GPU as
         ``(rows (T, P), sz)`` or a ``ResidentLoader``: ``(P_T (K,3,T) float64, amplitudes (K,T))`` by K15
@@ -571,6 +582,8 @@ class DeformableNMF:
         self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
         self._D_dev = None         # (id(self.D), fp32 device copy of D flattened to (P,K))
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
+        # after update_background: (b (X,Y,Z), f (T,)) fp32 CUDA, the rank-1 background b f_t of frame t in frame coordinates
+        self.background = None
         self._warned = set()
 
     @classmethod
@@ -822,6 +835,75 @@ class DeformableNMF:
                 images, state = ops.summary_images(fr, sz, sub=sub, neighbours=neighbours, state=state, first=s == 0,
                                                    finish=s + step >= T)
         return images
+
+    def _background_refusals(self, loader, who):
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
+            raise NotImplementedError(f"{who}: the loader holds a shard of the frames (the b step would need an all-reduce)")
+
+    def update_background(self, loader, iters=3):
+        """Fit the rank-1 background of the frames ``loader`` serves on what the current model leaves: Y_t ~ M_t + b f_t, with
+        M_t the model's prediction in frame coordinates -- ``fp.recon_image`` followed by K2's warp, the forward of the motion
+        loss -- and b >= 0 (X, Y, Z), f >= 0 one value per frame, by ``iters`` alternations of the two exact coordinate steps
+        from b = 1 (K19, ``ops.background_fit``), scaled so that f has mean 1 over the frames served.  The kernels subtract M_t
+        as they read; M_t is made piece by piece (at most 1 GiB of frames) and never held whole.  b lives in frame coordinates:
+        camera offset, autofluorescence and out-of-focus glow do not move with the animal's neurons, and a static b needs no
+        warp.  Stores and returns ``self.background = (b, f)``, fp32 CUDA, f (T,) indexed by frame time (0 for a frame the
+        loader did not serve)."""
+        self._background_refusals(loader, "update_background")
+        fp = self.fp
+        sz, P = fp.sz_list, fp.P
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            C = self.C.to(device, torch.float32).contiguous()
+            beta = fp.beta.detach()
+            piece = max(1, min(frames.shape[0], (1 << 30) // (4 * P), K2_MAX_FRAMES))
+            zeros = torch.zeros((piece, P), dtype=torch.float32, device=device)
+
+            def predict(s, e):
+                tt = order[s:e]
+                out = ops.warp_recon_grad(fp.recon_image(C, tt), None, None, None, sz, beta, tt, grad=None, gout=zeros[:e - s],
+                                          want_recon=True, want_loss=False, want_reg=False, workspace=self._ws_k2)
+                self._ws_k2 = out["workspace"]
+                return out["recon"]
+
+            b, f_served = ops.background_fit(frames, sz, iters, sub_fn=predict, piece=piece)
+            f = torch.zeros((fp.T,), dtype=torch.float32, device=device)
+            f[order.long()] = f_served
+        self.background = (b, f)
+        return self.background
+
+    def background_loader(self, loader):
+        """A ``ResidentLoader`` over ``max(Y_t - b f_t, 0)``, the frames of ``loader`` without the fitted background
+        (``update_background``; ValueError before one was fitted).  The clamp is there because the multiplicative updates need
+        Y >= 0, as the datasets' own clamp does.  It keeps the loader's batch size, shuffle flag, generator and volume, and
+        serves frame t as row t: a ``ResidentLoader`` or a ``DataLoader`` whose pass covers the frames 0 .. n-1."""
+        if self.background is None:
+            raise ValueError("background_loader: no background was fitted (update_background)")
+        self._background_refusals(loader, "background_loader")
+        b, f = self.background
+        batch_size = getattr(loader, "batch_size", None)
+        if not batch_size:
+            raise ValueError("background_loader: the loader has no batch_size (a ResidentLoader or a DataLoader)")
+        if isinstance(loader, ResidentLoader):
+            shuffle, generator = loader.shuffle, loader.generator
+        else:
+            from torch.utils.data import RandomSampler
+            sampler = getattr(loader, "sampler", None)
+            shuffle = isinstance(sampler, RandomSampler)
+            generator = getattr(sampler, "generator", None) or getattr(loader, "generator", None)
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            n = order.numel()
+            if isinstance(loader, ResidentLoader):
+                rows = ops.background_subtract(frames, b, f, times=order)
+            else:
+                at = torch.argsort(order.long())
+                if not bool((order[at].long() == torch.arange(n, device=order.device)).all()):
+                    raise ValueError("background_loader: one pass of the loader must serve the frames 0 .. n-1 once each")
+                rows = ops.background_subtract(frames, b, f, frame_ids=at, times=order[at])
+        return ResidentLoader(rows, self.fp.sz_list, batch_size, shuffle=shuffle, generator=generator)
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
                           live_spatial=False, iter_a=1, solver='mu', registered='nearest'):
@@ -1476,24 +1558,49 @@ class DeformableNMF:
                 print('Reg: ' + str(out["reg"][j * nf:(j + 1) * nf]))
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
-            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None):
+            spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
+            background=0):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
         Gauss-Newton, ``optimizer`` may then be None) and ``motion_smooth`` the temporal prior's weight for the calls made
         here (``'gn'`` only; None: the model's ``motion_smooth``, 0 unless set; the attribute is put back afterwards);
-        ``registered`` is ``update_footprints``' (``'linear'``: K17)."""
+        ``registered`` is ``update_footprints``' (``'linear'``: K17).  ``background=n > 0`` (K19): every sweep ends with
+        ``update_background(testloader, iters=n)`` on the frames as given, and the following sweeps read
+        ``background_loader(...)`` of both loaders, rebuilt after every background update; the first sweep sees the raw frames,
+        because a background fitted before the model explains anything would take the neurons' mean light with it.  0: no
+        background term, the path of a call without the argument."""
         _check_motion_solver(motion_solver, "fit")
         kept = self.motion_smooth
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
         _check_registered(registered, "fit")
+        if int(background) != background or background < 0:
+            raise ValueError(f"fit: background is a number of alternations >= 0, got {background!r}")
+        if background:
+            self._background_refusals(dataloader, "fit(background=)")
+            self._background_refusals(testloader, "fit(background=)")
         out = (None, None, None)
         self.motion_smooth = motion_smooth
         try:
-            for _ in range(outer):
-                self.update_motion(dataloader, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
-                out = self.update_footprints(testloader, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
+            train, test = dataloader, testloader
+            for sweep in range(outer):
+                self.update_motion(train, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
+                out = self.update_footprints(test, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
                                              iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
+                if background:
+                    self.update_background(testloader, iters=background)
+                    if sweep + 1 < outer:
+                        train = test = None      # the last sweep's cleaned frames go before the next ones are made
+                        test = self.background_loader(testloader)
+                        if dataloader is testloader:
+                            train = test
+                        elif isinstance(dataloader, ResidentLoader) and isinstance(testloader, ResidentLoader) \
+                                and dataloader.frames_2d().data_ptr() == testloader.frames_2d().data_ptr() and dataloader.T == testloader.T:
+                            # two loaders over one resident movie: one cleaned copy serves both
+                            train = ResidentLoader(test.frames_2d(), self.fp.sz_list, dataloader.batch_size, shuffle=dataloader.shuffle,
+                                                   generator=dataloader.generator)
+                        else:
+                            train = self.background_loader(dataloader)
         finally:
             self.motion_smooth = kept
         return out

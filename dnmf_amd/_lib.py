@@ -100,6 +100,11 @@ SIGNATURES = {
     "dnmf_warp_pullback": (_i, [_vp, _l, _l, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _l, _i, C.c_float, _vp, _vp, _vp]),
     "dnmf_summary_images_workspace": (_sz, [_vp, _i, _i, _i]),
     "dnmf_summary_images": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "dnmf_background_dots_workspace": (_sz, [_l, _i]),
+    "dnmf_background_dots": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_background_accum_workspace": (_sz, [_l, _i, _i]),
+    "dnmf_background_accum": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dnmf_background_subtract": (_i, [_vp, _l, _vp, _vp, _vp, _i, _vp, _l, _i, _vp, _l, _i, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

@@ -1310,6 +1310,162 @@ def summary_images(frames, sz, sub=None, frame_ids=None, neighbours='full', stat
     return dict(mean=images[0], std=images[1], max=images[2], corr=images[3]), state
 
 
+def _ld(t, P):
+    """The row stride of rows ``t``; that of a single row means nothing (a view through numpy's newaxis has 0)."""
+    return t.stride(0) if t.shape[0] != 1 else max(t.stride(0), P)
+
+
+def _background_rows(fn, frames, sub, frame_ids, P):
+    """The checks the two half-steps share -> (frame_ids int32 or None, frames of the call)."""
+    _rows(frames, fn, "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"{fn}: frames are rows (T, ld), got {tuple(frames.shape)}")
+    fid = _i32(frame_ids, frames.device) if frame_ids is not None else None
+    B = fid.numel() if fid is not None else frames.shape[0]
+    if sub is not None:
+        _rows(sub, fn, "sub", P, f" and rows of {P} floats")
+        if sub.dim() != 2 or sub.shape[0] < B:
+            raise ValueError(f"{fn}: sub must hold one row for each of the {B} frames, got {tuple(sub.shape)}")
+    return fid, B
+
+
+def _refused(lib, what):
+    return _lib.DnmfHipError(f"{what} refused: {lib.dnmf_last_error().decode(errors='replace')}")
+
+
+def background_state(sz, B, segment=0, device="cuda"):
+    """An empty state for ``background_accum`` calls of up to ``B`` frames each; pass it with ``first=True``."""
+    X, Y, Z = (int(s) for s in sz)
+    lib = _lib.load()
+    need = lib.dnmf_background_accum_workspace(X * Y * Z, int(B), int(segment))
+    if need == 0:
+        raise _refused(lib, "dnmf_background_accum_workspace")
+    return _workspace(None, need, device)
+
+
+def background_dots(frames, b, sub=None, frame_ids=None):
+    """K19, the f half-step.  frames (rows, ld >= P) fp32 CUDA rows, ``b`` fp32 CUDA of P voxels (any shape), ``sub`` (B, ld >= P)
+    the model's prediction of the frames of the call (None: nothing) -> ``(f, num, bb)``: ``num[j] = sum_p b_p (frames - sub)[j, p]``
+    (B float64), ``bb = sum_p b_p^2`` (one float64, on the GPU) and ``f = max(0, num) / bb`` rounded to fp32 (0 when bb == 0), the
+    exact minimiser of ``|frames - sub - b f|^2`` over f >= 0.  The difference is taken in float64 as the rows are read; no
+    subtracted movie is made.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order).  Float64 sums in a fixed
+    order: the same input gives the same bits.  Everything must be finite."""
+    b = _f32(b, "b").reshape(-1)
+    P = b.numel()
+    fid, B = _background_rows("background_dots", frames, sub, frame_ids, P)
+    dev = frames.device
+    lib = _lib.load()
+    need = lib.dnmf_background_dots_workspace(P, B)
+    if need == 0:
+        raise _refused(lib, "dnmf_background_dots_workspace")
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    num = torch.empty((B,), dtype=torch.float64, device=dev)
+    bb = torch.empty((1,), dtype=torch.float64, device=dev)
+    f = torch.empty((B,), dtype=torch.float32, device=dev)
+    with _timed("background_dots"):
+        rc = lib.dnmf_background_dots(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                      b.data_ptr(), P, B, num.data_ptr(), bb.data_ptr(), f.data_ptr(), ws.data_ptr(), _nbytes(ws),
+                                      _stream())
+    _lib.check(rc, "dnmf_background_dots")
+    return f, num, bb
+
+
+def background_accum(frames, f, sz, sub=None, frame_ids=None, state=None, first=True, finish=True, segment=0):
+    """K19, the b half-step.  frames (rows, ld >= X Y Z) fp32 CUDA rows, ``f`` fp32 CUDA with one value per frame of the call,
+    ``sub`` as in ``background_dots`` -> ``((b, num, ff) or None, state)``: over the frames seen since the state was reset
+    ``num[p] = sum_t f_t (frames - sub)[t, p]`` ((X, Y, Z) float64), ``ff = sum_t f_t^2`` (one float64, on the GPU) and
+    ``b = max(0, num) / ff`` rounded to fp32 ((X, Y, Z); 0 when ff == 0), the exact minimiser over b >= 0.  A movie larger than one
+    buffer goes in several calls: ``first=True`` resets ``state`` (None: a new one), later calls pass the returned ``state``
+    with ``first=False``, the last one ``finish=True`` (before that the triple is None); a later call may not be larger than
+    the first.  The result of several calls is that of one up to the order of the float64 sums.  ``segment``: frames per
+    workgroup (0: the kernel's choice).  No atomics: the same input gives the same bits."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _background_rows("background_accum", frames, sub, frame_ids, P)
+    f = _f32(f, "f").reshape(-1)
+    if f.numel() != B:
+        raise ValueError(f"background_accum: f must hold one value for each of the {B} frames, got {f.numel()}")
+    dev = frames.device
+    lib = _lib.load()
+    need = lib.dnmf_background_accum_workspace(P, B, int(segment))
+    if need == 0:
+        raise _refused(lib, "dnmf_background_accum_workspace")
+    if first:
+        state = _workspace(state, need, dev)
+    elif state is None or _nbytes(state) < need:
+        raise ValueError(f"background_accum: first=False needs the state of the earlier calls, and one of at least {need} bytes "
+                         "(a later call may not be larger than the first)")
+    b = torch.empty((X, Y, Z), dtype=torch.float32, device=dev) if finish else None
+    num = torch.empty((X, Y, Z), dtype=torch.float64, device=dev) if finish else None
+    ff = torch.empty((1,), dtype=torch.float64, device=dev) if finish else None
+    with _timed("background_accum"):
+        rc = lib.dnmf_background_accum(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                       f.data_ptr(), P, B, 1 if first else 0, 1 if finish else 0, int(segment), state.data_ptr(),
+                                       _nbytes(state), _ptr(b), _ptr(num), _ptr(ff), _stream())
+    _lib.check(rc, "dnmf_background_accum")
+    return ((b, num, ff) if finish else None), state
+
+
+def background_subtract(frames, b, f, frame_ids=None, times=None, out=None, clamp=True):
+    """K19.  ``out[j] = frames[row j] - b f[t_j]`` as one fp32 fused multiply-add per voxel, ``max(., 0)`` with ``clamp``: (B, P) fp32
+    CUDA rows.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order); ``times``: the entry of ``f`` of each frame of
+    the call (None: j; an entry ``f`` does not have makes the row NaN).  ``out=frames`` works in place (``frame_ids`` None)."""
+    b = _f32(b, "b").reshape(-1)
+    f = _f32(f, "f").reshape(-1)
+    P = b.numel()
+    _rows(frames, "background_subtract", "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"background_subtract: frames are rows (T, ld), got {tuple(frames.shape)}")
+    dev = frames.device
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    if fid is not None and fid.numel() != B:
+        raise ValueError(f"background_subtract: {fid.numel()} frame_ids for {B} times")
+    if fid is None and B > frames.shape[0]:
+        raise ValueError(f"background_subtract: {B} times for {frames.shape[0]} frames")
+    if out is None:
+        out = torch.empty((B, P), dtype=torch.float32, device=dev)
+    _rows(out, "background_subtract", "out", P, f" and rows of {P} floats")
+    if out.dim() != 2 or out.shape[0] < B:
+        raise ValueError(f"background_subtract: out must hold {B} rows, got {tuple(out.shape)}")
+    lib = _lib.load()
+    with _timed("background_subtract"):
+        rc = lib.dnmf_background_subtract(frames.data_ptr(), _ld(frames, P), _ptr(fid), b.data_ptr(), f.data_ptr(), f.numel(), _ptr(tt),
+                                          P, B, out.data_ptr(), _ld(out, P), 1 if clamp else 0, _stream())
+    _lib.check(rc, "dnmf_background_subtract")
+    return out
+
+
+def background_fit(frames, sz, iters, sub_fn=None, piece=None):
+    """The rank-1 background of resident rows: ``iters`` times the pair (``background_dots``, ``background_accum``) from b = 1,
+    then the scale that makes mean(f) = 1 -> ``(b (X, Y, Z), f (T,))`` fp32 CUDA, both >= 0 (tests/background_restatement.py:
+    ``fit``).  The rows go through in pieces of ``piece`` frames (None: at most 1 GiB of frames); ``sub_fn(s, e)`` returns the
+    rows to subtract from frames ``s:e`` ((e - s, ld >= P) fp32 CUDA, e.g. the model's prediction), so that they are never
+    held for the whole movie -- it is called twice per iteration and piece.  No host synchronisation."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    T = frames.shape[0]
+    if int(iters) < 1:
+        raise ValueError(f"background_fit: iters={iters}")
+    if piece is None:
+        piece = max(1, (1 << 30) // (4 * P))
+    piece = max(1, min(int(piece), T))
+    dev = frames.device
+    b = torch.ones((X, Y, Z), dtype=torch.float32, device=dev)
+    f = torch.empty((T,), dtype=torch.float32, device=dev)
+    cuts = [(s, min(T, s + piece)) for s in range(0, T, piece)]
+    state = None
+    for _ in range(int(iters)):
+        for s, e in cuts:
+            f[s:e] = background_dots(frames[s:e], b, sub=None if sub_fn is None else sub_fn(s, e))[0]
+        for n, (s, e) in enumerate(cuts):
+            res, state = background_accum(frames[s:e], f[s:e], (X, Y, Z), sub=None if sub_fn is None else sub_fn(s, e), state=state,
+                                          first=n == 0, finish=e == T)
+        b = res[0]
+    scale = f.mean()
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    return b.mul_(scale), f.div_(scale)
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -695,6 +695,48 @@ int dnmf_summary_images(const float *frames, long ldf, const float *sub, long ld
                         int neighbours, int first, int finish, int segment, void *state, size_t state_bytes, double *images,
                         dnmf_stream_t stream);
 
+/* ---- K19: a rank-1 background b (x) f on the residual, fitted by alternating exact coordinate steps, and its subtraction --------
+ * Model: frames[t, p] ~ sub[t, p] + b[p] f[t] with b >= 0 an image over the P voxels and f >= 0 one value per frame; sub is what the
+ * model already predicts (NULL: nothing).  r = (double)frames - (double)sub is exact and is never written: the two half-steps read
+ * the movie once each (8 B per voxel and frame with sub, 4 B without), in float64, without floating-point atomics -- the same input
+ * at the same addresses gives the same bits.  tests/background_restatement.py is the definition in float64.  Rows as in K18: ldf >= P
+ * floats, row frame_ids[j] of frames (or j) for the j-th frame of the call, row j of sub (lds >= P).  Rows whose start is 16-byte
+ * aligned are read 16 bytes at a time, others (P % 4 != 0) float by float.  Frames, sub, b and f must be finite: a value that is not
+ * poisons the sums it enters, nothing detects it.  No host synchronisation; nothing is launched on an error.
+ *
+ * dnmf_background_dots: num[j] = sum_p b[p] r[j, p] (float64, B values, may be NULL), *bb = sum_p b[p]^2 (float64, once per call,
+ *   may be NULL) and f[j] = (float)(max(0, num[j]) / bb), 0 when bb == 0 (B values).  One workgroup per (frame, segment of voxels),
+ *   float64 sums per lane reduced in a fixed tree, one partial per workgroup in the workspace; a second launch adds a frame's
+ *   partials in their order.  workspace: caller-owned, 8-byte aligned, dnmf_background_dots_workspace(P, B) bytes (0 on bad arguments).
+ *   DNMF_E_NULL: frames, b, f or workspace NULL;  DNMF_E_SHAPE: P or B < 1, ldf or lds < P;  DNMF_E_UNSUPPORTED: 2^31 voxels or more;
+ *   DNMF_E_WORKSPACE: a short or misaligned workspace.
+ *
+ * dnmf_background_accum: per voxel num[p] = sum_t f[t] r[t, p] over every frame since the state was reset (f[j] belongs to the j-th
+ *   frame of the call), ff = sum_t f[t]^2, and with finish != 0 a last launch writes b[p] = (float)(max(0, num[p]) / ff), 0 when
+ *   ff == 0 (P values), num (P float64, may be NULL) and *ff (may be NULL).  One workgroup per (tile of 1024 contiguous voxels, segment
+ *   of frames; segment > 0: that many frames each, 0: the kernel's choice, enough segments to fill the machine), float64 sums in
+ *   registers, the partial sums of a segment in the state; a second launch adds the segments to the state in their order.
+ *   state: caller-owned, 8-byte aligned, dnmf_background_accum_workspace(P, B, segment) bytes (0 on bad arguments; it does not
+ *   decrease with B, so the size for the largest call serves every call).  first != 0 resets it; a movie larger than one buffer is fed
+ *   in several calls and gives the result of one call up to the order of the sums.
+ *   DNMF_E_NULL: frames, f or state NULL, b NULL with finish;  DNMF_E_SHAPE: P or B < 1, segment < 0, ldf or lds < P;
+ *   DNMF_E_UNSUPPORTED: 2^31 voxels or more, more than 65535 segments;  DNMF_E_WORKSPACE: a short or misaligned state.
+ *
+ * dnmf_background_subtract: out[j, p] = fmaf(-b[p], f[t], frames[row, p]) in fp32 (one rounding), max(., 0) when clamp != 0;
+ *   t = times[j] or j, f has nf values (a t outside [0, nf) makes row j NaN).  out: B rows of ldo >= P floats; out == frames (in
+ *   place) is allowed with frame_ids NULL and ldo == ldf, any other overlap is not.  One launch, no workspace.
+ *   DNMF_E_NULL: frames, b, f or out NULL;  DNMF_E_SHAPE: P, B or nf < 1, ldf or ldo < P, B > nf without times, out == frames with
+ *   frame_ids or ldo != ldf;  DNMF_E_UNSUPPORTED: 2^31 voxels or more, 2^31 workgroups or more (split the call). */
+size_t dnmf_background_dots_workspace(long P, int B);
+int dnmf_background_dots(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *b, long P, int B,
+                         double *num, double *bb, float *f, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
+size_t dnmf_background_accum_workspace(long P, int B, int segment);
+int dnmf_background_accum(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *f, long P, int B,
+                          int first, int finish, int segment, void *state, size_t state_bytes, float *b, double *num, double *ff,
+                          dnmf_stream_t stream);
+int dnmf_background_subtract(const float *frames, long ldf, const int *frame_ids, const float *b, const float *f, int nf, const int *times,
+                             long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
