@@ -584,6 +584,8 @@ class DeformableNMF:
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
         # after update_background: (b (X,Y,Z), f (T,)) fp32 CUDA, the rank-1 background b f_t of frame t in frame coordinates
         self.background = None
+        # after clean_traces: a, b, F0, fitted, n_outliers per neuron (CUDA tensors, (K,)) of that call
+        self.last_clean = None
         self._warned = set()
 
     @classmethod
@@ -904,6 +906,20 @@ class DeformableNMF:
                     raise ValueError("background_loader: one pass of the loader must serve the frames 0 .. n-1 once each")
                 rows = ops.background_subtract(frames, b, f, frame_ids=at, times=order[at])
         return ResidentLoader(rows, self.fp.sz_list, batch_size, shuffle=shuffle, generator=generator)
+
+    def clean_traces(self, fps, **kw):
+        """The traces ``self.C`` cleaned up for plotting and analysis (K20, ``ops.clean_traces``; the reference's
+        ``Demix/Traces.py::cleanTraces``): acquisition outliers masked, single-frame jumps removed, every neuron's own bleaching
+        detrended, scaled to [0.05, 0.95] or to dF/F0 -> ``(traces (K, T) fp32, scales (K,), offsets (K,))`` on the GPU.  ``fps``:
+        frames per second; ``kw``: ``sigma_threshold``, ``detrend_mode``, ``interp_method``, ``smooth_method``, ``smooth_window``,
+        ``trim``, ``floor``.  ``self.C`` stays as it is; ``self.last_clean`` receives the per-neuron ``a``, ``b``, ``F0``, ``fitted``
+        and ``n_outliers`` of the call."""
+        with torch.no_grad():
+            C = self.C.detach().to(device, torch.float32)
+            out, scales, offsets, info = ops.clean_traces(C if C.stride(-1) == 1 else C.contiguous(), fps, **kw)
+        info.pop("workspace")
+        self.last_clean = info
+        return out, scales, offsets
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
                           live_spatial=False, iter_a=1, solver='mu', registered='nearest'):

@@ -1466,6 +1466,49 @@ def background_fit(frames, sz, iters, sub_fn=None, piece=None):
     return b.mul_(scale), f.div_(scale)
 
 
+def clean_traces(traces, fps, sigma_threshold=10, detrend_mode=2, interp_method=None, smooth_method=None, smooth_window=None,
+                 trim=True, floor=0.01, workspace=None):
+    """K20, the trace clean-up of tests/traces_restatement.py (``clean_traces``: mask, single-frame outliers, bleach detrend, dF/F0,
+    gap filling, smoothing, rescale) on the GPU.  traces (K, T) fp32 CUDA rows with unit inner stride -- any row stride, no copy
+    is made and the input is only read -> ``(traces (K, T) fp32, scales (K,), offsets (K,), info)`` on the GPU; ``info``: ``a``,
+    ``b``, ``F0`` (float64), ``fitted`` (bool), ``n_outliers`` (int32) per neuron and ``workspace``.  ``sigma_threshold`` None or
+    0: no outlier step; ``interp_method`` None or 'linear'; ``smooth_method`` None, 'movmean' or 'movmedian' over ``smooth_window``
+    frames ('causal', 'high' and 'low' name filters the reference does not contain: NotImplementedError).  Float64 inside, one
+    rounding to fp32, sums in a fixed order: the same input gives the same bits.  No host synchronisation."""
+    if traces.dim() != 2:
+        raise ValueError(f"clean_traces: traces are (K, T), got {tuple(traces.shape)}")
+    _rows(traces, "clean_traces", "traces")
+    if interp_method is not None and interp_method != "linear":
+        raise ValueError(f"clean_traces: interp_method={interp_method!r}: 'linear' or None")
+    if smooth_method in ("causal", "high", "low"):
+        raise NotImplementedError(f"clean_traces: smooth_method={smooth_method!r} names a filter (causalBandpassFilter / "
+                                  "highpassFilter / lowpassFilter) that the reference does not contain")
+    if smooth_method is not None and smooth_method not in ("movmean", "movmedian"):
+        raise ValueError(f"clean_traces: smooth_method={smooth_method!r}: 'movmean', 'movmedian' or None")
+    smooth = 0 if smooth_method is None or smooth_window is None else (1 if smooth_method == "movmean" else 2)
+    K, T = traces.shape
+    dev = traces.device
+    lib = _lib.load()
+    need = lib.dnmf_clean_traces_workspace(K, T)
+    if need == 0:
+        raise _refused(lib, "dnmf_clean_traces_workspace")
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    out = torch.empty((K, T), dtype=torch.float32, device=dev)
+    f64 = torch.empty((5, K), dtype=torch.float64, device=dev)      # scales, offsets, a, b, F0
+    i32 = torch.empty((2, K), dtype=torch.int32, device=dev)        # fitted, n_outliers
+    with _timed("clean_traces"):
+        rc = lib.dnmf_clean_traces(traces.data_ptr(), _ld(traces, T), K, T, float(fps),
+                                   0.0 if sigma_threshold is None else float(sigma_threshold), int(detrend_mode),
+                                   0 if interp_method is None else 1, smooth, int(smooth_window) if smooth else 0, 1 if trim else 0,
+                                   float(floor), out.data_ptr(), T, f64[0].data_ptr(), f64[1].data_ptr(), f64[2].data_ptr(),
+                                   f64[3].data_ptr(), f64[4].data_ptr(), i32[0].data_ptr(), i32[1].data_ptr(), workspace.data_ptr(),
+                                   _nbytes(workspace), _stream())
+    _lib.check(rc, "dnmf_clean_traces")
+    info = dict(a=f64[2], b=f64[3], F0=f64[4], fitted=i32[0] != 0, n_outliers=i32[1], workspace=workspace)
+    return out, f64[0], f64[1], info
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -3,7 +3,10 @@
 plots, against this repository's drop-in ``Demix.dNMF``.  Prints how well the recovered traces match the ground
 truth.  Needs an MI355X.
 
-    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50]
+    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS]
+
+``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
+print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
 """
 import argparse
 import os
@@ -24,6 +27,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--iter-c", type=int, default=50)
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--clean", type=float, default=None, metavar="FPS")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -45,6 +49,19 @@ def main():
     corr = [np.corrcoef(C[k], dataset.traces[k])[0, 1] for k in range(K)]
     print("A_t", A_t.shape, "Y_i", Y_i.shape, "Y", Y.shape)
     print("trace correlation with ground truth: min %.3f  median %.3f" % (min(corr), float(np.median(corr))))
+    if a.clean is not None:
+        cleaned = dnmf.clean_traces(a.clean)[0].cpu().numpy().astype(np.float64)
+
+        def median_corr(X):
+            cc = []
+            for k in range(K):
+                ok = ~np.isnan(cleaned[k])        # the frames the clean-up keeps, for both
+                cc.append(np.corrcoef(X[k][ok], np.asarray(dataset.traces[k])[ok])[0, 1] if ok.sum() > 2 else np.nan)
+            return float(np.nanmedian(cc))
+
+        print("median trace correlation with ground truth at %g fps: C %.3f  cleaned C %.3f  (outliers removed: %d, curves fitted: %d of %d)"
+              % (a.clean, median_corr(C), median_corr(cleaned), int(dnmf.last_clean["n_outliers"].sum()),
+                 int(dnmf.last_clean["fitted"].sum()), K))
     return corr
 
 

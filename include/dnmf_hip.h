@@ -737,6 +737,33 @@ int dnmf_background_accum(const float *frames, long ldf, const float *sub, long 
 int dnmf_background_subtract(const float *frames, long ldf, const int *frame_ids, const float *b, const float *f, int nf, const int *times,
                              long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream);
 
+/* ---- K20: trace clean-up: mask, single-frame outliers, bleach detrend, dF/F0, gap filling, smoothing, rescale ---------------------
+ * tests/traces_restatement.py (clean_traces) is the definition, step by step (S1 .. S6), in float64; this entry computes it for K
+ * traces of T frames: traces = K rows of ldt >= T floats, out = K rows of ldo >= T floats (the input is only read; out may not
+ * overlap it).  One workgroup per trace with the working trace as float64 in LDS, every output rounded once to fp32; three launches
+ * on the stream (per trace; one workgroup for what couples the traces, modes 1 and 3 only; per trace), no host synchronisation,
+ * nothing launched on an error.  Sums are taken in a fixed order without floating-point atomics: the same input gives the same bits.
+ * Medians and the percentile select by bisection on the 64-bit key of a value (one counting pass per key bit), never by sorting.
+ *   fps               frames per second (> 0): S1 masks the first floor(fps / 2 + 0.5) frames and the last one when trim != 0; the
+ *                     running median of S3 spans W = floor(10 fps + 0.5) frames
+ *   sigma_threshold   S2 (outliers and the median of three) runs when > 0
+ *   detrend_mode      0 none, 1 one curve for all traces, 2 one per trace, 3 one per trace and the division by max(median F0, 1)
+ *   interp            0 none, 1 linear (S4);  smooth: 0 none, 1 movmean, 2 movmedian over smooth_window >= 1 frames (S5)
+ *   floor_value       S1 masks values <= floor_value (and every value that is not finite)
+ * Outputs, K values each: scales, offsets (out = 0.9 (x - offset) / scale + 0.05 of the detrended x for modes 0 .. 2; mode 3:
+ * scale = max(median F0, 1), offset 0), a, b (the fitted curve a exp(b (t + 1)); NaN where none was fitted; mode 1: the common one),
+ * F0 (NaN for mode 0; mode 3: the common median), fitted (0 / 1), n_outliers (frames S2 removed).
+ * workspace: caller-owned, 8-byte aligned, dnmf_clean_traces_workspace(K, T) bytes (0 on bad arguments): the trace after S2 and its
+ * running median, float64.  T and K are limited by the LDS: at most 18 432 each; larger ones are refused, nothing is truncated.
+ * DNMF_E_NULL: any pointer NULL;  DNMF_E_SHAPE: K or T < 1, ldt or ldo < T, fps <= 0 or W < 1 with detrend_mode > 0,
+ * sigma_threshold < 0, a floor_value that is not finite, detrend_mode, interp or smooth outside their values, smooth_window < 1 with
+ * smooth;  DNMF_E_UNSUPPORTED: T or K above 18 432;  DNMF_E_WORKSPACE: a short or misaligned workspace. */
+size_t dnmf_clean_traces_workspace(int K, int T);
+int dnmf_clean_traces(const float *traces, long ldt, int K, int T, double fps, double sigma_threshold, int detrend_mode, int interp,
+                      int smooth, int smooth_window, int trim, double floor_value, float *out, long ldo, double *scales, double *offsets,
+                      double *a, double *b, double *F0, int *fitted, int *n_outliers, void *workspace, size_t workspace_bytes,
+                      dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
