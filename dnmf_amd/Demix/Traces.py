@@ -1,4 +1,4 @@
-"""``Demix/Traces.py`` of the reference: ``cleanTraces``.  The reference's body is half-translated MATLAB and does not parse;
+"""``Demix/Traces.py`` of the reference: ``cleanTraces``, and the step after it, ``deconvolveTraces`` (K21).  The reference's body is half-translated MATLAB and does not parse;
 what it describes is defined in tests/traces_restatement.py and computed by K20 (``ops.clean_traces``) on the GPU.  Its
 ``histogram_match`` is not here: its body concatenates 1-D arrays along an axis they lack."""
 from __future__ import annotations
@@ -40,3 +40,42 @@ def cleanTraces(traces, fps, sigma_threshold=10, detrend_mode=2, interp_method=N
     t = torch.from_numpy(np.ascontiguousarray(traces, dtype=np.float32)).cuda()
     out, scales, offsets, _ = ops.clean_traces(t, fps, **kw)
     return out.cpu().numpy(), scales.cpu().numpy(), offsets.cpu().numpy()
+
+
+def deconvolveTraces(traces, fps=None, decay_time=None, g=None, penalty=None, baseline=None, noise=None, baseline_percentile=10.0):
+    """When did each neuron fire: the AR(1), non-negative deconvolution of traces (K, T) (K21, ``ops.deconvolve_traces``;
+    tests/deconv_restatement.py is the definition) -> ``(c, s, info)``: the denoised calcium traces, the spikes
+    ``s_t = c_t - g c_{t-1} >= 0`` and a dict with ``g``, ``penalty``, ``baseline``, ``noise``, ``rss``, ``n_valid``, ``n_pools``
+    and ``ok`` per trace.  Frames that are not finite -- what ``cleanTraces`` masks -- carry no weight; the trace decays through
+    them.
+
+    decay_time   the indicator's decay time in seconds: ``g = exp(-1 / (decay_time fps))``; needs ``fps`` and excludes ``g``
+    g            the decay per frame in (0, 1); with neither, every trace's own ``ac(2) / ac(1)`` is taken
+    penalty      the weight of sum(s); None: per trace the one at which the residual reaches the noise level
+    baseline     None: the ``baseline_percentile``-th percentile of the valid frames, which sits below the true baseline by a
+                 fraction of the noise (a jointly optimised baseline is not offered)
+    noise        None: 1.4826 MAD / sqrt(2) of the differences of adjacent frames
+
+    Each of ``g``, ``penalty``, ``baseline``, ``noise`` is None, a number or one value per trace (NaN: estimate that one).  A trace
+    that cannot be treated has ``ok`` False and NaN rows.  A numpy array comes back as numpy arrays, a CUDA tensor as CUDA tensors;
+    the input is not modified."""
+    if decay_time is not None:
+        if g is not None:
+            raise ValueError("deconvolveTraces: give g or decay_time, not both")
+        if fps is None:
+            raise ValueError("deconvolveTraces: decay_time is in seconds and needs fps")
+        if not (float(decay_time) > 0 and float(fps) > 0):
+            raise ValueError(f"deconvolveTraces: decay_time={decay_time}, fps={fps}")
+        g = float(np.exp(-1.0 / (float(decay_time) * float(fps))))
+    kw = dict(g=g, penalty=penalty, baseline=baseline, noise=noise, baseline_percentile=baseline_percentile)
+    if isinstance(traces, torch.Tensor):
+        if not traces.is_cuda:
+            raise ValueError("deconvolveTraces: a tensor must live on the GPU (numpy arrays are taken from the host)")
+        t = traces if traces.dtype == torch.float32 and traces.stride(-1) == 1 else traces.float().contiguous()
+        c, s, info = ops.deconvolve_traces(t, **kw)
+        info.pop("workspace")
+        return c, s, info
+    t = torch.from_numpy(np.ascontiguousarray(traces, dtype=np.float32)).cuda()
+    c, s, info = ops.deconvolve_traces(t, **kw)
+    info.pop("workspace")
+    return c.cpu().numpy(), s.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}

@@ -586,6 +586,8 @@ class DeformableNMF:
         self.background = None
         # after clean_traces: a, b, F0, fitted, n_outliers per neuron (CUDA tensors, (K,)) of that call
         self.last_clean = None
+        # after deconvolve: g, penalty, baseline, noise, rss, n_valid, n_pools, ok per neuron (CUDA tensors, (K,)) of that call
+        self.last_deconv = None
         self._warned = set()
 
     @classmethod
@@ -920,6 +922,19 @@ class DeformableNMF:
         info.pop("workspace")
         self.last_clean = info
         return out, scales, offsets
+
+    def deconvolve(self, fps=None, decay_time=None, traces=None, **kw):
+        """When each neuron fired (K21, ``Demix.Traces.deconvolveTraces``): the AR(1), non-negative deconvolution of ``self.C``, or
+        of ``traces`` (K, T) -- e.g. what ``clean_traces`` returned, whose NaN frames carry no weight -> ``(c, s, info)`` on the GPU:
+        the denoised traces, the spikes and the per-neuron ``g``, ``penalty``, ``baseline``, ``noise``, ``rss``, ``n_valid``,
+        ``n_pools`` and ``ok``.  ``decay_time`` in seconds needs ``fps``; ``kw``: ``g``, ``penalty``, ``baseline``, ``noise``,
+        ``baseline_percentile``.  ``self.C`` stays as it is; ``self.last_deconv`` receives ``info``."""
+        from .Traces import deconvolveTraces
+        with torch.no_grad():
+            C = (self.C if traces is None else torch.as_tensor(traces)).detach().to(device, torch.float32)
+            c, s, info = deconvolveTraces(C, fps=fps, decay_time=decay_time, **kw)
+        self.last_deconv = info
+        return c, s, info
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
                           live_spatial=False, iter_a=1, solver='mu', registered='nearest'):

@@ -1509,6 +1509,62 @@ def clean_traces(traces, fps, sigma_threshold=10, detrend_mode=2, interp_method=
     return out, f64[0], f64[1], info
 
 
+def _per_trace(v, K, dev, fn, name, lo=None, hi=None, closed_lo=False):
+    """An option of ``deconvolve_traces`` -> a (K,) float64 tensor on ``dev`` (NaN: estimate) or None.  A number is checked
+    against its range here; the entries of an array are judged per trace by the kernel."""
+    if v is None:
+        return None
+    if not isinstance(v, torch.Tensor) and not hasattr(v, "__len__"):
+        x = float(v)
+        if x == x and ((lo is not None and (x < lo if closed_lo else x <= lo)) or (hi is not None and x >= hi)):
+            raise ValueError(f"{fn}: {name}={x}")
+        return torch.full((K,), x, dtype=torch.float64, device=dev)
+    t = torch.as_tensor(v).to(device=dev, dtype=torch.float64).contiguous()
+    if t.shape != (K,):
+        raise ValueError(f"{fn}: {name} is a number or one value per trace ({K}), got {tuple(t.shape)}")
+    return t
+
+
+def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, baseline_percentile=10.0, workspace=None):
+    """K21, the spike deconvolution of tests/deconv_restatement.py (``deconvolve_traces``) on the GPU: per trace y the c >= 0 that
+    minimises 1/2 sum w (y - b - c)^2 + penalty sum s with s_t = c_t - g c_{t-1} >= 0, w = 0 on the frames that are not finite
+    (what ``clean_traces`` masks).  traces (K, T) fp32 CUDA rows with unit inner stride -- any row stride, no copy is made and the
+    input is only read -> ``(c (K, T) fp32, s (K, T) fp32, info)`` on the GPU; ``info``: ``g``, ``penalty``, ``baseline``,
+    ``noise``, ``rss`` (float64), ``n_valid``, ``n_pools`` (int32), ``ok`` (bool) per trace and ``workspace``.  Each of ``g``,
+    ``penalty``, ``baseline``, ``noise``: None (estimate it), a number, or a ``(K,)`` array or tensor whose NaN entries are
+    estimated.  The estimated baseline is the ``baseline_percentile``-th percentile of the valid frames: it sits below the true
+    baseline by a fraction of the noise.  A trace that cannot be treated (too few valid frames, no decay in (0, 1), ...) has
+    ``ok`` False and NaN rows.  Float64 inside, one rounding to fp32, sums in a fixed order: the same input gives the same bits.
+    One launch, no host synchronisation."""
+    fn = "deconvolve_traces"
+    if traces.dim() != 2:
+        raise ValueError(f"{fn}: traces are (K, T), got {tuple(traces.shape)}")
+    _rows(traces, fn, "traces")
+    K, T = traces.shape
+    dev = traces.device
+    if not 0.0 <= float(baseline_percentile) <= 100.0:
+        raise ValueError(f"{fn}: baseline_percentile={baseline_percentile}")
+    opts = [_per_trace(g, K, dev, fn, "g", lo=0.0, hi=1.0), _per_trace(penalty, K, dev, fn, "penalty", lo=0.0, closed_lo=True),
+            _per_trace(baseline, K, dev, fn, "baseline"), _per_trace(noise, K, dev, fn, "noise", lo=0.0, closed_lo=True)]
+    lib = _lib.load()
+    need = lib.dnmf_deconvolve_traces_workspace(K, T)
+    if need == 0:
+        raise _refused(lib, "dnmf_deconvolve_traces_workspace")
+    if workspace is None or _nbytes(workspace) < need:
+        workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    c = torch.empty((K, T), dtype=torch.float32, device=dev)
+    s = torch.empty((K, T), dtype=torch.float32, device=dev)
+    out = torch.empty((K, 8), dtype=torch.float64, device=dev)
+    with _timed("deconvolve_traces"):
+        rc = lib.dnmf_deconvolve_traces(traces.data_ptr(), _ld(traces, T), K, T, *[_ptr(o) for o in opts], float(baseline_percentile),
+                                        c.data_ptr(), s.data_ptr(), T, out.data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                        _stream())
+    _lib.check(rc, "dnmf_deconvolve_traces")
+    info = dict(g=out[:, 0], penalty=out[:, 1], baseline=out[:, 2], noise=out[:, 3], rss=out[:, 4], n_valid=out[:, 5].to(torch.int32),
+                n_pools=out[:, 6].to(torch.int32), ok=out[:, 7] != 0, workspace=workspace)
+    return c, s, info
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

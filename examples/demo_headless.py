@@ -3,10 +3,12 @@
 plots, against this repository's drop-in ``Demix.dNMF``.  Prints how well the recovered traces match the ground
 truth.  Needs an MI355X.
 
-    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS]
+    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
+``--deconvolve``: also deconvolve the traces (``DeformableNMF.deconvolve``, K21), everything estimated, and print the median
+correlation of the simulator's traces with ``C`` and with ``b + c``, and the median estimated decay beside the simulator's e^-0.3.
 """
 import argparse
 import os
@@ -28,6 +30,7 @@ def main():
     ap.add_argument("--iter-c", type=int, default=50)
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--clean", type=float, default=None, metavar="FPS")
+    ap.add_argument("--deconvolve", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -62,6 +65,15 @@ def main():
         print("median trace correlation with ground truth at %g fps: C %.3f  cleaned C %.3f  (outliers removed: %d, curves fitted: %d of %d)"
               % (a.clean, median_corr(C), median_corr(cleaned), int(dnmf.last_clean["n_outliers"].sum()),
                  int(dnmf.last_clean["fitted"].sum()), K))
+    if a.deconvolve:
+        c, s, info = dnmf.deconvolve()
+        ok = info["ok"].cpu().numpy()
+        fit = (info["baseline"][:, None] + c).cpu().numpy().astype(np.float64)
+        truth = np.asarray(dataset.traces, np.float64)
+        print("median trace correlation with ground truth: C %.3f  b + c %.3f;  median estimated decay %.3f (simulator: %.3f);  %d of %d traces treated"
+              % (float(np.median([np.corrcoef(C[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
+                 float(np.median([np.corrcoef(fit[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
+                 float(np.nanmedian(info["g"].cpu().numpy())), float(np.exp(-0.3)), int(ok.sum()), K))
     return corr
 
 

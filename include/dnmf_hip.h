@@ -764,6 +764,34 @@ int dnmf_clean_traces(const float *traces, long ldt, int K, int T, double fps, d
                       double *a, double *b, double *F0, int *fitted, int *n_outliers, void *workspace, size_t workspace_bytes,
                       dnmf_stream_t stream);
 
+/* ---- K21: spike deconvolution of the traces: AR(1), non-negative ---------------------------------------------------------------------
+ * tests/deconv_restatement.py (deconvolve_traces) is the definition (D1 .. D6), in float64; this entry computes it for K traces of T
+ * frames: traces = K rows of ldt >= T floats, c and s = K rows of ldo >= T floats each (the input is only read; the outputs may
+ * not overlap it).  Per trace y, with w_t = 1 where y_t is finite and 0 elsewhere, c >= 0 minimises
+ *     1/2 sum_t w_t (y_t - b - c_t)^2 + lam sum_t s_t,   s_0 = c_0,  s_t = c_t - g c_{t-1} >= 0:
+ * c is the denoised calcium trace, s the spikes.  With x_t = c_t g^-t this is a weighted isotonic regression; it is solved exactly
+ * by pool-adjacent-violators, every lane on a segment of its own, then a stitch of the segments.  One launch, one workgroup per
+ * trace, float64 inside, c and s rounded once to fp32, no host synchronisation, nothing launched on an error.  Sums are taken in a
+ * fixed order without floating-point atomics: the same input gives the same bits.
+ *   g, penalty, baseline, noise   K doubles each on the device, or NULL; NULL or a NaN entry means "estimate" for that trace:
+ *                     g = ac(2) / ac(1) of the autocovariances over the valid pairs (D3); baseline = the baseline_percentile-th
+ *                     percentile (hazen) of the valid frames (D4); noise = 1.4826 MAD / sqrt(2) of the differences of adjacent valid
+ *                     frames (D2); penalty = the lam at which the residual sum of squares reaches noise^2 n_valid, bracketed by at most
+ *                     64 doublings from noise and 32 halvings, inside the kernel (D5)
+ *   info              K rows of 8 doubles: g, penalty, baseline, noise, RSS, n_valid, number of pools, ok (1 / 0)
+ * A trace is refused (ok = 0, its rows of c and s and the first five entries of info NaN) with fewer than 4 valid frames, with fewer
+ * than 2 adjacent valid pairs when the noise or g must be estimated, with ac(1) <= 0 or g outside (0, 1), with a given penalty < 0 or
+ * a given baseline that is not finite (D6).
+ * workspace: caller-owned, 8-byte aligned, dnmf_deconvolve_traces_workspace(K, T) bytes (0 on bad arguments): the pool records of
+ * traces of more than 6144 frames (24 bytes a frame; shorter traces keep them in LDS).  T and K: at most 18 432 each (what
+ * dnmf_clean_traces accepts); larger ones are refused, nothing is truncated.
+ * DNMF_E_NULL: traces, c, s, info or workspace NULL;  DNMF_E_SHAPE: K or T < 1, ldt or ldo < T, baseline_percentile outside
+ * [0, 100];  DNMF_E_UNSUPPORTED: T or K above 18 432;  DNMF_E_WORKSPACE: a short or misaligned workspace. */
+size_t dnmf_deconvolve_traces_workspace(int K, int T);
+int dnmf_deconvolve_traces(const float *traces, long ldt, int K, int T, const double *g, const double *penalty, const double *baseline,
+                           const double *noise, double baseline_percentile, float *c, float *s, long ldo, double *info, void *workspace,
+                           size_t workspace_bytes, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
