@@ -32,9 +32,17 @@ chunk template, where the reference's ``np.dstack`` (``motion_correct_batch_pwri
 to (X, Y) -- a bug of the reference (its rigid path stacks correctly, ``:1860``); the warp sums in fp32 where skimage uses
 float64 (within 1e-5 of the frame's range).
 
+``gSig_filt`` (``high_pass_filter_space`` ``:1262-1270``, K22 ``dnmf_high_pass_frames``, ``csrc/high_pass.hip``): the shifts are
+measured on a spatially high-pass-filtered copy of every frame -- a zero-sum Gaussian disc, reflected borders, slice by slice --
+and applied to the unfiltered frame (``tile_and_correct_3d`` ``:1581-1587``, ``:1640-1641``): what registers a movie whose static
+or slowly varying background outweighs its cells.  A given template is used as given (pass a filtered one); every template
+this class makes is filtered before it is used (``:1825-1829``, ``:1863-1864``).  The reference's 3-D rigid branch raises with
+``gSig_filt`` (``:1598-1600``); here, as an extension, the rigid pass measures on the filtered frames (K8) and moves the
+ORIGINAL frames by K9 with every patch given the frame's rigid shift -- an interpolating move, as the reference's 2-D path
+(``cv2.warpAffine``) makes.
+
 Not offered (``NotImplementedError``): the 2-D piecewise-corrected movie (``cv2.resize`` + ``cv2.remap``), the 2-D rigid
-correction (``cv2.warpAffine``), ``shifts_opencv=False`` (cubic resize of the shift field), memory-mapped files, ``dview``,
-``gSig_filt``.
+correction (``cv2.warpAffine``), ``shifts_opencv=False`` (cubic resize of the shift field), memory-mapped files, ``dview``.
 
 Parity: the 3-D piecewise path -- K8's patch shifts and K9's corrected movie and chunk template -- is pinned by the G11
 fixtures (``tests/golden/make_golden_motion.py``: the reference module itself, run under a Python with scikit-image, with
@@ -51,6 +59,18 @@ from .. import ops
 device = 'cuda'
 
 
+def high_pass_filter_space(img_orig, gSig_filt):
+    """Reference :1262-1270 on the GPU (K22): ``img_orig`` (X, Y) or (X, Y, Z) cast to float32 and correlated, slice by slice,
+    with the zero-sum Gaussian disc of ``gSig_filt[0]`` (``ops.high_pass_taps``), borders reflected (cv2's BORDER_REFLECT).
+    numpy in: float32 numpy out; a CUDA tensor in: a float32 CUDA tensor out."""
+    t = img_orig if torch.is_tensor(img_orig) else torch.from_numpy(np.ascontiguousarray(np.asarray(img_orig, dtype=np.float32)))
+    if t.dim() not in (2, 3):
+        raise ValueError(f"high_pass_filter_space: an image is (X, Y) or (X, Y, Z), got {tuple(t.shape)}")
+    sz = [int(v) for v in t.shape] + [1] * (3 - t.dim())
+    out = ops.high_pass_frames(t.to(device, torch.float32).reshape(1, -1).contiguous(), sz, gSig_filt).view(*t.shape)
+    return out if torch.is_tensor(img_orig) else out.cpu().numpy()
+
+
 class MotionCorrect(object):
     def __init__(self, video, min_mov=None, dview=None, max_shifts=(6, 6, 1), niter_rig=1, splits_rig=1,
                  num_splits_to_process_rig=None, strides=(96, 96, 1), overlaps=(32, 32, 1), splits_els=1,
@@ -60,8 +80,12 @@ class MotionCorrect(object):
         ops._lib.load()   # fail here, loudly, if the HIP library is not built
         if not shifts_opencv:
             raise NotImplementedError("MotionCorrect: shifts_opencv=False (cubic resize of the shift field) is not built")
-        if gSig_filt is not None or dview is not None:
-            raise NotImplementedError("MotionCorrect: gSig_filt / dview are not built")
+        if dview is not None:
+            raise NotImplementedError("MotionCorrect: dview (a process pool) is not built; the GPU walks the video in pieces of its own")
+        if gSig_filt is not None:
+            ops.high_pass_taps(gSig_filt)     # ValueError for an entry <= 0 or not finite
+            gSig_filt = tuple(float(v) for v in gSig_filt) if hasattr(gSig_filt, '__len__') else (float(gSig_filt),) * 2
+        self.gSig_filt = gSig_filt
         if type(video) is not list:
             video = [video]
         self.video = video
@@ -109,6 +133,17 @@ class MotionCorrect(object):
         sz = [int(s) for s in v.shape[1:]]
         return v.to(device, torch.float32).reshape(v.shape[0], -1).contiguous(), sz
 
+    def _filtered(self, frames, sz):
+        """Pieces (f0, rows) of the frames a registration reads: the rows themselves, or with ``gSig_filt`` their high-pass (K22) in
+        pieces of at most 1 GiB."""
+        T, P = frames.shape
+        if self.gSig_filt is None:
+            yield 0, frames
+            return
+        step = max(1, min(T, (1 << 30) // (4 * P)))
+        for f0 in range(0, T, step):
+            yield f0, ops.high_pass_frames(frames[f0:f0 + step], sz, self.gSig_filt)
+
     def motion_correct(self, template=None):
         """Reference :176-211."""
         if self.min_mov is None:
@@ -152,15 +187,16 @@ class MotionCorrect(object):
             frames, sz = self._frames(video_cur)
             if self.min_mov is None:
                 self.min_mov = float(frames.min())
-            if self.total_template_rig is None:
+            if self.gSig_filt is not None:
+                rigid, tmpl, moved = self._rigid_filtered(frames, sz)
+            elif self.total_template_rig is None:
                 tmpl = self._bin_median_3d(frames)                           # :1826
             else:
                 tmpl = torch.as_tensor(np.asarray(self.total_template_rig) if not torch.is_tensor(self.total_template_rig)
                                        else self.total_template_rig).to(device, torch.float32).reshape(-1)
             add = float(np.float32(-self.min_mov))                           # (:2122: passed on as a float32)
             step = max(1, min(frames.shape[0], (1 << 30) // (4 * frames.shape[1]))) if self.save_corrected else frames.shape[0]
-            rigid = None
-            for it in range(max(1, self.niter_rig)):
+            for it in range(max(1, self.niter_rig) if self.gSig_filt is None else 0):
                 last = it == max(1, self.niter_rig) - 1
                 tsum = tcount = None
                 parts, moved = [], []
@@ -175,12 +211,59 @@ class MotionCorrect(object):
                 new_temp = tsum / tcount                                     # nanmean :2057 (0 / 0: NaN)
                 new_temp = torch.where(torch.isnan(new_temp), new_temp[~torch.isnan(new_temp)].min(), new_temp)   # :2058
                 tmpl = new_temp
+                moved = [torch.cat(moved)] if moved else []
             if template is None:
                 self.total_template_rig = tmpl.view(*sz).cpu().numpy()
             self.templates_rig.append(tmpl.view(*sz).cpu().numpy())
             self.shifts_rig += [tuple(float(-v) for v in row) for row in rigid.cpu().numpy()]
             if moved:
-                self.mc.append(torch.cat(moved).view(-1, *sz).permute(1, 2, 3, 0).numpy())
+                self.mc.append(moved[0].view(-1, *sz).permute(1, 2, 3, 0).numpy())
+
+    def _rigid_filtered(self, frames, sz):
+        """The rigid pass with ``gSig_filt`` (an extension: the reference's 3-D rigid branch raises, :1598-1600): the first template
+        is the binned median of the FILTERED movie (:1825-1829) or the one given, as given; K8 measures every frame's shift on the
+        filtered rows (nothing filtered is moved); K9 moves the ORIGINAL rows, every patch given the frame's rigid shift in the
+        sign convention of ``x/y/z_shifts_els``; the new template is the NaN-aware mean of the moved originals, NaN -> min
+        (:2057-2058), then filtered (:1863-1864).  -> (shifts (T, 3) as K8 returns them, the last template (P,), [moved rows on
+        the host] with ``save_corrected``)."""
+        T, P = frames.shape
+        strides, overlaps, max_shifts = self._p3()
+        NP = len(ops.patch_grid(sz, strides, overlaps)[1])
+        if self.total_template_rig is None:
+            pieces = [rows for _, rows in self._filtered(frames, sz)]
+            tmpl = self._bin_median_3d(pieces[0] if len(pieces) == 1 else torch.cat(pieces))
+            del pieces
+        else:
+            tmpl = torch.as_tensor(np.asarray(self.total_template_rig) if not torch.is_tensor(self.total_template_rig)
+                                   else self.total_template_rig).to(device, torch.float32).reshape(-1)
+        add = float(np.float32(-self.min_mov))
+        step = max(1, min(T, (1 << 30) // (4 * P)))
+        niter = max(1, self.niter_rig)
+        for it in range(niter):
+            keep = self.save_corrected and it == niter - 1
+            tsum = tcount = None
+            parts, moved = [], []
+            for f0, rows in self._filtered(frames, sz):
+                r = ops.rigid_correct(rows, tmpl, sz, self.max_shifts, self.upsample_factor_fft, add_to_movie=add,
+                                      border_nan=self.border_nan, want_frames=False)[0]
+                parts.append(r)
+                del rows
+                for g0 in range(0, r.shape[0], step):
+                    table = self._rigid_table(r[g0:g0 + step], NP)
+                    out, tsum, tcount = ops.apply_pwrigid(frames[f0 + g0:f0 + g0 + step], table, sz, strides, overlaps,
+                                                          add_to_movie=add, tsum=tsum, tcount=tcount)
+                    if keep:
+                        moved.append(out.cpu())
+            new_temp = tsum / tcount                                         # nanmean :2057 (0 / 0: NaN)
+            new_temp = torch.where(torch.isnan(new_temp), new_temp[~torch.isnan(new_temp)].min(), new_temp)   # :2058
+            tmpl = ops.high_pass_frames(new_temp.view(1, P), sz, self.gSig_filt).view(P)     # :1863-1864
+        return torch.cat(parts), tmpl, ([torch.cat(moved)] if moved else [])
+
+    def _rigid_table(self, rigid, NP):
+        """(B, 3) rigid shifts as K8 returns them -> the (B, NP, 3) table K9 takes: every patch the frame's shift, signs as in
+        ``x/y/z_shifts_els`` (-x, -y, +z)."""
+        sign = torch.tensor([-1.0, -1.0, 1.0], dtype=torch.float32, device=rigid.device)
+        return (rigid * sign)[:, None, :].expand(-1, NP, -1).contiguous()
 
     def motion_correct_pwrigid(self, template=None, show_template=False):
         """Reference :260-328: fills ``x_shifts_els``, ``y_shifts_els``, ``z_shifts_els`` (one (NP,) array per frame),
@@ -188,7 +271,10 @@ class MotionCorrect(object):
         ``total_template_els``.  3-D videos with ``save_corrected=True`` also get the piecewise-rigid corrected movie (K9):
         ``mc_els`` (one (X, Y, Z, T) float32 array per video; ``mc`` keeps the rigid pass's movie, as the reference leaves
         it, :328), ``templates_els`` (one (X, Y, Z) chunk template per video, the NaN-aware mean of the corrected frames,
-        :2057-2058) and, when ``template`` is None, ``total_template_els`` = that template."""
+        :2057-2058) and, when ``template`` is None, ``total_template_els`` = that template.  With ``gSig_filt`` the shifts are
+        measured on the high-pass-filtered frames (K22) against the template as given -- pass a filtered one -- and K9 moves the
+        original frames (:1640-1641); without a template the pass registers against the filtered ``total_template_rig``, and
+        ``total_template_els`` is that filtered image unless a corrected movie is made."""
         self.x_shifts_els, self.y_shifts_els = [], []
         if self.is3D:
             self.z_shifts_els = []
@@ -208,9 +294,11 @@ class MotionCorrect(object):
                 tmpl = torch.as_tensor(np.asarray(template) if not torch.is_tensor(template) else template).to(
                     device, torch.float32).reshape(-1)
             self.total_template_els = tmpl.view(*sz) if self.is3D else tmpl.view(*sz[:2])
-            rigid, patch = ops.register_patches(frames, tmpl, sz, strides, overlaps, max_shifts,
-                                                self.max_deviation_rigid, self.upsample_factor_fft,
-                                                add_to_movie=-self.min_mov)
+            # (with gSig_filt the shifts are measured on the filtered rows, :1581-1587; frames are independent)
+            parts = [ops.register_patches(rows, tmpl, sz, strides, overlaps, max_shifts, self.max_deviation_rigid,
+                                          self.upsample_factor_fft, add_to_movie=-self.min_mov)[1]
+                     for _, rows in self._filtered(frames, sz)]
+            patch = parts[0] if len(parts) == 1 else torch.cat(parts)
             dims, starts = ops.patch_grid(sz, strides, overlaps)
             nd = 3 if self.is3D else 2
             grid = [tuple(int(v) for v in np.unravel_index(q, dims))[:nd] for q in range(len(starts))]
@@ -294,7 +382,9 @@ class MotionCorrect(object):
         """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
         made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,
         ``threshold``, ``background``): the ``points`` ``apply_shifts_points`` takes, float64 numpy, brightest first.  The
-        reference has no counterpart (its real data comes with annotated positions).
+        reference has no counterpart (its real data comes with annotated positions).  With ``gSig_filt`` and ``template=None``
+        the stored template is a high-pass-filtered image (zero mean, negative around every cell) unless a corrected movie was
+        made; pass ``background=0`` or search a summary image instead.
 
         ``image`` (keyword, default ``'template'``: the above, unchanged): ``'corr'``, ``'max'`` or ``'std'`` search that summary
         image of the stored corrected movie (``summary_images()``, K18; needs ``save_corrected=True``) -- the template averages
@@ -383,4 +473,4 @@ class MotionCorrect(object):
         return {'max_shifts': self.max_shifts, 'strides': self.strides, 'overlaps': self.overlaps,
                 'upsample_factor_grid': self.upsample_factor_grid, 'max_deviation_rigid': self.max_deviation_rigid,
                 'shifts_opencv': self.shifts_opencv, 'nonneg_movie': self.nonneg_movie, 'border_nan': self.border_nan,
-                'is3D': self.is3D}
+                'is3D': self.is3D, 'gSig_filt': self.gSig_filt}

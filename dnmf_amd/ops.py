@@ -1565,6 +1565,84 @@ def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, b
     return c, s, info
 
 
+def high_pass_taps(gSig):
+    """The (n, n) float64 numpy kernel of the reference's ``high_pass_filter_space`` (MotionCorrect.py:1263-1269):
+    ``n = (3 gSig[0]) // 2 * 2 + 1`` (entry 0 decides, the kernel is square), ``cv2.getGaussianKernel(n, gSig[0])`` written out
+    (``exp(-x^2 / (2 sigma^2))`` at ``x = i - (n - 1) / 2`` over its sum), its outer product with itself, the mean of the entries
+    ``>= ker2D[:, 0].max()`` (a disc) subtracted from those entries and every other entry set to 0: the kernel sums to zero.
+    The Gaussian is evaluated in OpenCV's order of operations -- ``exp((-0.5 / sigma^2) x x)``, times the reciprocal of the sum --
+    because the disc's rim has exact ties (6^2 + 8^2 = 10^2 at gSig 7) that the last bit decides: 309 taps this way, 317 with
+    ``-x x / (2 sigma^2)``."""
+    import numpy as np
+    try:
+        g = [float(v) for v in gSig]
+    except TypeError:
+        g = [float(gSig)]
+    if not g or any(not np.isfinite(v) or v <= 0 for v in g):
+        raise ValueError(f"high_pass_taps: gSig must be positive and finite, got {gSig!r}")
+    n = int((3 * g[0]) // 2 * 2 + 1)
+    x = np.arange(n, dtype=np.float64) - (n - 1) / 2
+    ker = np.exp((-0.5 / (g[0] * g[0])) * x * x)
+    ker = ker * (1.0 / ker.sum())
+    ker2D = ker[:, None] * ker[None, :]
+    nz = np.nonzero(ker2D >= ker2D[:, 0].max())
+    zz = np.nonzero(ker2D < ker2D[:, 0].max())
+    ker2D[nz] -= ker2D[nz].mean()
+    ker2D[zz] = 0
+    return ker2D
+
+
+_HIGH_PASS_TAPS = {}
+
+
+def _span(t, B, P):
+    """[first, last) byte addresses of rows ``t`` (the first B rows, or all of them for B = None)."""
+    rows = t.shape[0] if B is None else B
+    return t.data_ptr(), t.data_ptr() + 4 * ((rows - 1) * _ld(t, P) + P)
+
+
+def high_pass_frames(frames, sz, gSig, frame_ids=None, out=None, taps=None):
+    """K22.  frames (rows, ld >= X Y Z) fp32 CUDA rows -> ``out`` (B, P) fp32 CUDA rows (or (>= B, ldo >= P) given; it may not
+    overlap ``frames``): every frame correlated slice by slice with ``high_pass_taps(gSig)`` rounded to fp32, reflected at the
+    borders with period 2 N (cv2's BORDER_REFLECT), taps that are zero not applied -- ``high_pass_filter_space`` of the
+    reference.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order).  ``taps``: an (n, n) array to use in place of
+    the kernel of ``gSig`` (n odd, at most 31).  fp32 FMAs in a fixed order: the same input gives the same bits."""
+    import numpy as np
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    _rows(frames, "high_pass_frames", "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"high_pass_frames: frames are rows (T, ld), got {tuple(frames.shape)}")
+    dev = frames.device
+    if taps is None:
+        k = high_pass_taps(gSig)
+        key = (k.tobytes(), str(dev))
+        if key not in _HIGH_PASS_TAPS:
+            _HIGH_PASS_TAPS[key] = torch.from_numpy(k.astype(np.float32)).to(dev)
+        tp = _HIGH_PASS_TAPS[key]
+    else:
+        tp = torch.as_tensor(np.asarray(taps.cpu() if torch.is_tensor(taps) else taps, dtype=np.float32)).to(dev).contiguous()
+        if tp.dim() != 2 or tp.shape[0] != tp.shape[1]:
+            raise ValueError(f"high_pass_frames: taps are (n, n), got {tuple(tp.shape)}")
+    fid = _i32(frame_ids, dev) if frame_ids is not None else None
+    B = fid.numel() if fid is not None else frames.shape[0]
+    if out is None:
+        out = torch.empty((B, P), dtype=torch.float32, device=dev)
+    _rows(out, "high_pass_frames", "out", P, f" and rows of {P} floats")
+    if out.dim() != 2 or out.shape[0] < B:
+        raise ValueError(f"high_pass_frames: out must hold {B} rows, got {tuple(out.shape)}")
+    if B >= 1 and P >= 1:
+        (f0, f1), (o0, o1) = _span(frames, None, P), _span(out, B, P)
+        if o0 < f1 and f0 < o1:
+            raise ValueError("high_pass_frames: out overlaps frames (a voxel's neighbours are read after it is written)")
+    lib = _lib.load()
+    with _timed("high_pass_frames"):
+        rc = lib.dnmf_high_pass_frames(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3((X, Y, Z)), B, tp.data_ptr(), tp.shape[0],
+                                       out.data_ptr(), _ld(out, P), _stream())
+    _lib.check(rc, "dnmf_high_pass_frames")
+    return out
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

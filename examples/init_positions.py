@@ -56,6 +56,7 @@ def main():
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
     ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
     ap.add_argument("--motion-smooth", type=float, default=0.0, help="--gn: weight of the temporal smoothness prior (0: none)")
+    ap.add_argument("--gsig", type=float, default=None, help="register on high-pass-filtered frames: gSig_filt=(S, S) (K22)")
     ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
     a.detect = a.detect or a.detect_image is not None
@@ -71,7 +72,8 @@ def main():
     truth = np.asarray(dataset.positions)                            # (K, 3, T)
     stride = a.stride
     mc = MotionCorrect(video, max_shifts=(12, 12, 1), strides=(stride, stride, 1), overlaps=(stride // 2, stride // 2, 1),
-                       max_deviation_rigid=3, is3D=True, pw_rigid=True, save_corrected=image != "template")
+                       max_deviation_rigid=3, is3D=True, pw_rigid=True, save_corrected=image != "template",
+                       gSig_filt=None if a.gsig is None else (a.gsig, a.gsig))
     mc.motion_correct()                                              # template=None: rigid pass first
     # pts: the centres the tracks start from; sel / tr: rows of pts and the simulated neurons they are judged against
     if a.detect:

@@ -792,6 +792,21 @@ int dnmf_deconvolve_traces(const float *traces, long ldt, int K, int T, const do
                            const double *noise, double baseline_percentile, float *c, float *s, long ldo, double *info, void *workspace,
                            size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K22: spatial high-pass of every frame (the filter MotionCorrect's gSig_filt registers on) -----------------------------------------
+ * For B frames of a volume (X, Y, Z) (rows of ldf >= P floats, voxel p = (x Y + y) Z + z; row frame_ids[b] of frames, or b) and an
+ * (n, n) array of fp32 taps on the device, n odd, h = n / 2:
+ *     out[b, x, y, z] = sum over i, j with taps[i, j] != 0 of taps[i, j] * in[b, r_X(x + i - h), r_Y(y + j - h), z],
+ * r_N the reflection with period 2 N (m = p mod 2 N; m if m < N, else 2 N - 1 - m): cv2.filter2D with BORDER_REFLECT, slice by slice,
+ * as high_pass_filter_space (reference MotionCorrect.py:1262-1270) applies it.  An extent shorter than h (several bounces) and an
+ * extent of 1 are valid.  Taps that are zero are not applied, so a NaN spreads over the support of the taps only.
+ * tests/high_pass_restatement.py is the definition in float64.  fp32 fused multiply-adds in a fixed order (j ascending, then i
+ * ascending), no atomics: the same input gives the same bits.  One launch, no workspace, no host synchronisation.
+ *   out      B rows of ldo >= P floats (floats beyond P are left alone); it may not overlap the rows read.
+ * DNMF_E_NULL: frames, sz, taps or out NULL;  DNMF_E_SHAPE: a size, B or n < 1, an even n, ldf or ldo < P;  DNMF_E_UNSUPPORTED: n > 31
+ * (gSig > 10), 2^31 voxels or more.  Nothing is launched on an error. */
+int dnmf_high_pass_frames(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, const float *taps, int n,
+                          float *out, long ldo, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
