@@ -487,6 +487,18 @@ class ExponentialFP(nn.Module):
         return (b, f) if on_gpu else (b.cpu().numpy(), f.cpu().numpy())
 
     @staticmethod
+    def background_rank(video, iters=3, rank=2, inner=3):
+        """The rank-R background of ``video`` as it is (K23, ``ops.background_fit_rank``), 2 <= R <= 8: R images and R time courses,
+        ``(b (R, X, Y, Z), f (R, T))`` fp32, all >= 0 with mean(f_j) = 1, for a movie whose background has sources with different
+        time courses (a constant offset, a decaying glow, a rising one).  ``video`` and the return types as ``background`` has
+        them; ``rank=1`` is ``background(video, iters)``."""
+        if rank == 1:
+            return ExponentialFP.background(video, iters)
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "background_rank")
+        b, f = ops.background_fit_rank(rows, sz, iters, rank, inner=inner)
+        return (b, f) if on_gpu else (b.cpu().numpy(), f.cpu().numpy())
+
+    @staticmethod
     def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None):
         """Where the neurons are in every frame of ``video`` -- (T, X, Y, Z) values, or frames that already live on the GPU as
         ``(rows (T, P), sz)`` or a ``ResidentLoader``: ``(P_T (K,3,T) float64, amplitudes (K,T))`` by K15
@@ -582,7 +594,8 @@ class DeformableNMF:
         self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
         self._D_dev = None         # (id(self.D), fp32 device copy of D flattened to (P,K))
         self.stream_loader = True  # stage host loaders on the GPU once per pass (see _stage_epoch)
-        # after update_background: (b (X,Y,Z), f (T,)) fp32 CUDA, the rank-1 background b f_t of frame t in frame coordinates
+        # after update_background: (b (X,Y,Z), f (T,)) fp32 CUDA, the rank-1 background b f_t of frame t in frame coordinates;
+        # after update_background_rank with R >= 2: (b (R,X,Y,Z), f (R,T)), the background sum_j b_j f_j[t]
         self.background = None
         # after clean_traces: a, b, F0, fitted, n_outliers per neuron (CUDA tensors, (K,)) of that call
         self.last_clean = None
@@ -855,11 +868,30 @@ class DeformableNMF:
         camera offset, autofluorescence and out-of-focus glow do not move with the animal's neurons, and a static b needs no
         warp.  Stores and returns ``self.background = (b, f)``, fp32 CUDA, f (T,) indexed by frame time (0 for a frame the
         loader did not serve)."""
-        self._background_refusals(loader, "update_background")
+        return self._update_background(loader, iters, 1, 3, "update_background")
+
+    def update_background_rank(self, loader, iters=3, rank=2, inner=3):
+        """``update_background`` with R images and R time courses (K23, ``ops.background_fit_rank``), 2 <= R <= 8: Y_t ~ M_t +
+        sum_j b_j f_j[t], b (R, X, Y, Z) and f (R, T), each f_j of mean 1 over the frames served; ``inner``: the coordinate sweeps
+        per frame and per voxel of every half-step.  The time courses start as the indicators of R contiguous blocks of the
+        frame times, so the frames go through in the order of their times.  ``rank=1`` is ``update_background(loader, iters)``,
+        whatever ``inner`` is."""
+        return self._update_background(loader, iters, rank, inner, "update_background_rank")
+
+    def _update_background(self, loader, iters, rank, inner, who):
+        self._background_refusals(loader, who)
+        if int(rank) != rank or not 1 <= rank <= ops.BACKGROUND_RANKS[1]:
+            raise ValueError(f"{who}: rank={rank!r} (1 .. {ops.BACKGROUND_RANKS[1]})")
         fp = self.fp
         sz, P = fp.sz_list, fp.P
         with torch.no_grad():
             frames, order = self._gather_frames(loader)
+            if rank > 1:
+                if rank > order.numel():
+                    raise ValueError(f"{who}: rank={rank} for the {order.numel()} frames served")
+                if not bool((order[1:] > order[:-1]).all()):
+                    at = torch.argsort(order.long())
+                    frames, order = frames.index_select(0, at), order[at]
             C = self.C.to(device, torch.float32).contiguous()
             beta = fp.beta.detach()
             piece = max(1, min(frames.shape[0], (1 << 30) // (4 * P), K2_MAX_FRAMES))
@@ -872,15 +904,18 @@ class DeformableNMF:
                 self._ws_k2 = out["workspace"]
                 return out["recon"]
 
-            b, f_served = ops.background_fit(frames, sz, iters, sub_fn=predict, piece=piece)
-            f = torch.zeros((fp.T,), dtype=torch.float32, device=device)
-            f[order.long()] = f_served
+            if rank == 1:
+                b, f_served = ops.background_fit(frames, sz, iters, sub_fn=predict, piece=piece)
+            else:
+                b, f_served = ops.background_fit_rank(frames, sz, iters, rank, sub_fn=predict, piece=piece, inner=inner)
+            f = torch.zeros(f_served.shape[:-1] + (fp.T,), dtype=torch.float32, device=device)
+            f[..., order.long()] = f_served
         self.background = (b, f)
         return self.background
 
     def background_loader(self, loader):
         """A ``ResidentLoader`` over ``max(Y_t - b f_t, 0)``, the frames of ``loader`` without the fitted background
-        (``update_background``; ValueError before one was fitted).  The clamp is there because the multiplicative updates need
+        (``update_background``; ValueError before one was fitted; ``max(Y_t - sum_j b_j f_j[t], 0)`` for one of rank R).  The clamp is there because the multiplicative updates need
         Y >= 0, as the datasets' own clamp does.  It keeps the loader's batch size, shuffle flag, generator and volume, and
         serves frame t as row t: a ``ResidentLoader`` or a ``DataLoader`` whose pass covers the frames 0 .. n-1."""
         if self.background is None:
@@ -1590,7 +1625,7 @@ class DeformableNMF:
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
-            background=0):
+            background=0, background_rank=1):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
@@ -1600,13 +1635,16 @@ class DeformableNMF:
         ``update_background(testloader, iters=n)`` on the frames as given, and the following sweeps read
         ``background_loader(...)`` of both loaders, rebuilt after every background update; the first sweep sees the raw frames,
         because a background fitted before the model explains anything would take the neurons' mean light with it.  0: no
-        background term, the path of a call without the argument."""
+        background term, the path of a call without the argument.  ``background_rank=R``, 2 .. 8 (K23): those updates fit R
+        images with R time courses (``update_background_rank``); 1: the rank-1 term."""
         _check_motion_solver(motion_solver, "fit")
         kept = self.motion_smooth
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
         _check_registered(registered, "fit")
         if int(background) != background or background < 0:
             raise ValueError(f"fit: background is a number of alternations >= 0, got {background!r}")
+        if int(background_rank) != background_rank or not 1 <= background_rank <= ops.BACKGROUND_RANKS[1]:
+            raise ValueError(f"fit: background_rank={background_rank!r} (1 .. {ops.BACKGROUND_RANKS[1]})")
         if background:
             self._background_refusals(dataloader, "fit(background=)")
             self._background_refusals(testloader, "fit(background=)")
@@ -1619,7 +1657,10 @@ class DeformableNMF:
                 out = self.update_footprints(test, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
                                              iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
                 if background:
-                    self.update_background(testloader, iters=background)
+                    if background_rank == 1:
+                        self.update_background(testloader, iters=background)
+                    else:
+                        self.update_background_rank(testloader, iters=background, rank=background_rank)
                     if sweep + 1 < outer:
                         train = test = None      # the last sweep's cleaned frames go before the next ones are made
                         test = self.background_loader(testloader)

@@ -105,6 +105,11 @@ SIGNATURES = {
     "dnmf_background_accum_workspace": (_sz, [_l, _i, _i]),
     "dnmf_background_accum": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "dnmf_background_subtract": (_i, [_vp, _l, _vp, _vp, _vp, _i, _vp, _l, _i, _vp, _l, _i, _vp]),
+    "dnmf_background_dots_rank_workspace": (_sz, [_l, _i, _i]),
+    "dnmf_background_dots_rank": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _l, _i, _i, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_background_accum_rank_workspace": (_sz, [_l, _i, _i, _i]),
+    "dnmf_background_accum_rank": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _l, _i, _i, _i, _i, _i, _vp, _sz, _vp, _l, _vp, _vp, _vp]),
+    "dnmf_background_subtract_rank": (_i, [_vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _vp, _l, _i, _vp, _l, _i, _vp]),
     "dnmf_clean_traces_workspace": (_sz, [_i, _i]),
     "dnmf_clean_traces": (_i, [_vp, _l, _i, _i, _d, _d, _i, _i, _i, _i, _i, _d, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                _vp]),

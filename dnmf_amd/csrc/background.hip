@@ -10,6 +10,10 @@
 //           segment of frames; the sums live in registers, f_t is a uniform load.  A second launch adds the segments to the
 //           caller's state in their order, a third writes b.
 // No floating-point atomics: the same input at the same addresses gives the same bits.
+//
+// K23, further down: the same two passes for R images and R time courses (2 <= R <= 8) with R sums where K19 has one, the R x R Gram
+// matrix of the factor held fixed from a launch of its own, and a per-frame (per-voxel) non-negative solve by coordinate sweeps in
+// the finishing launch; tests/background_rank_restatement.py is its definition.  K19's kernels are as they were.
 #include <cstdint>
 
 #include "common.hpp"
@@ -309,6 +313,388 @@ __global__ __launch_bounds__(BG_THREADS) void background_subtract_kernel(Subtrac
     if (live > 3) o[p + 3] = r.w;
 }
 
+// ---- K23: rank R ---------------------------------------------------------------------------------------------------------------
+// R images b_c (rows of ldb floats) and R time courses f_c (rows of ldf_t floats), 2 <= R <= 8, R a template parameter so that the
+// R sums of a lane are registers.  A half-step is still one pass over the movie: the pass leaves R sums per frame (per voxel), a
+// small launch leaves the R x R Gram matrix of the factor held fixed, and the last launch solves every frame's (voxel's) R-variable
+// non-negative problem by `inner` cyclic coordinate sweeps in float64 from its current value, the Gram matrix in LDS.
+constexpr int BGR_MIN = 2, BGR_MAX = 8;
+constexpr long BG_GRAM_CHUNK = 4096;             // elements of a workgroup of the Gram launch
+constexpr size_t BGR_HEADER = 512;               // bytes: the R x R Gram matrix, float64, row-major
+
+__host__ __device__ constexpr int tri_at(int j, int i) { return j * (j + 1) / 2 + i; }   // (j, i), i <= j, in the packed triangle
+
+// x_j <- max(0, (N_j - sum_{i != j} G_ji x_i) / G_jj), 0 where G_jj == 0, j = 0 .. R-1, `inner` times; the products and
+// differences one by one, i ascending (tests/background_rank_restatement.py: sweep does the same operations in the same order)
+template <int R>
+__device__ __forceinline__ void bg_sweep(const double *G, const double (&N)[R], double (&x)[R], int inner) {
+    for (int it = 0; it < inner; ++it) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            double s = N[j];
+#pragma unroll
+            for (int i = 0; i < R; ++i)
+                if (i != j) s = s - G[j * R + i] * x[i];
+            const double d = G[j * R + j];
+            x[j] = d != 0.0 ? fmax(0.0, s / d) : 0.0;
+        }
+    }
+}
+
+// The packed lower triangle of X X^T over a chunk of the n columns of the R rows x (ld floats apart): one partial per workgroup.
+template <int R>
+__global__ __launch_bounds__(BG_THREADS) void background_gram_kernel(const float *__restrict__ x, long ld, long n, double *__restrict__ part) {
+    constexpr int NT = R * (R + 1) / 2;
+    __shared__ double red[BG_WAVES][NT];
+    const long i0 = (long)blockIdx.x * BG_GRAM_CHUNK;
+    const long i1 = n - i0 < BG_GRAM_CHUNK ? n : i0 + BG_GRAM_CHUNK;
+    double acc[NT];
+#pragma unroll
+    for (int k = 0; k < NT; ++k) acc[k] = 0.0;
+    for (long i = i0 + threadIdx.x; i < i1; i += BG_THREADS) {
+        double v[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) v[j] = (double)x[(long)j * ld + i];
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+#pragma unroll
+            for (int c = 0; c <= j; ++c) acc[tri_at(j, c)] = fma(v[j], v[c], acc[tri_at(j, c)]);
+    }
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+        const double s = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < NT) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < BG_WAVES; ++w) s += red[w][threadIdx.x];
+        part[(long)blockIdx.x * NT + threadIdx.x] = s;
+    }
+}
+
+// G (R x R, both triangles) = (first ? 0 : G) + the chunks in their order
+template <int R>
+__global__ __launch_bounds__(64) void background_gram_reduce_kernel(const double *__restrict__ part, long nchunks, int first, double *G) {
+    constexpr int NT = R * (R + 1) / 2;
+    const int k = threadIdx.x;
+    if (k >= R * R) return;
+    const int j = k / R, i = k - j * R;
+    const int t = j >= i ? tri_at(j, i) : tri_at(i, j);
+    double s = first ? 0.0 : G[k];
+    for (long c = 0; c < nchunks; ++c) s += part[c * NT + t];
+    G[k] = s;
+}
+
+struct DotsRankArgs {
+    const float *frames, *sub, *b;
+    long ldf, lds, ldb, P, seglen;
+    const int *frame_ids;
+    int nseg;
+    double *part;
+};
+
+// part[(frame, segment)][c] = sum over the segment's voxels of b_c (y - m)
+template <int R, bool SUB>
+__global__ __launch_bounds__(BG_THREADS) void background_dots_rank_kernel(DotsRankArgs a) {
+    __shared__ double red[BG_WAVES][R];
+    const int tid = threadIdx.x;
+    const long bid = blockIdx.x;
+    const int j = (int)(bid / a.nseg), s = (int)(bid - (long)j * a.nseg);
+    const long p0 = (long)s * a.seglen;
+    const long n = (a.P - p0 < a.seglen ? a.P - p0 : a.seglen);
+    const float *__restrict__ y = a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf + p0;
+    const float *__restrict__ m = SUB ? a.sub + (long)j * a.lds + p0 : nullptr;
+    const float *__restrict__ b = a.b + p0;
+    double acc[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) acc[c] = 0.0;
+    // as in K19: 16-byte loads from the first voxel at which y, m and every row of b are aligned, else float by float
+    const unsigned ph = word_phase(y);
+    bool vec = !SUB || word_phase(m) == ph;
+#pragma unroll
+    for (int c = 0; c < R; ++c) vec = vec && word_phase(b + (long)c * a.ldb) == ph;
+    long head = vec ? (long)((4 - ph) & 3) : n;
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    for (long i = tid; i < head; i += BG_THREADS) {
+        const double r = SUB ? (double)y[i] - (double)m[i] : (double)y[i];
+#pragma unroll
+        for (int c = 0; c < R; ++c) acc[c] = fma((double)b[(long)c * a.ldb + i], r, acc[c]);
+    }
+    const float4 *y4 = reinterpret_cast<const float4 *>(y + head);
+    const float4 *m4 = SUB ? reinterpret_cast<const float4 *>(m + head) : nullptr;
+#pragma unroll 2
+    for (long i = tid; i < n4; i += BG_THREADS) {
+        const float4 yv = y4[i];
+        const float4 mv = SUB ? m4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const double r0 = SUB ? (double)yv.x - (double)mv.x : (double)yv.x, r1 = SUB ? (double)yv.y - (double)mv.y : (double)yv.y;
+        const double r2 = SUB ? (double)yv.z - (double)mv.z : (double)yv.z, r3 = SUB ? (double)yv.w - (double)mv.w : (double)yv.w;
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+            const float4 bv = reinterpret_cast<const float4 *>(b + (long)c * a.ldb + head)[i];
+            acc[c] = fma((double)bv.x, r0, acc[c]);
+            acc[c] = fma((double)bv.y, r1, acc[c]);
+            acc[c] = fma((double)bv.z, r2, acc[c]);
+            acc[c] = fma((double)bv.w, r3, acc[c]);
+        }
+    }
+    for (long i = head + 4 * n4 + tid; i < n; i += BG_THREADS) {
+        const double r = SUB ? (double)y[i] - (double)m[i] : (double)y[i];
+#pragma unroll
+        for (int c = 0; c < R; ++c) acc[c] = fma((double)b[(long)c * a.ldb + i], r, acc[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+        const double v = wave_sum(acc[c]);
+        if ((tid & 63) == 0) red[tid >> 6][c] = v;
+    }
+    __syncthreads();
+    if (tid < R) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < BG_WAVES; ++w) t += red[w][tid];
+        a.part[bid * R + tid] = t;
+    }
+}
+
+// Per frame: N_c = the segments in their order, then the sweeps from the frame's current f; num is (R, B), q_out the Gram matrix
+template <int R>
+__global__ __launch_bounds__(BG_THREADS) void background_dots_rank_finish_kernel(const double *__restrict__ part, const double *__restrict__ Q,
+                                                                                 int nseg, int B, int inner, float *f, long ldf_t,
+                                                                                 double *__restrict__ num, double *__restrict__ q_out) {
+    __shared__ double G[R * R];
+    if (threadIdx.x < R * R) G[threadIdx.x] = Q[threadIdx.x];
+    __syncthreads();
+    if (blockIdx.x == 0 && q_out && threadIdx.x < R * R) q_out[threadIdx.x] = G[threadIdx.x];
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B) return;
+    double N[R], x[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+        double acc = 0.0;
+        for (int s = 0; s < nseg; ++s) acc += part[((long)t * nseg + s) * R + c];
+        N[c] = acc;
+        x[c] = (double)f[(long)c * ldf_t + t];
+        if (num) num[(long)c * B + t] = acc;
+    }
+    bg_sweep<R>(G, N, x, inner);
+#pragma unroll
+    for (int c = 0; c < R; ++c) f[(long)c * ldf_t + t] = (float)x[c];
+}
+
+struct AccumRankArgs {
+    const float *frames, *sub, *f;
+    long ldf, lds, ldf_t, P;
+    const int *frame_ids;
+    int B, seglen;
+    double *part;
+    size_t stride;
+};
+
+// part[segment][c][p] = sum over the segment's frames of f_c[t] (y - m): four voxels a lane, 4 R float64 sums in registers
+template <int R, bool SUB>
+__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_kernel(AccumRankArgs a) {
+    const long p = (long)blockIdx.x * BG_TILE + 4 * (long)threadIdx.x;
+    if (p >= a.P) return;
+    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
+    const int seg = blockIdx.y;
+    const int f0 = seg * a.seglen, f1 = min(a.B, f0 + a.seglen);
+    double s[R][4];
+#pragma unroll
+    for (int c = 0; c < R; ++c) s[c][0] = s[c][1] = s[c][2] = s[c][3] = 0.0;
+#pragma unroll 2
+    for (int j = f0; j < f1; ++j) {
+        const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
+        double r0 = (double)y.x, r1 = (double)y.y, r2 = (double)y.z, r3 = (double)y.w;
+        if (SUB) {
+            const float4 m = load4(a.sub + (long)j * a.lds, p, live);
+            r0 -= (double)m.x, r1 -= (double)m.y, r2 -= (double)m.z, r3 -= (double)m.w;
+        }
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+            const double fc = (double)a.f[(long)c * a.ldf_t + j];
+            s[c][0] = fma(fc, r0, s[c][0]);
+            s[c][1] = fma(fc, r1, s[c][1]);
+            s[c][2] = fma(fc, r2, s[c][2]);
+            s[c][3] = fma(fc, r3, s[c][3]);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+        double *out = a.part + ((size_t)seg * R + c) * a.stride + p;
+        out[0] = s[c][0];
+        if (live > 1) out[1] = s[c][1];
+        if (live > 2) out[2] = s[c][2];
+        if (live > 3) out[3] = s[c][3];
+    }
+}
+
+// sums[c][p] = (first ? 0 : sums[c][p]) + the segments in their order; c rides on gridDim.y
+__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_reduce_kernel(const double *__restrict__ part, size_t stride, int nseg, int R,
+                                                                                  long P, int first, double *__restrict__ sums) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
+    if (i >= P) return;
+    double acc = first ? 0.0 : sums[(size_t)c * stride + i];
+    for (int s = 0; s < nseg; ++s) acc += part[((size_t)s * R + c) * stride + i];
+    sums[(size_t)c * stride + i] = acc;
+}
+
+// Per voxel: the sweeps from the voxel's current b with W in LDS; num is (R, P), w_out the Gram matrix
+template <int R>
+__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_finish_kernel(const double *__restrict__ sums, size_t stride,
+                                                                                  const double *__restrict__ W, long P, int inner, float *b,
+                                                                                  long ldb, double *__restrict__ num, double *__restrict__ w_out) {
+    __shared__ double G[R * R];
+    if (threadIdx.x < R * R) G[threadIdx.x] = W[threadIdx.x];
+    __syncthreads();
+    if (blockIdx.x == 0 && w_out && threadIdx.x < R * R) w_out[threadIdx.x] = G[threadIdx.x];
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    double N[R], x[R];
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+        N[c] = sums[(size_t)c * stride + p];
+        x[c] = (double)b[(long)c * ldb + p];
+        if (num) num[(long)c * P + p] = N[c];
+    }
+    bg_sweep<R>(G, N, x, inner);
+#pragma unroll
+    for (int c = 0; c < R; ++c) b[(long)c * ldb + p] = (float)x[c];
+}
+
+struct SubtractRankArgs {
+    const float *frames, *b, *f;
+    long ldf, ldo, ldb, ldf_t, P, ntiles;
+    const int *frame_ids, *times;
+    int nf, clamp, R;
+    float *out;
+};
+
+// out = (float)((double)y - sum_c (double)b_c (double)f_c[t]), the products added one by one, c ascending
+__global__ __launch_bounds__(BG_THREADS) void background_subtract_rank_kernel(SubtractRankArgs a) {
+    const long bid = blockIdx.x;
+    const int j = (int)(bid / a.ntiles);
+    const long p = (bid - (long)j * a.ntiles) * BG_TILE + 4 * (long)threadIdx.x;
+    if (p >= a.P) return;
+    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
+    const int t = a.times ? a.times[j] : j;
+    const bool known = t >= 0 && t < a.nf;
+    const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    if (known)
+        for (int c = 0; c < a.R; ++c) {
+            const double fc = (double)a.f[(long)c * a.ldf_t + t];
+            const float4 b = load4(a.b + (long)c * a.ldb, p, live);
+            s0 = s0 + (double)b.x * fc, s1 = s1 + (double)b.y * fc, s2 = s2 + (double)b.z * fc, s3 = s3 + (double)b.w * fc;
+        }
+    float4 r;
+    r.x = (float)((double)y.x - s0), r.y = (float)((double)y.y - s1), r.z = (float)((double)y.z - s2), r.w = (float)((double)y.w - s3);
+    if (a.clamp) r.x = fmaxf(r.x, 0.0f), r.y = fmaxf(r.y, 0.0f), r.z = fmaxf(r.z, 0.0f), r.w = fmaxf(r.w, 0.0f);
+    if (!known) r.x = r.y = r.z = r.w = __builtin_nanf("");   // a time f has no entry for: the row becomes NaN
+    float *o = a.out + (long)j * a.ldo;
+    if (live == 4 && word_phase(o) == 0) {
+        *reinterpret_cast<float4 *>(o + p) = r;
+        return;
+    }
+    o[p] = r.x;
+    if (live > 1) o[p + 1] = r.y;
+    if (live > 2) o[p + 2] = r.z;
+    if (live > 3) o[p + 3] = r.w;
+}
+
+// ---- K23: the plans and the launches by R --------------------------------------------------------------------------------------
+int rank_check(const char *fn, int R, int inner) {
+    DNMF_REQUIRE(R >= BGR_MIN && R <= BGR_MAX, DNMF_E_UNSUPPORTED, "%s: R=%d components (%d .. %d; one component is K19's entry)", fn, R, BGR_MIN,
+                 BGR_MAX);
+    DNMF_REQUIRE(inner >= 1, DNMF_E_SHAPE, "%s: inner=%d sweeps", fn, inner);
+    return DNMF_OK;
+}
+
+size_t gram_bytes(long n, int R) { return bg_align((size_t)((n + BG_GRAM_CHUNK - 1) / BG_GRAM_CHUNK) * (R * (R + 1) / 2) * sizeof(double)); }
+
+struct DotsRankPlan {
+    DotsPlan d;
+    size_t off_gram, off_part, bytes;   // Q at 0, the chunks of the Gram launch, part (B, nseg, R) float64
+};
+
+int dots_rank_plan(const char *fn, long P, int B, int R, DotsRankPlan &g) {
+    int rc = rank_check(fn, R, 1);
+    if (rc != DNMF_OK) return rc;
+    rc = dots_plan(fn, P, B, g.d);
+    if (rc != DNMF_OK) return rc;
+    g.off_gram = BGR_HEADER;
+    g.off_part = g.off_gram + gram_bytes(P, R);
+    g.bytes = g.off_part + bg_align((size_t)B * g.d.nseg * R * sizeof(double));
+    return DNMF_OK;
+}
+
+struct AccumRankPlan {
+    AccumPlan a;
+    size_t off_sums, off_part, off_gram, bytes;   // W at 0 and sums (R, stride) persist between the calls; part and the chunks do not
+};
+
+int accum_rank_plan(const char *fn, long P, int B, int R, int segment, AccumRankPlan &g) {
+    int rc = rank_check(fn, R, 1);
+    if (rc != DNMF_OK) return rc;
+    rc = accum_plan(fn, P, B, segment, g.a);
+    if (rc != DNMF_OK) return rc;
+    const size_t arr = g.a.stride * sizeof(double);
+    const size_t cap = (g.a.bytes - g.a.off_part) / arr;
+    g.off_sums = BGR_HEADER;
+    g.off_part = g.off_sums + (size_t)R * arr;
+    g.off_gram = g.off_part + cap * R * arr;
+    g.bytes = g.off_gram + gram_bytes(B, R);
+    return DNMF_OK;
+}
+
+template <int R>
+void launch_gram(const float *x, long ld, long n, double *part, int first, double *G, hipStream_t st) {
+    const long nchunks = (n + BG_GRAM_CHUNK - 1) / BG_GRAM_CHUNK;
+    hipLaunchKernelGGL(background_gram_kernel<R>, dim3((unsigned)nchunks), dim3(BG_THREADS), 0, st, x, ld, n, part);
+    hipLaunchKernelGGL(background_gram_reduce_kernel<R>, dim3(1), dim3(64), 0, st, part, nchunks, first, G);
+}
+
+template <int R>
+void launch_dots_rank(const DotsRankArgs &a, int B, int inner, float *f, long ldf_t, double *num, double *q, double *Q, double *gram,
+                      hipStream_t st) {
+    launch_gram<R>(a.b, a.ldb, a.P, gram, 1, Q, st);
+    const dim3 grid((unsigned)((long)B * a.nseg));
+    if (a.sub) hipLaunchKernelGGL((background_dots_rank_kernel<R, true>), grid, dim3(BG_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((background_dots_rank_kernel<R, false>), grid, dim3(BG_THREADS), 0, st, a);
+    hipLaunchKernelGGL(background_dots_rank_finish_kernel<R>, dim3((unsigned)((B + BG_THREADS - 1) / BG_THREADS)), dim3(BG_THREADS), 0, st,
+                       a.part, Q, a.nseg, B, inner, f, ldf_t, num, q);
+}
+
+template <int R>
+void launch_accum_rank(const AccumRankArgs &a, const AccumRankPlan &g, int first, int finish, int inner, double *W, double *sums, double *gram,
+                       float *b, long ldb, double *num, double *w, hipStream_t st) {
+    const dim3 grid((unsigned)g.a.ntiles, (unsigned)g.a.nseg);
+    if (a.sub) hipLaunchKernelGGL((background_accum_rank_kernel<R, true>), grid, dim3(BG_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((background_accum_rank_kernel<R, false>), grid, dim3(BG_THREADS), 0, st, a);
+    const unsigned pblocks = (unsigned)((a.P + BG_THREADS - 1) / BG_THREADS);
+    hipLaunchKernelGGL(background_accum_rank_reduce_kernel, dim3(pblocks, (unsigned)R), dim3(BG_THREADS), 0, st, a.part, a.stride, g.a.nseg, R,
+                       a.P, first, sums);
+    launch_gram<R>(a.f, a.ldf_t, (long)a.B, gram, first, W, st);
+    if (finish)
+        hipLaunchKernelGGL(background_accum_rank_finish_kernel<R>, dim3(pblocks), dim3(BG_THREADS), 0, st, sums, a.stride, W, a.P, inner, b, ldb,
+                           num, w);
+}
+
+// R is a template parameter of the kernels: one case per supported value
+#define DNMF_BG_BY_RANK(R, CALL) \
+    switch (R) {                 \
+        case 2: CALL(2); break;  \
+        case 3: CALL(3); break;  \
+        case 4: CALL(4); break;  \
+        case 5: CALL(5); break;  \
+        case 6: CALL(6); break;  \
+        case 7: CALL(7); break;  \
+        default: CALL(8); break; \
+    }
+
 }  // namespace
 }  // namespace dnmf
 
@@ -395,6 +781,96 @@ int dnmf_background_subtract(const float *frames, long ldf, const int *frame_ids
     DNMF_REQUIRE(a.ntiles * B < (1L << 31), DNMF_E_UNSUPPORTED, "dnmf_background_subtract: %ld workgroups (split the call)", a.ntiles * B);
     hipLaunchKernelGGL(background_subtract_kernel, dim3((unsigned)(a.ntiles * B)), dim3(BG_THREADS), 0, (hipStream_t)stream, a);
     return check_launch("dnmf_background_subtract");
+}
+
+size_t dnmf_background_dots_rank_workspace(long P, int B, int R) {
+    dnmf::DotsRankPlan g;
+    if (dnmf::dots_rank_plan("dnmf_background_dots_rank_workspace", P, B, R, g) != DNMF_OK) return 0;
+    return g.bytes;
+}
+
+int dnmf_background_dots_rank(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *b, long ldb, int R,
+                              long P, int B, int inner, float *f, long ldf_t, double *num, double *q, void *workspace, size_t workspace_bytes,
+                              dnmf_stream_t stream) {
+    using namespace dnmf;
+    const char *fn = "dnmf_background_dots_rank";
+    DNMF_REQUIRE(frames && b && f && workspace, DNMF_E_NULL, "%s: NULL argument", fn);
+    int rc = rank_check(fn, R, inner);
+    if (rc != DNMF_OK) return rc;
+    DotsRankPlan g;
+    rc = dots_rank_plan(fn, P, B, R, g);
+    if (rc != DNMF_OK) return rc;
+    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P) && ldb >= P, DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld ldb=%ld below a row of P=%ld", fn, ldf, lds, ldb, P);
+    DNMF_REQUIRE(ldf_t >= B, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of B=%d", fn, ldf_t, B);
+    DNMF_REQUIRE(workspace_bytes >= g.bytes, DNMF_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu", fn, workspace_bytes, g.bytes);
+    DNMF_REQUIRE(((size_t)workspace & 7) == 0, DNMF_E_WORKSPACE, "%s: workspace must be 8-byte aligned", fn);
+    char *w = static_cast<char *>(workspace);
+    DotsRankArgs a;
+    a.frames = frames, a.sub = sub, a.b = b, a.ldf = ldf, a.lds = lds, a.ldb = ldb, a.P = P, a.seglen = g.d.seglen, a.frame_ids = frame_ids;
+    a.nseg = g.d.nseg, a.part = reinterpret_cast<double *>(w + g.off_part);
+    double *Q = reinterpret_cast<double *>(w), *gram = reinterpret_cast<double *>(w + g.off_gram);
+    const hipStream_t st = (hipStream_t)stream;
+#define DNMF_BG_CALL(N) launch_dots_rank<N>(a, B, inner, f, ldf_t, num, q, Q, gram, st)
+    DNMF_BG_BY_RANK(R, DNMF_BG_CALL)
+#undef DNMF_BG_CALL
+    return check_launch(fn);
+}
+
+size_t dnmf_background_accum_rank_workspace(long P, int B, int R, int segment) {
+    dnmf::AccumRankPlan g;
+    if (dnmf::accum_rank_plan("dnmf_background_accum_rank_workspace", P, B, R, segment, g) != DNMF_OK) return 0;
+    return g.bytes;
+}
+
+int dnmf_background_accum_rank(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *f, long ldf_t, int R,
+                               long P, int B, int first, int finish, int segment, int inner, void *state, size_t state_bytes, float *b, long ldb,
+                               double *num, double *w_out, dnmf_stream_t stream) {
+    using namespace dnmf;
+    const char *fn = "dnmf_background_accum_rank";
+    DNMF_REQUIRE(frames && f && state, DNMF_E_NULL, "%s: NULL argument", fn);
+    DNMF_REQUIRE(b || !finish, DNMF_E_NULL, "%s: b is NULL with finish", fn);
+    int rc = rank_check(fn, R, inner);
+    if (rc != DNMF_OK) return rc;
+    AccumRankPlan g;
+    rc = accum_rank_plan(fn, P, B, R, segment, g);
+    if (rc != DNMF_OK) return rc;
+    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P) && (!finish || ldb >= P), DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld ldb=%ld below a row of P=%ld", fn, ldf,
+                 lds, ldb, P);
+    DNMF_REQUIRE(ldf_t >= B, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of B=%d", fn, ldf_t, B);
+    DNMF_REQUIRE(state_bytes >= g.bytes, DNMF_E_WORKSPACE, "%s: state of %zu bytes, need %zu", fn, state_bytes, g.bytes);
+    DNMF_REQUIRE(((size_t)state & 7) == 0, DNMF_E_WORKSPACE, "%s: state must be 8-byte aligned", fn);
+    char *w = static_cast<char *>(state);
+    double *W = reinterpret_cast<double *>(w), *sums = reinterpret_cast<double *>(w + g.off_sums);
+    double *gram = reinterpret_cast<double *>(w + g.off_gram);
+    AccumRankArgs a;
+    a.frames = frames, a.sub = sub, a.f = f, a.ldf = ldf, a.lds = lds, a.ldf_t = ldf_t, a.P = P, a.frame_ids = frame_ids, a.B = B;
+    a.seglen = g.a.seglen, a.part = reinterpret_cast<double *>(w + g.off_part), a.stride = g.a.stride;
+    const hipStream_t st = (hipStream_t)stream;
+#define DNMF_BG_CALL(N) launch_accum_rank<N>(a, g, first != 0, finish != 0, inner, W, sums, gram, b, ldb, num, w_out, st)
+    DNMF_BG_BY_RANK(R, DNMF_BG_CALL)
+#undef DNMF_BG_CALL
+    return check_launch(fn);
+}
+
+int dnmf_background_subtract_rank(const float *frames, long ldf, const int *frame_ids, const float *b, long ldb, const float *f, long ldf_t, int R,
+                                  int nf, const int *times, long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream) {
+    using namespace dnmf;
+    const char *fn = "dnmf_background_subtract_rank";
+    DNMF_REQUIRE(frames && b && f && out, DNMF_E_NULL, "%s: NULL argument", fn);
+    const int rc = rank_check(fn, R, 1);
+    if (rc != DNMF_OK) return rc;
+    DNMF_REQUIRE(P >= 1 && B >= 1 && nf >= 1, DNMF_E_SHAPE, "%s: P=%ld voxels, B=%d frames, nf=%d", fn, P, B, nf);
+    DNMF_REQUIRE(ldf >= P && ldo >= P && ldb >= P, DNMF_E_SHAPE, "%s: ldf=%ld ldo=%ld ldb=%ld below a row of P=%ld", fn, ldf, ldo, ldb, P);
+    DNMF_REQUIRE(ldf_t >= nf, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of nf=%d", fn, ldf_t, nf);
+    DNMF_REQUIRE(times || B <= nf, DNMF_E_SHAPE, "%s: B=%d frames but f has %d values and times is NULL", fn, B, nf);
+    DNMF_REQUIRE(out != frames || (!frame_ids && ldo == ldf), DNMF_E_SHAPE, "%s: in place (out == frames) needs frame_ids NULL and ldo == ldf", fn);
+    DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, P);
+    SubtractRankArgs a;
+    a.frames = frames, a.b = b, a.f = f, a.ldf = ldf, a.ldo = ldo, a.ldb = ldb, a.ldf_t = ldf_t, a.P = P, a.ntiles = (P + BG_TILE - 1) / BG_TILE;
+    a.frame_ids = frame_ids, a.times = times, a.nf = nf, a.clamp = clamp != 0, a.R = R, a.out = out;
+    DNMF_REQUIRE(a.ntiles * B < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld workgroups (split the call)", fn, a.ntiles * B);
+    hipLaunchKernelGGL(background_subtract_rank_kernel, dim3((unsigned)(a.ntiles * B)), dim3(BG_THREADS), 0, (hipStream_t)stream, a);
+    return check_launch(fn);
 }
 
 }  // extern "C"

@@ -1409,7 +1409,10 @@ def background_accum(frames, f, sz, sub=None, frame_ids=None, state=None, first=
 def background_subtract(frames, b, f, frame_ids=None, times=None, out=None, clamp=True):
     """K19.  ``out[j] = frames[row j] - b f[t_j]`` as one fp32 fused multiply-add per voxel, ``max(., 0)`` with ``clamp``: (B, P) fp32
     CUDA rows.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order); ``times``: the entry of ``f`` of each frame of
-    the call (None: j; an entry ``f`` does not have makes the row NaN).  ``out=frames`` works in place (``frame_ids`` None)."""
+    the call (None: j; an entry ``f`` does not have makes the row NaN).  ``out=frames`` works in place (``frame_ids`` None).
+    ``f`` as (R, T) with ``b`` of R images is the rank-R background of K23: ``background_subtract_rank``."""
+    if isinstance(f, torch.Tensor) and f.dim() == 2:
+        return background_subtract_rank(frames, b, f, frame_ids=frame_ids, times=times, out=out, clamp=clamp)
     b = _f32(b, "b").reshape(-1)
     f = _f32(f, "f").reshape(-1)
     P = b.numel()
@@ -1433,6 +1436,211 @@ def background_subtract(frames, b, f, frame_ids=None, times=None, out=None, clam
                                           P, B, out.data_ptr(), _ld(out, P), 1 if clamp else 0, _stream())
     _lib.check(rc, "dnmf_background_subtract")
     return out
+
+
+BACKGROUND_RANKS = (2, 8)    # the R of K23's entries; one component is K19
+
+
+def _rank_rows(fn, name, t, n, n_name):
+    """(R, ...) fp32 CUDA values as R rows of ``n`` floats with unit inner stride -> (rows (R, n), R)."""
+    if not isinstance(t, torch.Tensor) or t.dim() < 2:
+        raise ValueError(f"{fn}: {name} holds R rows of {n} {n_name}")
+    t = t.reshape(t.shape[0], -1)
+    _rows(t, fn, name)
+    if t.shape[1] != n:
+        raise ValueError(f"{fn}: {name} holds R rows of {n} {n_name}, got {tuple(t.shape)}")
+    return t, t.shape[0]
+
+
+def _check_rank(fn, R, inner=1):
+    if not BACKGROUND_RANKS[0] <= R <= BACKGROUND_RANKS[1]:
+        raise ValueError(f"{fn}: {R} components ({BACKGROUND_RANKS[0]} .. {BACKGROUND_RANKS[1]}; one component is K19)")
+    if int(inner) < 1:
+        raise ValueError(f"{fn}: inner={inner} sweeps")
+
+
+def background_state_rank(sz, B, rank, segment=0, device="cuda"):
+    """An empty state for ``background_accum_rank`` calls of up to ``B`` frames each; pass it with ``first=True``."""
+    X, Y, Z = (int(s) for s in sz)
+    lib = _lib.load()
+    need = lib.dnmf_background_accum_rank_workspace(X * Y * Z, int(B), int(rank), int(segment))
+    if need == 0:
+        raise _refused(lib, "dnmf_background_accum_rank_workspace")
+    return _workspace(None, need, device)
+
+
+def _dots_rank(frames, b, f, sub, fid, B, P, R, inner):
+    """The launch of ``background_dots_rank`` on checked arguments; ``f`` (R, B) rows are the start and receive the result."""
+    dev = frames.device
+    lib = _lib.load()
+    need = lib.dnmf_background_dots_rank_workspace(P, B, R)
+    if need == 0:
+        raise _refused(lib, "dnmf_background_dots_rank_workspace")
+    ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    num = torch.empty((R, B), dtype=torch.float64, device=dev)
+    q = torch.empty((R, R), dtype=torch.float64, device=dev)
+    with _timed("background_dots_rank"):
+        rc = lib.dnmf_background_dots_rank(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                           b.data_ptr(), _ld(b, P), R, P, B, int(inner), f.data_ptr(), _ld(f, B), num.data_ptr(),
+                                           q.data_ptr(), ws.data_ptr(), _nbytes(ws), _stream())
+    _lib.check(rc, "dnmf_background_dots_rank")
+    return f, num, q
+
+
+def background_dots_rank(frames, b, f, sub=None, frame_ids=None, inner=3):
+    """K23, the f half-step of a rank-R background (2 <= R <= 8).  frames, ``sub``, ``frame_ids`` as ``background_dots`` takes
+    them; ``b`` R images (R, ...) of P voxels each, ``f`` (R, B) the current time courses of the frames of the call, both fp32 CUDA
+    -> ``(f_new (R, B), num (R, B), q (R, R))``: ``num[j, t] = sum_p b_j[p] (frames - sub)[t, p]`` and ``q = B B^T`` in float64, and
+    per frame ``inner`` cyclic sweeps ``f_j <- max(0, (num_j - sum_{i != j} q_ji f_i) / q_jj)`` (0 where q_jj == 0) in float64 from
+    ``f``, rounded once to fp32 (tests/background_rank_restatement.py).  One pass over the movie whatever R is.  ``f`` is not
+    changed.  Float64 sums in a fixed order: the same input gives the same bits."""
+    fn = "background_dots_rank"
+    if not isinstance(b, torch.Tensor) or b.dim() < 2:
+        raise ValueError(f"{fn}: b holds R images")
+    P = b[0].numel()
+    b, R = _rank_rows(fn, "b", b, P, "voxels")
+    _check_rank(fn, R, inner)
+    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    f, Rf = _rank_rows(fn, "f", f, B, "frames (one value for each frame of the call)")
+    if Rf != R:
+        raise ValueError(f"{fn}: {R} images but {Rf} time courses")
+    return _dots_rank(frames, b, f.clone(), sub, fid, B, P, R, inner)
+
+
+def background_accum_rank(frames, f, sz, b=None, sub=None, frame_ids=None, state=None, first=True, finish=True, segment=0, inner=3):
+    """K23, the b half-step of a rank-R background.  frames, ``sub``, ``frame_ids``, ``state`` / ``first`` / ``finish`` /
+    ``segment`` as ``background_accum`` takes them; ``f`` (R, B) fp32 CUDA, the time courses of the frames of the call; ``b``
+    (R, X, Y, Z) the current images (None: zeros), read by the finishing call only -> ``((b_new, num, w) or None, state)``:
+    over the frames seen since the state was reset ``num[j, p] = sum_t f_j[t] (frames - sub)[t, p]`` ((R, X, Y, Z) float64) and
+    ``w = F F^T`` ((R, R) float64), and per voxel ``inner`` cyclic sweeps from ``b`` as in ``background_dots_rank``, rounded once to
+    fp32 ((R, X, Y, Z)).  ``b`` is not changed.  Every call on one state has the same volume and R."""
+    fn = "background_accum_rank"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    f, R = _rank_rows(fn, "f", f, B, "frames (one value for each frame of the call)")
+    _check_rank(fn, R, inner)
+    dev = frames.device
+    lib = _lib.load()
+    need = lib.dnmf_background_accum_rank_workspace(P, B, R, int(segment))
+    if need == 0:
+        raise _refused(lib, "dnmf_background_accum_rank_workspace")
+    if first:
+        state = _workspace(state, need, dev)
+    elif state is None or _nbytes(state) < need:
+        raise ValueError(f"{fn}: first=False needs the state of the earlier calls, and one of at least {need} bytes "
+                         "(a later call may not be larger than the first)")
+    out = num = w = None
+    if finish:
+        if b is None:
+            out = torch.zeros((R, X, Y, Z), dtype=torch.float32, device=dev)
+        else:
+            rows, Rb = _rank_rows(fn, "b", b, P, "voxels")
+            if Rb != R:
+                raise ValueError(f"{fn}: {R} time courses but {Rb} images")
+            out = rows.clone().reshape(R, X, Y, Z)
+        num = torch.empty((R, X, Y, Z), dtype=torch.float64, device=dev)
+        w = torch.empty((R, R), dtype=torch.float64, device=dev)
+    with _timed("background_accum_rank"):
+        rc = lib.dnmf_background_accum_rank(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                            f.data_ptr(), _ld(f, B), R, P, B, 1 if first else 0, 1 if finish else 0, int(segment),
+                                            int(inner), state.data_ptr(), _nbytes(state), _ptr(out), P, _ptr(num), _ptr(w), _stream())
+    _lib.check(rc, "dnmf_background_accum_rank")
+    return ((out, num, w) if finish else None), state
+
+
+def background_subtract_rank(frames, b, f, frame_ids=None, times=None, out=None, clamp=True):
+    """K23.  ``out[j] = fp32(float64(frames[row j]) - sum_c float64(b_c) float64(f_c[t_j]))``, the products added with c ascending,
+    ``max(., 0)`` with ``clamp``: ``b`` R images (R, ...), ``f`` (R, T); everything else as ``background_subtract``."""
+    fn = "background_subtract_rank"
+    if not isinstance(b, torch.Tensor) or b.dim() < 2:
+        raise ValueError(f"{fn}: b holds R images")
+    P = b[0].numel()
+    b, R = _rank_rows(fn, "b", b, P, "voxels")
+    if not isinstance(f, torch.Tensor) or f.dim() != 2 or f.shape[0] != R:
+        raise ValueError(f"{fn}: f is (R={R}, T)")
+    _rows(f, fn, "f")
+    _check_rank(fn, R)
+    nf = f.shape[1]
+    _rows(frames, fn, "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"{fn}: frames are rows (T, ld), got {tuple(frames.shape)}")
+    dev = frames.device
+    fid, tt, B = _ids(frames, frame_ids, times, dev)
+    if fid is not None and fid.numel() != B:
+        raise ValueError(f"{fn}: {fid.numel()} frame_ids for {B} times")
+    if fid is None and B > frames.shape[0]:
+        raise ValueError(f"{fn}: {B} times for {frames.shape[0]} frames")
+    if out is None:
+        out = torch.empty((B, P), dtype=torch.float32, device=dev)
+    _rows(out, fn, "out", P, f" and rows of {P} floats")
+    if out.dim() != 2 or out.shape[0] < B:
+        raise ValueError(f"{fn}: out must hold {B} rows, got {tuple(out.shape)}")
+    lib = _lib.load()
+    with _timed("background_subtract_rank"):
+        rc = lib.dnmf_background_subtract_rank(frames.data_ptr(), _ld(frames, P), _ptr(fid), b.data_ptr(), _ld(b, P), f.data_ptr(),
+                                               _ld(f, nf), R, nf, _ptr(tt), P, B, out.data_ptr(), _ld(out, P), 1 if clamp else 0,
+                                               _stream())
+    _lib.check(rc, "dnmf_background_subtract_rank")
+    return out
+
+
+def _pieces(P, T, piece):
+    """The cuts of T resident rows into pieces of ``piece`` frames (None: at most 1 GiB of frames)."""
+    if piece is None:
+        piece = max(1, (1 << 30) // (4 * P))
+    piece = max(1, min(int(piece), T))
+    return [(s, min(T, s + piece)) for s in range(0, T, piece)]
+
+
+def background_fit_rank(frames, sz, iters, rank, sub_fn=None, piece=None, inner=3):
+    """The rank-R background of resident rows (K23), 2 <= R <= 8: R images and R time courses -> ``(b (R, X, Y, Z), f (R, T))`` fp32
+    CUDA, all >= 0 (tests/background_rank_restatement.py: ``fit``).  F starts as the indicators of R contiguous blocks of the
+    rows, b from one b-step on them (the clipped block means); then ``iters`` times the pair (``background_dots_rank``,
+    ``background_accum_rank``) with ``inner`` coordinate sweeps per frame and per voxel, then per component the scale that makes
+    mean(f_j) = 1.  ``sub_fn`` and ``piece`` as ``background_fit`` takes them; ``sub_fn`` is called once more per piece, for the
+    start.  ``rank=1`` is ``background_fit``, whatever ``inner`` is.  No host synchronisation."""
+    if int(rank) != rank or rank < 1:
+        raise ValueError(f"background_fit_rank: rank={rank!r}")
+    if rank == 1:
+        return background_fit(frames, sz, iters, sub_fn=sub_fn, piece=piece)
+    if int(iters) < 1:
+        raise ValueError(f"background_fit_rank: iters={iters}")
+    X, Y, Z = (int(s) for s in sz)
+    P, T, R = X * Y * Z, frames.shape[0], int(rank)
+    cuts = _pieces(P, T, piece)
+    dev = frames.device
+    _check_rank("background_fit_rank", R, inner)
+    if R > T:
+        raise ValueError(f"background_fit_rank: rank={R} for {T} frames")
+    _rows(frames, "background_fit_rank", "frames", P, f" and rows of {P} floats")
+    # the start: component j owns the contiguous block of frames with (t R) // T == j
+    t = torch.arange(T, device=dev)
+    f = torch.zeros((R, T), dtype=torch.float32, device=dev)
+    f[(t * R) // T, t] = 1.0
+    b = torch.zeros((R, X, Y, Z), dtype=torch.float32, device=dev)
+    state = None
+
+    def sub(s, e):
+        return None if sub_fn is None else sub_fn(s, e)
+
+    def b_step(b):
+        nonlocal state
+        for n, (s, e) in enumerate(cuts):
+            res, state = background_accum_rank(frames[s:e], f[:, s:e], (X, Y, Z), b=b, sub=sub(s, e), state=state, first=n == 0,
+                                               finish=e == T, inner=inner)
+        return res[0]
+
+    b = b_step(b)
+    for _ in range(int(iters)):
+        for s, e in cuts:
+            m = sub(s, e)
+            fid, B = _background_rows("background_fit_rank", frames[s:e], m, None, P)
+            _dots_rank(frames[s:e], b.reshape(R, P), f[:, s:e], m, fid, B, P, R, inner)      # in place, on the rows of f
+        b = b_step(b)
+    scale = f.mean(dim=1)
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    return b.mul_(scale[:, None, None, None]), f.div_(scale[:, None])
 
 
 def background_fit(frames, sz, iters, sub_fn=None, piece=None):

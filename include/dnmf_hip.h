@@ -737,6 +737,45 @@ int dnmf_background_accum(const float *frames, long ldf, const float *sub, long 
 int dnmf_background_subtract(const float *frames, long ldf, const int *frame_ids, const float *b, const float *f, int nf, const int *times,
                              long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream);
 
+/* ---- K23: a rank-R background sum_c b_c (x) f_c on the residual, 2 <= R <= 8 ---------------------------------------------------------
+ * Model: frames[t, p] ~ sub[t, p] + sum_{c < R} b_c[p] f_c[t], b_c >= 0, f_c >= 0; r, rows, frame_ids, sub, the alignment rule, the
+ * finiteness rule and the error codes as in K19.  b: R rows of ldb >= P floats; f: R rows of ldf_t floats (>= B, the frames of the
+ * call; >= nf for subtract).  tests/background_rank_restatement.py is the definition in float64.  A half-step is one pass over the
+ * movie whatever R is (8 B per voxel and frame with sub, 4 B without): the pass leaves R float64 sums per frame (per voxel), a small
+ * launch the R x R Gram matrix of the factor held fixed, and the last launch solves every frame's (voxel's) non-negative problem
+ *     min over x >= 0 of x^T G x - 2 N^T x      by `inner` >= 1 cyclic sweeps  x_j <- max(0, (N_j - sum_{i != j} G_ji x_i) / G_jj),
+ * j = 0 .. R-1, 0 where G_jj == 0, in float64 from the current value (the f or b passed in), rounded once to fp32.  `inner` is a
+ * parameter of the algorithm, not a tolerance.  R is a template parameter of the kernels (the R, or 4 R, sums of a lane are registers).
+ * Float64 sums in a fixed order, no floating-point atomics: the same input at the same addresses gives the same bits.  No host
+ * synchronisation; nothing is launched on an error.
+ *
+ * dnmf_background_dots_rank: num[c * B + j] = sum_p b_c[p] r[j, p] ((R, B) float64, may be NULL), q = B^T B ((R, R) float64, may be
+ *   NULL), and f[c * ldf_t + j] is read as the start of frame j's solve and overwritten with its result.  One workgroup per (frame,
+ *   segment of voxels) as in K19 with R sums a lane (the rows of b are read again for every frame, from cache); the Gram launch has
+ *   one workgroup per 4096 voxels.  workspace: caller-owned, 8-byte aligned, dnmf_background_dots_rank_workspace(P, B, R) bytes.
+ *
+ * dnmf_background_accum_rank: per voxel num[c * P + p] = sum_t f_c[t] r[t, p] over every frame since the state was reset, W = F F^T
+ *   over the same frames, and with finish != 0 b[c * ldb + p] is read as the start of voxel p's solve and overwritten with its result;
+ *   num ((R, P) float64) and w ((R, R) float64) may be NULL.  Tiles, segments, first / finish / segment and the state as in K19, with
+ *   4 R sums a lane; state: dnmf_background_accum_rank_workspace(P, B, R, segment) bytes (it does not decrease with B); every call on
+ *   one state has the same P and R.
+ *
+ * dnmf_background_subtract_rank: out[j, p] = (float)((double)frames[row, p] - sum_c (double)b_c[p] (double)f_c[t]), the products
+ *   added one by one with c ascending, max(., 0) when clamp != 0; t, nf, the NaN row, in-place use and the codes as in K19.
+ *
+ * DNMF_E_UNSUPPORTED: R outside 2 .. 8 (one component is K19's entry), and K19's cases;  DNMF_E_SHAPE: inner < 1, ldb < P, ldf_t < B
+ * (subtract: < nf), and K19's cases;  DNMF_E_NULL, DNMF_E_WORKSPACE as in K19. */
+size_t dnmf_background_dots_rank_workspace(long P, int B, int R);
+int dnmf_background_dots_rank(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *b, long ldb, int R,
+                              long P, int B, int inner, float *f, long ldf_t, double *num, double *q, void *workspace, size_t workspace_bytes,
+                              dnmf_stream_t stream);
+size_t dnmf_background_accum_rank_workspace(long P, int B, int R, int segment);
+int dnmf_background_accum_rank(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *f, long ldf_t, int R,
+                               long P, int B, int first, int finish, int segment, int inner, void *state, size_t state_bytes, float *b, long ldb,
+                               double *num, double *w, dnmf_stream_t stream);
+int dnmf_background_subtract_rank(const float *frames, long ldf, const int *frame_ids, const float *b, long ldb, const float *f, long ldf_t, int R,
+                                  int nf, const int *times, long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream);
+
 /* ---- K20: trace clean-up: mask, single-frame outliers, bleach detrend, dF/F0, gap filling, smoothing, rescale ---------------------
  * tests/traces_restatement.py (clean_traces) is the definition, step by step (S1 .. S6), in float64; this entry computes it for K
  * traces of T frames: traces = K rows of ldt >= T floats, out = K rows of ldo >= T floats (the input is only read; out may not
