@@ -45,7 +45,11 @@ __global__ __launch_bounds__(256) void mu_temporal_kernel(const float *__restric
 // The same rounds when G has a known pattern (K3n: footprints whose boxes never meet have G = 0 for every warp).
 // nbr (K,NN): for row k the columns that can be non-zero, ascending, padded with columns outside the pattern.  The
 // dense kernel adds the terms in ascending column order and a term with G = 0 adds an exact zero, so the result is
-// bit-identical to mu_temporal_kernel's; only the work shrinks from K to NN terms per row and round.
+// identical to mu_temporal_kernel's while every trace of the frame is finite; only the work shrinks from K to NN terms
+// per row and round.  Once a trace overflows (G[k][k] = 0 with r[k] > 0: c[k] grows by 1/1e-32 a round, inf after ten)
+// the two part: the dense form, like the reference's numpy, turns the whole frame NaN through 0 * inf, this form only
+// the rows whose list names the overflowing neuron -- and, a round later each, the rows that list those, padding
+// columns included (tests/test_gpu_mu_temporal.py::test_overflowing_trace).
 template <int NN>
 __global__ __launch_bounds__(256) void mu_temporal_nbr_kernel(const float *__restrict__ G, const float *__restrict__ r,
                                                               float *__restrict__ C, long ldc, int K, int iters,
@@ -78,7 +82,8 @@ __global__ __launch_bounds__(256) void mu_temporal_nbr_kernel(const float *__res
 
 // The same again, reading the slot tables K3n left in its workspace instead of a dense G: entry (k,l) is the ordered
 // sum over the chunks of slot pair_slot[k][l] -- exactly what gram_lists_finish_kernel would have written -- and r[k]
-// the sum of slot k.  Saves writing and re-reading (T,K,K).
+// the sum of slot k.  Saves writing and re-reading (T,K,K).  Equal to mu_temporal_nbr_kernel on the finished G, r bit
+// for bit, and so to the dense form under the same condition: while every trace of the frame is finite.
 template <int NN>
 __global__ __launch_bounds__(256) void mu_temporal_slots_kernel(const float *__restrict__ slab, int nchunks, int nslot,
                                                                 const int *__restrict__ pair_slot,

@@ -399,7 +399,8 @@ def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_strid
 
 def mu_temporal(G, r, C, iters: int, nbr=None):
     """K4 without the neighbour term: C (K,T) fp32 updated in place.  ``nbr`` (K,NN) int32: the columns of G that
-    can be non-zero per row (``pack_footprints_lists``) -- same result, NN instead of K terms per row."""
+    can be non-zero per row (``pack_footprints_lists``) -- same result while every trace is finite, NN instead of K terms
+    per row."""
     _f32(G, "G"), _f32(r, "r")
     if not (C.is_cuda and C.dtype == torch.float32 and C.stride(1) == 1):
         raise ValueError("mu_temporal: C must be float32 CUDA with unit inner stride")
@@ -414,11 +415,14 @@ def mu_temporal(G, r, C, iters: int, nbr=None):
 
 
 def mu_temporal_step(G, r, Cin, Cout, gamma: float, c_left=None, c_right=None):
-    """K4, one round with the neighbour term; Cin/Cout (K,T) float64."""
+    """K4, one round with the neighbour term; Cin/Cout (K,T) float64 with the same row stride (the ABI has one ldc)."""
     _f32(G, "G"), _f32(r, "r")
     for t, n in ((Cin, "Cin"), (Cout, "Cout")):
         if not (t.is_cuda and t.dtype == torch.float64 and t.stride(1) == 1):
             raise ValueError(f"mu_temporal_step: {n} must be float64 CUDA with unit inner stride")
+    if Cout.stride(0) != Cin.stride(0):
+        raise ValueError(f"mu_temporal_step: Cin and Cout must have the same row stride, got Cin.stride(0)="
+                         f"{Cin.stride(0)} and Cout.stride(0)={Cout.stride(0)}")
     T, K = r.shape
     _lib.check(_lib.load().dnmf_mu_temporal_step(G.data_ptr(), r.data_ptr(), Cin.data_ptr(), Cout.data_ptr(),
                                                  Cin.stride(0), K, T, float(gamma), _ptr(c_left), _ptr(c_right),
