@@ -372,9 +372,21 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
     return state
 
 
-def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_stride=0, workspace=None, bf16=False):
+def _gram_out(out, B, K, dev, fn):
+    """``(G, r)``: new (B,K,K) and (B,K) tensors, or the caller's pair ``out`` after a check of what the kernels write."""
+    if out is None:
+        return torch.empty((B, K, K), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.float32, device=dev)
+    G, r = out
+    _f32(G, "out[0]"), _f32(r, "out[1]")
+    if tuple(G.shape) != (B, K, K) or tuple(r.shape) != (B, K):
+        raise ValueError(f"{fn}: out must be (G ({B},{K},{K}), r ({B},{K})), got {tuple(G.shape)} and {tuple(r.shape)}")
+    return G, r
+
+
+def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_stride=0, workspace=None, bf16=False, out=None):
     """K3 (``bf16=True``: K3b, operands rounded to bf16, fp32 accumulate).  Returns G (B,K,K), r (B,K) for the
-    frames listed.  ``beta`` None: no warp (each voxel's own footprint row, weight 1)."""
+    frames listed (written into the pair ``out`` when given).  ``beta`` None: no warp (each voxel's own footprint row,
+    weight 1)."""
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
     dev = Apk.device
@@ -386,8 +398,7 @@ def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_strid
     _rows(frames, "warp_gram_rhs", "frames")
     need = lib.dnmf_warp_gram_rhs_workspace(P, K, B)
     workspace = _workspace(workspace, need, dev)
-    G = torch.empty((B, K, K), dtype=torch.float32, device=dev)
-    r = torch.empty((B, K), dtype=torch.float32, device=dev)
+    G, r = _gram_out(out, B, K, dev, "warp_gram_rhs")
     with _timed("warp_gram_rhs_bf16" if bf16 else "warp_gram_rhs"):
         rc = (lib.dnmf_warp_gram_rhs_bf16 if bf16 else lib.dnmf_warp_gram_rhs)(
             Apk.data_ptr(), Apk.shape[-1], K, a_frame_stride, X, Y, Z, _ptr(beta), B if beta is None else beta.shape[2],
@@ -676,9 +687,9 @@ LISTS_MAX_SLOTS = 3800
 LISTS_COUNTERS = None
 
 
-def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, workspace=None, finish=True):
-    """K3n.  Returns G (B,K,K), r (B,K), workspace; with ``finish=False`` G and r are None and the slot tables stay
-    in ``workspace`` for ``mu_temporal_slots``."""
+def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, workspace=None, finish=True, out=None):
+    """K3n.  Returns G (B,K,K), r (B,K), workspace (G and r written into the pair ``out`` when given); with
+    ``finish=False`` G and r are None and the slot tables stay in ``workspace`` for ``mu_temporal_slots``."""
     global LISTS_COUNTERS
     X, Y, Z = (int(s) for s in sz)
     dev = beta.device
@@ -689,8 +700,7 @@ def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, work
     nslot = layout["nslot"]
     need = lib.dnmf_warp_gram_rhs_lists_workspace(nslot, K, X, Y, Z, B)
     workspace = _workspace(workspace, need, dev)
-    G = torch.empty((B, K, K), dtype=torch.float32, device=dev) if finish else None
-    r = torch.empty((B, K), dtype=torch.float32, device=dev) if finish else None
+    G, r = _gram_out(out, B, K, dev, "warp_gram_rhs_lists") if finish else (None, None)
     counters = None
     if TIMING is not None:
         if LISTS_COUNTERS is None:
@@ -1877,8 +1887,9 @@ SPARSE_COUNTERS = None
 SPARSE_VARIANT = 'table'
 
 
-def warp_gram_rhs_sparse(Aps, K, order, row_mask, sz, beta, times, frames, frame_ids=None, workspace=None, variant=None):
-    """K3s.  Returns G (B,K,K), r (B,K) in the original neuron order."""
+def warp_gram_rhs_sparse(Aps, K, order, row_mask, sz, beta, times, frames, frame_ids=None, workspace=None, variant=None,
+                         out=None):
+    """K3s.  Returns G (B,K,K), r (B,K) in the original neuron order (written into the pair ``out`` when given)."""
     global SPARSE_COUNTERS
     lt = (variant or SPARSE_VARIANT) == 'table'
     X, Y, Z = (int(s) for s in sz)
@@ -1891,8 +1902,7 @@ def warp_gram_rhs_sparse(Aps, K, order, row_mask, sz, beta, times, frames, frame
     _rows(frames, "warp_gram_rhs_sparse", "frames")
     need = (lib.dnmf_warp_gram_rhs_sparse_lt_workspace if lt else lib.dnmf_warp_gram_rhs_sparse_workspace)(P, K, B)
     workspace = _workspace(workspace, need, dev)
-    G = torch.empty((B, K, K), dtype=torch.float32, device=dev)
-    r = torch.empty((B, K), dtype=torch.float32, device=dev)
+    G, r = _gram_out(out, B, K, dev, "warp_gram_rhs_sparse")
     counters = None
     if TIMING is not None:
         if SPARSE_COUNTERS is None:
