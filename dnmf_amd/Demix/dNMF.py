@@ -20,6 +20,8 @@ There is no CPU fallback: without ``libdnmf_hip.so`` and a GPU these classes rai
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -601,6 +603,8 @@ class DeformableNMF:
         self.last_clean = None
         # after deconvolve: g, penalty, baseline, noise, rss, n_valid, n_pools, ok per neuron (CUDA tensors, (K,)) of that call
         self.last_deconv = None
+        # after evaluate_components: r_values, snr, frame_corr, raw, images, boxes, n_active and keep of that call
+        self.last_evaluation = None
         self._warned = set()
 
     @classmethod
@@ -852,6 +856,121 @@ class DeformableNMF:
                 images, state = ops.summary_images(fr, sz, sub=sub, neighbours=neighbours, state=state, first=s == 0,
                                                    finish=s + step >= T)
         return images
+
+    def evaluate_components(self, loader, registered='linear', active=0.25, margin=2, floor=1e-3, min_r=0.5, min_snr=1.0):
+        """Which of the K components explain anything (K24, ``ops.component_stats``): one pass over the registered frames
+        ``loader`` serves.  On the box of neuron k (``ops.component_boxes(fp.A, sz, floor, margin)``) and for frame t,
+        e_t = Y_t - S_t + a_k C[k, t] -- the residual of the model S_t = A C_t (``fp.recon_image``) with the neuron's own
+        contribution put back.  Returns, and stores in ``self.last_evaluation``, a dict of CUDA tensors:
+        ``raw`` (K, n) the least-squares amplitude of a_k in e_t with a free offset, the neuron's raw trace, and ``frame_corr``
+        (K, n) the Pearson correlation of a_k and e_t, per frame served in the order of the frame times; ``images`` (K, vmax)
+        the mean of e_t over the neuron's ``n_active = ceil(active n)`` active frames, on its box (x slowest, NaN past the
+        box); ``r_values`` (K) the Pearson correlation of a_k with that image; ``snr`` (K) = (mean of raw over the active
+        frames - median of raw) / noise, noise = MAD(diff(raw)) / (0.6745 sqrt 2), the estimator ``deconvolve`` uses;
+        ``boxes`` (K, 6) int32; ``keep`` (K) bool = ``r_values >= min_r`` and ``snr >= min_snr``, NaN failing
+        (``select_components(keep)`` drops the others).
+        The active frames of neuron k are those with the largest leave-one-out score (C[k, t-1] + C[k, t+1]) / 2 -- the one
+        neighbour that exists at the two ends, ties to the earlier frame -- not those with the largest C[k, t]: the trace of a
+        component on nothing is <a, noise_t> / |a|^2, so its largest entries pick the frames whose noise happens to look
+        like a, and their mean image inherits the footprint's shape.  Calcium traces are correlated in time and the noise is
+        not, so the neighbours find a real neuron's active frames and say nothing about the noise of frame t.
+        ``min_r`` and ``min_snr`` are parameters, not tolerances: their defaults sit in the gap that a planted video of six
+        cells and two components on nothing leaves between the two groups (tests/test_components_host.py measures it:
+        r_values above 0.8 against below 0.3, snr above 2 against below 0.8).
+        ``registered='linear'`` (K17, zero padding like ``summary_images``) or ``'nearest'`` (K7) registers the frames under
+        the current ``fp.beta`` first; ``None`` takes them as they are, which is right only where the warp is the identity.  A
+        frame with a sample that is not finite inside a neuron's box counts for nothing in that neuron's figures and is NaN
+        in its ``raw`` and ``frame_corr``.  The frames go through in pieces of at most 1 GiB."""
+        who = "evaluate_components"
+        if registered is not None:
+            _check_registered(registered, who)
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
+            raise NotImplementedError(f"{who}: the loader holds a shard of the frames (the mean images would need an all-reduce)")
+        if not 0 < active <= 1:
+            raise ValueError(f"{who}: active={active!r} is the fraction of the frames that count as active, in (0, 1]")
+        fp = self.fp
+        sz, P, K = fp.sz_list, fp.P, fp.K
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            if not bool((order[1:] > order[:-1]).all()):
+                at = torch.argsort(order.long())
+                frames, order = frames.index_select(0, at), order[at]
+            T = frames.shape[0]
+            C = self.C.to(device, torch.float32).contiguous()
+            Cs = C[:, order.long()].contiguous()                     # the traces of the frames served, in time order
+            A_rows = fp._layout("rows", (), lambda: fp.A.reshape(P, K).t().contiguous())
+            boxes = ops.component_boxes(fp.A, sz, floor=floor, margin=margin)
+            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
+            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
+                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
+                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            score = Cs.double()
+            if T > 1:
+                score = torch.cat((Cs[:, 1:2], 0.5 * (Cs[:, :-2].double() + Cs[:, 2:].double()), Cs[:, -2:-1]), 1).double()
+            n_active = min(T, max(1, int(math.ceil(active * T))))
+            top = torch.sort(score, dim=1, descending=True, stable=True).indices[:, :n_active]
+            w = torch.zeros((K, T), dtype=torch.float32, device=device).scatter_(1, top, 1.0)
+            step = max(1, min(T, (1 << 30) // (4 * P)))
+            state, raw, corr = None, [], []
+            for s in range(0, T, step):
+                fr, tt = frames[s:s + step], order[s:s + step]
+                sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
+                if registered is not None:
+                    fr = fp.registered_video(fr, times=tt, interpolation=registered)
+                out, state = ops.component_stats(fr, sz, A_rows, boxes, Cs[:, s:s + step], w[:, s:s + step], sub=sub, state=state,
+                                                 first=s == 0, finish=s + step >= T)
+                raw.append(out["raw"])
+                corr.append(out["frame_corr"])
+            raw, corr = torch.cat(raw, 1), torch.cat(corr, 1)
+            snr = ops.component_snr(raw, w)
+            keep = (out["r_values"] >= min_r) & (snr >= min_snr)     # a NaN compares False
+        self.last_evaluation = dict(r_values=out["r_values"], snr=snr, frame_corr=corr, raw=raw, images=out["image"], boxes=boxes,
+                                    n_active=n_active, keep=keep)
+        return self.last_evaluation
+
+    # what select_components forgets, with every last_* result: the caches and workspaces with a K-shaped extent
+    _K_SHAPED = ("_ws_k2", "_ws_k3", "_S_bufs", "_S_zero", "_gram_nbr", "_sl", "_ws_k5", "_spatial_buf", "_ws_mg", "_D_dev")
+
+    def select_components(self, keep):
+        """Shrink the model in place to the neurons ``keep`` -- a bool mask (K,) or indices, e.g. ``evaluate_components(...)
+        ['keep']`` -- in the order given (a mask: ascending): ``fp.A``, ``fp.pos``, ``fp.sigma``, ``fp.K``, ``C``, ``D`` and
+        ``K``; ``fp.beta`` stays, the warp is shared.  Every packed layout, K-shaped cache and workspace and every
+        ``last_*`` result of an earlier call is forgotten.  ValueError for an empty selection or an index out of range.
+        Returns the number kept."""
+        fp = self.fp
+        K = fp.K
+        sel = torch.as_tensor(keep).detach().cpu()
+        if sel.dtype == torch.bool:
+            if tuple(sel.shape) != (K,):
+                raise ValueError(f"select_components: a mask must be ({K},), got {tuple(sel.shape)}")
+            sel = torch.nonzero(sel).reshape(-1)
+        elif sel.dtype.is_floating_point or sel.dim() != 1:
+            raise ValueError("select_components: keep is a bool mask (K,) or a list of indices")
+        sel = sel.long()
+        if sel.numel() == 0:
+            raise ValueError("select_components: the selection is empty")
+        if int(sel.min()) < 0 or int(sel.max()) >= K:
+            raise ValueError(f"select_components: index out of range for K={K}: {sel.tolist()}")
+        if self._nchan() != 1:
+            raise NotImplementedError("select_components: one channel only")
+        with torch.no_grad():
+            at = sel.to(fp.A.device)
+            fp.A = fp.A.index_select(3, at).contiguous()
+            fp.pos = fp.pos.index_select(0, at.to(fp.pos.device))
+            fp.sigma = fp.sigma.index_select(0, at.to(fp.sigma.device))
+            self.C = self.C.index_select(0, at.to(self.C.device)).contiguous()
+            self.A = self.A.index_select(0, at.to(self.A.device))
+        if self.D is not None:
+            self.D = np.ascontiguousarray(self.D[..., sel.numpy()])
+        fp.K = int(sel.numel())
+        if hasattr(self, "K"):
+            self.K = fp.K
+        fp.invalidate_layouts()
+        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
+            setattr(self, name, None)
+        return fp.K
 
     def _background_refusals(self, loader, who):
         if self._nchan() != 1:

@@ -116,6 +116,9 @@ SIGNATURES = {
     "dnmf_deconvolve_traces_workspace": (_sz, [_i, _i]),
     "dnmf_deconvolve_traces": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
     "dnmf_high_pass_frames": (_i, [_vp, _l, _vp, _vp, _i, _vp, _i, _vp, _l, _vp]),
+    "dnmf_component_stats_workspace": (_sz, [_vp, _vp, _i, _i, _i]),
+    "dnmf_component_stats": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _i, _i, _i, _vp, _sz,
+                                  _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

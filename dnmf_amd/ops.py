@@ -1865,6 +1865,106 @@ def high_pass_frames(frames, sz, gSig, frame_ids=None, out=None, taps=None):
     return out
 
 
+COMPONENT_MAX_VOXELS = 4096   # the largest box of K24 (K13's limit)
+
+
+def component_boxes(A, sz, floor=1e-3, margin=2):
+    """(K, 6) int32 ``(x0, x1, y0, y1, z0, z1)``, inclusive: per neuron the bounding box of ``A[:, k] > floor max A[:, k]``,
+    grown by ``margin`` voxels and cut to the volume -- the boxes ``component_stats`` takes.  ``A`` (..., K), on its device.  A
+    footprint that is zero everywhere gets the whole volume."""
+    X, Y, Z = (int(s) for s in sz)
+    K = A.shape[-1]
+    A4 = A.reshape(X, Y, Z, K)
+    on = A4 > float(floor) * A4.amax(dim=(0, 1, 2))
+    boxes = torch.empty((K, 6), dtype=torch.int32, device=A.device)
+    for d, S in enumerate((X, Y, Z)):
+        hit = on.any(dim=tuple(i for i in range(3) if i != d))                         # (S, K)
+        idx = torch.arange(S, device=A.device)[:, None]
+        lo = torch.where(hit, idx, S - 1).amin(0)
+        hi = torch.where(hit, idx, 0).amax(0)
+        none = ~hit.any(0)
+        boxes[:, 2 * d] = torch.where(none, 0, (lo - int(margin)).clamp_min(0))
+        boxes[:, 2 * d + 1] = torch.where(none, S - 1, (hi + int(margin)).clamp_max(S - 1))
+    return boxes
+
+
+def component_snr(raw, w):
+    """(K,) float64: (mean of raw[k] over the valid frames with w[k] > 0 - median of raw[k] over the valid frames) / noise_k,
+    noise_k = MAD(diff(raw[k, valid])) / (0.6745 sqrt 2), the estimator K21 documents; a frame is valid where ``raw`` is
+    finite.  NaN with fewer than 4 valid frames, without a valid active frame or with a zero noise.  ``raw`` (K, T) from
+    ``component_stats``, ``w`` (K, T) its weights.  Float64 torch on the (K, T) arrays: O(K T), not a hot path."""
+    raw = raw.double()
+    K = raw.shape[0]
+    out = torch.full((K,), float("nan"), dtype=torch.float64, device=raw.device)
+    ok = torch.isfinite(raw)
+    act = ok & (w > 0)
+    scale = 0.6745 * 2.0 ** 0.5
+    for k in torch.nonzero((ok.sum(1) >= 4) & act.any(1)).reshape(-1).tolist():
+        x = raw[k, ok[k]]
+        d = x[1:] - x[:-1]
+        noise = torch.quantile((d - torch.quantile(d, 0.5)).abs(), 0.5) / scale
+        out[k] = torch.where(noise > 0, (raw[k, act[k]].mean() - torch.quantile(x, 0.5)) / noise, out[k])
+    return out
+
+
+def component_stats(frames, sz, A_rows, boxes, C, w, sub=None, frame_ids=None, state=None, first=True, finish=True, segment=0):
+    """K24.  Per-component statistics on registered frames -> ``(dict, state)``.  ``frames`` (rows, ld >= P) fp32 CUDA rows in
+    footprint coordinates, ``A_rows`` (K, >= P) fp32 the footprints as rows, ``boxes`` (K, 6) int32 inclusive boxes of at most
+    4096 voxels (``component_boxes``), ``C`` and ``w`` (K, B) fp32 the traces and the weights >= 0 of the call's frames, in
+    their order; ``sub`` (B, ld >= P) fp32 rows: what the model predicts (row j for the j-th frame), None: nothing;
+    ``frame_ids``: the rows of ``frames`` to take.  With e_t = frames_t - sub_t + a C[k, t] on the box of neuron k, the
+    float64 CUDA tensors ``sums`` (K, B, 3: sum e, sum e^2, sum a e), ``foot`` (K, 3: n, sum a, sum a^2), ``frame_corr``
+    (K, B: Pearson of a and e_t), ``raw`` (K, B: the least-squares amplitude of a in e_t with a free offset), and, of every
+    frame since the state was reset, ``image`` (K, vmax: the w-weighted mean of e_t over the box, x slowest, NaN past a box's
+    n) and ``r_values`` (K: Pearson of a and the image) -- both None with ``finish=False``.  NaN where a variance is not
+    positive or the weights sum to 0; an (k, t) whose box holds a sample that is not finite is NaN and has no part in the
+    image.  A movie larger than one buffer goes in several calls with the same boxes and footprints, as in
+    ``summary_images``: ``first=True`` resets ``state``, the last call has ``finish=True``; a later call may not be larger
+    than the first.  float64 sums in a fixed order, no atomics: the same input gives the same bits.  ``segment``: frames per
+    workgroup (0: the kernel's choice)."""
+    fn = "component_stats"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    dev = frames.device
+    if A_rows.dim() != 2:
+        raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
+    _rows(A_rows, fn, "A_rows", P, f" and rows of {P} floats")
+    K = A_rows.shape[0]
+    for name, t in (("C", C), ("w", w)):
+        _rows(t, fn, name, B, f" and rows of {B} floats")
+        if t.dim() != 2 or t.shape[0] != K:
+            raise ValueError(f"{fn}: {name} must be ({K}, {B}), got {tuple(t.shape)}")
+    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
+    if tuple(bh.shape) != (K, 6):
+        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
+    bd = bh.to(dev)
+    lib = _lib.load()
+    sz3 = _int3((X, Y, Z))
+    need = lib.dnmf_component_stats_workspace(sz3, bh.data_ptr(), K, B, int(segment))
+    if need == 0:
+        raise _refused(lib, "dnmf_component_stats_workspace")
+    if first:
+        state = _workspace(state, need, dev)
+    elif state is None:
+        raise ValueError(f"{fn}: first=False needs the state of the earlier calls")
+    ext = bh[:, 1::2] - bh[:, 0::2] + 1
+    vmax = int(ext.prod(1).max())
+    f64 = dict(dtype=torch.float64, device=dev)
+    sums, foot = torch.empty((K, B, 3), **f64), torch.empty((K, 3), **f64)
+    frame_corr, raw = torch.empty((K, B), **f64), torch.empty((K, B), **f64)
+    image = torch.empty((K, vmax), **f64) if finish else None
+    r_values = torch.empty((K,), **f64) if finish else None
+    with _timed("component_stats"):
+        rc = lib.dnmf_component_stats(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid), sz3,
+                                      B, A_rows.data_ptr(), _ld(A_rows, P), bh.data_ptr(), bd.data_ptr(), K, C.data_ptr(), _ld(C, B),
+                                      w.data_ptr(), _ld(w, B), 1 if first else 0, 1 if finish else 0, int(segment), state.data_ptr(),
+                                      _nbytes(state), sums.data_ptr(), foot.data_ptr(), frame_corr.data_ptr(), raw.data_ptr(),
+                                      _ptr(image), vmax, _ptr(r_values), _stream())
+    _lib.check(rc, "dnmf_component_stats")
+    return dict(sums=sums, foot=foot, frame_corr=frame_corr, raw=raw, image=image, r_values=r_values), state
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--clean", type=float, default=None, metavar="FPS")
     ap.add_argument("--deconvolve", action="store_true")
+    ap.add_argument("--evaluate", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -74,6 +75,12 @@ def main():
               % (float(np.median([np.corrcoef(C[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
                  float(np.median([np.corrcoef(fit[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
                  float(np.nanmedian(info["g"].cpu().numpy())), float(np.exp(-0.3)), int(ok.sum()), K))
+    if a.evaluate:
+        ev = dnmf.evaluate_components(testloader)
+        np.set_printoptions(precision=2, suppress=True, linewidth=160)
+        print("component evaluation over %d active frames each: r_values %s" % (ev["n_active"], ev["r_values"].cpu().numpy()))
+        print("snr %s" % ev["snr"].cpu().numpy())
+        print("keep %s  (%d of %d)" % (ev["keep"].int().cpu().numpy(), int(ev["keep"].sum()), K))
     return corr
 
 

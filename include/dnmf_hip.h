@@ -846,6 +846,49 @@ int dnmf_deconvolve_traces(const float *traces, long ldt, int K, int T, const do
 int dnmf_high_pass_frames(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, const float *taps, int n,
                           float *out, long ldo, dnmf_stream_t stream);
 
+/* ---- K24: per-component statistics on the registered movie: does a fitted component explain anything? --------------------------------
+ * For K neurons and B frames of a volume (X, Y, Z) (rows of ldf >= P floats, voxel p = (x Y + y) Z + z; row frame_ids[j] of frames, or
+ * j, for the j-th frame of the call; row j of sub, lds >= P floats, or NULL: nothing is subtracted), everything in the coordinates of
+ * the footprints.  Neuron k has a box boxes[k] = (x0, x1, y0, y1, z0, z1), inclusive (the layout of dnmf_pack_footprints_lists' bbox),
+ * of n voxels u in the order x slowest, z fastest, and the footprint values a(u) = A[k lda + u] (K rows of lda >= P floats).  With
+ *     e_t(u) = ((double)frames_t(u) - (double)sub_t(u)) + (double)a(u) (double)C[k ldc + j]
+ * -- the residual with the neuron's own contribution put back; C (K rows of ldc >= B floats) in the call's frame order:
+ *   sums        (K, B, 3) float64: sum e, sum e^2, sum a e over the box;
+ *   foot        (K, 3) float64: n, sum a, sum a^2;
+ *   frame_corr  (K, B) float64: Pearson of a and e_t on the box, (n sum ae - sum a sum e) / sqrt((n sum a^2 - (sum a)^2)(n sum e^2 -
+ *               (sum e)^2));
+ *   raw         (K, B) float64: (n sum ae - sum a sum e) / (n sum a^2 - (sum a)^2), the least-squares amplitude of a in e_t with a free
+ *               offset -- the neuron's raw trace;  both NaN where a variance is not positive;
+ *   image       (K, ldi >= the largest n) float64: sum_t w[k, t] e_t(u) / sum_t w[k, t] over every frame since the state was reset, w (K
+ *               rows of ldw >= B floats) >= 0 and finite; NaN past a box's n and where the weights sum to 0;
+ *   r_values    (K) float64: Pearson of a and image[k] on the box; NaN where the weights sum to 0 or a variance is not positive.
+ * tests/components_restatement.py is the definition in float64.  An (k, t) whose box holds a sample that is not finite is invalid: its
+ * three sums, frame_corr and raw are NaN and it takes no part in image[k], as if its weight were 0.  The test is on e_t: a C[k, t] or
+ * a footprint value on the box that is not finite makes the (k, t) invalid in the same way.  w is the caller's to keep >= 0 and
+ * finite: it is not checked, and a weight that is not finite makes image[k] and r_values[k] NaN or meaningless.
+ * One workgroup per (neuron, segment of frames) -- segment > 0: that many frames each; 0: the kernel's choice, enough segments to fill
+ * the machine; a lane keeps its voxels' footprint values and float64 image sums in registers for the whole segment.  The per-frame
+ * sums are reduced across the lanes in a fixed order; a second launch adds the segments of a neuron in their order and forms foot,
+ * frame_corr, raw and, with finish, image and r_values.  No floating-point atomics: the same input gives the same bits.
+ *   boxes      (K, 6) int32 on the HOST: checked before anything is launched, and the size of the largest box sizes the state;
+ *   boxes_dev  the same (K, 6) int32 on the device: what the kernels read;
+ *   state      caller-owned, 8-byte aligned, dnmf_component_stats_workspace(sz, boxes, K, B, segment) bytes (0 on bad arguments; it
+ *              does not decrease with B): the weight sums, the image sums and the partial sums of the segments of one call.  first != 0
+ *              resets it; a movie larger than one buffer is fed in several calls with the same sz, boxes and A.  The per-frame outputs
+ *              (sums, frame_corr, raw) belong to the call; foot is written by every call.
+ *   finish     != 0: the second launch also writes image and r_values.
+ * No host synchronisation.
+ * DNMF_E_NULL: a NULL buffer (sub and frame_ids may be; image and r_values without finish);  DNMF_E_SHAPE: a size, K or B < 1,
+ * segment < 0, a box that is empty or reaches outside the volume, ldf, lds or lda < P, ldc or ldw < B, ldi below the largest box;
+ * DNMF_E_UNSUPPORTED: a box of more than 4096 voxels (K13's limit: 16 voxels a lane), 2^31 voxels or more, more than 65535 segments;
+ * DNMF_E_WORKSPACE: a short or misaligned state.  Nothing is launched on an error. */
+size_t dnmf_component_stats_workspace(const int *sz, const int *boxes, int K, int B, int segment);
+int dnmf_component_stats(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const int *sz, int B,
+                         const float *A, long lda, const int *boxes, const int *boxes_dev, int K, const float *C, long ldc,
+                         const float *w, long ldw, int first, int finish, int segment, void *state, size_t state_bytes,
+                         double *sums, double *foot, double *frame_corr, double *raw, double *image, long ldi, double *r_values,
+                         dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
