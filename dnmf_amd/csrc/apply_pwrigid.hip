@@ -15,7 +15,7 @@
 // filter h[k] = sqrt(3) z1^|k|, z1 = sqrt(3) - 2, applied to the signal mirrored about its end samples.  |z1|^13 < 4e-8,
 // so h is cut at |k| <= 12 (a relative error of 1e-7) and the indices fold back into the axis (period 2n - 2), which
 // serves short axes (n = 2 .. 12) the same way as long ones.
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
@@ -245,8 +245,6 @@ int pw_chunk(long P, int B) {
     return (int)c;
 }
 
-size_t pw_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace dnmf
 
@@ -258,7 +256,7 @@ size_t dnmf_apply_pwrigid_workspace(int X, int Y, int Z, const int *strides, con
     if (dnmf_register_patches_grid(X, Y, Z, strides, overlaps, nullptr, nullptr) <= 0) return 0;
     const long P = (long)X * Y * Z;
     const int Bc = pw_chunk(P, B);
-    return 2 * pw_align((size_t)Bc * P * sizeof(float)) + pw_align((size_t)Bc * 2 * sizeof(unsigned));
+    return 2 * align256((size_t)Bc * P * sizeof(float)) + align256((size_t)Bc * 2 * sizeof(unsigned));
 }
 
 int dnmf_apply_pwrigid(const float *frames, long ldf, const int *frame_ids, int B, int X, int Y, int Z, const int *strides,
@@ -279,8 +277,8 @@ int dnmf_apply_pwrigid(const float *frames, long ldf, const int *frame_ids, int 
     const int Bc = pw_chunk(P, B);
     char *ws = static_cast<char *>(workspace);
     float *bufA = reinterpret_cast<float *>(ws);
-    float *bufB = reinterpret_cast<float *>(ws + pw_align((size_t)Bc * P * sizeof(float)));
-    unsigned *lohi = reinterpret_cast<unsigned *>(ws + 2 * pw_align((size_t)Bc * P * sizeof(float)));
+    float *bufB = reinterpret_cast<float *>(ws + align256((size_t)Bc * P * sizeof(float)));
+    unsigned *lohi = reinterpret_cast<unsigned *>(ws + 2 * align256((size_t)Bc * P * sizeof(float)));
     const long YZ = (long)Y * Z;
     const unsigned bP = (unsigned)((P + 255) / 256);
     for (int f0 = 0; f0 < B; f0 += Bc) {

@@ -16,7 +16,7 @@
 // the finishing launch; tests/background_rank_restatement.py is its definition.  K19's kernels are as they were.
 #include <cstdint>
 
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
@@ -28,28 +28,6 @@ constexpr int BG_DOTS_TARGET_BLOCKS = 4096;
 constexpr int BG_ACC_MIN_SEGMENT = 16;           // frames: below this the partial sums cost more traffic than the frames
 constexpr int BG_ACC_TARGET_BLOCKS = 2048;
 constexpr size_t BG_HEADER = 256;                // bytes: sum f^2
-
-__host__ __device__ constexpr size_t bg_align(size_t n) { return (n + 255) / 256 * 256; }
-
-// sum over the 64 lanes, valid in lane 0 (a fixed tree)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup, valid in thread 0: the waves in their order.  `red` holds BG_WAVES doubles and is free again after
-// the next barrier.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int w = 0; w < BG_WAVES; ++w) s += red[w];
-    return s;
-}
 
 __device__ __forceinline__ unsigned word_phase(const void *p) { return (unsigned)(((uintptr_t)p >> 2) & 3); }
 
@@ -70,8 +48,8 @@ int dots_plan(const char *fn, long P, int B, DotsPlan &g) {
     g.seglen = (len + BG_DOTS_MIN_SEG - 1) / BG_DOTS_MIN_SEG * BG_DOTS_MIN_SEG;
     g.nseg = (int)((P + g.seglen - 1) / g.seglen);
     DNMF_REQUIRE((long)B * g.nseg < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld workgroups", fn, (long)B * g.nseg);
-    g.off_bb = bg_align((size_t)B * g.nseg * sizeof(double));
-    g.bytes = g.off_bb + bg_align((size_t)g.nseg * sizeof(double));
+    g.off_bb = align256((size_t)B * g.nseg * sizeof(double));
+    g.bytes = g.off_bb + align256((size_t)g.nseg * sizeof(double));
     return DNMF_OK;
 }
 
@@ -134,12 +112,12 @@ __global__ __launch_bounds__(BG_THREADS) void background_dots_kernel(DotsArgs a)
     double sum, sumq;
     if (j == 0) {   // the first frame's workgroups also sum b^2 over their segment
         dots_segment<SUB, true>(y, m, b, n, sum, sumq);
-        const double tq = block_sum(sumq, red + BG_WAVES);
+        const double tq = block_sum0<BG_THREADS>(sumq, red + BG_WAVES);
         if (threadIdx.x == 0) a.bbpart[s] = tq;
     } else {
         dots_segment<SUB, false>(y, m, b, n, sum, sumq);
     }
-    const double t = block_sum(sum, red);
+    const double t = block_sum0<BG_THREADS>(sum, red);
     if (threadIdx.x == 0) a.part[bid] = t;
 }
 
@@ -159,37 +137,23 @@ __global__ __launch_bounds__(BG_THREADS) void background_dots_finish_kernel(cons
 }
 
 // ---- accum ---------------------------------------------------------------------------------------------------------------------
-struct AccumPlan {
+struct AccumPlan : SegmentPlan {
     long ntiles;
-    int seglen, nseg;
     size_t stride;   // doubles of one (P,) array
     size_t off_sums, off_part, bytes;
 };
 
 int accum_plan(const char *fn, long P, int B, int segment, AccumPlan &g) {
     DNMF_REQUIRE(P >= 1 && B >= 1, DNMF_E_SHAPE, "%s: P=%ld voxels, B=%d frames", fn, P, B);
-    DNMF_REQUIRE(segment >= 0, DNMF_E_SHAPE, "%s: segment=%d", fn, segment);
     DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, P);
     g.ntiles = (P + BG_TILE - 1) / BG_TILE;
-    long cap;   // the most segments a call of B frames can have: it sizes the state, and does not decrease with B
-    if (segment > 0) {
-        g.seglen = segment;
-        cap = ((long)B + segment - 1) / segment;
-    } else {
-        long want = (BG_ACC_TARGET_BLOCKS + g.ntiles - 1) / g.ntiles;
-        const long most = ((long)B + BG_ACC_MIN_SEGMENT - 1) / BG_ACC_MIN_SEGMENT;
-        if (want > most) want = most;
-        g.seglen = (int)((B + want - 1) / want);
-        cap = want;
-    }
-    DNMF_REQUIRE(cap <= 65535, DNMF_E_UNSUPPORTED, "%s: %ld segments of %d frames (they ride on gridDim.y: at most 65535)", fn, cap,
-                 g.seglen);
-    g.nseg = (int)(((long)B + g.seglen - 1) / g.seglen);
-    const size_t arr = bg_align((size_t)P * sizeof(double));
+    const int rc = segment_plan(fn, B, segment, g.ntiles, BG_ACC_TARGET_BLOCKS, BG_ACC_MIN_SEGMENT, g);
+    if (rc != DNMF_OK) return rc;
+    const size_t arr = align256((size_t)P * sizeof(double));
     g.stride = arr / sizeof(double);
     g.off_sums = BG_HEADER;
     g.off_part = g.off_sums + arr;
-    g.bytes = g.off_part + (size_t)cap * arr;
+    g.bytes = g.off_part + (size_t)g.cap * arr;
     return DNMF_OK;
 }
 
@@ -262,7 +226,7 @@ __global__ __launch_bounds__(BG_THREADS) void background_accum_reduce_kernel(con
             const double v = (double)f[j];
             q = fma(v, v, q);
         }
-        const double t = block_sum(q, red);
+        const double t = block_sum0<BG_THREADS>(q, red);
         if (threadIdx.x == 0) *ff = (first ? 0.0 : *ff) + t;
     }
 }
@@ -613,7 +577,7 @@ int rank_check(const char *fn, int R, int inner) {
     return DNMF_OK;
 }
 
-size_t gram_bytes(long n, int R) { return bg_align((size_t)((n + BG_GRAM_CHUNK - 1) / BG_GRAM_CHUNK) * (R * (R + 1) / 2) * sizeof(double)); }
+size_t gram_bytes(long n, int R) { return align256((size_t)((n + BG_GRAM_CHUNK - 1) / BG_GRAM_CHUNK) * (R * (R + 1) / 2) * sizeof(double)); }
 
 struct DotsRankPlan {
     DotsPlan d;
@@ -627,7 +591,7 @@ int dots_rank_plan(const char *fn, long P, int B, int R, DotsRankPlan &g) {
     if (rc != DNMF_OK) return rc;
     g.off_gram = BGR_HEADER;
     g.off_part = g.off_gram + gram_bytes(P, R);
-    g.bytes = g.off_part + bg_align((size_t)B * g.d.nseg * R * sizeof(double));
+    g.bytes = g.off_part + align256((size_t)B * g.d.nseg * R * sizeof(double));
     return DNMF_OK;
 }
 
@@ -642,10 +606,9 @@ int accum_rank_plan(const char *fn, long P, int B, int R, int segment, AccumRank
     rc = accum_plan(fn, P, B, segment, g.a);
     if (rc != DNMF_OK) return rc;
     const size_t arr = g.a.stride * sizeof(double);
-    const size_t cap = (g.a.bytes - g.a.off_part) / arr;
     g.off_sums = BGR_HEADER;
     g.off_part = g.off_sums + (size_t)R * arr;
-    g.off_gram = g.off_part + cap * R * arr;
+    g.off_gram = g.off_part + (size_t)g.a.cap * R * arr;
     g.bytes = g.off_gram + gram_bytes(B, R);
     return DNMF_OK;
 }

@@ -10,91 +10,22 @@
 // window per key bit (lane t reads key[lo + j]: neighbouring lanes, neighbouring LDS words), the percentile and the median of F0 one
 // block-wide count per bit.  Bits below the lowest set bit of any value of the trace are skipped (a trace that came from fp32 has at
 // least 28 of them).  Sums: a lane adds its frames t = lane, lane + CT_THREADS, ... in that order, a wave reduces in a fixed tree,
-// the waves are added in their order -- no floating-point atomics, the same input gives the same bits.
+// the waves are added in their order (block_ops.hpp, which also has the key helpers) -- no floating-point atomics, the same input
+// gives the same bits.
 #include <cmath>
 #include <cstdint>
 
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
 
-constexpr int CT_THREADS = 1024, CT_WAVES = CT_THREADS / 64;
+constexpr int CT_THREADS = 1024;
 constexpr int CT_STATIC_LDS = 16 * 1024;                   // bytes set aside for the static arrays below (they take 8.2 KiB)
 constexpr int CT_MAX_ELEMS = (160 * 1024 - CT_STATIC_LDS) / 8;   // doubles of the dynamic part: 18 432
 constexpr size_t CT_HEADER = 256;                          // bytes: a, b, fitted of mode 1, median F0 of mode 3
 constexpr int CT_FIT_ITERS = 20, CT_FIT_HALVINGS = 10;     // tests/traces_restatement.py: FIT_ITERS, FIT_HALVINGS
 constexpr double CT_FIT_SLACK = 1e-8;                      // FIT_SLACK there
-constexpr uint64_t NANKEY = ~0ull;
-
-__host__ __device__ constexpr size_t ct_align(size_t n) { return (n + 255) / 256 * 256; }
-
-__device__ __forceinline__ double ct_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// value -> key with key(a) < key(b) <=> a < b; every NaN -> NANKEY, above every value
-__device__ __forceinline__ uint64_t to_key(double v) {
-    if (v != v) return NANKEY;
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-
-__device__ __forceinline__ double from_key(uint64_t k) {
-    if (k == NANKEY) return ct_nan();
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-
-struct OpSum {
-    template <typename T>
-    __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpOr {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a | b; }
-};
-struct OpMinKey {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a < b ? a : b; }
-};
-struct OpFmin {   // NaN is the neutral element: nanmin
-    __device__ double operator()(double a, double b) const { return fmin(a, b); }
-};
-struct OpFmax {
-    __device__ double operator()(double a, double b) const { return fmax(a, b); }
-};
-
-// Reduction over the workgroup, the same value in every lane: the wave in a fixed tree, then the waves in their order.
-// `red` holds CT_WAVES values of 8 bytes and is free again on return.  Every lane of the workgroup must call it.
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, void *redv) {
-    T *red = static_cast<T *>(redv);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_down(v, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = red[0];
-#pragma unroll
-    for (int w = 1; w < CT_WAVES; ++w) s = op(s, red[w]);
-    __syncthreads();
-    return s;
-}
-
-// The lowest key bit that any value of x[0..n) has set (63 when there is none): 0 as soon as one value is negative, whose key is
-// the complement of its bits.
-__device__ __forceinline__ int lowest_bit(const double *x, int n, void *red) {
-    uint64_t bits = 0;
-    for (int t = threadIdx.x; t < n; t += CT_THREADS) {
-        const double v = x[t];
-        if (v == v) {
-            const uint64_t u = (uint64_t)__double_as_longlong(v);
-            bits |= (u >> 63) ? 1ull : u;
-        }
-    }
-    bits = block_reduce(bits, OpOr(), red) & ~(1ull << 63);
-    return bits ? __builtin_ctzll(bits) : 63;
-}
-
-__device__ __forceinline__ void to_keys(double *x, int n) {
-    for (int t = threadIdx.x; t < n; t += CT_THREADS) x[t] = __longlong_as_double((long long)to_key(x[t]));
-    __syncthreads();
-}
 
 // Median of key[lo..hi] (lo <= hi inside the array) without its NANKEYs; NaN when nothing is left, or, with INCLUDENAN, when one
 // entry is a NANKEY.  One pass over the window per key bit from 63 down to lowbit; an even count takes the float64 mean of the two
@@ -103,7 +34,7 @@ template <bool INCLUDENAN>
 __device__ __forceinline__ double window_median(const uint64_t *key, int lo, int hi, int lowbit) {
     int n = 0;
     for (int j = lo; j <= hi; ++j) n += key[j] != NANKEY;
-    if (n == 0 || (INCLUDENAN && n != hi - lo + 1)) return ct_nan();
+    if (n == 0 || (INCLUDENAN && n != hi - lo + 1)) return quiet_nan();
     const int k = (n - 1) >> 1;
     uint64_t pre = 0;
     for (int bit = 63; bit >= lowbit; --bit) {
@@ -130,35 +61,8 @@ __device__ __forceinline__ void running_median(const uint64_t *key, int T, int W
     const int h = W / 2;
     for (int t = threadIdx.x; t < T; t += CT_THREADS) {
         const int lo = max(0, t - h), hi = (int)min((long)T - 1, (long)t - h + W - 1);
-        out[t] = hi >= lo ? window_median<INCLUDENAN>(key, lo, hi, lowbit) : ct_nan();
+        out[t] = hi >= lo ? window_median<INCLUDENAN>(key, lo, hi, lowbit) : quiet_nan();
     }
-}
-
-// The k-th and (k + 1)-th smallest (from 0; the k-th again when there is no further one) of the keys above `above` that are
-// no NANKEY, 0 <= k < their count.  One block-wide count per key bit.
-__device__ __forceinline__ void block_select_pair(const uint64_t *key, int n, uint64_t above, int k, int count, int lowbit, void *red,
-                                                  double &v0, double &v1) {
-    uint64_t pre = 0;
-    for (int bit = 63; bit >= lowbit; --bit) {
-        const uint64_t cand = pre | (1ull << bit);
-        int c = 0;
-        for (int t = threadIdx.x; t < n; t += CT_THREADS) {
-            const uint64_t kk = key[t];
-            c += kk > above && kk < cand;
-        }
-        if (block_reduce(c, OpSum(), red) <= k) pre = cand;
-    }
-    int cle = 0;
-    uint64_t nxt = NANKEY;
-    for (int t = threadIdx.x; t < n; t += CT_THREADS) {
-        const uint64_t kk = key[t];
-        cle += kk > above && kk <= pre;
-        if (kk > pre && kk < nxt) nxt = kk;
-    }
-    cle = block_reduce(cle, OpSum(), red);
-    nxt = block_reduce(nxt, OpMinKey(), red);
-    v0 = from_key(pre);
-    v1 = (k + 1 >= count || cle >= k + 2) ? v0 : from_key(nxt);
 }
 
 // ---- the exponential fit -------------------------------------------------------------------------------------------------------
@@ -177,7 +81,7 @@ __device__ __forceinline__ FitEval fit_eval(const double *y, int T, double b, vo
             see += e * e, sye += v * e, sxee += x * e * e;
         }
     }
-    see = block_reduce(see, OpSum(), red), sye = block_reduce(sye, OpSum(), red), sxee = block_reduce(sxee, OpSum(), red);
+    see = block_reduce<CT_THREADS>(see, OpSum(), red), sye = block_reduce<CT_THREADS>(sye, OpSum(), red), sxee = block_reduce<CT_THREADS>(sxee, OpSum(), red);
     FitEval r;
     r.a = sye / see;
     const double c = sxee / see;
@@ -190,7 +94,7 @@ __device__ __forceinline__ FitEval fit_eval(const double *y, int T, double b, vo
             f += res * res, num += u * res, den += u * u;
         }
     }
-    r.f = block_reduce(f, OpSum(), red), num = block_reduce(num, OpSum(), red), den = block_reduce(den, OpSum(), red);
+    r.f = block_reduce<CT_THREADS>(f, OpSum(), red), num = block_reduce<CT_THREADS>(num, OpSum(), red), den = block_reduce<CT_THREADS>(den, OpSum(), red);
     const double q = num / (r.a * den);
     r.db = (r.a * den != 0.0 && isfinite(q)) ? q : 0.0;
     return r;
@@ -198,7 +102,7 @@ __device__ __forceinline__ FitEval fit_eval(const double *y, int T, double b, vo
 
 // least-squares a exp(b x) on the samples of y: the log-linear fit of the positive ones, then damped Gauss-Newton steps
 __device__ __forceinline__ void fit_exp(const double *y, int T, void *red, double &a_out, double &b_out) {
-    double ymax = ct_nan();
+    double ymax = quiet_nan();
     int npos = 0;
     double sx = 0.0;
     for (int t = threadIdx.x; t < T; t += CT_THREADS) {
@@ -206,7 +110,7 @@ __device__ __forceinline__ void fit_exp(const double *y, int T, void *red, doubl
         if (v == v) ymax = fmax(ymax, v);
         if (v > 0.0) ++npos, sx += (double)(t + 1);
     }
-    ymax = block_reduce(ymax, OpFmax(), red), npos = block_reduce(npos, OpSum(), red), sx = block_reduce(sx, OpSum(), red);
+    ymax = block_reduce<CT_THREADS>(ymax, OpFmax(), red), npos = block_reduce<CT_THREADS>(npos, OpSum(), red), sx = block_reduce<CT_THREADS>(sx, OpSum(), red);
     double b = 0.0;
     if (npos >= 2) {
         const double lmax = log(ymax), xm = sx / (double)npos;
@@ -218,7 +122,7 @@ __device__ __forceinline__ void fit_exp(const double *y, int T, void *red, doubl
                 num += dx * (log(v) - lmax), den += dx * dx;
             }
         }
-        num = block_reduce(num, OpSum(), red), den = block_reduce(den, OpSum(), red);
+        num = block_reduce<CT_THREADS>(num, OpSum(), red), den = block_reduce<CT_THREADS>(den, OpSum(), red);
         if (den > 0.0) b = num / den;
     }
     FitEval cur = fit_eval(y, T, b, red);
@@ -254,8 +158,7 @@ struct CtArgs {
 // running median of x[0..T) (LDS, destroyed: left as keys) into grow (a global row), back into x; -> valid outputs
 template <bool INCLUDENAN>
 __device__ __forceinline__ int median_through(double *x, int T, int W, double *grow, void *red) {
-    const int lowbit = lowest_bit(x, T, red);
-    to_keys(x, T);
+    const int lowbit = to_keys<CT_THREADS>(x, T, red);
     running_median<INCLUDENAN>(reinterpret_cast<const uint64_t *>(x), T, W, lowbit, grow);
     __syncthreads();
     int nv = 0;
@@ -264,20 +167,20 @@ __device__ __forceinline__ int median_through(double *x, int T, int W, double *g
         x[t] = v, nv += v == v;
     }
     __syncthreads();
-    return block_reduce(nv, OpSum(), red);
+    return block_reduce<CT_THREADS>(nv, OpSum(), red);
 }
 
 // ---- phase A -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
     extern __shared__ __attribute__((aligned(16))) double x[];
-    __shared__ double red[CT_WAVES];
+    __shared__ double red[CT_THREADS / 64];
     const int k = blockIdx.x, tid = threadIdx.x, T = g.T;
     const float *row = g.in + (long)k * g.ldi;
     double *wx = g.wx + (size_t)k * T, *wy = g.wy + (size_t)k * T;
     // S1
     for (int t = tid; t < T; t += CT_THREADS) {
         double v = (double)row[t];
-        if (!isfinite(v) || v <= g.floor_ || (g.trim && (t < g.lead || t == T - 1))) v = ct_nan();
+        if (!isfinite(v) || v <= g.floor_ || (g.trim && (t < g.lead || t == T - 1))) v = quiet_nan();
         x[t] = v;
     }
     __syncthreads();
@@ -290,14 +193,14 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
             const double v = x[t];
             if (v == v) ++n, s += v;
         }
-        n = block_reduce(n, OpSum(), red), s = block_reduce(s, OpSum(), red);
+        n = block_reduce<CT_THREADS>(n, OpSum(), red), s = block_reduce<CT_THREADS>(s, OpSum(), red);
         const double mean = s / (double)n;
         double q = 0.0;
         for (int t = tid; t < T; t += CT_THREADS) {
             const double v = x[t];
             if (v == v) q += (v - mean) * (v - mean);
         }
-        q = block_reduce(q, OpSum(), red);
+        q = block_reduce<CT_THREADS>(q, OpSum(), red);
         const double thr = g.sigma * sqrt(q / (double)(n - 1)) + mean;
         unsigned flags = 0;   // bit i: frame tid + i CT_THREADS is extreme (T <= CT_MAX_ELEMS: at most 18 frames a lane)
         int i = 0;
@@ -310,9 +213,9 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
         __syncthreads();
         i = 0;
         for (int t = tid; t < T; t += CT_THREADS, ++i)
-            if (flags >> i & 1) x[t] = ct_nan();
+            if (flags >> i & 1) x[t] = quiet_nan();
         __syncthreads();
-        nout = block_reduce(nout, OpSum(), red);
+        nout = block_reduce<CT_THREADS>(nout, OpSum(), red);
         // median of three, the window cut at the ends; a NaN in it gives NaN
         for (int t = tid; t < T; t += CT_THREADS) {
             const double c = x[t];
@@ -323,7 +226,7 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
             else {
                 const double l = x[t - 1], r = x[t + 1];
                 m = fmax(fmin(l, c), fmin(fmax(l, c), r));
-                if (l != l || c != c || r != r) m = ct_nan();
+                if (l != l || c != c || r != r) m = quiet_nan();
             }
             wx[t] = m;
         }
@@ -333,34 +236,33 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
     } else {
         for (int t = tid; t < T; t += CT_THREADS) wx[t] = x[t];
     }
-    double F0 = ct_nan(), a = ct_nan(), b = ct_nan(), scale = 1.0, offset = 0.0;
+    double F0 = quiet_nan(), a = quiet_nan(), b = quiet_nan(), scale = 1.0, offset = 0.0;
     int fitted = 0;
     if (g.mode > 0) {
         // F0: the 5th percentile of the entries > 0.1 (MATLAB's prctile)
-        const int lowbit = lowest_bit(x, T, red);
-        to_keys(x, T);
+        const int lowbit = to_keys<CT_THREADS>(x, T, red);
         const uint64_t *key = reinterpret_cast<const uint64_t *>(x);
         const uint64_t above = to_key(0.1);
         int n = 0;
         for (int t = tid; t < T; t += CT_THREADS) n += key[t] > above && key[t] != NANKEY;
-        n = block_reduce(n, OpSum(), red);
+        n = block_reduce<CT_THREADS>(n, OpSum(), red);
         if (n > 0) {
             double pos = (double)n * 5.0 / 100.0 - 0.5;
             pos = fmin(fmax(pos, 0.0), (double)(n - 1));
             const double fl = floor(pos);
             double v0, v1;
-            block_select_pair(key, T, above, (int)fl, n, lowbit, red, v0, v1);
+            block_select_pair<CT_THREADS>(key, T, above, (int)fl, n, lowbit, red, v0, v1);
             F0 = v0 + (pos - fl) * (v1 - v0);
         }
         if (g.mode == 1) {
             // the reference's global variant: every trace to [0, 1] first
             for (int t = tid; t < T; t += CT_THREADS) x[t] = wx[t];
             __syncthreads();
-            double lo = ct_nan(), hi = ct_nan();
+            double lo = quiet_nan(), hi = quiet_nan();
             for (int t = tid; t < T; t += CT_THREADS) lo = fmin(lo, x[t]);
-            offset = block_reduce(lo, OpFmin(), red);
+            offset = block_reduce<CT_THREADS>(lo, OpFmin(), red);
             for (int t = tid; t < T; t += CT_THREADS) hi = fmax(hi, x[t] - offset);
-            scale = block_reduce(hi, OpFmax(), red);
+            scale = block_reduce<CT_THREADS>(hi, OpFmax(), red);
             for (int t = tid; t < T; t += CT_THREADS) wx[t] = (x[t] - offset) / scale;
         } else {
             running_median<false>(key, T, g.W, lowbit, wy);
@@ -371,7 +273,7 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
                 x[t] = v, nv += v == v;
             }
             __syncthreads();
-            nv = block_reduce(nv, OpSum(), red);
+            nv = block_reduce<CT_THREADS>(nv, OpSum(), red);
             fitted = (double)nv > 0.1 * (double)T;
             if (fitted) fit_exp(x, T, red, a, b);
         }
@@ -385,7 +287,7 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_a_kernel(CtArgs g) {
 // ---- phase B -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CT_THREADS) void clean_traces_b_kernel(CtArgs g) {
     extern __shared__ __attribute__((aligned(16))) double x[];
-    __shared__ double red[CT_WAVES];
+    __shared__ double red[CT_THREADS / 64];
     const int tid = threadIdx.x, T = g.T, K = g.K;
     if (g.mode == 1) {
         for (int t = tid; t < T; t += CT_THREADS) {   // the mean over the traces, in their order
@@ -395,28 +297,23 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_b_kernel(CtArgs g) {
                 const double v = g.wx[(size_t)k * T + t];
                 if (v == v) s += v, ++n;
             }
-            x[t] = n ? s / (double)n : ct_nan();
+            x[t] = n ? s / (double)n : quiet_nan();
         }
         __syncthreads();
         const int nv = median_through<false>(x, T, g.W, g.wy, red);
-        double a = ct_nan(), b = ct_nan();
+        double a = quiet_nan(), b = quiet_nan();
         const int fitted = (double)nv > 0.1 * (double)T;
         if (fitted) fit_exp(x, T, red, a, b);
         if (tid == 0) g.hdr[0] = a, g.hdr[1] = b, g.hdr[2] = (double)fitted;
     } else {   // mode 3: the median of the F0 that are no NaN
         for (int k = tid; k < K; k += CT_THREADS) x[k] = g.F0[k];
         __syncthreads();
-        to_keys(x, K);
+        to_keys<CT_THREADS>(x, K, red);   // its lowest bit is not used: every bit is searched
         const uint64_t *key = reinterpret_cast<const uint64_t *>(x);
         int n = 0;
         for (int k = tid; k < K; k += CT_THREADS) n += key[k] != NANKEY;
-        n = block_reduce(n, OpSum(), red);
-        double med = ct_nan();
-        if (n > 0) {
-            double v0, v1;
-            block_select_pair(key, K, 0, (n - 1) >> 1, n, 0, red, v0, v1);
-            med = (n & 1) ? v0 : 0.5 * (v0 + v1);
-        }
+        n = block_reduce<CT_THREADS>(n, OpSum(), red);
+        const double med = n > 0 ? block_median<CT_THREADS>(key, K, n, 0, red) : quiet_nan();
         if (tid == 0) g.hdr[3] = med;
     }
 }
@@ -424,7 +321,7 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_b_kernel(CtArgs g) {
 // ---- phase C -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CT_THREADS) void clean_traces_c_kernel(CtArgs g) {
     extern __shared__ __attribute__((aligned(16))) double x[];
-    __shared__ double red[CT_WAVES];
+    __shared__ double red[CT_THREADS / 64];
     __shared__ int s_first[CT_THREADS], s_last[CT_THREADS];
     const int k = blockIdx.x, tid = threadIdx.x, T = g.T;
     const double *wx = g.wx + (size_t)k * T;
@@ -487,7 +384,7 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_c_kernel(CtArgs g) {
         const int h = g.sw / 2;
         for (int t = tid; t < T; t += CT_THREADS) {
             const int lo = max(0, t - h), hi = (int)min((long)T - 1, (long)t - h + g.sw - 1);
-            double s = ct_nan();
+            double s = quiet_nan();
             if (hi >= lo) {
                 s = x[lo];
                 for (int j = lo + 1; j <= hi; ++j) s += x[j];
@@ -503,11 +400,11 @@ __global__ __launch_bounds__(CT_THREADS) void clean_traces_c_kernel(CtArgs g) {
     }
     // S6
     if (g.mode < 3) {
-        double lo = ct_nan(), hi = ct_nan();
+        double lo = quiet_nan(), hi = quiet_nan();
         for (int t = tid; t < T; t += CT_THREADS) lo = fmin(lo, x[t]);
-        const double noff = block_reduce(lo, OpFmin(), red);
+        const double noff = block_reduce<CT_THREADS>(lo, OpFmin(), red);
         for (int t = tid; t < T; t += CT_THREADS) hi = fmax(hi, x[t] - noff);
-        const double nscale = block_reduce(hi, OpFmax(), red);
+        const double nscale = block_reduce<CT_THREADS>(hi, OpFmax(), red);
         for (int t = tid; t < T; t += CT_THREADS) x[t] = (x[t] - noff) / nscale * 0.9 + 0.05;
         offset = offset + (doff + noff) * scale;
         scale = scale * nscale;
@@ -526,7 +423,7 @@ int ct_plan(const char *fn, int K, int T, CtPlan &p) {
     DNMF_REQUIRE(K >= 1 && T >= 1, DNMF_E_SHAPE, "%s: K=%d traces, T=%d frames", fn, K, T);
     DNMF_REQUIRE(T <= CT_MAX_ELEMS && K <= CT_MAX_ELEMS, DNMF_E_UNSUPPORTED,
                  "%s: K=%d, T=%d: a trace (and the F0 of all traces) must fit %d float64 in LDS", fn, K, T, CT_MAX_ELEMS);
-    const size_t arr = ct_align((size_t)K * T * sizeof(double));
+    const size_t arr = align256((size_t)K * T * sizeof(double));
     p.off_x = CT_HEADER, p.off_y = CT_HEADER + arr, p.bytes = CT_HEADER + 2 * arr;
     p.lds = (unsigned)(sizeof(double) * (size_t)(T > K ? T : K));
     p.lds = (p.lds + 15u) & ~15u;

@@ -11,7 +11,7 @@
 // and only then does the frame's w e enter the image sums.  A segment's image sums go to the state; a second launch adds
 // the segments of a neuron in their order (no floating-point atomics: the same input gives the same bits) and forms the
 // per-frame and per-neuron figures.
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
@@ -21,14 +21,11 @@ constexpr int CS_MAX_VOXELS = 4096;     // K13's limit: 16 voxels a lane
 constexpr int CS_MIN_SEGMENT = 16;      // frames: below this the partial image sums cost more traffic than the frames
 constexpr int CS_TARGET_BLOCKS = 2048;
 
-__host__ __device__ constexpr size_t cs_align(size_t n) { return (n + 255) / 256 * 256; }
-
-struct ComponentPlan {
+struct ComponentPlan : SegmentPlan {
     int X, Y, Z, K, vmax, slots;
     long P;
-    int seglen, nseg;
     size_t vstride;                                              // doubles between the image sums of two (neuron, segment)s
-    size_t cap, off_w, off_img, off_pw, off_pimg, bytes;         // cap: the most segments a call of B frames can have
+    size_t off_w, off_img, off_pw, off_pimg, bytes;
 };
 
 // Everything the two entries agree on; validates what both take.  boxes is a host array.
@@ -36,7 +33,6 @@ int component_plan(const char *fn, const int *sz, const int *boxes, int K, int B
     DNMF_REQUIRE(sz && boxes, DNMF_E_NULL, "%s: sz or boxes is NULL", fn);
     DNMF_REQUIRE(sz[0] >= 1 && sz[1] >= 1 && sz[2] >= 1, DNMF_E_SHAPE, "%s: volume %dx%dx%d", fn, sz[0], sz[1], sz[2]);
     DNMF_REQUIRE(K >= 1 && B >= 1, DNMF_E_SHAPE, "%s: K=%d neurons, B=%d frames", fn, K, B);
-    DNMF_REQUIRE(segment >= 0, DNMF_E_SHAPE, "%s: segment=%d", fn, segment);
     g.X = sz[0], g.Y = sz[1], g.Z = sz[2], g.K = K;
     g.P = (long)g.X * g.Y * g.Z;
     DNMF_REQUIRE(g.P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, g.P);
@@ -55,29 +51,15 @@ int component_plan(const char *fn, const int *sz, const int *boxes, int K, int B
     const int per_lane = (g.vmax + CS_THREADS - 1) / CS_THREADS;
     g.slots = 1;
     while (g.slots < per_lane) g.slots *= 2;
-    long cap;
-    if (segment > 0) {
-        g.seglen = segment;
-        cap = ((long)B + segment - 1) / segment;
-    } else {
-        // enough workgroups to fill the machine, segments no shorter than CS_MIN_SEGMENT frames
-        long want = (CS_TARGET_BLOCKS + (long)K - 1) / K;
-        const long most = ((long)B + CS_MIN_SEGMENT - 1) / CS_MIN_SEGMENT;
-        if (want > most) want = most;
-        g.seglen = (int)((B + want - 1) / want);
-        cap = want;
-    }
-    DNMF_REQUIRE(cap <= 65535, DNMF_E_UNSUPPORTED, "%s: %ld segments of %d frames (they ride on gridDim.y: at most 65535)", fn, cap,
-                 g.seglen);
-    g.nseg = (int)(((long)B + g.seglen - 1) / g.seglen);
-    g.cap = (size_t)cap;
-    g.vstride = cs_align((size_t)g.vmax * sizeof(double)) / sizeof(double);
-    const size_t Ks = (size_t)K;
+    const int rc = segment_plan(fn, B, segment, K, CS_TARGET_BLOCKS, CS_MIN_SEGMENT, g);
+    if (rc != DNMF_OK) return rc;
+    g.vstride = align256((size_t)g.vmax * sizeof(double)) / sizeof(double);
+    const size_t Ks = (size_t)K, cap = (size_t)g.cap;
     g.off_w = 0;
-    g.off_img = g.off_w + cs_align(Ks * sizeof(double));
+    g.off_img = g.off_w + align256(Ks * sizeof(double));
     g.off_pw = g.off_img + Ks * g.vstride * sizeof(double);
-    g.off_pimg = g.off_pw + cs_align(Ks * g.cap * sizeof(double));
-    g.bytes = g.off_pimg + Ks * g.cap * g.vstride * sizeof(double);
+    g.off_pimg = g.off_pw + align256(Ks * cap * sizeof(double));
+    g.bytes = g.off_pimg + Ks * cap * g.vstride * sizeof(double);
     return DNMF_OK;
 }
 
@@ -110,15 +92,8 @@ __device__ __forceinline__ int box_offset(const Box &q, int i, int Y, int Z) {
     return ((q.x0 + bx) * Y + q.y0 + by) * Z + q.z0 + bz;
 }
 
-// the sum over the wave, in lane 0, in a fixed order
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-
-// The sums of three values over the workgroup, in every lane, in a fixed order.  red: CS_WAVES x 3 doubles of LDS that no lane
-// still reads.
+// The sums of three values over the workgroup behind one barrier, in every lane, in block_reduce's order (block_ops.hpp).  red:
+// CS_WAVES x 3 doubles of LDS that no lane still reads.
 __device__ __forceinline__ void block_sum3(double &a, double &b, double &c, double *red) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     a = wave_sum(a), b = wave_sum(b), c = wave_sum(c);

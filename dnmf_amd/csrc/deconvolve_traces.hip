@@ -15,16 +15,16 @@
 // D5's search for the penalty calls 2 and 3 in a loop inside the kernel (block-uniform control flow, no host synchronisation).
 // The records take 24 bytes a frame: up to DC_LDS_FRAMES frames they live in LDS, longer traces keep them in the caller's workspace
 // and only the 8 T bytes of keys in LDS.  The trace itself is read from its fp32 row (L2) whenever it is needed.
-// The selection helpers are those of clean_traces.hip (K20).
+// The reductions and the selection helpers are those of block_ops.hpp, which K20 uses too.
 #include <cmath>
 #include <cstdint>
 
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
 
-constexpr int DC_THREADS = 1024, DC_WAVES = DC_THREADS / 64;
+constexpr int DC_THREADS = 1024;
 constexpr int DC_STATIC_LDS = 16 * 1024;                           // bytes set aside for the static arrays below (they take 8.2 KiB)
 constexpr int DC_DYNAMIC_LDS = 160 * 1024 - DC_STATIC_LDS;
 constexpr int DC_RECORD = 24;                                      // bytes of a pool record: num, den (double), len, prev (int)
@@ -33,97 +33,6 @@ constexpr int DC_MAX_ELEMS = DC_DYNAMIC_LDS / 8;                   // 18 432: th
 constexpr size_t DC_HEADER = 256;
 constexpr int DC_DOUBLINGS = 64, DC_HALVINGS = 32, DC_MIN_VALID = 4;   // tests/deconv_restatement.py: DOUBLINGS, HALVINGS, MIN_VALID
 constexpr int DC_INFO = 8;                                         // doubles of info per trace
-constexpr uint64_t NANKEY = ~0ull;
-
-__host__ __device__ constexpr size_t dc_align(size_t n) { return (n + 255) / 256 * 256; }
-
-__device__ __forceinline__ double dc_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// value -> key with key(a) < key(b) <=> a < b; every NaN -> NANKEY, above every value
-__device__ __forceinline__ uint64_t to_key(double v) {
-    if (v != v) return NANKEY;
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-
-__device__ __forceinline__ double from_key(uint64_t k) {
-    if (k == NANKEY) return dc_nan();
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~(1ull << 63)) : ~k));
-}
-
-struct OpSum {
-    template <typename T>
-    __device__ T operator()(T a, T b) const { return a + b; }
-};
-struct OpOr {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a | b; }
-};
-struct OpMinKey {
-    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return a < b ? a : b; }
-};
-
-// Reduction over the workgroup, the same value in every lane: the wave in a fixed tree, then the waves in their order.
-// `red` holds DC_WAVES values of 8 bytes and is free again on return.  Every lane of the workgroup must call it.
-template <typename T, typename Op>
-__device__ __forceinline__ T block_reduce(T v, Op op, void *redv) {
-    T *red = static_cast<T *>(redv);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_down(v, off, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    T s = red[0];
-#pragma unroll
-    for (int w = 1; w < DC_WAVES; ++w) s = op(s, red[w]);
-    __syncthreads();
-    return s;
-}
-
-// x[0..n) (doubles, NaN = none) -> keys in place; returns the lowest key bit that any value has set (63 when there is none; 0 as
-// soon as one value is negative, whose key is the complement of its bits): the bits below it need no pass.
-__device__ __forceinline__ int to_keys(double *x, int n, void *red) {
-    uint64_t bits = 0;
-    for (int t = threadIdx.x; t < n; t += DC_THREADS) {
-        const double v = x[t];
-        if (v == v) {
-            const uint64_t u = (uint64_t)__double_as_longlong(v);
-            bits |= (u >> 63) ? 1ull : u;
-        }
-        x[t] = __longlong_as_double((long long)to_key(v));
-    }
-    bits = block_reduce(bits, OpOr(), red) & ~(1ull << 63);   // ends with a barrier: the keys are visible
-    return bits ? __builtin_ctzll(bits) : 63;
-}
-
-// The k-th and (k + 1)-th smallest (from 0; the k-th again when there is no further one) of the keys that are no NANKEY,
-// 0 <= k < count.  One block-wide count per key bit.
-__device__ __forceinline__ void block_select_pair(const uint64_t *key, int n, int k, int count, int lowbit, void *red, double &v0,
-                                                  double &v1) {
-    uint64_t pre = 0;
-    for (int bit = 63; bit >= lowbit; --bit) {
-        const uint64_t cand = pre | (1ull << bit);
-        int c = 0;
-        for (int t = threadIdx.x; t < n; t += DC_THREADS) c += key[t] < cand;
-        if (block_reduce(c, OpSum(), red) <= k) pre = cand;
-    }
-    int cle = 0;
-    uint64_t nxt = NANKEY;
-    for (int t = threadIdx.x; t < n; t += DC_THREADS) {
-        const uint64_t kk = key[t];
-        cle += kk <= pre;
-        if (kk > pre && kk < nxt) nxt = kk;
-    }
-    cle = block_reduce(cle, OpSum(), red);
-    nxt = block_reduce(nxt, OpMinKey(), red);
-    v0 = from_key(pre);
-    v1 = (k + 1 >= count || cle >= k + 2) ? v0 : from_key(nxt);
-}
-
-// np.median of the `count` >= 1 keys that are no NANKEY
-__device__ __forceinline__ double block_median(const uint64_t *key, int n, int count, int lowbit, void *red) {
-    double v0, v1;
-    block_select_pair(key, n, (count - 1) >> 1, count, lowbit, red, v0, v1);
-    return (count & 1) ? v0 : 0.5 * (v0 + v1);
-}
 
 struct DcArgs {
     const float *in;
@@ -255,21 +164,21 @@ __device__ __forceinline__ Solved solve(const Pools &P, double lam, float *c_out
             if (WRITE) c_out[t] = (float)c, s_out[t] = (float)s;
         }
     }
-    r.rss = block_reduce(r.rss, OpSum(), P.red);
-    r.positive = block_reduce(r.positive, OpSum(), P.red);
-    if (WRITE) r.pools = block_reduce(r.pools, OpSum(), P.red);
+    r.rss = block_reduce<DC_THREADS>(r.rss, OpSum(), P.red);
+    r.positive = block_reduce<DC_THREADS>(r.positive, OpSum(), P.red);
+    if (WRITE) r.pools = block_reduce<DC_THREADS>(r.pools, OpSum(), P.red);
     return r;   // the reductions end with a barrier: the records may be written again
 }
 
 __device__ __forceinline__ bool given(const double *a, int k, double &v) {
-    v = a ? a[k] : dc_nan();
+    v = a ? a[k] : quiet_nan();
     return v == v;
 }
 
 template <bool WS>
 __global__ __launch_bounds__(DC_THREADS) void deconvolve_traces_kernel(DcArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
-    __shared__ double red[DC_WAVES];
+    __shared__ double red[DC_THREADS / 64];
     __shared__ int s_top[DC_THREADS], s_last[DC_THREADS];
     const int k = blockIdx.x, tid = threadIdx.x, T = a.T;
     const float *row = a.in + (long)k * a.ldi;
@@ -287,8 +196,8 @@ __global__ __launch_bounds__(DC_THREADS) void deconvolve_traces_kernel(DcArgs a)
             if (t + 2 < T && isfinite((double)row[t + 2])) ++n2;
         }
     }
-    n_valid = block_reduce(n_valid, OpSum(), red), n1 = block_reduce(n1, OpSum(), red), n2 = block_reduce(n2, OpSum(), red);
-    sum = block_reduce(sum, OpSum(), red);
+    n_valid = block_reduce<DC_THREADS>(n_valid, OpSum(), red), n1 = block_reduce<DC_THREADS>(n1, OpSum(), red), n2 = block_reduce<DC_THREADS>(n2, OpSum(), red);
+    sum = block_reduce<DC_THREADS>(sum, OpSum(), red);
     double g, lam, b, sigma;
     const bool has_g = given(a.g, k, g), has_lam = given(a.penalty, k, lam), has_b = given(a.baseline, k, b);
     const bool has_sigma = given(a.noise, k, sigma);
@@ -299,54 +208,54 @@ __global__ __launch_bounds__(DC_THREADS) void deconvolve_traces_kernel(DcArgs a)
         for (int t = tid; t < T; t += DC_THREADS) {
             const double y = (double)row[t];
             if (isfinite(y)) {
-                const double y1 = t + 1 < T ? (double)row[t + 1] : dc_nan(), y2 = t + 2 < T ? (double)row[t + 2] : dc_nan();
+                const double y1 = t + 1 < T ? (double)row[t + 1] : quiet_nan(), y2 = t + 2 < T ? (double)row[t + 2] : quiet_nan();
                 if (isfinite(y1)) p1 += (y - m) * (y1 - m);
                 if (isfinite(y2)) p2 += (y - m) * (y2 - m);
             }
         }
-        p1 = block_reduce(p1, OpSum(), red), p2 = block_reduce(p2, OpSum(), red);
-        const double ac1 = p1 / (double)n1, ac2 = n2 > 0 ? p2 / (double)n2 : dc_nan();
-        g = ac1 > 0.0 ? ac2 / ac1 : dc_nan();
+        p1 = block_reduce<DC_THREADS>(p1, OpSum(), red), p2 = block_reduce<DC_THREADS>(p2, OpSum(), red);
+        const double ac1 = p1 / (double)n1, ac2 = n2 > 0 ? p2 / (double)n2 : quiet_nan();
+        g = ac1 > 0.0 ? ac2 / ac1 : quiet_nan();
     }
     ok = ok && g > 0.0 && g < 1.0;
     uint64_t *key = reinterpret_cast<uint64_t *>(dyn);
     if (ok && !has_b) {   // D4
         for (int t = tid; t < T; t += DC_THREADS) {
             const double y = (double)row[t];
-            dyn[t] = isfinite(y) ? y : dc_nan();
+            dyn[t] = isfinite(y) ? y : quiet_nan();
         }
-        const int lowbit = to_keys(dyn, T, red);
+        const int lowbit = to_keys<DC_THREADS>(dyn, T, red);
         double pos = (double)n_valid * a.pct / 100.0 - 0.5;
         pos = fmin(fmax(pos, 0.0), (double)(n_valid - 1));
         const double fl = floor(pos);
         double v0, v1;
-        block_select_pair(key, T, (int)fl, n_valid, lowbit, red, v0, v1);
+        block_select_pair<DC_THREADS, false>(key, T, 0, (int)fl, n_valid, lowbit, red, v0, v1);
         b = v0 + (pos - fl) * (v1 - v0);
     }
     ok = ok && isfinite(b) && !(has_lam && lam < 0.0);
     if (ok && !has_sigma) {   // D2
         if (n1 >= 2) {
             for (int t = tid; t < T; t += DC_THREADS) {
-                const double y0 = (double)row[t], y1 = t + 1 < T ? (double)row[t + 1] : dc_nan();
-                dyn[t] = isfinite(y0) && isfinite(y1) ? y1 - y0 : dc_nan();
+                const double y0 = (double)row[t], y1 = t + 1 < T ? (double)row[t + 1] : quiet_nan();
+                dyn[t] = isfinite(y0) && isfinite(y1) ? y1 - y0 : quiet_nan();
             }
-            int lowbit = to_keys(dyn, T, red);
-            const double med = block_median(key, T, n1, lowbit, red);
+            int lowbit = to_keys<DC_THREADS>(dyn, T, red);
+            const double med = block_median<DC_THREADS>(key, T, n1, lowbit, red);
             for (int t = tid; t < T; t += DC_THREADS) {
-                const double y0 = (double)row[t], y1 = t + 1 < T ? (double)row[t + 1] : dc_nan();
-                dyn[t] = isfinite(y0) && isfinite(y1) ? fabs((y1 - y0) - med) : dc_nan();
+                const double y0 = (double)row[t], y1 = t + 1 < T ? (double)row[t + 1] : quiet_nan();
+                dyn[t] = isfinite(y0) && isfinite(y1) ? fabs((y1 - y0) - med) : quiet_nan();
             }
-            lowbit = to_keys(dyn, T, red);
-            sigma = 1.4826 * block_median(key, T, n1, lowbit, red) / sqrt(2.0);
+            lowbit = to_keys<DC_THREADS>(dyn, T, red);
+            sigma = 1.4826 * block_median<DC_THREADS>(key, T, n1, lowbit, red) / sqrt(2.0);
         } else {
-            sigma = dc_nan();
+            sigma = quiet_nan();
         }
     }
     if (!ok) {   // D6 (block-uniform)
         const float nanf_ = __int_as_float(0x7fc00000);
         for (int t = tid; t < T; t += DC_THREADS) c_out[t] = nanf_, s_out[t] = nanf_;
         if (tid == 0) {
-            for (int i = 0; i < 5; ++i) info[i] = dc_nan();
+            for (int i = 0; i < 5; ++i) info[i] = quiet_nan();
             info[5] = (double)n_valid, info[6] = 0.0, info[7] = 0.0;
         }
         return;
@@ -403,7 +312,7 @@ int dc_plan(const char *fn, int K, int T, DcPlan &p) {
                  "%s: K=%d, T=%d: at most %d traces of at most %d frames (a trace's float64 keys must fit LDS)", fn, K, T,
                  DC_MAX_ELEMS, DC_MAX_ELEMS);
     p.ws = T > DC_LDS_FRAMES;
-    p.bytes = DC_HEADER + (p.ws ? dc_align((size_t)K * (size_t)T * DC_RECORD) : 0);
+    p.bytes = DC_HEADER + (p.ws ? align256((size_t)K * (size_t)T * DC_RECORD) : 0);
     p.lds = (unsigned)((size_t)T * (p.ws ? 8 : DC_RECORD));
     p.lds = (p.lds + 15u) & ~15u;
     return DNMF_OK;

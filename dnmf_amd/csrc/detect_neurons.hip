@@ -18,6 +18,7 @@
 //            filter's response to that footprint through per-axis tables h_axis in LDS, exclusion (-inf) of the voxels within
 //            min_distance, and the new maxima of the tiles the window touched.  The steps are separated by __syncthreads; R
 //            and the table live in the caller's workspace and are only touched by this workgroup.
+#include "block_ops.hpp"
 #include "matched_filter.hpp"
 
 namespace dnmf {
@@ -252,8 +253,6 @@ __global__ __launch_bounds__(DT_THREADS) void pursuit_kernel(float *R, float *tm
     for (int i = found + tid; i < K; i += DT_THREADS) amplitudes[i] = nan;
     if (tid == 0) *count = found;
 }
-
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // 0 ok, else the error already recorded
 int detect_geometry(const char *fn, const int *sz, int K, double sigma, double min_distance, DetectGeom &g) {

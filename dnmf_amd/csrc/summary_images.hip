@@ -9,7 +9,7 @@
 // with x0 the voxel's value in the first frame after the reset.  The differences are exact in float64, so a constant voxel
 // has a variance of exactly 0.  The partial sums of a segment go to the workspace; a second kernel adds the segments to the
 // state in a fixed order (no floating-point atomics: the same input gives the same bits), a third writes the images.
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
@@ -21,8 +21,6 @@ constexpr int SI_TARGET_BLOCKS = 1024;
 constexpr int SI_MAX_Z = 137;        // two staged tiles within 48 KiB of LDS
 constexpr size_t SI_HEADER = 256;    // bytes: the frame count
 
-__host__ __device__ constexpr size_t si_align(size_t n) { return (n + 255) / 256 * 256; }
-
 // The half-set of the 26 directions in lexicographic order, m = 0..12: (0,0,1) (0,1,-1) (0,1,0) (0,1,1) (1,-1,-1) ... (1,1,1).
 __host__ __device__ constexpr int dir_dx(int m) { return m >= 4 ? 1 : 0; }
 __host__ __device__ constexpr int dir_dy(int m) { return m == 0 ? 0 : (m <= 3 ? 1 : (m - 4) / 3 - 1); }
@@ -33,10 +31,10 @@ __host__ __device__ constexpr int dir_of(bool full, bool hasz, int k) {
 }
 __host__ __device__ constexpr int dir_count(bool full, bool hasz) { return full ? (hasz ? 13 : 4) : (hasz ? 3 : 2); }
 
-struct SummaryPlan {
+struct SummaryPlan : SegmentPlan {
     int X, Y, Z, full, nd;
     long P, plane;
-    int ntx, ntc, seglen, nseg;
+    int ntx, ntc;
     size_t off_sums, off_max, off_pivot, off_part, off_pmax, bytes;   // sums: (2 + nd, P) float64
 };
 
@@ -47,36 +45,21 @@ int summary_plan(const char *fn, const int *sz, int neighbours, int B, int segme
     DNMF_REQUIRE(B >= 1, DNMF_E_SHAPE, "%s: B=%d frames", fn, B);
     DNMF_REQUIRE(neighbours == DNMF_NEIGHBOURS_FACE || neighbours == DNMF_NEIGHBOURS_FULL, DNMF_E_SHAPE,
                  "%s: neighbours=%d (0 face, 1 full)", fn, neighbours);
-    DNMF_REQUIRE(segment >= 0, DNMF_E_SHAPE, "%s: segment=%d", fn, segment);
     g.X = sz[0], g.Y = sz[1], g.Z = sz[2], g.full = neighbours == DNMF_NEIGHBOURS_FULL;
     g.P = (long)g.X * g.Y * g.Z, g.plane = (long)g.Y * g.Z;
     DNMF_REQUIRE(g.P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, g.P);
     DNMF_REQUIRE(g.Z <= SI_MAX_Z, DNMF_E_UNSUPPORTED, "%s: Z=%d, at most %d (the halo of a tile is Z + 1 columns)", fn, g.Z, SI_MAX_Z);
     g.nd = dir_count(g.full, g.Z > 1);
     g.ntx = (g.X + SI_TX - 1) / SI_TX, g.ntc = (int)((g.plane + SI_TC - 1) / SI_TC);
-    const long tiles = (long)g.ntx * g.ntc;
-    long cap;   // the most segments a call of B frames can have: it sizes the state, and does not decrease with B
-    if (segment > 0) {
-        g.seglen = segment;
-        cap = ((long)B + segment - 1) / segment;
-    } else {
-        // enough workgroups to fill the machine, segments no shorter than SI_MIN_SEGMENT frames
-        long want = (SI_TARGET_BLOCKS + tiles - 1) / tiles;
-        const long most = ((long)B + SI_MIN_SEGMENT - 1) / SI_MIN_SEGMENT;
-        if (want > most) want = most;
-        g.seglen = (int)((B + want - 1) / want);
-        cap = want;
-    }
-    DNMF_REQUIRE(cap <= 65535, DNMF_E_UNSUPPORTED, "%s: %ld segments of %d frames (they ride on gridDim.y: at most 65535)", fn, cap,
-                 g.seglen);
-    g.nseg = (int)(((long)B + g.seglen - 1) / g.seglen);
-    const size_t P = (size_t)g.P, sums = si_align((size_t)(2 + g.nd) * P * sizeof(double)), fl = si_align(P * sizeof(float));
+    const int rc = segment_plan(fn, B, segment, (long)g.ntx * g.ntc, SI_TARGET_BLOCKS, SI_MIN_SEGMENT, g);
+    if (rc != DNMF_OK) return rc;
+    const size_t P = (size_t)g.P, sums = align256((size_t)(2 + g.nd) * P * sizeof(double)), fl = align256(P * sizeof(float));
     g.off_sums = SI_HEADER;
     g.off_max = g.off_sums + sums;
     g.off_pivot = g.off_max + fl;
     g.off_part = g.off_pivot + fl;
-    g.off_pmax = g.off_part + (size_t)cap * sums;
-    g.bytes = g.off_pmax + (size_t)cap * fl;
+    g.off_pmax = g.off_part + (size_t)g.cap * sums;
+    g.bytes = g.off_pmax + (size_t)g.cap * fl;
     return DNMF_OK;
 }
 

@@ -8,7 +8,7 @@
 //
 // None of the three is bound by bandwidth: K T small independent problems on data that is already on the device.  All
 // arithmetic is float64 (fp32 only where a value is stored: beta, the frames).
-#include "common.hpp"
+#include "block_ops.hpp"
 
 namespace dnmf {
 namespace {
@@ -39,12 +39,6 @@ __device__ __forceinline__ void basis10(double x, double y, double z, double *f)
     f[0] = 1.0, f[1] = x, f[2] = y, f[3] = z;
     f[4] = x * x, f[5] = y * y, f[6] = z * z;
     f[7] = x * y, f[8] = x * z, f[9] = y * z;
-}
-
-__device__ __forceinline__ double wave_sum_all(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // ---- K11 ---------------------------------------------------------------------------------------------------------
@@ -295,9 +289,7 @@ __global__ __launch_bounds__(256) void roi_signals_kernel(const float *__restric
             ++n;                                           // a padded zero
         }
     }
-    sum = wave_sum_all(sum);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    sum = wave_sum_all(sum), n = wave_sum_all(n);
     if (lane == 0) out[item] = n > 0 ? sum / (double)n : __builtin_nan("");
 }
 

@@ -78,6 +78,59 @@ def _workspace(workspace, need, dev):
     return workspace
 
 
+def _refused(lib, what):
+    return _lib.DnmfHipError(f"{what} refused: {lib.dnmf_last_error().decode(errors='replace')}")
+
+
+def _need(lib, entry, *args):
+    """The bytes the workspace entry ``entry`` asks for; 0 is the library's refusal, raised with its text."""
+    need = getattr(lib, entry)(*args)
+    if need == 0:
+        raise _refused(lib, entry)
+    return need
+
+
+def _stream_state(fn, state, need, first, dev, sized=True):
+    """The state of one call of a movie that goes in several: with ``first`` ``state`` while it holds ``need`` bytes, else a new
+    one; a later call must bring the state of the earlier ones, with ``sized`` one of ``need`` bytes (without it the library
+    judges the size)."""
+    if first:
+        return _workspace(state, need, dev)
+    if state is None or (sized and _nbytes(state) < need):
+        size = f", and one of at least {need} bytes (a later call may not be larger than the first)" if sized else ""
+        raise ValueError(f"{fn}: first=False needs the state of the earlier calls{size}")
+    return state
+
+
+def _ld(t, P):
+    """The row stride of rows ``t``; that of a single row means nothing (a view through numpy's newaxis has 0)."""
+    return t.stride(0) if t.shape[0] != 1 else max(t.stride(0), P)
+
+
+def _frame_rows(fn, frames, sub, frame_ids, P):
+    """The checks of every call that reads frames as rows of ``P`` floats -> (frame_ids int32 or None, frames of the call)."""
+    _rows(frames, fn, "frames", P, f" and rows of {P} floats")
+    if frames.dim() != 2:
+        raise ValueError(f"{fn}: frames are rows (T, ld), got {tuple(frames.shape)}")
+    fid = _i32(frame_ids, frames.device) if frame_ids is not None else None
+    B = fid.numel() if fid is not None else frames.shape[0]
+    if sub is not None:
+        _rows(sub, fn, "sub", P, f" and rows of {P} floats")
+        if sub.dim() != 2 or sub.shape[0] < B:
+            raise ValueError(f"{fn}: sub must hold one row for each of the {B} frames, got {tuple(sub.shape)}")
+    return fid, B
+
+
+def _out_rows(fn, out, B, P, dev):
+    """``out`` as ``B`` rows of ``P`` floats to write (None: new ones)."""
+    if out is None:
+        return torch.empty((B, P), dtype=torch.float32, device=dev)
+    _rows(out, fn, "out", P, f" and rows of {P} floats")
+    if out.dim() != 2 or out.shape[0] < B:
+        raise ValueError(f"{fn}: out must hold {B} rows, got {tuple(out.shape)}")
+    return out
+
+
 def _int3(v):
     return (ctypes.c_int * 3)(*[int(x) for x in v])
 
@@ -1188,9 +1241,7 @@ def detect_neurons(image, sz, K, shape_std=3, min_distance=None, threshold=0.0, 
     bg = float(image.median()) if background is None else float(background)
     dev = image.device
     lib = _lib.load()
-    need = lib.dnmf_detect_neurons_workspace(_int3((X, Y, Z)), K, sigma)
-    if need == 0:
-        raise _lib.DnmfHipError(f"dnmf_detect_neurons_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
+    need = _need(lib, "dnmf_detect_neurons_workspace", _int3((X, Y, Z)), K, sigma)
     workspace = _workspace(workspace, need, dev)
     positions = torch.empty((K, 3), dtype=torch.float32, device=dev)
     amplitudes = torch.empty((K,), dtype=torch.float32, device=dev)
@@ -1268,10 +1319,7 @@ def summary_images_state(sz, B, neighbours='full', segment=0, device="cuda"):
     largest); pass it with ``first=True``."""
     if neighbours not in NEIGHBOURS:
         raise ValueError(f"summary_images_state: neighbours must be 'face' or 'full', got {neighbours!r}")
-    lib = _lib.load()
-    need = lib.dnmf_summary_images_workspace(_int3(sz), NEIGHBOURS[neighbours], int(B), int(segment))
-    if need == 0:
-        raise _lib.DnmfHipError(f"dnmf_summary_images_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
+    need = _need(_lib.load(), "dnmf_summary_images_workspace", _int3(sz), NEIGHBOURS[neighbours], int(B), int(segment))
     return _workspace(None, need, device)
 
 
@@ -1291,70 +1339,26 @@ def summary_images(frames, sz, sub=None, frame_ids=None, neighbours='full', stat
     P = X * Y * Z
     if neighbours not in NEIGHBOURS:
         raise ValueError(f"summary_images: neighbours must be 'face' or 'full', got {neighbours!r}")
-    _rows(frames, "summary_images", "frames", P, f" and rows of {P} floats")
-    if frames.dim() != 2:
-        raise ValueError(f"summary_images: frames are rows (T, ld), got {tuple(frames.shape)}")
+    fid, B = _frame_rows("summary_images", frames, sub, frame_ids, P)
     dev = frames.device
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    if sub is not None:
-        _rows(sub, "summary_images", "sub", P, f" and rows of {P} floats")
-        if sub.dim() != 2 or sub.shape[0] < B:
-            raise ValueError(f"summary_images: sub must hold one row for each of the {B} frames, got {tuple(sub.shape)}")
     lib = _lib.load()
-    need = lib.dnmf_summary_images_workspace(_int3((X, Y, Z)), NEIGHBOURS[neighbours], B, int(segment))
-    if need == 0:
-        raise _lib.DnmfHipError(f"dnmf_summary_images_workspace refused: {lib.dnmf_last_error().decode(errors='replace')}")
-    if first:
-        state = _workspace(state, need, dev)
-    elif state is None or _nbytes(state) < need:
-        raise ValueError(f"summary_images: first=False needs the state of the earlier calls, and one of at least {need} bytes "
-                         "(a later call may not be larger than the first)")
+    need = _need(lib, "dnmf_summary_images_workspace", _int3((X, Y, Z)), NEIGHBOURS[neighbours], B, int(segment))
+    state = _stream_state("summary_images", state, need, first, dev)
     images = torch.empty((4, X, Y, Z), dtype=torch.float64, device=dev) if finish else None
-    # the row stride of a single row means nothing (a view through numpy's newaxis has 0)
-    ldf = frames.stride(0) if frames.shape[0] != 1 else max(frames.stride(0), P)
-    lds = 0 if sub is None else (sub.stride(0) if sub.shape[0] != 1 else max(sub.stride(0), P))
     with _timed("summary_images"):
-        rc = lib.dnmf_summary_images(frames.data_ptr(), ldf, _ptr(sub), lds, _ptr(fid), _int3((X, Y, Z)), B, NEIGHBOURS[neighbours],
-                                     1 if first else 0, 1 if finish else 0, int(segment), state.data_ptr(), _nbytes(state),
-                                     _ptr(images), _stream())
+        rc = lib.dnmf_summary_images(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                     _int3((X, Y, Z)), B, NEIGHBOURS[neighbours], 1 if first else 0, 1 if finish else 0, int(segment),
+                                     state.data_ptr(), _nbytes(state), _ptr(images), _stream())
     _lib.check(rc, "dnmf_summary_images")
     if not finish:
         return None, state
     return dict(mean=images[0], std=images[1], max=images[2], corr=images[3]), state
 
 
-def _ld(t, P):
-    """The row stride of rows ``t``; that of a single row means nothing (a view through numpy's newaxis has 0)."""
-    return t.stride(0) if t.shape[0] != 1 else max(t.stride(0), P)
-
-
-def _background_rows(fn, frames, sub, frame_ids, P):
-    """The checks the two half-steps share -> (frame_ids int32 or None, frames of the call)."""
-    _rows(frames, fn, "frames", P, f" and rows of {P} floats")
-    if frames.dim() != 2:
-        raise ValueError(f"{fn}: frames are rows (T, ld), got {tuple(frames.shape)}")
-    fid = _i32(frame_ids, frames.device) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    if sub is not None:
-        _rows(sub, fn, "sub", P, f" and rows of {P} floats")
-        if sub.dim() != 2 or sub.shape[0] < B:
-            raise ValueError(f"{fn}: sub must hold one row for each of the {B} frames, got {tuple(sub.shape)}")
-    return fid, B
-
-
-def _refused(lib, what):
-    return _lib.DnmfHipError(f"{what} refused: {lib.dnmf_last_error().decode(errors='replace')}")
-
-
 def background_state(sz, B, segment=0, device="cuda"):
     """An empty state for ``background_accum`` calls of up to ``B`` frames each; pass it with ``first=True``."""
     X, Y, Z = (int(s) for s in sz)
-    lib = _lib.load()
-    need = lib.dnmf_background_accum_workspace(X * Y * Z, int(B), int(segment))
-    if need == 0:
-        raise _refused(lib, "dnmf_background_accum_workspace")
-    return _workspace(None, need, device)
+    return _workspace(None, _need(_lib.load(), "dnmf_background_accum_workspace", X * Y * Z, int(B), int(segment)), device)
 
 
 def background_dots(frames, b, sub=None, frame_ids=None):
@@ -1366,13 +1370,11 @@ def background_dots(frames, b, sub=None, frame_ids=None):
     order: the same input gives the same bits.  Everything must be finite."""
     b = _f32(b, "b").reshape(-1)
     P = b.numel()
-    fid, B = _background_rows("background_dots", frames, sub, frame_ids, P)
+    fid, B = _frame_rows("background_dots", frames, sub, frame_ids, P)
     dev = frames.device
     lib = _lib.load()
-    need = lib.dnmf_background_dots_workspace(P, B)
-    if need == 0:
-        raise _refused(lib, "dnmf_background_dots_workspace")
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    need = _need(lib, "dnmf_background_dots_workspace", P, B)
+    ws =torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
     num = torch.empty((B,), dtype=torch.float64, device=dev)
     bb = torch.empty((1,), dtype=torch.float64, device=dev)
     f = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -1395,21 +1397,15 @@ def background_accum(frames, f, sz, sub=None, frame_ids=None, state=None, first=
     workgroup (0: the kernel's choice).  No atomics: the same input gives the same bits."""
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    fid, B = _background_rows("background_accum", frames, sub, frame_ids, P)
+    fid, B = _frame_rows("background_accum", frames, sub, frame_ids, P)
     f = _f32(f, "f").reshape(-1)
     if f.numel() != B:
         raise ValueError(f"background_accum: f must hold one value for each of the {B} frames, got {f.numel()}")
     dev = frames.device
     lib = _lib.load()
-    need = lib.dnmf_background_accum_workspace(P, B, int(segment))
-    if need == 0:
-        raise _refused(lib, "dnmf_background_accum_workspace")
-    if first:
-        state = _workspace(state, need, dev)
-    elif state is None or _nbytes(state) < need:
-        raise ValueError(f"background_accum: first=False needs the state of the earlier calls, and one of at least {need} bytes "
-                         "(a later call may not be larger than the first)")
-    b = torch.empty((X, Y, Z), dtype=torch.float32, device=dev) if finish else None
+    need = _need(lib, "dnmf_background_accum_workspace", P, B, int(segment))
+    state = _stream_state("background_accum", state, need, first, dev)
+    b =torch.empty((X, Y, Z), dtype=torch.float32, device=dev) if finish else None
     num = torch.empty((X, Y, Z), dtype=torch.float64, device=dev) if finish else None
     ff = torch.empty((1,), dtype=torch.float64, device=dev) if finish else None
     with _timed("background_accum"):
@@ -1418,6 +1414,17 @@ def background_accum(frames, f, sz, sub=None, frame_ids=None, state=None, first=
                                        _nbytes(state), _ptr(b), _ptr(num), _ptr(ff), _stream())
     _lib.check(rc, "dnmf_background_accum")
     return ((b, num, ff) if finish else None), state
+
+
+def _subtract_rows(fn, frames, frame_ids, times, P):
+    """The checks the two subtractions share -> (frame_ids, times: int32 or None, frames of the call)."""
+    _frame_rows(fn, frames, None, None, P)
+    fid, tt, B = _ids(frames, frame_ids, times, frames.device)
+    if fid is not None and fid.numel() != B:
+        raise ValueError(f"{fn}: {fid.numel()} frame_ids for {B} times")
+    if fid is None and B > frames.shape[0]:
+        raise ValueError(f"{fn}: {B} times for {frames.shape[0]} frames")
+    return fid, tt, B
 
 
 def background_subtract(frames, b, f, frame_ids=None, times=None, out=None, clamp=True):
@@ -1430,20 +1437,8 @@ def background_subtract(frames, b, f, frame_ids=None, times=None, out=None, clam
     b = _f32(b, "b").reshape(-1)
     f = _f32(f, "f").reshape(-1)
     P = b.numel()
-    _rows(frames, "background_subtract", "frames", P, f" and rows of {P} floats")
-    if frames.dim() != 2:
-        raise ValueError(f"background_subtract: frames are rows (T, ld), got {tuple(frames.shape)}")
-    dev = frames.device
-    fid, tt, B = _ids(frames, frame_ids, times, dev)
-    if fid is not None and fid.numel() != B:
-        raise ValueError(f"background_subtract: {fid.numel()} frame_ids for {B} times")
-    if fid is None and B > frames.shape[0]:
-        raise ValueError(f"background_subtract: {B} times for {frames.shape[0]} frames")
-    if out is None:
-        out = torch.empty((B, P), dtype=torch.float32, device=dev)
-    _rows(out, "background_subtract", "out", P, f" and rows of {P} floats")
-    if out.dim() != 2 or out.shape[0] < B:
-        raise ValueError(f"background_subtract: out must hold {B} rows, got {tuple(out.shape)}")
+    fid, tt, B = _subtract_rows("background_subtract", frames, frame_ids, times, P)
+    out = _out_rows("background_subtract", out, B, P, frames.device)
     lib = _lib.load()
     with _timed("background_subtract"):
         rc = lib.dnmf_background_subtract(frames.data_ptr(), _ld(frames, P), _ptr(fid), b.data_ptr(), f.data_ptr(), f.numel(), _ptr(tt),
@@ -1476,10 +1471,7 @@ def _check_rank(fn, R, inner=1):
 def background_state_rank(sz, B, rank, segment=0, device="cuda"):
     """An empty state for ``background_accum_rank`` calls of up to ``B`` frames each; pass it with ``first=True``."""
     X, Y, Z = (int(s) for s in sz)
-    lib = _lib.load()
-    need = lib.dnmf_background_accum_rank_workspace(X * Y * Z, int(B), int(rank), int(segment))
-    if need == 0:
-        raise _refused(lib, "dnmf_background_accum_rank_workspace")
+    need = _need(_lib.load(), "dnmf_background_accum_rank_workspace", X * Y * Z, int(B), int(rank), int(segment))
     return _workspace(None, need, device)
 
 
@@ -1487,10 +1479,8 @@ def _dots_rank(frames, b, f, sub, fid, B, P, R, inner):
     """The launch of ``background_dots_rank`` on checked arguments; ``f`` (R, B) rows are the start and receive the result."""
     dev = frames.device
     lib = _lib.load()
-    need = lib.dnmf_background_dots_rank_workspace(P, B, R)
-    if need == 0:
-        raise _refused(lib, "dnmf_background_dots_rank_workspace")
-    ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    need = _need(lib, "dnmf_background_dots_rank_workspace", P, B, R)
+    ws =torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
     num = torch.empty((R, B), dtype=torch.float64, device=dev)
     q = torch.empty((R, R), dtype=torch.float64, device=dev)
     with _timed("background_dots_rank"):
@@ -1514,7 +1504,7 @@ def background_dots_rank(frames, b, f, sub=None, frame_ids=None, inner=3):
     P = b[0].numel()
     b, R = _rank_rows(fn, "b", b, P, "voxels")
     _check_rank(fn, R, inner)
-    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
     f, Rf = _rank_rows(fn, "f", f, B, "frames (one value for each frame of the call)")
     if Rf != R:
         raise ValueError(f"{fn}: {R} images but {Rf} time courses")
@@ -1531,19 +1521,13 @@ def background_accum_rank(frames, f, sz, b=None, sub=None, frame_ids=None, state
     fn = "background_accum_rank"
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
     f, R = _rank_rows(fn, "f", f, B, "frames (one value for each frame of the call)")
     _check_rank(fn, R, inner)
     dev = frames.device
     lib = _lib.load()
-    need = lib.dnmf_background_accum_rank_workspace(P, B, R, int(segment))
-    if need == 0:
-        raise _refused(lib, "dnmf_background_accum_rank_workspace")
-    if first:
-        state = _workspace(state, need, dev)
-    elif state is None or _nbytes(state) < need:
-        raise ValueError(f"{fn}: first=False needs the state of the earlier calls, and one of at least {need} bytes "
-                         "(a later call may not be larger than the first)")
+    need = _need(lib, "dnmf_background_accum_rank_workspace", P, B, R, int(segment))
+    state = _stream_state(fn, state, need, first, dev)
     out = num = w = None
     if finish:
         if b is None:
@@ -1576,20 +1560,8 @@ def background_subtract_rank(frames, b, f, frame_ids=None, times=None, out=None,
     _rows(f, fn, "f")
     _check_rank(fn, R)
     nf = f.shape[1]
-    _rows(frames, fn, "frames", P, f" and rows of {P} floats")
-    if frames.dim() != 2:
-        raise ValueError(f"{fn}: frames are rows (T, ld), got {tuple(frames.shape)}")
-    dev = frames.device
-    fid, tt, B = _ids(frames, frame_ids, times, dev)
-    if fid is not None and fid.numel() != B:
-        raise ValueError(f"{fn}: {fid.numel()} frame_ids for {B} times")
-    if fid is None and B > frames.shape[0]:
-        raise ValueError(f"{fn}: {B} times for {frames.shape[0]} frames")
-    if out is None:
-        out = torch.empty((B, P), dtype=torch.float32, device=dev)
-    _rows(out, fn, "out", P, f" and rows of {P} floats")
-    if out.dim() != 2 or out.shape[0] < B:
-        raise ValueError(f"{fn}: out must hold {B} rows, got {tuple(out.shape)}")
+    fid, tt, B = _subtract_rows(fn, frames, frame_ids, times, P)
+    out = _out_rows(fn, out, B, P, frames.device)
     lib = _lib.load()
     with _timed("background_subtract_rank"):
         rc = lib.dnmf_background_subtract_rank(frames.data_ptr(), _ld(frames, P), _ptr(fid), b.data_ptr(), _ld(b, P), f.data_ptr(),
@@ -1649,7 +1621,7 @@ def background_fit_rank(frames, sz, iters, rank, sub_fn=None, piece=None, inner=
     for _ in range(int(iters)):
         for s, e in cuts:
             m = sub(s, e)
-            fid, B = _background_rows("background_fit_rank", frames[s:e], m, None, P)
+            fid, B = _frame_rows("background_fit_rank", frames[s:e], m, None, P)
             _dots_rank(frames[s:e], b.reshape(R, P), f[:, s:e], m, fid, B, P, R, inner)      # in place, on the rows of f
         b = b_step(b)
     scale = f.mean(dim=1)
@@ -1711,9 +1683,7 @@ def clean_traces(traces, fps, sigma_threshold=10, detrend_mode=2, interp_method=
     K, T = traces.shape
     dev = traces.device
     lib = _lib.load()
-    need = lib.dnmf_clean_traces_workspace(K, T)
-    if need == 0:
-        raise _refused(lib, "dnmf_clean_traces_workspace")
+    need = _need(lib, "dnmf_clean_traces_workspace", K, T)
     if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
     out = torch.empty((K, T), dtype=torch.float32, device=dev)
@@ -1769,9 +1739,7 @@ def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, b
     opts = [_per_trace(g, K, dev, fn, "g", lo=0.0, hi=1.0), _per_trace(penalty, K, dev, fn, "penalty", lo=0.0, closed_lo=True),
             _per_trace(baseline, K, dev, fn, "baseline"), _per_trace(noise, K, dev, fn, "noise", lo=0.0, closed_lo=True)]
     lib = _lib.load()
-    need = lib.dnmf_deconvolve_traces_workspace(K, T)
-    if need == 0:
-        raise _refused(lib, "dnmf_deconvolve_traces_workspace")
+    need = _need(lib, "dnmf_deconvolve_traces_workspace", K, T)
     if workspace is None or _nbytes(workspace) < need:
         workspace = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
     c = torch.empty((K, T), dtype=torch.float32, device=dev)
@@ -1832,9 +1800,7 @@ def high_pass_frames(frames, sz, gSig, frame_ids=None, out=None, taps=None):
     import numpy as np
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    _rows(frames, "high_pass_frames", "frames", P, f" and rows of {P} floats")
-    if frames.dim() != 2:
-        raise ValueError(f"high_pass_frames: frames are rows (T, ld), got {tuple(frames.shape)}")
+    fid, B = _frame_rows("high_pass_frames", frames, None, frame_ids, P)
     dev = frames.device
     if taps is None:
         k = high_pass_taps(gSig)
@@ -1846,13 +1812,7 @@ def high_pass_frames(frames, sz, gSig, frame_ids=None, out=None, taps=None):
         tp = torch.as_tensor(np.asarray(taps.cpu() if torch.is_tensor(taps) else taps, dtype=np.float32)).to(dev).contiguous()
         if tp.dim() != 2 or tp.shape[0] != tp.shape[1]:
             raise ValueError(f"high_pass_frames: taps are (n, n), got {tuple(tp.shape)}")
-    fid = _i32(frame_ids, dev) if frame_ids is not None else None
-    B = fid.numel() if fid is not None else frames.shape[0]
-    if out is None:
-        out = torch.empty((B, P), dtype=torch.float32, device=dev)
-    _rows(out, "high_pass_frames", "out", P, f" and rows of {P} floats")
-    if out.dim() != 2 or out.shape[0] < B:
-        raise ValueError(f"high_pass_frames: out must hold {B} rows, got {tuple(out.shape)}")
+    out = _out_rows("high_pass_frames", out, B, P, dev)
     if B >= 1 and P >= 1:
         (f0, f1), (o0, o1) = _span(frames, None, P), _span(out, B, P)
         if o0 < f1 and f0 < o1:
@@ -1925,7 +1885,7 @@ def component_stats(frames, sz, A_rows, boxes, C, w, sub=None, frame_ids=None, s
     fn = "component_stats"
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    fid, B = _background_rows(fn, frames, sub, frame_ids, P)
+    fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
     dev = frames.device
     if A_rows.dim() != 2:
         raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
@@ -1941,13 +1901,9 @@ def component_stats(frames, sz, A_rows, boxes, C, w, sub=None, frame_ids=None, s
     bd = bh.to(dev)
     lib = _lib.load()
     sz3 = _int3((X, Y, Z))
-    need = lib.dnmf_component_stats_workspace(sz3, bh.data_ptr(), K, B, int(segment))
-    if need == 0:
-        raise _refused(lib, "dnmf_component_stats_workspace")
-    if first:
-        state = _workspace(state, need, dev)
-    elif state is None:
-        raise ValueError(f"{fn}: first=False needs the state of the earlier calls")
+    need = _need(lib, "dnmf_component_stats_workspace", sz3, bh.data_ptr(), K, B, int(segment))
+    # the boxes may change between the calls, and with them the bytes: the library judges a later call's state
+    state = _stream_state(fn, state, need, first, dev, sized=False)
     ext = bh[:, 1::2] - bh[:, 0::2] + 1
     vmax = int(ext.prod(1).max())
     f64 = dict(dtype=torch.float64, device=dev)
