@@ -1,6 +1,7 @@
 """``Demix/Traces.py`` of the reference: ``cleanTraces``, and the step after it, ``deconvolveTraces`` (K21).  The reference's body is half-translated MATLAB and does not parse;
 what it describes is defined in tests/traces_restatement.py and computed by K20 (``ops.clean_traces``) on the GPU.  Its
-``histogram_match`` is not here: its body concatenates 1-D arrays along an axis they lack."""
+``histogram_match`` is K25 (``ops.histogram_match``): one line of its body is broken (it concatenates 1-D arrays along an axis
+they lack where the design matrix was meant); what the rest states is defined in tests/histmatch_restatement.py."""
 from __future__ import annotations
 
 import numpy as np
@@ -79,3 +80,38 @@ def deconvolveTraces(traces, fps=None, decay_time=None, g=None, penalty=None, ba
     c, s, info = ops.deconvolve_traces(t, **kw)
     info.pop("workspace")
     return c.cpu().numpy(), s.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+
+
+def histogram_match(a, b, nbins, type):
+    """The moving trace ``a`` rescaled so that its histogram resembles that of the reference trace ``b`` (K25,
+    ``ops.histogram_match``; tests/histmatch_restatement.py is the definition) -> ``(atransform, distance)``.  The ``nbins``
+    quantiles of both are taken at ``linspace(0, 1, nbins)`` over their finite samples, the quantiles of ``b`` are regressed on
+    ``[quantiles of a, 1]`` -- ``type='regular'``: least squares; ``'non-negative'``: with both coefficients >= 0, as ``nnls``
+    would -- and ``atransform = a beta0 + beta1``, NaN where ``a`` is not finite.  ``distance`` is the RMS mismatch of the matched
+    quantiles (the reference declares a histogram distance and returns NaN).  The two traces need neither the same length nor
+    the same missing frames.
+
+    a 1-D and b 1-D: ``atransform`` like ``a`` and a scalar distance.  a (K, Ta) and b (K, Tb) or (Tb,), one reference for
+    all: (K, Ta) and (K,).  A row without a finite sample on either side comes back NaN.  A numpy array comes back as numpy
+    arrays (``atransform`` float32, ``distance`` float64), a CUDA tensor as CUDA tensors; the input is not modified."""
+    if type not in ("regular", "non-negative"):
+        raise ValueError(f"histogram_match: type={type!r}: 'regular' or 'non-negative'")
+    tensors = isinstance(a, torch.Tensor)
+    if tensors and not a.is_cuda:
+        raise ValueError("histogram_match: a tensor must live on the GPU (numpy arrays are taken from the host)")
+
+    def rows(x):
+        if isinstance(x, torch.Tensor):
+            x = x.to("cuda")
+            return x if x.dtype == torch.float32 and x.stride(-1) == 1 else x.float().contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()
+    ta, tb = rows(a), rows(b)
+    single = ta.dim() == 1
+    if single and tb.dim() != 1:
+        raise ValueError(f"histogram_match: a is one trace, b must be one too, got {tuple(tb.shape)}")
+    out, _, distance, _ = ops.histogram_match(ta[None, :] if single else ta, tb, nbins, nonneg=type == "non-negative")
+    if single:
+        out, distance = out[0], distance[0]
+    if tensors:
+        return out, distance
+    return out.cpu().numpy(), (float(distance) if single else distance.cpu().numpy())

@@ -603,6 +603,8 @@ class DeformableNMF:
         self.last_clean = None
         # after deconvolve: g, penalty, baseline, noise, rss, n_valid, n_pools, ok per neuron (CUDA tensors, (K,)) of that call
         self.last_deconv = None
+        # after match_traces: beta (K, 2), distance (K,), ok (K,) of that call (CUDA tensors)
+        self.last_match = None
         # after evaluate_components: r_values, snr, frame_corr, raw, images, boxes, n_active and keep of that call
         self.last_evaluation = None
         self._warned = set()
@@ -1089,6 +1091,26 @@ class DeformableNMF:
             c, s, info = deconvolveTraces(C, fps=fps, decay_time=decay_time, **kw)
         self.last_deconv = info
         return c, s, info
+
+    def match_traces(self, reference, nbins=100, type='regular', traces=None):
+        """The traces in the units of ``reference`` (K25, ``Demix.Traces.histogram_match``): NMF leaves the scale of every trace
+        arbitrary, and per neuron the affine map that carries the quantiles of its trace onto those of its reference puts the two
+        in the same units -- robust to a few wild frames, and without a frame-to-frame correspondence.  Matches ``self.C``, or
+        ``traces`` (K, T) -- e.g. what ``clean_traces`` returned, whose NaN frames count for nothing.  ``reference``: (K, T') or
+        (T',), one for all -- ROI traces from ``roi_signals``, another channel's traces, ground truth; array or tensor ->
+        the matched traces (K, T) fp32 on the GPU.  ``type``: 'regular' or 'non-negative' (both coefficients >= 0).  ``self.C``
+        stays as it is; ``self.last_match`` receives ``beta`` (K, 2: scale, offset), ``distance`` (K,) and ``ok`` (K,) of the
+        call."""
+        if type not in ("regular", "non-negative"):
+            raise ValueError(f"match_traces: type={type!r}: 'regular' or 'non-negative'")
+        with torch.no_grad():
+            C = (self.C if traces is None else torch.as_tensor(traces)).detach().to(device, torch.float32)
+            ref = torch.as_tensor(reference).detach().to(device, torch.float32)
+            out, beta, distance, info = ops.histogram_match(C if C.stride(-1) == 1 else C.contiguous(),
+                                                            ref if ref.stride(-1) == 1 else ref.contiguous(), nbins,
+                                                            nonneg=type == "non-negative")
+        self.last_match = dict(beta=beta, distance=distance, ok=info[:, 2] != 0)
+        return out
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
                           live_spatial=False, iter_a=1, solver='mu', registered='nearest'):

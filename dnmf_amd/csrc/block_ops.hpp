@@ -1,5 +1,6 @@
-// What the analysis kernels (K11 .. K13, K18 .. K24) share: wave and workgroup reductions in a fixed order, order statistics on
-// the monotone 64-bit key of a float64, and the host-side plan of a call whose frames go in segments.  The hot path (K2, K3*, K4*,
+// What the analysis kernels (K11 .. K13, K18 .. K25) share: wave and workgroup reductions in a fixed order, order statistics on
+// the monotone 64-bit key of a float64 (one by bisection, many by a workgroup sort), and the host-side plan of a call whose frames
+// go in segments.  The hot path (K2, K3*, K4*,
 // K7, K16) keeps its own fp32 reductions (common.hpp: wave_sum_last).
 //
 // The contract of the reductions.  "The same input gives the same bits" is a promise of every kernel that includes this file, and
@@ -153,6 +154,40 @@ __device__ __forceinline__ double block_median(const uint64_t *key, int n, int c
     double v0, v1;
     block_select_pair<THREADS, false>(key, n, 0, (count - 1) >> 1, count, lowbit, red, v0, v1);
     return (count & 1) ? v0 : 0.5 * (v0 + v1);
+}
+
+// The power of two at or above n >= 1: the keys that block_sort_keys needs room for.
+__host__ __device__ constexpr int sort_size(int n) {
+    int p = 1;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+// key[0..n) -> ascending, in place, NANKEYs last; for callers that want many order statistics of one row (after the sort the k-th
+// smallest is key[k]), where block_select_pair would cost 64 counting passes each.  `key` must have room for sort_size(n) keys:
+// [n, sort_size(n)) is filled with NANKEY here and holds NANKEY on return.  The caller's own writes of key[0..n) need no barrier
+// before the call (the fill touches other slots and a barrier follows it); the call ends with a barrier, and every lane of the
+// workgroup must reach it.
+// The contract of the order: a bitonic network over P = sort_size(n) slots -- for k = 2, 4, .. P and j = k / 2, k / 4, .. 1 the
+// slots l < (l | j) with bit j of l clear are compared and exchanged towards ascending where bit k of l is clear, descending
+// elsewhere; one barrier after each of the log2(P) (log2(P) + 1) / 2 steps, nothing but LDS.  Keys are totally ordered and equal
+// keys are the same bits, so the sorted row does not depend on the network at all: the same input gives the same bits, and an
+// exchange of equal keys is skipped.  Banks: for j >= 32 the 32 lanes of a half-wave read 32 consecutive keys (one 256-byte bank
+// row: no conflict); for j < 32 they read 32 keys out of 64 consecutive ones, two bank rows: 2-way.
+template <int THREADS>
+__device__ __forceinline__ void block_sort_keys(uint64_t *key, int n) {
+    const int P = sort_size(n);
+    for (int t = n + (int)threadIdx.x; t < P; t += THREADS) key[t] = NANKEY;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += THREADS) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const uint64_t a = key[lo], b = key[hi];
+                if ((lo & k) == 0 ? a > b : a < b) key[lo] = b, key[hi] = a;
+            }
+            __syncthreads();
+        }
 }
 
 // ---- the frame segments of a streamed call (host) ------------------------------------------------------------------------------

@@ -1755,6 +1755,49 @@ def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, b
     return c, s, info
 
 
+def histogram_match(a, b, nbins, nonneg=False, out=None, quantiles=False):
+    """K25, the quantile-matched rescaling of tests/histmatch_restatement.py (``histogram_match``) on the GPU: per row the affine
+    map ``a beta0 + beta1`` that carries the ``nbins`` quantiles of the moving trace ``a`` onto those of the reference trace ``b``
+    (least squares on the matched quantiles; ``nonneg``: under beta0 >= 0 and beta1 >= 0).  a (K, Ta) and b (K, Tb) -- or
+    (Tb,), one row shared by all -- fp32 CUDA rows with unit inner stride: any row stride, no copy is made and the inputs are only
+    read; samples that are not finite count for nothing and the two sides need neither the same length nor the same mask ->
+    ``(out (K, Ta) fp32, beta (K, 2) float64, distance (K,) float64, info (K, 3) int32: na, nb, ok)`` on the GPU, and with
+    ``quantiles`` also ``qa`` and ``qb`` (K, nbins) float64.  ``out``: rows to write into (K, Ta), else new ones.  A row without
+    a valid sample on either side has ok = 0 and NaN results.  Ta, Tb <= 16 384, 2 <= nbins <= 1024, K <= 18 432: anything else
+    is refused.  Float64 inside, one rounding to fp32, sums in a fixed order: the same input gives the same bits.  One launch,
+    no host synchronisation."""
+    fn = "histogram_match"
+    if a.dim() != 2 or b.dim() not in (1, 2):
+        raise ValueError(f"{fn}: a is (K, Ta) and b (K, Tb) or (Tb,), got {tuple(a.shape)} and {tuple(b.shape)}")
+    _rows(a, fn, "a")
+    _rows(b, fn, "b")
+    K, Ta = a.shape
+    Tb = b.shape[-1]
+    dev = a.device
+    if b.device != dev:
+        raise ValueError(f"{fn}: a is on {dev}, b on {b.device}")
+    if b.dim() == 2 and b.shape[0] != K:
+        raise ValueError(f"{fn}: b must hold one row for each of the {K} rows of a, or be one row (Tb,); got {tuple(b.shape)}")
+    if out is None:
+        out = torch.empty((K, Ta), dtype=torch.float32, device=dev)
+    else:
+        _rows(out, fn, "out")
+        if out.shape != (K, Ta) or out.device != dev:
+            raise ValueError(f"{fn}: out must be {(K, Ta)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    nbins = int(nbins)
+    lib = _lib.load()
+    beta = torch.empty((K, 2), dtype=torch.float64, device=dev)
+    distance = torch.empty((K,), dtype=torch.float64, device=dev)
+    info = torch.empty((K, 3), dtype=torch.int32, device=dev)
+    q = torch.empty((2, K, max(nbins, 0)), dtype=torch.float64, device=dev) if quantiles else None
+    with _timed("histogram_match"):
+        rc = lib.dnmf_histogram_match(a.data_ptr(), _ld(a, Ta), Ta, b.data_ptr(), 0 if b.dim() == 1 else _ld(b, Tb), Tb, K, nbins,
+                                      1 if nonneg else 0, out.data_ptr(), _ld(out, Ta), beta.data_ptr(), distance.data_ptr(),
+                                      info.data_ptr(), _ptr(q[0] if quantiles else None), _ptr(q[1] if quantiles else None), _stream())
+    _lib.check(rc, "dnmf_histogram_match")
+    return (out, beta, distance, info, q[0], q[1]) if quantiles else (out, beta, distance, info)
+
+
 def high_pass_taps(gSig):
     """The (n, n) float64 numpy kernel of the reference's ``high_pass_filter_space`` (MotionCorrect.py:1263-1269):
     ``n = (3 gSig[0]) // 2 * 2 + 1`` (entry 0 decides, the kernel is square), ``cv2.getGaussianKernel(n, gSig[0])`` written out

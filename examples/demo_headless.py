@@ -3,12 +3,14 @@
 plots, against this repository's drop-in ``Demix.dNMF``.  Prints how well the recovered traces match the ground
 truth.  Needs an MI355X.
 
-    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve]
+    python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
 ``--deconvolve``: also deconvolve the traces (``DeformableNMF.deconvolve``, K21), everything estimated, and print the median
 correlation of the simulator's traces with ``C`` and with ``b + c``, and the median estimated decay beside the simulator's e^-0.3.
+``--match``: also put the traces in the simulator's units (``DeformableNMF.match_traces``, K25) and print the median over neurons
+of the RMS difference between the simulator's traces and ``C`` before and after, beside the correlation, which the map leaves alone.
 """
 import argparse
 import os
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--clean", type=float, default=None, metavar="FPS")
     ap.add_argument("--deconvolve", action="store_true")
+    ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
@@ -75,6 +78,17 @@ def main():
               % (float(np.median([np.corrcoef(C[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
                  float(np.median([np.corrcoef(fit[k], truth[k])[0, 1] for k in range(K) if ok[k]])),
                  float(np.nanmedian(info["g"].cpu().numpy())), float(np.exp(-0.3)), int(ok.sum()), K))
+    if a.match:
+        truth = np.asarray(dataset.traces, np.float64)
+        matched = dnmf.match_traces(dataset.traces).cpu().numpy().astype(np.float64)
+
+        def median_rms(X):
+            return float(np.median(np.sqrt(np.mean((X - truth) ** 2, axis=1))))
+
+        print("median RMS difference from ground truth: C %.4f  matched C %.4f  (median trace correlation %.3f; median scale %.3f, "
+              "median quantile distance %.4f)"
+              % (median_rms(C.astype(np.float64)), median_rms(matched), float(np.median(corr)),
+                 float(dnmf.last_match["beta"][:, 0].median()), float(dnmf.last_match["distance"].median())))
     if a.evaluate:
         ev = dnmf.evaluate_components(testloader)
         np.set_printoptions(precision=2, suppress=True, linewidth=160)

@@ -889,6 +889,36 @@ int dnmf_component_stats(const float *frames, long ldf, const float *sub, long l
                          double *sums, double *foot, double *frame_corr, double *raw, double *image, long ldi, double *r_values,
                          dnmf_stream_t stream);
 
+/* ---- K25: histogram_match: the affine map that carries a moving trace's quantiles onto a reference trace's ---------------------------
+ * tests/histmatch_restatement.py (histogram_match) is the definition (H1 .. H5), in float64; this entry computes it for K rows:
+ * a = K rows of lda >= Ta floats (the moving traces), b = K rows of ldb >= Tb floats, or ONE row shared by every row of a when
+ * ldb = 0 (the reference traces), out = K rows of ldo >= Ta floats (the inputs are only read; out may not overlap them).  Per row:
+ *   H1  the valid samples of a, and separately of b, are the finite ones (na, nb of them); a and b need no frame-to-frame
+ *       correspondence: lengths and masks may differ;
+ *   H2  nbins quantiles of each, qa and qb, at the exact rational indices j (n - 1) / (nbins - 1) of the sorted valid samples, linearly
+ *       interpolated -- np.quantile(x, np.linspace(0, 1, nbins)) with the two samples picked by integer arithmetic;
+ *   H3  beta = the least-squares fit of qb on [qa, 1], centred (a constant moving trace: beta0 = 0, beta1 = mean qb); with nonneg = 1
+ *       the exact minimiser under beta0 >= 0 and beta1 >= 0 (what nnls on that design returns): the free solution where it is
+ *       feasible, else the better of the two boundary solutions;
+ *   H4  out_t = a_t beta0 + beta1, NaN where a_t is not finite;
+ *   H5  distance = sqrt(mean_j (beta0 qa_j + beta1 - qb_j)^2), the RMS mismatch of the matched quantiles.
+ * Two deviations from the reference's Demix/Traces.py::histogram_match, both stated in the restatement: H1 drops +-inf as well as
+ * NaN (one infinite sample would make every fit NaN), and H5 computes the distance the reference declares but returns as NaN.
+ * One launch, one workgroup per row, float64 inside, out rounded once to fp32, no workspace, no host synchronisation, nothing launched
+ * on an error.  A row's samples are sorted as 64-bit keys in LDS (a bitonic network, csrc/block_ops.hpp: block_sort_keys), after
+ * which every quantile is two reads; sums are taken in a fixed order without floating-point atomics: the same input gives the same
+ * bits.
+ *   nonneg     0: 'regular', 1: 'non-negative'
+ *   beta       (K, 2) doubles: beta0 (scale), beta1 (offset);  distance: K doubles
+ *   info       (K, 3) int32: na, nb, ok.  A row with na = 0 or nb = 0 is refused: ok = 0, beta, distance and its row of out NaN
+ *   qa, qb     (K, nbins) doubles each, or NULL: the quantiles (NaN for a side without a valid sample)
+ * Limits, set by the LDS (8 bytes a key up to the next power of two, 16 bytes a bin: 144 of the CU's 160 KiB at the limits): Ta and Tb
+ * at most 16 384, nbins at most 1024, K at most 18 432; larger ones are refused, nothing is truncated.
+ * DNMF_E_NULL: a, b, out, beta, distance or info NULL;  DNMF_E_SHAPE: K, Ta or Tb < 1, nbins < 2, nonneg outside {0, 1}, lda or ldo
+ * < Ta, ldb neither 0 nor >= Tb;  DNMF_E_UNSUPPORTED: above the limits. */
+int dnmf_histogram_match(const float *a, long lda, int Ta, const float *b, long ldb, int Tb, int K, int nbins, int nonneg, float *out,
+                         long ldo, double *beta, double *distance, int *info, double *qa, double *qb, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
