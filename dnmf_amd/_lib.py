@@ -10,11 +10,12 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DNMF_LIB selects another build of the library (kernel-variant timing, ablations); the product default is in-tree
 LIB_PATH = os.environ.get("DNMF_LIB") or os.path.join(_HERE, "libdnmf_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _vp, _i, _l, _sz, _d = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_double
 
-# name -> (restype, argtypes); mirrors include/dnmf_hip.h line by line
+# name -> (restype, argtypes); mirrors include/dnmf_hip.h line by line (written by hand: the header is not part of an installed
+# package; tests/test_abi_and_host.py compares every entry with the header's prototype)
 SIGNATURES = {
     "dnmf_version": (_i, []),
     "dnmf_last_error": (C.c_char_p, []),
@@ -44,7 +45,7 @@ SIGNATURES = {
     "dnmf_mu_temporal": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp]),
     "dnmf_mu_temporal_nbr": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp, _i, _vp]),
     "dnmf_mu_temporal_slots": (_i, [_vp, _i, _i, _vp, _vp, _l, _i, _i, _i, _vp, _i, _vp]),
-    "dnmf_warp_gram_rhs_lists_chunks": (_i, [_i, _i, _i, _i]),
+    "dnmf_warp_gram_rhs_lists_chunks": (_i, [_i, _i, _i, _i, _i, _i]),
     "dnmf_mu_temporal_step": (_i, [_vp, _vp, _vp, _vp, _l, _i, _i, _d, _vp, _vp, _vp]),
     "dnmf_hals_temporal": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _vp, _i, _vp, _vp]),
     "dnmf_hals_temporal_slots": (_i, [_vp, _i, _i, _vp, _vp, _l, _i, _i, _i, _vp, _i, _vp, _vp]),
@@ -63,7 +64,7 @@ SIGNATURES = {
     "dnmf_pack_footprints_lists": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dnmf_warp_gram_rhs_lists_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
     "dnmf_warp_gram_rhs_lists": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _vp, _vp, _vp,
-                                      _vp, _sz, _vp, _vp]),
+                                      _vp, _sz, _vp, _i, _i, _vp]),
     "dnmf_recon_image_lists": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _l, _vp, _i, _vp, _l, _vp]),
     "dnmf_recon_image_lists_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _l, _vp, _i, _vp, _l, _i, _vp]),
     "dnmf_motion_grad_lists_workspace": (_sz, [_i, _i, _i, _i, _i]),
@@ -78,9 +79,10 @@ SIGNATURES = {
     "dnmf_mu_spatial_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _vp]),
     "dnmf_register_patches_grid": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "dnmf_register_patches_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),
-    "dnmf_register_patches": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_register_patches": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _i, _vp]),
     "dnmf_rigid_correct_workspace": (_sz, [_i, _i, _i, _i]),
-    "dnmf_rigid_correct": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _i, C.c_float, _i, _vp, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
+    "dnmf_rigid_correct": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _i, C.c_float, _i, _vp, _vp, _l, _vp, _vp, _vp, _sz, _i,
+                                _vp]),
     "dnmf_apply_pwrigid_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),
     "dnmf_apply_pwrigid": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_float, _vp, _l, _vp, _vp, _vp, _sz, _vp]),
     "dnmf_apply_shifts_points": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp]),

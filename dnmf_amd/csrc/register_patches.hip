@@ -409,11 +409,6 @@ struct McPlan {
     int items;
 };
 
-static bool mc_use_mfma() {
-    const char *e = getenv("DNMF_K8_VALU");     // 1: the vector-ALU kernel (the checker of the MFMA one); read at every call
-    return !(e && e[0] == '1');
-}
-
 // a buffer of the workspace and the float2 values it holds
 struct McBuf {
     float2 *p;
@@ -421,12 +416,13 @@ struct McBuf {
 };
 
 // One axis pass writing McAxis.out = (items, outer, m, inner) into `out`; a pass that would write past the buffer is refused.
-static int mc_launch_axis(McAxis a, int items, McBuf out, hipStream_t st) {
+// valu: 0 the MFMA kernel, 1 the vector-ALU kernel kept as its checker.
+static int mc_launch_axis(McAxis a, int items, McBuf out, int valu, hipStream_t st) {
     const size_t extent = (size_t)items * a.outer * a.m * a.inner;
     DNMF_REQUIRE(extent <= out.cap, DNMF_E_WORKSPACE, "K8: an axis pass writes %zu values into a buffer of %zu", extent, out.cap);
     a.out = out.p;
     const long ncol = (long)a.outer * a.inner;
-    if (mc_use_mfma()) {
+    if (!valu) {
         dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((a.m + 63) / 64), (unsigned)items);
         hipLaunchKernelGGL(mc_axis_mfma_kernel, grid, dim3(256), (size_t)a.n * a.uf * sizeof(float2), st, a);
         return 0;
@@ -522,6 +518,7 @@ __global__ __launch_bounds__(256) void mc_shifted_frames_kernel(const float2 *im
 struct McRun {
     hipStream_t st;
     int X, Y, Z, uf, region, max_dev;
+    int valu;                 // which axis kernel (mc_launch_axis)
     float add;
     McBuf bufA, bufB, inv1, inv2, cc, tF_full, tF_patch;
     int *win, *pos_up, *peak, *iota, *mshift, *starts, *spos;
@@ -536,13 +533,13 @@ struct McRun {
         // z: voxels -> A
         a.mode = 0, a.frames = src, a.ldf = ld, a.frame_ids = ids;
         a.outer = bx.n[0] * bx.n[1], a.n = bx.n[2], a.inner = 1, a.m = bx.n[2];
-        int rc = mc_launch_axis(a, nitems, A, st);
+        int rc = mc_launch_axis(a, nitems, A, valu, st);
         // y: A -> B
         a.mode = 1, a.in = A.p, a.outer = bx.n[0], a.n = bx.n[1], a.inner = bx.n[2], a.m = bx.n[1];
-        if (rc == 0) rc = mc_launch_axis(a, nitems, Bf, st);
+        if (rc == 0) rc = mc_launch_axis(a, nitems, Bf, valu, st);
         // x: B -> A
         a.in = Bf.p, a.outer = 1, a.n = bx.n[0], a.inner = bx.n[1] * bx.n[2], a.m = bx.n[0];
-        return rc == 0 ? mc_launch_axis(a, nitems, A, st) : rc;
+        return rc == 0 ? mc_launch_axis(a, nitems, A, valu, st) : rc;
     }
     // P = spec conj(tspec) onto mm positions per axis (numerators in posbuf (items or 1, 3, MC_MW), over ufac) -> cc (items, mm^3)
     int inverse(const McBoxes &bx, const float2 *spec, const float2 *tspec, const int *posbuf, int pstride, int mm, int ufac,
@@ -552,15 +549,15 @@ struct McRun {
         // x (with the product): (1, n0, n1 n2) -> (1, mm, n1 n2)
         a.mode = 2, a.in = spec, a.other = tspec, a.outer = 1, a.n = bx.n[0], a.inner = bx.n[1] * bx.n[2], a.pos_off = 0;
         a.scale = 1.0f / (float)bx.n[0];
-        int rc = mc_launch_axis(a, nitems, inv1, st);
+        int rc = mc_launch_axis(a, nitems, inv1, valu, st);
         // y: (mm, n1, n2) -> (mm, mm, n2)
         a.mode = 1, a.in = inv1.p, a.outer = mm, a.n = bx.n[1], a.inner = bx.n[2], a.pos_off = MC_MW;
         a.scale = 1.0f / (float)bx.n[1];
-        if (rc == 0) rc = mc_launch_axis(a, nitems, inv2, st);
+        if (rc == 0) rc = mc_launch_axis(a, nitems, inv2, valu, st);
         // z: (mm mm, n2, 1) -> (mm mm, mm, 1)
         a.in = inv2.p, a.outer = mm * mm, a.n = bx.n[2], a.inner = 1, a.pos_off = 2 * MC_MW;
         a.scale = 1.0f / (float)bx.n[2];
-        return rc == 0 ? mc_launch_axis(a, nitems, cc, st) : rc;
+        return rc == 0 ? mc_launch_axis(a, nitems, cc, valu, st) : rc;
     }
     // one registration pass over `nitems` boxes: window -> peak -> upsampled -> shifts
     int registration(const McBoxes &bx, const float2 *spec, const float2 *tspec, const float *rigid, int first, int nitems,
@@ -690,10 +687,11 @@ size_t dnmf_register_patches_workspace(int X, int Y, int Z, const int *strides, 
 int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
                           const int *strides, const int *overlaps, const int *max_shifts, int max_deviation_rigid,
                           int upsample_factor, float add_to_movie, float *rigid_shifts, float *patch_shifts, void *workspace,
-                          size_t workspace_bytes, dnmf_stream_t stream) {
+                          size_t workspace_bytes, int valu, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(frames && tmpl && strides && overlaps && max_shifts && rigid_shifts && patch_shifts && workspace, DNMF_E_NULL,
                  "dnmf_register_patches: NULL argument");
+    DNMF_REQUIRE(valu == 0 || valu == 1, DNMF_E_SHAPE, "dnmf_register_patches: valu=%d (0 MFMA, 1 vector ALU)", valu);
     DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && B > 0 && ldf >= (long)X * Y * Z, DNMF_E_SHAPE,
                  "dnmf_register_patches: X=%d Y=%d Z=%d B=%d ldf=%ld", X, Y, Z, B, ldf);
     int dims[3];
@@ -715,7 +713,7 @@ int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, i
                  dnmf_register_patches_workspace(X, Y, Z, strides, overlaps, B));
     McRun r{};
     r.st = (hipStream_t)stream, r.X = X, r.Y = Y, r.Z = Z, r.add = add_to_movie, r.uf = upsample_factor;
-    r.region = mc_region(upsample_factor), r.max_dev = max_deviation_rigid;
+    r.region = mc_region(upsample_factor), r.max_dev = max_deviation_rigid, r.valu = valu;
     const long P = (long)X * Y * Z;
     const long pvox = (long)NP * w[0] * w[1] * w[2];
     const int Bc = mc_chunk(P > pvox ? P : pvox, B, NP);
@@ -809,9 +807,10 @@ size_t dnmf_rigid_correct_workspace(int X, int Y, int Z, int B) {
 int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
                        const int *max_shifts, int upsample_factor, float add_to_movie, int border_nan, float *rigid_shifts,
                        float *corrected, long ldc, float *tsum, int *tcount, void *workspace, size_t workspace_bytes,
-                       dnmf_stream_t stream) {
+                       int valu, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(frames && tmpl && max_shifts && rigid_shifts && workspace, DNMF_E_NULL, "dnmf_rigid_correct: NULL argument");
+    DNMF_REQUIRE(valu == 0 || valu == 1, DNMF_E_SHAPE, "dnmf_rigid_correct: valu=%d (0 MFMA, 1 vector ALU)", valu);
     DNMF_REQUIRE((tsum == nullptr) == (tcount == nullptr), DNMF_E_NULL, "dnmf_rigid_correct: tsum and tcount go together");
     const long P = (long)X * Y * Z;
     DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && B > 0 && ldf >= P && (!corrected || ldc >= P), DNMF_E_SHAPE,
@@ -830,7 +829,7 @@ int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int 
                  "dnmf_rigid_correct: workspace %zu < %zu bytes", workspace_bytes, dnmf_rigid_correct_workspace(X, Y, Z, B));
     McRun r{};
     r.st = (hipStream_t)stream, r.X = X, r.Y = Y, r.Z = Z, r.add = add_to_movie, r.uf = upsample_factor;
-    r.region = mc_region(upsample_factor), r.max_dev = 0;
+    r.region = mc_region(upsample_factor), r.max_dev = 0, r.valu = valu;
     const int Bc = mc_rigid_chunk(P, B);
     int nmax = X > Y ? X : Y;
     nmax = nmax > Z ? nmax : Z;
@@ -859,11 +858,11 @@ int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int 
         McAxis a{};
         a.bx = full, a.uf = r.uf, a.sign = 1, a.pos = spos, a.pos_item_stride = 3 * nmax, a.mode = 1;
         a.in = r.bufA.p, a.outer = 1, a.n = X, a.inner = Y * Z, a.m = X, a.pos_off = 0, a.scale = 1.0f / (float)X;
-        rc = mc_launch_axis(a, nf, r.bufB, r.st);
+        rc = mc_launch_axis(a, nf, r.bufB, r.valu, r.st);
         a.in = r.bufB.p, a.outer = X, a.n = Y, a.inner = Z, a.m = Y, a.pos_off = nmax, a.scale = 1.0f / (float)Y;
-        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufA, r.st);
+        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufA, r.valu, r.st);
         a.in = r.bufA.p, a.outer = X * Y, a.n = Z, a.inner = 1, a.m = Z, a.pos_off = 2 * nmax, a.scale = 1.0f / (float)Z;
-        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufB, r.st);
+        if (rc == 0) rc = mc_launch_axis(a, nf, r.bufB, r.valu, r.st);
         if (rc) break;
         if (border_nan == 2) {
             hipLaunchKernelGGL(mc_fill_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, r.st, fmin, nf, __builtin_inff());

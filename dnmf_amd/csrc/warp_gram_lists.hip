@@ -41,7 +41,6 @@
 // Files.  warp_gram_lists.hpp: the parameters, the kernel template and its launchers.  This file: the pack, mask, pairs and
 // finish kernels, the host side, the entry points and the Z == 1 instantiations.  warp_gram_lists_z.hip: the Z >= 2
 // instantiations -- apart only so that the two compile side by side (about 23 s and 50 s), with the same flags.
-#include <cstdlib>
 
 #include "warp_gram_lists.hpp"
 
@@ -267,14 +266,11 @@ static long lists_max_chunks(int B) {
     return want < 1 ? 1 : (want > 64 ? 64 : want);
 }
 
-// DNMF_LISTS_CHUNKS=n in the environment (1 .. 64) asks for n chunks per frame instead: the parity tests use it to give a
+// chunks = n (1 .. 64) asks for n chunks per frame instead of the library's choice (0): the parity tests use it to give a
 // wave of a small problem the long runs of tiles (and of equal lists) it has at the bench size.
-static void lists_choose_chunks(int ntiles, int B, int &nchunks, int &chunk_len) {
+static void lists_choose_chunks(int ntiles, int B, int chunks, int &nchunks, int &chunk_len) {
     long want = lists_max_chunks(B);
-    if (const char *e = getenv("DNMF_LISTS_CHUNKS")) {
-        const long n = strtol(e, nullptr, 10);
-        if (n >= 1 && n <= want) want = n;   // never more tables than the workspace was sized for
-    }
+    if (chunks >= 1 && chunks <= want) want = chunks;   // never more tables than the workspace was sized for
     if (want > ntiles) want = ntiles;
     chunk_len = (int)((ntiles + want - 1) / want);
     nchunks = (ntiles + chunk_len - 1) / chunk_len;
@@ -287,20 +283,17 @@ static int lists_words(int K) { return K <= 64 ? 1 : (K <= 128 ? 2 : 4); }
 // frames (0.89 ms against 0.51 in one kernel); 256x256x1000, K=50: 16 tiles per wave, 0.92 against 0.58.  The density
 // of the footprints does not decide it: 512x512x4000 with K=200 (45 % of the tiles list more than four neurons) takes
 // 9.1 ms in two launches and 12.2 in one.
-// DNMF_LISTS_PASSES=1|2 in the environment overrides the choice (the parity tests run both forms on small problems).
-static int lists_passes(int chunk_len) {
-    if (const char *e = getenv("DNMF_LISTS_PASSES")) {
-        if (e[0] == '1' && e[1] == 0) return 1;
-        if (e[0] == '2' && e[1] == 0) return 2;
-    }
-    return chunk_len < 100 ? 1 : 2;
-}
+// passes = 1 | 2 overrides the choice (0) (the parity tests run both forms on small problems).
+static int lists_passes(int chunk_len, int passes) { return passes ? passes : (chunk_len < 100 ? 1 : 2); }
 
-// tiles, chunks and tables of a launch on p.vol with p.B frames
-static void lists_plan(ListParams &p) {
+// the launch forms a caller may ask for: passes 0 | 1 | 2, chunks 0 .. 64, 0 the library's choice
+static bool lists_form_ok(int passes, int chunks) { return passes >= 0 && passes <= 2 && chunks >= 0 && chunks <= 64; }
+
+// tiles, chunks and tables of a launch on p.vol with p.B frames in the form (passes, chunks)
+static void lists_plan(ListParams &p, int passes, int chunks) {
     lists_tile_shape(p.vol, p.lgx, p.lgy, p.lgz, p.ntx, p.nty, p.ntz, p.ntiles);
-    lists_choose_chunks(p.ntiles, p.B, p.nchunks, p.chunk_len);
-    p.tables = p.nchunks * lists_passes(p.chunk_len);
+    lists_choose_chunks(p.ntiles, p.B, chunks, p.nchunks, p.chunk_len);
+    p.tables = p.nchunks * lists_passes(p.chunk_len, passes);
 }
 
 template <int NW>
@@ -379,10 +372,11 @@ size_t dnmf_warp_gram_rhs_lists_workspace(int nslot, int K, int X, int Y, int Z,
 int dnmf_warp_gram_rhs_lists(const float *At, const int *bbox, const int *pair_slot, const void *axis_masks, int nslot, int K,
                              int X, int Y, int Z, const float *beta, int T, const int *times, int B, const float *frames,
                              long ldf, const int *frame_ids, float *G, float *r, void *workspace, size_t workspace_bytes,
-                             unsigned long long *counters, dnmf_stream_t stream) {
+                             unsigned long long *counters, int passes, int chunks, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(At && bbox && pair_slot && axis_masks && beta && frames && workspace && (!G == !r), DNMF_E_NULL,
                  "dnmf_warp_gram_rhs_lists: NULL buffer");
+    DNMF_REQUIRE(lists_form_ok(passes, chunks), DNMF_E_SHAPE, "dnmf_warp_gram_rhs_lists: passes=%d chunks=%d", passes, chunks);
     DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && K > 0 && T > 0 && B > 0 && nslot > K, DNMF_E_SHAPE,
                  "dnmf_warp_gram_rhs_lists: X=%d Y=%d Z=%d K=%d T=%d B=%d nslot=%d", X, Y, Z, K, T, B, nslot);
     DNMF_REQUIRE(K <= 64 * LISTS_MAXW, DNMF_E_UNSUPPORTED, "dnmf_warp_gram_rhs_lists: K=%d > %d", K, 64 * LISTS_MAXW);
@@ -402,7 +396,7 @@ int dnmf_warp_gram_rhs_lists(const float *At, const int *bbox, const int *pair_s
     p.slab = static_cast<float *>(workspace);
     p.tile_masks = reinterpret_cast<unsigned long long *>(static_cast<char *>(workspace) + lists_slab_bytes(nslot, B));
     p.counters = counters;
-    lists_plan(p);
+    lists_plan(p, passes, chunks);
     DNMF_REQUIRE(workspace_bytes >= dnmf_warp_gram_rhs_lists_workspace(nslot, K, X, Y, Z, B), DNMF_E_WORKSPACE,
                  "dnmf_warp_gram_rhs_lists: workspace %zu < %zu bytes", workspace_bytes,
                  dnmf_warp_gram_rhs_lists_workspace(nslot, K, X, Y, Z, B));
@@ -430,12 +424,12 @@ int dnmf_warp_gram_rhs_lists(const float *At, const int *bbox, const int *pair_s
     return check_launch("dnmf_warp_gram_rhs_lists");
 }
 
-int dnmf_warp_gram_rhs_lists_chunks(int X, int Y, int Z, int B) {
+int dnmf_warp_gram_rhs_lists_chunks(int X, int Y, int Z, int B, int passes, int chunks) {
     using namespace dnmf;
-    if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0) return 0;
+    if (X <= 0 || Y <= 0 || Z <= 0 || B <= 0 || !lists_form_ok(passes, chunks)) return 0;
     ListParams p{};
     p.vol = make_volume(X, Y, Z), p.B = B;
-    lists_plan(p);
+    lists_plan(p, passes, chunks);
     return p.tables;
 }
 

@@ -12,6 +12,11 @@ from . import _lib
 
 # bench.py sets TIMING = {} to collect (start, end) HIP events around the named kernels, on their stream
 TIMING = None
+# launch form of K3n as (passes, chunks), 0 = the library's choice: passes 1 | 2 launches, chunks 1 .. 64 per frame.  The
+# tests set it to run every form on small problems; warp_gram_rhs_lists and the *_slots consumers of its tables read it.
+LISTS_FORM = (0, 0)
+# True: K8's axis transforms run in the vector-ALU kernel kept as the checker of the MFMA one
+K8_VALU = False
 
 
 def _stream() -> int:
@@ -740,9 +745,25 @@ LISTS_MAX_SLOTS = 3800
 LISTS_COUNTERS = None
 
 
-def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, workspace=None, finish=True, out=None):
+def _lists_form(passes, chunks):
+    """(passes, chunks) of a K3n launch: the arguments, or ``LISTS_FORM`` where they are None."""
+    return (int(LISTS_FORM[0] if passes is None else passes), int(LISTS_FORM[1] if chunks is None else chunks))
+
+
+def _lists_tables(sz, B, passes=None, chunks=None):
+    """Slot tables per frame that a K3n launch of B frames in the form (passes, chunks) leaves in its workspace."""
+    X, Y, Z = (int(s) for s in sz)
+    n = _lib.load().dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, int(B), *_lists_form(passes, chunks))
+    if n <= 0:
+        raise ValueError(f"K3n: no launch form passes, chunks = {_lists_form(passes, chunks)} on {X}x{Y}x{Z}, {B} frames")
+    return n
+
+
+def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, workspace=None, finish=True, out=None,
+                        passes=None, chunks=None):
     """K3n.  Returns G (B,K,K), r (B,K), workspace (G and r written into the pair ``out`` when given); with
-    ``finish=False`` G and r are None and the slot tables stay in ``workspace`` for ``mu_temporal_slots``."""
+    ``finish=False`` G and r are None and the slot tables stay in ``workspace`` for ``mu_temporal_slots``.
+    ``passes``, ``chunks``: the launch form (None: from ``LISTS_FORM``; 0: the library's choice)."""
     global LISTS_COUNTERS
     X, Y, Z = (int(s) for s in sz)
     dev = beta.device
@@ -764,32 +785,31 @@ def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, work
             layout["At"].data_ptr(), layout["bbox"].data_ptr(), layout["pair_slot"].data_ptr(),
             layout["axis_masks"].data_ptr(), nslot, K, X, Y, Z,
             beta.data_ptr(), beta.shape[2], _ptr(tt), B, frames.data_ptr(), frames.stride(0), _ptr(fid), _ptr(G),
-            _ptr(r), workspace.data_ptr(), _nbytes(workspace), _ptr(counters), _stream())
+            _ptr(r), workspace.data_ptr(), _nbytes(workspace), _ptr(counters), *_lists_form(passes, chunks), _stream())
     _lib.check(rc, "dnmf_warp_gram_rhs_lists")
     return G, r, workspace
 
 
-def mu_temporal_slots(layout, workspace, sz, C, iters: int):
+def mu_temporal_slots(layout, workspace, sz, C, iters: int, passes=None, chunks=None):
     """K4 straight from the slot tables ``warp_gram_rhs_lists(..., finish=False)`` left in ``workspace``; C (K,T) fp32
-    updated in place (T = the frames of that launch).  Needs ``layout["nbr"]``."""
-    X, Y, Z = (int(s) for s in sz)
+    updated in place (T = the frames of that launch, ``passes`` and ``chunks`` those of that launch).  Needs ``layout["nbr"]``."""
     if not (C.is_cuda and C.dtype == torch.float32 and C.stride(1) == 1):
         raise ValueError("mu_temporal_slots: C must be float32 CUDA with unit inner stride")
     K, T = C.shape
     lib = _lib.load()
     nbr = layout["nbr"]
     with _timed("mu_temporal_slots"):
-        rc = lib.dnmf_mu_temporal_slots(workspace.data_ptr(), lib.dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, T),
+        rc = lib.dnmf_mu_temporal_slots(workspace.data_ptr(), _lists_tables(sz, T, passes, chunks),
                                         layout["nslot"], layout["pair_slot"].data_ptr(), C.data_ptr(), C.stride(0), K, T,
                                         int(iters), nbr.data_ptr(), nbr.shape[1], _stream())
     _lib.check(rc, "dnmf_mu_temporal_slots")
     return C
 
 
-def hals_temporal_slots(layout, workspace, sz, C, iters: int, kkt=False):
+def hals_temporal_slots(layout, workspace, sz, C, iters: int, kkt=False, passes=None, chunks=None):
     """K4h straight from the slot tables ``warp_gram_rhs_lists(..., finish=False)`` left in ``workspace``; C (K,T) fp32
-    updated in place (T = the frames of that launch).  Needs ``layout["nbr"]``.  ``kkt`` as for ``hals_temporal``."""
-    X, Y, Z = (int(s) for s in sz)
+    updated in place (T = the frames of that launch, ``passes`` and ``chunks`` those of that launch).  Needs
+    ``layout["nbr"]``.  ``kkt`` as for ``hals_temporal``."""
     if not (C.is_cuda and C.dtype == torch.float32 and C.dim() == 2 and C.stride(1) == 1):
         raise ValueError("hals_temporal_slots: C must be float32 CUDA with unit inner stride")
     if int(iters) < 0:
@@ -801,7 +821,7 @@ def hals_temporal_slots(layout, workspace, sz, C, iters: int, kkt=False):
     lib = _lib.load()
     out = torch.empty((T,), dtype=torch.float64, device=C.device) if kkt else None
     with _timed("hals_temporal_slots"):
-        rc = lib.dnmf_hals_temporal_slots(workspace.data_ptr(), lib.dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, T),
+        rc = lib.dnmf_hals_temporal_slots(workspace.data_ptr(), _lists_tables(sz, T, passes, chunks),
                                           layout["nslot"], layout["pair_slot"].data_ptr(), C.data_ptr(), C.stride(0), K, T,
                                           int(iters), nbr.data_ptr(), nbr.shape[1], _ptr(out), _stream())
     _lib.check(rc, "dnmf_hals_temporal_slots")
@@ -1012,9 +1032,9 @@ def patch_grid(sz, strides, overlaps):
 
 
 def register_patches(frames, tmpl, sz, strides, overlaps, max_shifts, max_deviation_rigid=3, upsample_factor=10,
-                     add_to_movie=0.0, frame_ids=None):
+                     add_to_movie=0.0, frame_ids=None, valu=None):
     """K8.  frames (>=B, P) fp32 CUDA rows, tmpl (P) -> rigid shifts (B,3) and per-patch shifts (B,NP,3) (signs -x, -y, +z:
-    the reference's ``x/y/z_shifts_els``)."""
+    the reference's ``x/y/z_shifts_els``).  ``valu``: the vector-ALU axis kernel instead of the MFMA one (None: ``K8_VALU``)."""
     X, Y, Z = (int(s) for s in sz)
     _rows(frames, "register_patches", "frames")
     dev = frames.device
@@ -1034,7 +1054,7 @@ def register_patches(frames, tmpl, sz, strides, overlaps, max_shifts, max_deviat
     with _timed("register_patches"):
         rc = lib.dnmf_register_patches(frames.data_ptr(), frames.stride(0), _ptr(fid), B, tm.data_ptr(), X, Y, Z, st, ov, ms,
                                        int(max_deviation_rigid), int(upsample_factor), float(add_to_movie), rigid.data_ptr(),
-                                       patch.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+                                       patch.data_ptr(), ws.data_ptr(), ws.numel(), int(K8_VALU if valu is None else valu), _stream())
     _lib.check(rc, "dnmf_register_patches")
     return rigid, patch
 
@@ -1043,10 +1063,11 @@ _BORDER = {False: 0, True: 1, 'min': 2, 'copy': 3}     # border_nan of apply_shi
 
 
 def rigid_correct(frames, tmpl, sz, max_shifts, upsample_factor=10, add_to_movie=0.0, border_nan=True, frame_ids=None,
-                  want_frames=False, tsum=None, tcount=None):
+                  want_frames=False, tsum=None, tcount=None, valu=None):
     """K8, rigid pass.  frames (>=B, P) fp32 CUDA rows, tmpl (P) -> (rigid shifts (B,3) as register_translation_3d returns
     them, corrected frames (B,P) or None, tsum (P) fp32, tcount (P) int32): the per-voxel sums and counts of the finite
-    corrected values are ADDED into ``tsum`` / ``tcount`` when given (a video walked in pieces), else start from zero."""
+    corrected values are ADDED into ``tsum`` / ``tcount`` when given (a video walked in pieces), else start from zero.
+    ``valu`` as for ``register_patches``."""
     X, Y, Z = (int(s) for s in sz)
     _rows(frames, "rigid_correct", "frames")
     dev = frames.device
@@ -1063,7 +1084,8 @@ def rigid_correct(frames, tmpl, sz, max_shifts, upsample_factor=10, add_to_movie
     with _timed("rigid_correct"):
         rc = lib.dnmf_rigid_correct(frames.data_ptr(), frames.stride(0), _ptr(fid), B, tm.data_ptr(), X, Y, Z, ms,
                                     int(upsample_factor), float(add_to_movie), _BORDER[border_nan], rigid.data_ptr(),
-                                    _ptr(out), P, tsum.data_ptr(), tcount.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+                                    _ptr(out), P, tsum.data_ptr(), tcount.data_ptr(), ws.data_ptr(), ws.numel(),
+                                    int(K8_VALU if valu is None else valu), _stream())
     _lib.check(rc, "dnmf_rigid_correct")
     return rigid, out, tsum, tcount
 

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define DNMF_ABI_VERSION 6
+#define DNMF_ABI_VERSION 7
 
 #define DNMF_OK 0
 #define DNMF_E_NULL (-1)      /* required pointer is NULL */
@@ -183,16 +183,24 @@ int dnmf_warp_gram_rhs_sparse_lt(const float *Aps, int Ks, int K, const int *ord
  *   counters: NULL, or 2 x uint64 INCREMENTED by the (tile, neuron) evaluations and the (tile, pair) sums done.
  *   Long videos: the tiles with more than four neurons are evaluated by a second launch on a side stream the library
  *   keeps (forked from `stream` behind the lists, joined back to it before the call's last kernel): ordering on
- *   `stream` is as if everything ran there. */
+ *   `stream` is as if everything ran there.
+ *   passes, chunks: the launch form, 0 = the library's choice (what every product caller passes).  passes 1 | 2: one
+ *   launch, or the second one above, instead of the choice by tiles per wave; chunks 1 .. 64: that many chunks per frame
+ *   (clipped to the number of tiles; a request above what the workspace is sized for falls back to the library's choice).
+ *   Other values are refused (DNMF_E_SHAPE) before anything is launched.  Results differ between forms only in the order of
+ *   fp32 additions.
+ * dnmf_warp_gram_rhs_lists_chunks: slot tables per frame that a launch in the form (passes, chunks) writes; 0 for a
+ *   bad shape or a refused form. */
 size_t dnmf_lists_axis_masks_bytes(int X, int Y, int Z, int K);
 int dnmf_pack_footprints_lists(const float *A, int X, int Y, int Z, int K, float *At, int *bbox, int *pair_slot,
                                int *nslot, void *axis_masks, dnmf_stream_t stream);
 size_t dnmf_warp_gram_rhs_lists_workspace(int nslot, int K, int X, int Y, int Z, int B);
-int dnmf_warp_gram_rhs_lists_chunks(int X, int Y, int Z, int B); /* chunk tables per frame the launch will write */
+int dnmf_warp_gram_rhs_lists_chunks(int X, int Y, int Z, int B, int passes, int chunks);
 int dnmf_warp_gram_rhs_lists(const float *At, const int *bbox, const int *pair_slot, const void *axis_masks, int nslot,
                              int K, int X, int Y, int Z, const float *beta, int T, const int *times, int B,
                              const float *frames, long ldf, const int *frame_ids, float *G, float *r, void *workspace,
-                             size_t workspace_bytes, unsigned long long *counters, dnmf_stream_t stream);
+                             size_t workspace_bytes, unsigned long long *counters, int passes, int chunks,
+                             dnmf_stream_t stream);
 
 /* Reconstruction image from the K3n layout: S (halo layout) as dnmf_recon_image, summing per tile of 4 x 64 voxels only the neurons
  * whose box meets the tile (static lists); bound by writing S.  K <= 256.  At and S 16-byte aligned, lds a multiple of 4
@@ -237,8 +245,8 @@ int dnmf_mu_temporal(const float *G, const float *r, float *C, long ldc, int K, 
 int dnmf_mu_temporal_nbr(const float *G, const float *r, float *C, long ldc, int K, int T, int iters, const int *nbr,
                          int NN, dnmf_stream_t stream);
 /* The same straight from the slot tables of K3n: call dnmf_warp_gram_rhs_lists with G = r = NULL (the tables then stay
- * in its workspace as (T, nchunks, nslot) floats, nchunks = dnmf_warp_gram_rhs_lists_chunks(X,Y,Z,T)) and hand the
- * workspace in as `slab`.  Bit-identical to finishing into a dense G first; saves writing and re-reading (T,K,K). */
+ * in its workspace as (T, nchunks, nslot) floats, nchunks = dnmf_warp_gram_rhs_lists_chunks(X,Y,Z,T,passes,chunks) of the
+ * same form) and hand the workspace in as `slab`.  Bit-identical to finishing into a dense G first; saves writing and re-reading (T,K,K). */
 int dnmf_mu_temporal_slots(const float *slab, int nchunks, int nslot, const int *pair_slot, float *C, long ldc, int K,
                            int T, int iters, const int *nbr, int NN, dnmf_stream_t stream);
 int dnmf_mu_temporal_step(const float *G, const float *r, const double *Cin, double *Cout, long ldc, int K,
@@ -416,13 +424,15 @@ int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs
  * tile_and_correct_3d's total_shifts (-x, -y, +z), i.e. what the class stores in x/y/z_shifts_els.  strides, overlaps,
  * max_shifts: 3 host ints each.  All device buffers fp32.  A search window holds at most 32 shifts per axis: max_shifts = 0
  * searches the whole axis, as numpy's empty slice cc[0:-0] does in the reference, and is refused (DNMF_E_UNSUPPORTED) on
- * an axis longer than 32 voxels.  upsample_factor = 1 returns the integer peak of the window, as the reference does. */
+ * an axis longer than 32 voxels.  upsample_factor = 1 returns the integer peak of the window, as the reference does.
+ * valu (here and in dnmf_rigid_correct): 0 runs the axis transforms as f32 MFMAs, 1 on the vector ALU (the kernel kept as the
+ * checker of the MFMA one); any other value is refused (DNMF_E_SHAPE). */
 int dnmf_register_patches_grid(int X, int Y, int Z, const int *strides, const int *overlaps, int *dims, int *starts);
 size_t dnmf_register_patches_workspace(int X, int Y, int Z, const int *strides, const int *overlaps, int B);
 int dnmf_register_patches(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
                           const int *strides, const int *overlaps, const int *max_shifts, int max_deviation_rigid,
                           int upsample_factor, float add_to_movie, float *rigid_shifts, float *patch_shifts, void *workspace,
-                          size_t workspace_bytes, dnmf_stream_t stream);
+                          size_t workspace_bytes, int valu, dnmf_stream_t stream);
 /* Rigid correction of the frames against a template (tile_and_correct_3d :1518-1574 with max_deviation_rigid == 0, the
  * pass motion_correct_batch_rigid :1770-1877 makes to build the template a piecewise-rigid pass starts from):
  * rigid_shifts (B,3) as register_translation_3d returns them (the reference's shifts_rig holds their negatives, :1574);
@@ -436,7 +446,7 @@ size_t dnmf_rigid_correct_workspace(int X, int Y, int Z, int B);
 int dnmf_rigid_correct(const float *frames, long ldf, const int *frame_ids, int B, const float *tmpl, int X, int Y, int Z,
                        const int *max_shifts, int upsample_factor, float add_to_movie, int border_nan, float *rigid_shifts,
                        float *corrected, long ldc, float *tsum, int *tcount, void *workspace, size_t workspace_bytes,
-                       dnmf_stream_t stream);
+                       int valu, dnmf_stream_t stream);
 /* apply_shifts_points :351-371: points (K,3), patch_shifts (T,NP,3) as above, centers (NP,3) = patch start + strides / 2 ->
  * out (K,3,T): out[k,0/1,t] = p - (s[t] - s[0]), out[k,2,t] = p + (s[t] - s[0]) with s the shifts of the patch whose
  * centre is nearest to point k. */

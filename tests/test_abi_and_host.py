@@ -35,8 +35,86 @@ def test_every_declared_symbol_is_exported(lib):
     assert sorted(_lib.SIGNATURES) == names
 
 
+_CTYPE = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "double": ctypes.c_double,
+          "float": ctypes.c_float, "dnmf_stream_t": ctypes.c_void_p, "dnmf_comm_t": ctypes.c_void_p}
+
+
+def header_prototypes():
+    """{name: (restype, [argtypes])} of every dnmf_* prototype of include/dnmf_hip.h, as ctypes: comments and preprocessor
+    lines stripped, any pointer (and the two handle typedefs) a c_void_p, a ``const char *`` result a c_char_p."""
+    text = open(os.path.join(ROOT, "include", "dnmf_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+
+    def ctype(decl, name):
+        if "*" in decl:
+            return ctypes.c_void_p
+        words = [w for w in decl.split() if w != "const"]
+        if words[-1] not in _CTYPE:      # a parameter name follows the type
+            words.pop()
+        assert len(words) == 1 and words[0] in _CTYPE, f"{name}: type of '{decl}'"
+        return _CTYPE[words[0]]
+
+    out = {}
+    for res, name, args in re.findall(r"([A-Za-z_][\w \t]*?[\s*]+)(dnmf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        args = " ".join(args.split())
+        restype = ctypes.c_char_p if re.fullmatch(r"const\s+char\s*\*\s*", res) else ctype(res, name)
+        assert name not in out, f"{name} declared twice"
+        out[name] = (restype, [] if args in ("", "void") else [ctype(a, name) for a in args.split(",")])
+    return out
+
+
+def test_every_prototype_equals_its_ctypes_signature(lib):
+    """The binding whole: result type and argument list of every function the header declares against
+    ``_lib.SIGNATURES``, and one ABI version in the header, the binding and the library as built."""
+    from dnmf_amd import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions() == sorted(_lib.SIGNATURES) and len(protos) >= 96
+    for name, proto in protos.items():
+        assert proto == _lib.SIGNATURES[name], f"{name}: header {proto} != SIGNATURES {_lib.SIGNATURES[name]}"
+    version = re.search(r"^#define\s+DNMF_ABI_VERSION\s+(\d+)\s*$", open(os.path.join(ROOT, "include", "dnmf_hip.h")).read(), re.M)
+    assert int(version.group(1)) == _lib.ABI_VERSION == lib.dnmf_version()
+
+
+def test_kernel_forms_are_arguments_not_environment(lib, monkeypatch):
+    """The launch form of K3n and the axis kernel of K8 are arguments.  (0, 0) is the library's choice: the table counts a
+    build with the former four-argument dnmf_warp_gram_rhs_lists_chunks returned; passes 1 | 2 times chunks 1 | 3 gives
+    passes x chunks tables while the chunks fit the tiles (3 at 24 x 20, 1024 at 512 x 512); the environment variables
+    that once chose the forms change nothing; values outside passes 0..2, chunks 0..64, valu 0..1 are refused before any
+    HIP call."""
+    shapes = (((24, 20, 1, 4), 3, 3), ((512, 512, 1, 4000), 10, 1024))
+
+    def counts():
+        got = [lib.dnmf_warp_gram_rhs_lists_chunks(*shape, 0, 0) for shape, _, _ in shapes]
+        return got + [lib.dnmf_warp_gram_rhs_lists_chunks(*shape, p, c) for shape, _, _ in shapes for p in (1, 2) for c in (1, 3)]
+
+    expected = [auto for _, auto, _ in shapes] + [p * min(c, ntiles) for _, _, ntiles in shapes for p in (1, 2) for c in (1, 3)]
+    assert counts() == expected
+    assert lib.dnmf_warp_gram_rhs_lists_chunks(8, 32, 1, 4, 2, 3) == 2 * 1         # one tile: the request is clipped to it
+    assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 4000, 0, 64) == 10     # above what the workspace holds: the choice
+    for name, value in (("DNMF_LISTS_PASSES", "1"), ("DNMF_LISTS_CHUNKS", "3"), ("DNMF_K8_VALU", "1")):
+        monkeypatch.setenv(name, value)
+    assert counts() == expected
+    for passes, chunks in ((3, 0), (-1, 0), (0, 65), (0, -1)):
+        assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 4000, passes, chunks) == 0
+    buf = ctypes.create_string_buffer(64)
+    a = ctypes.addressof(buf)
+    I3 = ctypes.c_int * 3
+    gram = lambda passes, chunks: lib.dnmf_warp_gram_rhs_lists(a, a, a, a, 10, 3, 4, 4, 1, a, 1, None, 1, a, 16, None, a, a, a,
+                                                               1 << 20, None, passes, chunks, None)
+    for passes, chunks in ((3, 0), (0, 65)):
+        assert gram(passes, chunks) == -2 and b"passes=" in lib.dnmf_last_error()
+    patches = lambda valu: lib.dnmf_register_patches(a, 20 * 20, None, 1, a, 20, 20, 1, I3(8, 8, 1), I3(4, 4, 0), I3(0, 12, 0), 3,
+                                                     10, 0.0, a, a, a, 64, valu, None)
+    rigid = lambda valu: lib.dnmf_rigid_correct(a, 20 * 20, None, 1, a, 20, 20, 1, I3(0, 12, 0), 10, 0.0, 1, a, None, 0, None,
+                                                None, a, 64, valu, None)
+    for call in (patches, rigid):
+        assert call(2) == -2 and b"valu=2" in lib.dnmf_last_error()
+        assert call(0) == call(1) == -4       # both kernels go on to the workspace check
+
+
 def test_version_and_padding(lib):
-    assert lib.dnmf_version() == 6
+    assert lib.dnmf_version() == 7
     assert [lib.dnmf_padded_k(k) for k in (0, 1, 10, 15, 16, 50, 100, 111, 112, 200)] == \
         [0, 16, 16, 16, 32, 64, 112, 112, 128, 208]
 
@@ -63,14 +141,14 @@ def test_argument_errors_are_reported_without_a_gpu(lib):
     # slot tables (5 chunks per frame at B = 4000, two tables per chunk: one per launch; rounded up to 256 bytes), then one
     # 2-word list and one 16-byte descriptor per frame and tile
     slab = (4000 * 2 * 5 * 461 * 4 + 255) // 256 * 256
-    assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 4000) == 10     # tables a consumer sums per frame
-    assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 400) == 41      # short video: one launch, one table per chunk
+    assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 4000, 0, 0) == 10     # tables a consumer sums per frame
+    assert lib.dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, 400, 0, 0) == 41      # short video: one launch, one table per chunk
     assert lib.dnmf_warp_gram_rhs_lists_workspace(461, 100, 512, 512, 1, 4000) == slab + 4000 * 1024 * (2 * 8 + 16)
     rc = lib.dnmf_warp_gram_rhs_lists(addr, addr, addr, addr, 5000, 3, 4, 4, 1, addr, 1, None, 1, addr, 16, None, addr, addr,
-                                      addr, 1 << 20, None, None)
+                                      addr, 1 << 20, None, 0, 0, None)
     assert rc == -3 and b"pattern slots" in lib.dnmf_last_error()
     rc = lib.dnmf_warp_gram_rhs_lists(addr, addr, addr, addr, 10, 3, 4, 4, 1, addr, 1, None, 1, addr, 16, None, addr, addr,
-                                      addr, 8, None, None)
+                                      addr, 8, None, 0, 0, None)
     assert rc == -4
     assert lib.dnmf_recon_image_lists(addr, addr, 3, 4, 4, 1, addr, 4, None, 2, addr, 16, None) == -2    # lds < 8 x 32
     assert lib.dnmf_mu_temporal_nbr(addr, addr, addr, 4, 3, 4, 1, addr, 12, None) == -3                   # NN not 8/16/32
@@ -330,14 +408,14 @@ def test_position_initialiser_refuses_windows_it_cannot_hold(lib):
     a = ctypes.addressof(buf)
     for ms, rc in (((0, 5, 1), -3), ((5, 0, 1), -3), ((17, 5, 1), -3)):
         assert lib.dnmf_register_patches(a, 64 * 40 * 2, None, 1, a, 64, 40, 2, I3(16, 12, 1), I3(8, 8, 1), I3(*ms), 3, 10, 0.0,
-                                         a, a, a, 64, None) == rc, ms
+                                         a, a, a, 64, 0, None) == rc, ms
         assert lib.dnmf_rigid_correct(a, 64 * 40 * 2, None, 1, a, 64, 40, 2, I3(*ms), 10, 0.0, 1, a, None, 0, None, None, a, 64,
-                                      None) == rc, ms
+                                      0, None) == rc, ms
     # an axis of at most 32 voxels is searched whole whatever max_shifts says; a small workspace is then the only objection
     assert lib.dnmf_register_patches(a, 20 * 20, None, 1, a, 20, 20, 1, I3(8, 8, 1), I3(4, 4, 0), I3(0, 12, 0), 3, 10, 0.0,
-                                     a, a, a, 64, None) == -4
+                                     a, a, a, 64, 0, None) == -4
     assert lib.dnmf_rigid_correct(a, 20 * 20, None, 1, a, 20, 20, 1, I3(0, 12, 0), 10, 0.0, 1, a, None, 0, None, None, a, 64,
-                                  None) == -4
+                                  0, None) == -4
 
 
 def sl_splits(X, Y, Z, T):

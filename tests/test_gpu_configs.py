@@ -77,8 +77,9 @@ def test_bench_path_vs_fixture_G9(M, O, monkeypatch, label, passes):
     """Fixture G9 (one outer iteration of the reference's demo loop, produced by the reference itself) through the
     bench's path: resident loader, fused Adam epoch (one K2 launch per group of equal mini-batch size on the cached
     reconstruction images), neuron-list Gram kernel; same tolerances as the list-loader test of the same fixture."""
-    if passes != "auto":   # both launch forms of K3n on this problem (DNMF_LISTS_PASSES, warp_gram_lists.hip)
-        monkeypatch.setenv("DNMF_LISTS_PASSES", passes)
+    if passes != "auto":   # both launch forms of K3n on this problem (ops.LISTS_FORM)
+        from dnmf_amd import ops
+        monkeypatch.setattr(ops, "LISTS_FORM", (int(passes), 0))
     g = golden("G9_loop")
     lr, epochs, shuffled, bs = g[label + "_cfg"]
     bs = int(bs)
@@ -162,8 +163,9 @@ def test_bench_path_slot_tables_vs_oracle(M, O, monkeypatch, passes):
     against the CPU oracle on the same batches.  Off-lattice start and well-conditioned Gram matrices (every
     footprint inside the volume), so the tolerances are the tight ones: beta 2e-3 of the largest displacement,
     C rtol 1e-4."""
-    if passes != "auto":   # both launch forms of K3n on this problem (DNMF_LISTS_PASSES, warp_gram_lists.hip)
-        monkeypatch.setenv("DNMF_LISTS_PASSES", passes)
+    if passes != "auto":   # both launch forms of K3n on this problem (ops.LISTS_FORM)
+        from dnmf_amd import ops
+        monkeypatch.setattr(ops, "LISTS_FORM", (int(passes), 0))
     rng = np.random.RandomState(11)
     sz, K, T, bs = [96, 80, 1], 12, 8, 4
     pos = np.stack([12 + rng.rand(K) * 72, 12 + rng.rand(K) * 56, np.zeros(K)], 1).astype(np.float32)

@@ -19,7 +19,7 @@ and G and r are preset to a non-zero pattern (an entry that is never written is 
 
 Bound (gram_restatement.tol), per frame and entry:  2e-5 absG[k,l] + sum_v (|a_k| e_l + |a_l| e_k + e_k e_l) for G, 2e-5 absr[k]
 + sum_v |y| e_k for r, e_k(v) = 4 spacing_fp32(umax) L_k(v) + 1e-6 m_k(v); a zero bound asks for an exact zero.  K3n runs in
-nine launch forms (DNMF_LISTS_PASSES auto | 1 | 2 times DNMF_LISTS_CHUNKS auto | 1 | 3: one wave per frame with runs of equal
+nine launch forms (passes auto | 1 | 2 times chunks auto | 1 | 3, the arguments of ops.warp_gram_rhs_lists: one wave per frame with runs of equal
 lists; a ragged last chunk with list changes inside a run), each twice into one workspace (bit-identical) and each to the same
 bound.  Between forms: K3s and K3n agree with K3 within the sum of their two bounds, entry by entry.
 Slot-table route (warp_gram_rhs_lists(finish=False) + mu_temporal_slots, 7 rounds, gamma None, one case per Z form):
@@ -160,7 +160,7 @@ def test_large_volumes_are_past_the_offset_threshold(ops):
         tx, ty, tz = GR.tile_shape((X, Y, Z))
         ntiles = -(-X // tx) * -(-Y // ty) * -(-Z // tz)
         chunk_len = -(-ntiles // 64)
-        assert chunk_len >= 100 and lib.dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, 2) == 2 * -(-ntiles // chunk_len)
+        assert chunk_len >= 100 and lib.dnmf_warp_gram_rhs_lists_chunks(X, Y, Z, 2, 0, 0) == 2 * -(-ntiles // chunk_len)
     assert [GR.CASES[n][0][2] for n in GR.LARGE] == [1, 2, 4]
     for n in GR.SMALL:
         assert ops.halo_voxels(GR.CASES[n][0]) * 4 < 2 ** 24
@@ -195,7 +195,7 @@ def test_dense_and_zero_skipping_forms(ops, name):
 
 
 @pytest.mark.parametrize("name", list(GR.CASES))
-def test_neuron_list_forms(ops, name, monkeypatch):
+def test_neuron_list_forms(ops, name):
     """K3n in its nine launch forms against float64, each twice into one workspace, and against K3 where K3 takes K."""
     c = GR.gram_case(name)
     sz, K, B = c["sz"], c["K"], len(c["times"])
@@ -212,15 +212,14 @@ def test_neuron_list_forms(ops, name, monkeypatch):
     seen, ws, tables = {}, None, set()
     from dnmf_amd import _lib
     for passes, chunks in FORMS:
-        for var, val in (("DNMF_LISTS_PASSES", passes), ("DNMF_LISTS_CHUNKS", chunks)):
-            monkeypatch.delenv(var, raising=False) if val == "auto" else monkeypatch.setenv(var, val)
-        tables.add(_lib.load().dnmf_warp_gram_rhs_lists_chunks(*sz, B))
+        form = {"passes": 0 if passes == "auto" else int(passes), "chunks": 0 if chunks == "auto" else int(chunks)}
+        tables.add(_lib.load().dnmf_warp_gram_rhs_lists_chunks(*sz, B, form["passes"], form["chunks"]))
         out = preset(B, K)
         _, _, ws = ops.warp_gram_rhs_lists(ly, K, sz, d["beta"], d["times"], d["frames"], frame_ids=d["frame_ids"], workspace=ws,
-                                           out=out)
+                                           out=out, **form)
         out2 = preset(B, K)
         _, _, ws2 = ops.warp_gram_rhs_lists(ly, K, sz, d["beta"], d["times"], d["frames"], frame_ids=d["frame_ids"], workspace=ws,
-                                            out=out2)
+                                            out=out2, **form)
         assert ws2 is ws and torch.equal(out[0], out2[0]) and torch.equal(out[1], out2[1]), f"{name} passes {passes} chunks {chunks}"
         G, r = out[0].cpu().numpy(), out[1].cpu().numpy()
         what = f"K3n passes {passes} chunks {chunks}"

@@ -102,14 +102,13 @@ def test_headline_geometry_vs_oracle(M, O, monkeypatch, Z, T):
         dn.gram_kernel = kernel
         check(kernel)
     dn.gram_kernel = "lists"
-    monkeypatch.setenv("DNMF_LISTS_PASSES", "2")       # both launches, side stream, separate tables: what the bench runs
+    monkeypatch.setattr(ops, "LISTS_FORM", (2, 0))     # both launches, side stream, separate tables: what the bench runs
     check("lists, two launches")
-    monkeypatch.setenv("DNMF_LISTS_CHUNKS", "1")       # one chunk per frame: the long runs of tiles of the bench
+    monkeypatch.setattr(ops, "LISTS_FORM", (2, 1))     # one chunk per frame: the long runs of tiles of the bench
     check("lists, two launches, one chunk per frame")
-    monkeypatch.setenv("DNMF_LISTS_PASSES", "1")
+    monkeypatch.setattr(ops, "LISTS_FORM", (1, 1))
     check("lists, one launch, one chunk per frame")
-    monkeypatch.delenv("DNMF_LISTS_PASSES")
-    monkeypatch.delenv("DNMF_LISTS_CHUNKS")
+    monkeypatch.setattr(ops, "LISTS_FORM", (0, 0))
     # ---- 50 temporal updates through update_footprints (K3n + K4 on the slot tables)
     Cref = O.mu_temporal_from_gram(np.moveaxis(Gref, 0, 2), rref.T, C, None, 50)
     dn.gram_kernel = 'auto'
@@ -119,13 +118,12 @@ def test_headline_geometry_vs_oracle(M, O, monkeypatch, Z, T):
 
 
 @pytest.mark.parametrize("passes", ["1", "2"])
-def test_neuron_list_gram_with_cancelling_quadratic_terms(M, monkeypatch, passes):
+def test_neuron_list_gram_with_cancelling_quadratic_terms(M, passes):
     """K3n's tile lists come from interval arithmetic on the ten terms of the coordinate polynomial plus a margin for the
     rounding of either evaluation.  With quadratic coefficients of order 0.1-1 at 512x512 whose terms cancel along a band
     (q_x = x + c x (x - y): the identity on the diagonal), the partial sums reach |c| 512^2 ~ 10^5 voxels and the chain's
     rounding ~0.1 voxel -- more than a fixed margin; the margin therefore grows with the summed term magnitudes
     (common.hpp: tap_range).  The result must be the dense kernel's: same zero pattern, 2e-6 of the largest entry."""
-    monkeypatch.setenv("DNMF_LISTS_PASSES", passes)
     from dnmf_amd import ops
     rng = np.random.RandomState(11)
     sz, K, T = [512, 512, 1], 60, 6
@@ -141,7 +139,7 @@ def test_neuron_list_gram_with_cancelling_quadratic_terms(M, monkeypatch, passes
         fp.beta.copy_(torch.from_numpy(beta).cuda())
     frames = torch.rand(T, 512 * 512, device="cuda")
     Gd, rd, _ = ops.warp_gram_rhs(fp.packed_footprints(), K, sz, fp.beta.detach(), None, frames)
-    Gn, rn, _ = ops.warp_gram_rhs_lists(fp.packed_lists(), K, sz, fp.beta.detach(), None, frames)
+    Gn, rn, _ = ops.warp_gram_rhs_lists(fp.packed_lists(), K, sz, fp.beta.detach(), None, frames, passes=int(passes))
     assert int((Gd.abs().amax(dim=(1, 2)) > 0).sum()) == T      # every frame still sees footprints
     for i in range(T):
         scale = float(Gd[i].abs().max())

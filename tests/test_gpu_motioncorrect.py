@@ -251,8 +251,8 @@ def test_two_dimensional_video(ops, MO):
         mc.motion_correct_rigid()
 
 
-def test_matrix_pipe_kernel_equals_the_vector_kernel(ops, monkeypatch):
-    """K8's axis transform runs as f32 MFMAs (mc_axis_mfma_kernel); DNMF_K8_VALU=1 selects the vector-ALU kernel it replaced.
+def test_matrix_pipe_kernel_equals_the_vector_kernel(ops):
+    """K8's axis transform runs as f32 MFMAs (mc_axis_mfma_kernel); valu=True selects the vector-ALU kernel it replaced.
     Same shifts (a bin apart at most, 98 % identical: the sums over j run in a different order) and the same moved frames to
     1e-5 of the range, on a volume with odd sizes, a patch grid and every pass (forward, windowed inverse, upsampled inverse,
     the full inverse on a shifted grid)."""
@@ -262,9 +262,8 @@ def test_matrix_pipe_kernel_equals_the_vector_kernel(ops, monkeypatch):
     add = -float(video.min())
     res = {}
     for mode in ("0", "1"):
-        monkeypatch.setenv("DNMF_K8_VALU", mode)
-        rigid, patch = ops.register_patches(frames, tm, sz, (20, 14, 2), (10, 8, 1), (6, 5, 1), 3, 10, add)
-        r2, out, _, _ = ops.rigid_correct(frames, tm, sz, (6, 5, 1), 10, add, False, want_frames=True)
+        rigid, patch = ops.register_patches(frames, tm, sz, (20, 14, 2), (10, 8, 1), (6, 5, 1), 3, 10, add, valu=mode == "1")
+        r2, out, _, _ = ops.rigid_correct(frames, tm, sz, (6, 5, 1), 10, add, False, want_frames=True, valu=mode == "1")
         res[mode] = (rigid.cpu().numpy(), patch.cpu().numpy(), r2.cpu().numpy(), out.cpu().numpy())
     for a, b in zip(res["0"][:3], res["1"][:3]):
         assert np.abs(a - b).max() <= 0.1 + 1e-4 and (np.abs(a - b) < 1e-4).mean() >= 0.98
@@ -356,8 +355,8 @@ def check_rigid(ops, MO, video, template, sz, max_shifts, uf=10):
 ])
 def test_short_axes_register_patches_vs_oracle(ops, MO, monkeypatch, valu, sz, strides, overlaps, max_shifts):
     """Boxes whose second axis is shorter than the 32 kept window indices: the partial inverses hold (items, 32, 32, n2),
-    more than the (items, 32, n1, n2) of a long axis.  Both axis kernels (DNMF_K8_VALU)."""
-    monkeypatch.setenv("DNMF_K8_VALU", valu)
+    more than the (items, 32, n1, n2) of a long axis.  Both axis kernels (ops.K8_VALU)."""
+    monkeypatch.setattr(ops, "K8_VALU", valu == "1")
     video, template, _, _ = synthetic_video(sz, 6, 30, seed=sum(sz) + 3)
     rig = check_patches(ops, MO, video, template, sz, strides, overlaps, max_shifts)
     assert np.abs(rig[:, :2]).max() > 1.0
@@ -366,7 +365,7 @@ def test_short_axes_register_patches_vs_oracle(ops, MO, monkeypatch, valu, sz, s
 @pytest.mark.parametrize("valu", ["0", "1"])
 @pytest.mark.parametrize("sz,max_shifts", [([64, 16, 4], (5, 3, 1)), ([20, 20, 1], (3, 3, 0)), ([40, 8, 16], (4, 2, 3))])
 def test_short_axes_rigid_correct_vs_oracle(ops, MO, monkeypatch, valu, sz, max_shifts):
-    monkeypatch.setenv("DNMF_K8_VALU", valu)
+    monkeypatch.setattr(ops, "K8_VALU", valu == "1")
     video, template, _, _ = synthetic_video(sz, 6, 30, seed=sum(sz) + 4, piecewise=False)
     ref = check_rigid(ops, MO, video, template, sz, max_shifts)
     assert np.abs(ref[:, :2]).max() > 1.0
@@ -501,12 +500,12 @@ def test_workspace_tail_untouched_and_unwritten_rows_unread(ops, kind):
         if kind == "patches":
             out = torch.empty((T, NP, 3), device="cuda")
             rc = lib.dnmf_register_patches(frames.data_ptr(), P, None, T, tm.data_ptr(), *sz, strides, overlaps, ms, 3, 10, add,
-                                           rigid.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+                                           rigid.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), 0, ops._stream())
         else:
             out = torch.empty((T, P), device="cuda")
             tsum, tcount = torch.zeros(P, device="cuda"), torch.zeros(P, dtype=torch.int32, device="cuda")
             rc = lib.dnmf_rigid_correct(frames.data_ptr(), P, None, T, tm.data_ptr(), *sz, I3(5, 3, 1), 10, add, 1, rigid.data_ptr(),
-                                        out.data_ptr(), P, tsum.data_ptr(), tcount.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream())
+                                        out.data_ptr(), P, tsum.data_ptr(), tcount.data_ptr(), ws.data_ptr(), ws.numel(), 0, ops._stream())
         _lib.check(rc, kind)
         torch.cuda.synchronize()
         assert torch.equal(ws[need:], sentinel), fill

@@ -480,7 +480,7 @@ def test_full_size_long_video_lists_vs_dense(M):
     sz, K, T = [512, 512, 1], 100, 1700
     frames, positions, _ = Simulator.generate_video_resident(K, T, sz, 3, .2, -120, {"sigma": [5, 5, .01], "ls": [10, 10, 10]})
     frames.clamp_(min=0)
-    assert ops._lib.load().dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, T) == 2 * 10   # two launches, ten chunks each
+    assert ops._lib.load().dnmf_warp_gram_rhs_lists_chunks(512, 512, 1, T, 0, 0) == 2 * 10   # two launches, ten chunks each
 
     def model(kernel):
         torch.manual_seed(4)
@@ -516,9 +516,9 @@ def test_full_size_neuron_list_path(M, passes, monkeypatch):
     tables, through the same size-independent properties -- identity warp => A^T A; integer shifts => Gram of the
     shifted footprints; S = A.C against a float64 product; the fused update_footprints equals the two-step one bit
     for bit; a full sweep through the model leaves finite, non-negative traces."""
-    if passes != "auto":   # both launch forms of K3n on this problem (DNMF_LISTS_PASSES, warp_gram_lists.hip)
-        monkeypatch.setenv("DNMF_LISTS_PASSES", passes)
     from dnmf_amd import ops
+    if passes != "auto":   # both launch forms of K3n on this problem (ops.LISTS_FORM)
+        monkeypatch.setattr(ops, "LISTS_FORM", (int(passes), 0))
     torch.manual_seed(0)
     sz, K, T = [512, 512, 1], 100, 8
     pos = torch.rand(K, 3) * torch.tensor([512.0, 512.0, 0.0])
@@ -696,11 +696,10 @@ def test_neuron_list_gram_equals_dense(M, O, sz, K, T, sigma, passes, monkeypatc
     volume edges, K up to 200 (four list words), warps that push part of the volume outside, an axis longer than
     65536 (IEEE division instead of the shortcut).  Sums agree to fp32
     summation order; the pattern of exact zeros of G is the dense kernel's; two launches agree bitwise."""
-    if passes != "auto":   # both launch forms of K3n on this problem (DNMF_LISTS_PASSES, warp_gram_lists.hip)
-        monkeypatch.setenv("DNMF_LISTS_PASSES", passes[0])
-        if "long runs" in passes:   # one wave walks the whole frame: runs of tiles with one and the same list
-            monkeypatch.setenv("DNMF_LISTS_CHUNKS", "1")
     from dnmf_amd import ops
+    if passes != "auto":   # both launch forms of K3n on this problem (ops.LISTS_FORM)
+        # "long runs": one wave walks the whole frame, runs of tiles with one and the same list
+        monkeypatch.setattr(ops, "LISTS_FORM", (int(passes[0]), 1 if "long runs" in passes else 0))
     rng = np.random.RandomState(K + sz[0])
     pos = rng.rand(K, 3) * np.array(sz)
     A = O.gaussian_footprints(sz, pos, np.full(K, sigma))
@@ -812,9 +811,9 @@ def test_neuron_list_gram_under_strong_warps(M, O, passes, monkeypatch):
     range from mild to violent (shifts up to the volume size, shear and scale of order one, quadratic terms that bend
     the volume by tens of voxels, one frame with non-finite coefficients): the result must still be the dense
     kernel's."""
-    if passes != "auto":   # both launch forms of K3n on this problem (DNMF_LISTS_PASSES, warp_gram_lists.hip)
-        monkeypatch.setenv("DNMF_LISTS_PASSES", passes)
     from dnmf_amd import ops
+    if passes != "auto":   # both launch forms of K3n on this problem (ops.LISTS_FORM)
+        monkeypatch.setattr(ops, "LISTS_FORM", (int(passes), 0))
     rng = np.random.RandomState(123)
     sz, K, T = [112, 96, 1], 60, 40
     pos = rng.rand(K, 3) * np.array(sz)
