@@ -588,9 +588,13 @@ class DeformableNMF:
         # error per squared voxel of frame-to-frame change of a warp coefficient.  0 = none, every frame fitted on its own.  An
         # attribute like motion_chunk, not a parameter: update_motion keeps the parameter list it had
         self.motion_smooth = 0.0
+        # which coefficients update_motion(solver='gn') fits (K16o, see _update_motion_gn): 'translation', 'affine' or
+        # 'quadratic' (the default: all of them, the path as it was), 'graded' = the three in turn, or any sequence of
+        # (order, iterations) stages.  An attribute for the same reason
+        self.motion_order = 'quadratic'
         self._stage_buf = None     # device copy of the frames a host loader served in its last pass
         # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam -- and prior when smooth > 0 -- (CUDA
-        # tensors, (T,)); else None
+        # tensors, (T,)), and stages when motion_order is set: a list, per stage a dict(order, sse0, sse); else None
         self.last_motion_gn = None
         self._reg_buf = None       # registered frames (K7 / K17) of the last update_footprints(live_spatial=True)
         self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
@@ -1406,7 +1410,10 @@ class DeformableNMF:
         is ignored, as the reference's gradient-free reg term is.  ``self.motion_smooth`` > 0 (``solver='gn'`` only; with any
         other solver, or negative or not finite, a ValueError) adds the temporal prior ``motion_smooth`` * sum_t |theta_t -
         theta_{t+1}|^2 to the mean squared error (K16s, see ``_update_motion_gn``): a frame whose neurons are dark is then
-        carried by its neighbours in time instead of keeping its start.
+        carried by its neighbours in time instead of keeping its start.  ``self.motion_order`` (``solver='gn'`` only, checked the
+        same way) chooses the coefficients that are fitted: ``'translation'``, ``'affine'``, ``'quadratic'`` (the default: all),
+        ``'graded'`` -- the three in turn with ``iters`` iterations each, which reaches a warp several voxels away where the full
+        order diverges -- or a sequence of ``(order, iterations)`` stages (K16o, see ``_update_motion_gn``).
 
         A ``ResidentLoader`` hands over rows that already live on the GPU.  Any other loader (the stock
         ``torch.utils.data.DataLoader`` of demo.py:33-35) is iterated once per epoch by a background thread while this
@@ -1414,8 +1421,9 @@ class DeformableNMF:
         as four launches when the optimiser is the demo's plain Adam (``_motion_epoch``), else step by step."""
         _check_motion_solver(solver, "update_motion")
         smooth = _check_motion_smooth(self.motion_smooth, solver, "update_motion")
+        order = _check_motion_order(self.motion_order, solver, "update_motion")
         if solver == 'gn':
-            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma, smooth)
+            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma, smooth, order)
         fp = self.fp
         beta = fp.beta
         # reconstruction images of all frames (C is constant inside this call): built when first needed -- the fused
@@ -1476,7 +1484,7 @@ class DeformableNMF:
                     print('Recon: ' + str(out["loss"][0]))
                     print('Reg: ' + str(out["reg"]))
 
-    def _update_motion_gn(self, dataloader, iters, damping, gamma=0, smooth=0.0):
+    def _update_motion_gn(self, dataloader, iters, damping, gamma=0, smooth=0.0, order='quadratic'):
         """``update_motion(solver='gn')``: Levenberg-Marquardt on the 30 (12 at Z = 1) coefficients of every frame.
 
         The loss is a sum over frames and frame t only sees ``beta[:, :, t]``, so the frames are independent small dense
@@ -1521,11 +1529,23 @@ class DeformableNMF:
               24x20x1  smooth 1e-4  0.007  0.006  0.012  0.027  0.015  0.011  0.010
               24x20x2  smooth 0     0      0      0      0.402  0      0      0
               24x20x2  smooth 1e-4  0.017  0.013  0.017  0.030  0.028  0.024  0.023
-          (0: below 5e-5).  At ``smooth`` = 1e-3 / 1e-2 every frame is 0.04 - 0.12 / 0.14 - 0.26 voxel off."""
+          (0: below 5e-5).  At ``smooth`` = 1e-3 / 1e-2 every frame is 0.04 - 0.12 / 0.14 - 0.26 voxel off.
+
+        ``order`` (the model's ``motion_order``; K16o, ``dnmf_lm_step_order``; tests/gn_order_restatement.py is the definition): a
+        name, or stages ``((order, iterations), ...)`` run one after the other on each chunk -- ``'graded'`` is translation,
+        affine, quadratic with ``iters`` iterations each.  A stage steps on the rows of the centred basis of its degree only (K16
+        still returns the whole H and g; the step restricts them) and leaves the other rows of ``fp.beta`` bit for bit; it
+        starts a fresh ``lm_state`` at the coefficients the stage before it accepted and ends with its own accept-only step.
+        A chunk's images are still built once.  ``last_motion_gn`` gains ``stages``: a list with, per stage, dict(order, sse0,
+        sse), per frame as above; the other keys describe the call: ``sse0`` from the first stage, ``sse`` / ``lam`` / ``prior``
+        from the last, the counts summed.  ``'quadratic'``, the default, is the loop above, launch for launch, and its
+        ``last_motion_gn`` has the keys it had: no ``stages``."""
         fp = self.fp
         iters = int(iters)
         if iters < 0:
             raise ValueError(f"update_motion(solver='gn'): iters={iters}")
+        schedule = [(o, iters) for o in MOTION_GRADED] if order == 'graded' else [(order, iters)] if isinstance(order, str) \
+            else list(order)
         if self.verbose and gamma:
             print(f"update_motion(solver='gn'): gamma={gamma} ignored (the reg term is gradient-free in the reference)")
         chans = self._channels()
@@ -1540,6 +1560,9 @@ class DeformableNMF:
                  "accepted": torch.zeros((fp.T,), dtype=torch.int32, device=device),
                  "rejected": torch.zeros((fp.T,), dtype=torch.int32, device=device),
                  "lam": torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)}
+        if order != 'quadratic':         # the default keeps the keys it had
+            stats["stages"] = [{"order": o, "sse0": torch.full_like(stats["sse0"], float('nan')),
+                                "sse": torch.full_like(stats["sse"], float('nan'))} for o, _ in schedule]
         beta_ref = None
         if smooth:
             stats["prior"] = torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)
@@ -1557,9 +1580,9 @@ class DeformableNMF:
                 if "S" not in bufs or bufs["S"][0].shape[0] < n:
                     bufs["S"] = [torch.empty((n, lds), dtype=torch.float32, device=device) for _ in chans]
                 S = [f.recon_image(Cdev, tt, out=buf[:n]) for (f, _), buf in zip(chans, bufs["S"])]
-                # colours: [rows of S, rows of fr, model times, state, normal equations]; one colour of all frames without the
-                # prior, else the frames of even t and those of odd t (each a launch of pairwise non-adjacent frames)
-                colours = [[None, ff, tt, ops.lm_state(n, device), None]]
+                # colours: [rows of S, rows of fr, model times]; one colour of all frames without the prior, else the frames
+                # of even t and those of odd t (each a launch of pairwise non-adjacent frames)
+                colours = [(None, ff, tt)]
                 if smooth:
                     colours = []
                     th = host_times[s0:s0 + chunk]
@@ -1567,26 +1590,34 @@ class DeformableNMF:
                         pick = torch.nonzero(th % 2 == parity).reshape(-1)          # CPU
                         if pick.numel():
                             sel, pick = pick.to(device, torch.int32), pick.to(device)
-                            colours.append([sel, sel if ff is None else ff[pick].contiguous(), tt[pick].contiguous(),
-                                            ops.lm_state(pick.numel(), device), None])
-                for it in range(iters + 1):
-                    for col in colours:
-                        sel, cf, ct, state, eqs = col
-                        for c, ((f, cols), Sc) in enumerate(zip(chans, S)):
-                            eqs = ops.warp_normal_eqs(Sc, sel, fr if cols is None else fr[:, cols], cf, fp.sz_list, beta, ct,
-                                                      out=eqs, accumulate=c > 0, workspace=bufs.get("ws"))
-                            bufs["ws"] = eqs["workspace"]
-                        col[4] = eqs
-                        ops.lm_step(state, eqs, fp.sz_list, beta, ct, lam0=damping, accept_only=it == iters, smooth=smooth,
-                                    n_residuals=row, beta_ref=beta_ref)
-                for _, _, ct, state, _ in colours:
-                    idx = ct.long()
-                    stats["sse0"][idx], stats["sse"][idx], stats["lam"][idx] = state["sse0"], state["sse"], state["lam"]
-                    stats["accepted"][idx], stats["rejected"][idx] = state["counts"][:, 0], state["counts"][:, 1]
-                    if smooth:
-                        stats["prior"][idx] = state["prior"]
-                    if self.verbose:
-                        print(f"GN frames {int(ct[0])}..: sse {float(state['sse0'].sum()):.6g} -> {float(state['sse'].sum()):.6g}")
+                            colours.append((sel, sel if ff is None else ff[pick].contiguous(), tt[pick].contiguous()))
+                for k, (stage_order, stage_iters) in enumerate(schedule):
+                    # per colour its state and normal equations: every stage starts a fresh state at what is in beta
+                    work = [[ops.lm_state(ct.numel(), device), None] for _, _, ct in colours]
+                    for it in range(stage_iters + 1):
+                        for (sel, cf, ct), w in zip(colours, work):
+                            state, eqs = w
+                            for c, ((f, cols), Sc) in enumerate(zip(chans, S)):
+                                eqs = ops.warp_normal_eqs(Sc, sel, fr if cols is None else fr[:, cols], cf, fp.sz_list, beta, ct,
+                                                          out=eqs, accumulate=c > 0, workspace=bufs.get("ws"))
+                                bufs["ws"] = eqs["workspace"]
+                            w[1] = eqs
+                            ops.lm_step(state, eqs, fp.sz_list, beta, ct, lam0=damping, accept_only=it == stage_iters,
+                                        smooth=smooth, n_residuals=row, beta_ref=beta_ref, order=stage_order)
+                    for (_, _, ct), (state, _) in zip(colours, work):
+                        idx = ct.long()
+                        if "stages" in stats:
+                            stats["stages"][k]["sse0"][idx], stats["stages"][k]["sse"][idx] = state["sse0"], state["sse"]
+                        if k == 0:
+                            stats["sse0"][idx], stats["accepted"][idx], stats["rejected"][idx] = state["sse0"], 0, 0
+                        stats["sse"][idx], stats["lam"][idx] = state["sse"], state["lam"]
+                        stats["accepted"][idx] += state["counts"][:, 0]
+                        stats["rejected"][idx] += state["counts"][:, 1]
+                        if smooth:
+                            stats["prior"][idx] = state["prior"]
+                        if self.verbose:
+                            print(f"GN frames {int(ct[0])}.. ({stage_order}): sse {float(state['sse0'].sum()):.6g} -> "
+                                  f"{float(state['sse'].sum()):.6g}")
 
         with torch.no_grad():
             staged = None
@@ -1766,7 +1797,7 @@ class DeformableNMF:
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
-            background=0, background_rank=1):
+            background=0, background_rank=1, motion_order=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
@@ -1777,10 +1808,13 @@ class DeformableNMF:
         ``background_loader(...)`` of both loaders, rebuilt after every background update; the first sweep sees the raw frames,
         because a background fitted before the model explains anything would take the neurons' mean light with it.  0: no
         background term, the path of a call without the argument.  ``background_rank=R``, 2 .. 8 (K23): those updates fit R
-        images with R time courses (``update_background_rank``); 1: the rank-1 term."""
+        images with R time courses (``update_background_rank``); 1: the rank-1 term.  ``motion_order`` is the model's
+        ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``)."""
         _check_motion_solver(motion_solver, "fit")
-        kept = self.motion_smooth
+        kept, kept_order = self.motion_smooth, self.motion_order
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
+        motion_order = kept_order if motion_order is None else motion_order
+        _check_motion_order(motion_order, motion_solver, "fit")
         _check_registered(registered, "fit")
         if int(background) != background or background < 0:
             raise ValueError(f"fit: background is a number of alternations >= 0, got {background!r}")
@@ -1790,7 +1824,7 @@ class DeformableNMF:
             self._background_refusals(dataloader, "fit(background=)")
             self._background_refusals(testloader, "fit(background=)")
         out = (None, None, None)
-        self.motion_smooth = motion_smooth
+        self.motion_smooth, self.motion_order = motion_smooth, motion_order
         try:
             train, test = dataloader, testloader
             for sweep in range(outer):
@@ -1815,7 +1849,7 @@ class DeformableNMF:
                         else:
                             train = self.background_loader(dataloader)
         finally:
-            self.motion_smooth = kept
+            self.motion_smooth, self.motion_order = kept, kept_order
         return out
 
 
@@ -1962,6 +1996,33 @@ def _check_motion_smooth(smooth, solver, who):
         raise ValueError(f"{who}: motion_smooth={smooth} is supported by the motion solver 'gn' only (got {solver!r}); "
                          "Adam steps on the reference's loss, which has no temporal term")
     return smooth
+
+
+MOTION_GRADED = ('translation', 'affine', 'quadratic')
+
+
+def _check_motion_order(order, solver, who):
+    """``motion_order`` as ``_update_motion_gn`` takes it: one of ``MOTION_GRADED`` or 'graded', or a tuple of (order,
+    iterations) stages; anything but the default only with the Gauss-Newton solver."""
+    if isinstance(order, str):
+        if order != 'graded' and order not in MOTION_GRADED:
+            raise ValueError(f"{who}: motion_order={order!r}: expected one of {MOTION_GRADED}, 'graded' or a sequence of "
+                             "(order, iterations) stages")
+    else:
+        try:
+            stages = tuple((o, int(n)) for o, n in order)
+            if not stages or any(o not in MOTION_GRADED or n < 0 for o, n in stages) or any(int(n) != n for _, n in order):
+                stages = ()
+        except (TypeError, ValueError):
+            stages = ()
+        if not stages:
+            raise ValueError(f"{who}: motion_order={order!r}: a schedule is a non-empty sequence of (order, iterations) with order "
+                             f"one of {MOTION_GRADED} and iterations an int >= 0")
+        order = stages
+    if order != 'quadratic' and solver != 'gn':
+        raise ValueError(f"{who}: motion_order={order!r} is supported by the motion solver 'gn' only (got {solver!r}); Adam steps "
+                         "on all of beta")
+    return order
 
 
 def _hals_refuse_shards(gamma, group):

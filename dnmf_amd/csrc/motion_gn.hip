@@ -277,26 +277,28 @@ __global__ __launch_bounds__(256) void warp_normal_eqs_finish_kernel(const float
 }
 
 // ---- the Levenberg-Marquardt step ----------------------------------------------------------------------------------
-// active unknowns: all 30, or at Z == 1 the 12 without z: lm_act(nact, i) = parameter index of the i-th
-__device__ __forceinline__ int lm_act(int nact, int i) {
-    if (nact == 30) return i;
+// active unknowns: all 30, or at Z == 1 the 12 without z: lm_act(nfull, i) = parameter index of the i-th.  Both lists go up
+// by the degree of the basis term, so the unknowns of a warp order (K16o) are the first lm_order_count of them.
+__device__ __forceinline__ int lm_act(int nfull, int i) {
+    if (nfull == 30) return i;
     constexpr int AZ[6] = {0, 1, 2, 4, 5, 7};
     return AZ[i >> 1] * 3 + (i & 1);
 }
 
-// The damped solve both step kernels end with, by the one wave of the block (all 64 threads call it, after a barrier that
-// follows the last write of Ha / ga / bacc):  (H' + l diag(H') + tiny I) delta = -g' on the active unknowns, scaled to a unit
-// diagonal, float64 Cholesky, two triangular solves, d beta = M delta, beta[:, :, t] = fp32(bacc + d beta).  H' = Ha, g' = ga;
-// with PRIOR, H' = Ha + hadd I and g' = ga + gadd (gadd: 30 doubles in LDS by parameter index) on the active unknowns.
-// Ha, ga and bacc are the state the calling kernel has just written: plain pointers, nothing here may be read as invariant.
+// The damped solve the step kernels end with, by the one wave of the block (all 64 threads call it, after a barrier that
+// follows the last write of Ha / ga / bacc):  (H' + l diag(H') + tiny I) delta = -g' on the first nact of the nfull (30 or 12)
+// active unknowns, scaled to a unit diagonal, float64 Cholesky, two triangular solves, d beta = M delta, beta[:, :, t] =
+// fp32(bacc + d beta).  H' = Ha, g' = ga; with PRIOR, H' = Ha + hadd I and g' = ga + gadd (gadd: 30 doubles in LDS by parameter
+// index) on those unknowns.  Ha, ga and bacc are the state the calling kernel has just written: plain pointers, nothing here
+// may be read as invariant.
 template <bool PRIOR>
-__device__ void lm_damped_solve(const double *Ha, const double *ga, double l, int nact, const double *__restrict__ M,
+__device__ void lm_damped_solve(const double *Ha, const double *ga, double l, int nact, int nfull, const double *__restrict__ M,
                                 const float *bacc, float *beta, int T, int t, double hadd, const double *gadd) {
     __shared__ double A[30][31];
     __shared__ double rhs[30], sc[30], dl[30];
     __shared__ int okflag;
     const int j = threadIdx.x;
-    auto act = [nact](int i) { return lm_act(nact, i); };
+    auto act = [nfull](int i) { return lm_act(nfull, i); };
     auto diag = [&](int i) {
         if constexpr (PRIOR) return Ha[act(i) * 31] + hadd;
         else return Ha[act(i) * 31];
@@ -400,7 +402,7 @@ __global__ __launch_bounds__(64) void lm_step_kernel(const double *__restrict__ 
         if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
         return;
     }
-    lm_damped_solve<false>(Hacc + (long)b * 900, gacc + b * 30, l, nact, M, beta_acc + b * 30, beta, T, t, 0.0, nullptr);
+    lm_damped_solve<false>(Hacc + (long)b * 900, gacc + b * 30, l, nact, nact, M, beta_acc + b * 30, beta, T, t, 0.0, nullptr);
 }
 
 // K16s: the step with the temporal prior m sum_{s in N_t} |theta_t - theta_s|^2, theta = Minv beta per coordinate on the active
@@ -493,7 +495,116 @@ __global__ __launch_bounds__(64) void lm_step_smooth_kernel(const double *__rest
         if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
         return;
     }
-    lm_damped_solve<true>(Hacc + (long)b * 900, gacc + b * 30, l, nact, M, beta_acc + b * 30, beta, T, t, m * (double)nn, gadd);
+    lm_damped_solve<true>(Hacc + (long)b * 900, gacc + b * 30, l, nact, nact, M, beta_acc + b * 30, beta, T, t, m * (double)nn,
+                          gadd);
+}
+
+// K16o: the step on the unknowns of one warp order -- the rows of the centred basis of degree <= order (0: row 0, 1: rows
+// 0 .. 3, 2: all ten) without the z rows and the z component at Z == 1.  lm_order_count of the nfull active unknowns.
+__device__ __forceinline__ int lm_order_count(int nfull, int order) {
+    const int rows = nfull == 30 ? (order == 0 ? 1 : order == 1 ? 4 : 10) : (order == 0 ? 1 : order == 1 ? 3 : 6);
+    return rows * (nfull == 30 ? 3 : 2);
+}
+
+// lm_step_smooth_kernel over that set: K16's H and g are taken whole and restricted here, so the damped system, its diagonal
+// scaling and tiny, the prior (theta, both sides of the accept test, hadd and gadd) all see the selected unknowns only, and the
+// bookkeeping is the same.  M takes centred terms of a degree to raw rows of that degree or lower, so d beta is an exact zero
+// on the rows above the order; they are put back from beta_acc all the same, which makes "untouched" a matter of bits (-0.0,
+// a NaN's payload) and not of arithmetic.  m == 0: no prior, Minv / beta_ref / prior are not read (they may be NULL) and the
+// solve is lm_step_kernel's instantiation; order == 2 is then lm_step_kernel, and with m != 0 lm_step_smooth_kernel, step for step.
+__global__ __launch_bounds__(64) void lm_step_order_kernel(const double *__restrict__ H, const double *__restrict__ g,
+                                                           const double *__restrict__ sse, int nfull, int order,
+                                                           const double *__restrict__ M, const double *__restrict__ Minv,
+                                                           float *__restrict__ beta, int T, const int *__restrict__ times,
+                                                           double *__restrict__ Hacc, double *__restrict__ gacc,
+                                                           double *__restrict__ sse_acc, double *__restrict__ sse0,
+                                                           double *__restrict__ lam, float *__restrict__ beta_acc,
+                                                           int *__restrict__ counts, double nu, double lam0, double lam_min,
+                                                           double lam_max, int accept_only, float *beta_ref, double m,
+                                                           double *__restrict__ prior) {
+    __shared__ double thn[2][30];       // theta of the neighbours in use
+    __shared__ double sq[2][30];        // squared distances to them: [0] of the trial, [1] of the accepted point
+    __shared__ double gadd[30];
+    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
+    const int a = j / 3, d = j - a * 3;
+    const int nact = lm_order_count(nfull, order);
+    const bool unknown = j < 30 && GN_EX[a] + GN_EY[a] + GN_EZ[a] <= order && (nfull == 30 || (GN_EZ[a] == 0 && d < 2));
+    const bool first = counts[b * 3 + 2] == 0;
+    // theta of a column held with stride ld between its 30 entries; exact zero outside the selected unknowns
+    auto theta = [&](const float *col, long ld) {
+        double v = 0.0;
+        if (unknown)
+            for (int c = 0; c < 10; ++c) v = fma(Minv[a * 10 + c], (double)col[(long)(c * 3 + d) * ld], v);
+        return v;
+    };
+    int nn = 0;                         // block-uniform
+    double th_trial = 0.0, th_old = 0.0, p_trial = 0.0, p_acc = 0.0;
+    if (m != 0.0) {
+        for (int side = -1; side <= 1; side += 2) {
+            const int s = t + side;
+            if (s < 0 || s >= T) continue;
+            const float v = j < 30 ? beta_ref[(long)j * T + s] : 0.0f;
+            if (!__all(v - v == 0.0f)) continue;    // a column with a NaN or an inf is no neighbour
+            if (j < 30) thn[nn][j] = theta(beta_ref + s, T);
+            ++nn;
+        }
+        th_trial = theta(beta + t, T);
+        th_old = first ? 0.0 : theta(beta_acc + b * 30, 1);
+        __syncthreads();
+        if (j < 30) {
+            double qt = 0.0, qa = 0.0;
+            for (int i = 0; i < nn; ++i) {
+                const double dt = th_trial - thn[i][j], da = th_old - thn[i][j];
+                qt += dt * dt, qa += da * da;
+            }
+            sq[0][j] = qt, sq[1][j] = qa;
+        }
+        __syncthreads();
+        if (nn > 0) {                   // every thread adds the 30 terms in the same order: one value in the whole wave
+            for (int i = 0; i < 30; ++i) p_trial += sq[0][i], p_acc += sq[1][i];
+            p_trial *= m, p_acc *= m;
+        }
+    }
+    const double st = sse[b], sa = sse_acc[b];
+    const double ft = st + p_trial, fa = sa + p_acc;
+    const bool accept = first || (ft - ft == 0.0 && ft < fa);   // finite and below
+    double l = first ? lam0 : lam[b];
+    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
+    __syncthreads();   // every thread has read the state before it changes
+    if (accept) {
+        for (int i = j; i < 900; i += 64) Hacc[(long)b * 900 + i] = H[(long)b * 900 + i];
+        if (j < 30) {
+            const float bt = beta[(long)j * T + t];
+            gacc[b * 30 + j] = g[b * 30 + j];
+            beta_acc[b * 30 + j] = bt;
+            if (m != 0.0) beta_ref[(long)j * T + t] = bt;
+        }
+    }
+    if (m != 0.0 && j < 30) {
+        const double th = accept ? th_trial : th_old;
+        double ga = 0.0;
+        for (int i = 0; i < nn; ++i) ga += th - thn[i][j];
+        gadd[j] = m * ga;
+    }
+    if (j == 0) {
+        lam[b] = l;
+        if (m != 0.0) prior[b] = accept ? p_trial : p_acc;
+        if (accept) sse_acc[b] = st;
+        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
+        else counts[b * 3 + (accept ? 0 : 1)] += 1;
+    }
+    __syncthreads();
+    if (accept_only) {
+        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+        return;
+    }
+    if (m != 0.0)
+        lm_damped_solve<true>(Hacc + (long)b * 900, gacc + b * 30, l, nact, nfull, M, beta_acc + b * 30, beta, T, t, m * (double)nn,
+                              gadd);
+    else
+        lm_damped_solve<false>(Hacc + (long)b * 900, gacc + b * 30, l, nact, nfull, M, beta_acc + b * 30, beta, T, t, 0.0, nullptr);
+    // thread j wrote entry j a moment ago: its own store, in program order
+    if (j < 30 && GN_EX[a] + GN_EY[a] + GN_EZ[a] > order) beta[(long)j * T + t] = beta_acc[b * 30 + j];
 }
 
 }  // namespace dnmf
@@ -583,6 +694,28 @@ int dnmf_lm_step_smooth(const double *H, const double *g, const double *sse, int
                        Minv, beta, T, times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max,
                        accept_only, beta_ref, m, prior);
     return check_launch("dnmf_lm_step_smooth");
+}
+
+int dnmf_lm_step_order(const double *H, const double *g, const double *sse, int B, int Z, int order, const double *M,
+                       const double *Minv, float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc,
+                       double *sse0, double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min,
+                       double lam_max, int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(H && g && sse && M && beta && times && H_acc && g_acc && sse_acc && sse0 && lam && beta_acc && counts, DNMF_E_NULL,
+                 "dnmf_lm_step_order: NULL buffer");
+    DNMF_REQUIRE(B > 0 && Z > 0 && T > 0, DNMF_E_SHAPE, "dnmf_lm_step_order: B=%d Z=%d T=%d", B, Z, T);
+    DNMF_REQUIRE(order >= 0 && order <= 2, DNMF_E_SHAPE, "dnmf_lm_step_order: order=%d (0 translation, 1 affine, 2 quadratic)", order);
+    DNMF_REQUIRE(nu > 1.0 && lam0 > 0.0 && lam_min > 0.0 && lam_max >= lam_min, DNMF_E_SHAPE,
+                 "dnmf_lm_step_order: nu=%g lam0=%g lam_min=%g lam_max=%g (want nu > 1, 0 < lam_min <= lam_max, lam0 > 0)", nu,
+                 lam0, lam_min, lam_max);
+    DNMF_REQUIRE(m >= 0.0 && m - m == 0.0, DNMF_E_SHAPE, "dnmf_lm_step_order: m=%g (want a finite weight >= 0)", m);
+    DNMF_REQUIRE(m == 0.0 || (Minv && beta_ref && prior), DNMF_E_NULL, "dnmf_lm_step_order: NULL Minv, beta_ref or prior with m != 0");
+    DNMF_REQUIRE(m == 0.0 || beta_ref != beta, DNMF_E_SHAPE,
+                 "dnmf_lm_step_order: beta_ref must not be beta (it holds accepted points only)");
+    hipLaunchKernelGGL(lm_step_order_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, H, g, sse, Z > 1 ? 30 : 12, order,
+                       M, Minv, beta, T, times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max,
+                       accept_only, beta_ref, m, prior);
+    return check_launch("dnmf_lm_step_order");
 }
 
 }  // extern "C"

@@ -376,7 +376,7 @@ def _centred(sz, dev):
 
 
 def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_max=1e9, accept_only=False, smooth=0.0,
-            n_residuals=None, beta_ref=None):
+            n_residuals=None, beta_ref=None, order="quadratic"):
     """One Levenberg-Marquardt step per frame on the device (``dnmf_lm_step``).  ``eqs``: ``warp_normal_eqs``' result at the
     trial coefficients ``beta[:, :, times]``; ``state``: ``lm_state(B, device)``.  The trial is accepted when its sse is finite
     and below the accepted one (always on a frame's first call), ``beta[:, :, times]`` then receives the next trial -- or, with
@@ -385,7 +385,13 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
     ``smooth`` != 0: the step with the temporal prior (``dnmf_lm_step_smooth``), weight m = ``smooth`` * ``n_residuals`` (default:
     the voxels of ``sz``; pass voxels x colour channels).  ``beta_ref`` (10,3,T) fp32 holds every frame's accepted coefficients:
     read at t +- 1, written at t on accept, never ``beta`` itself.  ``state`` gains ``prior`` (B) float64.  The frames of one call
-    must be pairwise non-adjacent; a ``times`` given as a host sequence is checked, a device tensor is the caller's word."""
+    must be pairwise non-adjacent; a ``times`` given as a host sequence is checked, a device tensor is the caller's word.
+
+    ``order`` (``WARP_ORDERS``): ``'translation'`` or ``'affine'`` step on the rows of the centred basis of that degree only
+    (K16o, ``dnmf_lm_step_order``; with or without the prior) and leave the other rows of ``beta[:, :, times]`` as they are, bit
+    for bit; ``eqs`` is the same.  ``'quadratic'``, the default, is the two entries above."""
+    if order not in WARP_ORDERS:
+        raise ValueError(f"lm_step: order must be one of {sorted(WARP_ORDERS)}, got {order!r}")
     dev = beta.device
     _f32(beta, "beta")
     smooth = float(smooth)
@@ -409,6 +415,19 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
         if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"lm_step: {name} must be a contiguous float64 CUDA tensor")
     M, Minv = _centred(sz, dev)
+    if smooth != 0.0 and ("prior" not in state or state["prior"].shape[0] < B):
+        state["prior"] = torch.zeros((state["counts"].shape[0],), dtype=torch.float64, device=dev)
+    n = int(sz[0]) * int(sz[1]) * int(sz[2]) if n_residuals is None else int(n_residuals)
+    if order != "quadratic":
+        rc = _lib.load().dnmf_lm_step_order(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), WARP_ORDERS[order], M.data_ptr(),
+                                            Minv.data_ptr(), beta.data_ptr(), beta.shape[2], tt.data_ptr(), state["H"].data_ptr(),
+                                            state["g"].data_ptr(), state["sse"].data_ptr(), state["sse0"].data_ptr(),
+                                            state["lam"].data_ptr(), state["beta"].data_ptr(), state["counts"].data_ptr(), float(nu),
+                                            float(lam0), float(lam_min), float(lam_max), 1 if accept_only else 0,
+                                            beta_ref.data_ptr() if smooth else None, smooth * n,
+                                            state["prior"].data_ptr() if smooth else None, _stream())
+        _lib.check(rc, "dnmf_lm_step_order")
+        return state
     if smooth == 0.0:
         rc = _lib.load().dnmf_lm_step(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), beta.data_ptr(),
                                       beta.shape[2], tt.data_ptr(), state["H"].data_ptr(), state["g"].data_ptr(),
@@ -417,9 +436,6 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
                                       float(lam_max), 1 if accept_only else 0, _stream())
         _lib.check(rc, "dnmf_lm_step")
         return state
-    if "prior" not in state or state["prior"].shape[0] < B:
-        state["prior"] = torch.zeros((state["counts"].shape[0],), dtype=torch.float64, device=dev)
-    n = int(sz[0]) * int(sz[1]) * int(sz[2]) if n_residuals is None else int(n_residuals)
     rc = _lib.load().dnmf_lm_step_smooth(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), M.data_ptr(), Minv.data_ptr(),
                                          beta.data_ptr(), beta.shape[2], tt.data_ptr(), state["H"].data_ptr(),
                                          state["g"].data_ptr(), state["sse"].data_ptr(), state["sse0"].data_ptr(),

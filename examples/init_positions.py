@@ -6,7 +6,7 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 MI355X.
 
     python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track]
-                                      [--gn [--motion-smooth S]]
+                                      [--gn [--motion-smooth S] [--motion-order ORDER]]
                                       [--detect-image {template,corr,max,std}]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
@@ -25,7 +25,9 @@ printed for both sets of tracks.
 ``--gn``: every fit is repeated with the Gauss-Newton motion solver (``fit(..., motion_solver='gn')``: K16 + Levenberg-Marquardt
 steps per frame, ``--gn-iters`` of them, no learning rate) and its three numbers are printed beside Adam's.  ``--motion-smooth S``
 gives that fit the temporal prior (``fit(..., motion_smooth=S)``, K16s: S in mean squared error per squared voxel of
-frame-to-frame change of a warp coefficient); the numbers with it are unmeasured.
+frame-to-frame change of a warp coefficient); the numbers with it are unmeasured.  ``--motion-order ORDER`` fits only the
+coefficients of that order -- ``translation``, ``affine``, ``quadratic`` (the default: all) -- or, with ``graded``, the three in
+turn with ``--gn-iters`` iterations each (``fit(..., motion_order=ORDER)``, K16o); the numbers with it are unmeasured too.
 """
 import argparse
 import os
@@ -56,12 +58,16 @@ def main():
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
     ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
     ap.add_argument("--motion-smooth", type=float, default=0.0, help="--gn: weight of the temporal smoothness prior (0: none)")
+    ap.add_argument("--motion-order", choices=("translation", "affine", "quadratic", "graded"), default="quadratic",
+                    help="--gn: the coefficients the fit moves; graded: translation, then affine, then all")
     ap.add_argument("--gsig", type=float, default=None, help="register on high-pass-filtered frames: gSig_filt=(S, S) (K22)")
     ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
     a = ap.parse_args()
     a.detect = a.detect or a.detect_image is not None
     if a.motion_smooth and not a.gn:
         ap.error("--motion-smooth needs --gn (the Adam fit has no temporal term)")
+    if a.motion_order != "quadratic" and not a.gn:
+        ap.error("--motion-order needs --gn (the Adam fit steps on all of beta)")
     image = a.detect_image or "template"
     torch.manual_seed(0)
     np.random.seed(0)
@@ -122,7 +128,7 @@ def main():
             loader = dataset.loader(a.batch)
             if solver == "gn":
                 dn.fit(loader, loader, None, a.batch, outer=1, epochs=a.gn_iters, gamma_c=0, iter_c=30, motion_solver='gn',
-                       motion_smooth=a.motion_smooth)
+                       motion_smooth=a.motion_smooth, motion_order=a.motion_order)
             else:
                 dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
             where = dn.positions()
@@ -132,7 +138,8 @@ def main():
             roi = get_roi_signals(dataset.video, torch.from_numpy(inside), np.array([3, 3, 0]))
             label = start
             if solver == "gn":
-                label += f" (gn, {a.gn_iters} iterations" + (f", smooth {a.motion_smooth:g})" if a.motion_smooth else ")")
+                label += (f" (gn, {a.gn_iters} iterations" + (f", smooth {a.motion_smooth:g}" if a.motion_smooth else "")
+                          + (f", order {a.motion_order})" if a.motion_order != "quadratic" else ")"))
             print(f"{label} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
                   f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "
                   f"dnmf.positions() {median_corr(np.nan_to_num(roi)):.3f}")

@@ -646,6 +646,26 @@ int dnmf_lm_step_smooth(const double *H, const double *g, const double *sse, int
                         double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min, double lam_max,
                         int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream);
 
+/* K16o: the step for one warp order (csrc/motion_gn.hip, lm_step_order_kernel).  dnmf_lm_step's arguments, order after Z, and
+ * dnmf_lm_step_smooth's Minv, beta_ref, m and prior.  The unknowns are the rows of the centred basis of degree <= order:
+ *   order 0 (translation): row 0;  1 (affine): rows 0 .. 3;  2 (quadratic): all ten
+ * -- 3, 12 or 30 unknowns; at Z == 1, where the z rows and the z component stay out, 2, 6 or 12.  H, g and sse are K16's, whole:
+ * the restriction happens here, so one set of normal equations serves every order.  Over the selected unknowns everything is
+ * as the two steps above have it over all of them: the damped system (its diagonal scaling and tiny from the restricted
+ * block's own diagonal), accept / reject, the damping bounds, accept_only, a pivot that is not positive and finite, H == 0, a
+ * NaN frame; and with m != 0 the prior, theta = Minv beta taken on the selected unknowns only in the accept test, in prior (B)
+ * and in H' and g'.  M takes a centred term to raw rows of its degree or lower, so the rows of beta[:, :, times[b]] above the
+ * order (1 .. 9 under order 0, 4 .. 9 under order 1) keep their bits.
+ * m == 0: no prior; Minv, beta_ref and prior are not read and may be NULL, the frames need not be non-adjacent.  m != 0:
+ * dnmf_lm_step_smooth's CONTRACT holds.  order == 2 takes dnmf_lm_step's steps (m == 0) or dnmf_lm_step_smooth's (m != 0), bit for
+ * bit; those two stay the entries of the default path.  tests/gn_order_restatement.py is the definition.
+ * DNMF_E_NULL: a NULL buffer (Minv, beta_ref, prior: only with m != 0);  DNMF_E_SHAPE: as dnmf_lm_step_smooth, or order outside
+ * 0 .. 2. */
+int dnmf_lm_step_order(const double *H, const double *g, const double *sse, int B, int Z, int order, const double *M,
+                       const double *Minv, float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc,
+                       double *sse0, double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min,
+                       double lam_max, int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream);
+
 /* ---- K17: the trilinear registered movie under the fitted warp ----------------------------------------------------------------
  * For every frame j < B (column t = times[j] of beta, or j when times is NULL; row frame_ids[j] of frames, or j) and every lattice
  * point u = (i, j, k) of the footprint volume: the x with q_t(x) = u, and the frame sampled trilinearly at x.  Conventions as K11 /

@@ -9,8 +9,11 @@ off the identity (bench.py's ``displaced_beta``):
 
   --smooth S an LM iteration with the temporal prior (``model.motion_smooth = S``, ``update_motion(solver='gn')``: the same
              work in twice the launches, ``dnmf_lm_step_smooth``) beside the one without, in the ``iteration`` line
+  --order O  ``steps``: the step alone on K16's output -- ``dnmf_lm_step`` beside ``dnmf_lm_step_order`` at ``translation``,
+             ``affine`` and ``quadratic`` (3 / 12 / 30 unknowns; 2 / 6 / 12 at Z = 1) -- and, for O other than ``quadratic``, an LM
+             iteration with ``model.motion_order = O`` in the ``iteration`` line (``graded``: a round of its three stages)
 
-    python tools/time_motion_gn.py [--frames 4000] [--neurons 100] [--smooth 1e-4]
+    python tools/time_motion_gn.py [--frames 4000] [--neurons 100] [--smooth 1e-4] [--order graded]
 
 Every measurement is a process of its own under a time limit; the first one that fails ends the script.  One JSON line each.
 """
@@ -77,7 +80,40 @@ def step_kernels(Z, K, T):
     return {"step": "kernels", "Z": Z, "K": K, "T": T, "k2_ms": t2, "k16_ms": t16, "ratio": t16 / t2}
 
 
-def step_iteration(Z, K, T, smooth=0.0):
+def step_steps(Z, K, T):
+    """The step alone, B = T frames: one K16 evaluation, then each entry on a fresh state (the first call: accept + solve)."""
+    import torch
+    from dnmf_amd import _lib, ops
+    _, model, sz, frames = setup(Z, K, T)
+    S = model._recon_cache()[0]
+    times = torch.arange(T, dtype=torch.int32, device="cuda")
+    beta = model.fp.beta.detach()
+    start = beta.clone()
+    eqs = ops.warp_normal_eqs(S, times, frames, None, sz, beta, times)
+    state = ops.lm_state(T, "cuda")
+    M, Minv = ops._centred(sz, beta.device)
+    lib = _lib.load()
+
+    def run(order):
+        state["counts"].zero_()
+        beta.copy_(start)
+        if order is None:
+            ops.lm_step(state, eqs, sz, beta, times)
+            return
+        rc = lib.dnmf_lm_step_order(eqs["H"].data_ptr(), eqs["g"].data_ptr(), eqs["sse"].data_ptr(), T, Z, order, M.data_ptr(),
+                                    Minv.data_ptr(), beta.data_ptr(), T, times.data_ptr(), state["H"].data_ptr(),
+                                    state["g"].data_ptr(), state["sse"].data_ptr(), state["sse0"].data_ptr(), state["lam"].data_ptr(),
+                                    state["beta"].data_ptr(), state["counts"].data_ptr(), 10.0, 1e-3, 1e-9, 1e9, 0, None, 0.0, None,
+                                    ops._stream())
+        _lib.check(rc, "dnmf_lm_step_order")
+
+    out = {"step": "steps", "Z": Z, "K": K, "T": T, "lm_step_ms": median_ms(lambda: run(None))}
+    for name, order in ops.WARP_ORDERS.items():
+        out[f"lm_step_order_{name}_ms"] = median_ms(lambda: run(order))
+    return out
+
+
+def step_iteration(Z, K, T, smooth=0.0, order="quadratic"):
     import torch
     dNMF, model, sz, frames = setup(Z, K, T)
     loader = dNMF.ResidentLoader(frames, sz, 100)
@@ -110,6 +146,12 @@ def step_iteration(Z, K, T, smooth=0.0):
         s5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
         model.motion_smooth = 0.0
         out.update(smooth=smooth, gn_smooth_iters1_ms=s1, gn_smooth_iters5_ms=s5, lm_smooth_iteration_ms=(s5 - s1) / 4)
+    if order != "quadratic":
+        model.motion_order = order
+        o1 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=1))
+        o5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
+        model.motion_order = "quadratic"
+        out.update(order=order, gn_order_iters1_ms=o1, gn_order_iters5_ms=o5, lm_order_iteration_ms=(o5 - o1) / 4)
     return out
 
 
@@ -117,19 +159,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4000)
     ap.add_argument("--neurons", type=int, default=100)
-    ap.add_argument("--step", choices=["kernels", "iteration"])
+    ap.add_argument("--step", choices=["kernels", "iteration", "steps"])
     ap.add_argument("--z", type=int, default=1)
     ap.add_argument("--smooth", type=float, default=0.0, help="also time an LM iteration with this temporal prior weight")
+    ap.add_argument("--order", choices=["translation", "affine", "quadratic", "graded"], default=None,
+                    help="also time the step per warp order, and an LM iteration with this motion_order")
     ap.add_argument("--limit", type=int, default=240, help="seconds a measurement may take")
     a = ap.parse_args()
     if a.step:
-        out = step_kernels(a.z, a.neurons, a.frames) if a.step == "kernels" else step_iteration(a.z, a.neurons, a.frames, a.smooth)
+        out = step_kernels(a.z, a.neurons, a.frames) if a.step == "kernels" else step_steps(a.z, a.neurons, a.frames) \
+            if a.step == "steps" else step_iteration(a.z, a.neurons, a.frames, a.smooth, a.order or "quadratic")
         print(json.dumps(out), flush=True)
         return 0
     for z in (1, 2):
-        for step in ("kernels", "iteration"):
+        for step in ("kernels", "iteration") + (("steps",) if a.order else ()):
             cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--step", step, "--z", str(z),
                    "--frames", str(a.frames), "--neurons", str(a.neurons), "--smooth", str(a.smooth)]
+            if a.order:
+                cmd += ["--order", a.order]
             rc = subprocess.run(cmd, cwd=ROOT).returncode
             if rc != 0:
                 print(f"time_motion_gn: {step} at Z={z} ended with status {rc}; stopping", flush=True)
