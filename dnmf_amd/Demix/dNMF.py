@@ -611,6 +611,8 @@ class DeformableNMF:
         self.last_match = None
         # after evaluate_components: r_values, snr, frame_corr, raw, images, boxes, n_active and keep of that call
         self.last_evaluation = None
+        # after merge_components: pairs, overlap, corr, groups, merged and K of that call
+        self.last_merge = None
         self._warned = set()
 
     @classmethod
@@ -977,6 +979,99 @@ class DeformableNMF:
         for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
             setattr(self, name, None)
         return fp.K
+
+    def merge_components(self, thr=0.85, min_overlap=0.1, floor=1e-3, margin=0, traces=None, iters=10, dry_run=False):
+        """Merge the components that sit on one cell (K26; tests/merge_restatement.py is the definition).  The proposal step
+        often yields two centres a voxel or two apart for one cell; both halves pass ``evaluate_components``, and their traces
+        steal from each other.  Two components are joined when their boxes (``ops.component_boxes(fp.A, sz, floor, margin)``;
+        margin 0: boxes that only touch through a margin are no candidates) intersect, the cosine of their footprints on the
+        boxes' intersection is at least ``min_overlap`` and the Pearson correlation of their traces -- of ``traces`` (K, T)
+        when given, e.g. what ``clean_traces`` or ``deconvolve`` returned, over the frames where both are finite; else of
+        ``self.C`` -- is at least ``thr``; groups are the connected components of these edges.  A group becomes one
+        component a' = sum u_k a_k, c' = sum w_k c_k, the rank-1 non-negative factor of sum_k a_k c_k^T (``ops.merge_plan``:
+        ``iters`` alternating rounds in coefficient space, scaled to the norm of the dominant member); the merge always combines
+        ``self.C``, whose merged rows must be finite and >= 0 (ValueError).  Its ``pos`` is the members' mean weighted by
+        sqrt(|a_k|^2 |c_k|^2), its ``sigma`` and its row of ``self.A`` the dominant member's, its ``D`` the constructor's
+        formula at the new ``pos``.
+        The model shrinks in place as in ``select_components``: ``fp.A``, ``fp.pos``, ``fp.sigma``, ``fp.K``, ``C``, ``A``, ``D``
+        and ``K`` are replaced, ``fp.beta`` stays, every packed layout, K-shaped cache and ``last_*`` result is forgotten.
+        Returns, and stores in ``self.last_merge``, a dict: ``pairs`` (N, 2), ``overlap`` and ``corr`` (N,) CUDA tensors of the
+        candidate pairs, ``groups`` a list of lists of old indices (ascending, ordered by their lowest member), ``merged`` the
+        number of groups of two or more, ``K`` the new component count.  ``dry_run=True`` computes the dict and leaves the
+        model bit for bit (``last_merge`` apart); so does a call in which nothing merges.
+        ``thr`` and ``min_overlap`` are parameters, not tolerances: their defaults sit in the gap that a planted model of six
+        cells leaves (tests/test_merge_host.py measures it, 24 x 20 x {1, 2}, T = 40, three seeds): the two halves of a split
+        cell correlate at 0.981 or more and overlap at 0.946, distinct cells 1.5 sigma apart (overlap 0.34) with independent
+        traces correlate at 0.75 or less, and cells that share a trace 8.6 voxels apart overlap at 0.016.
+        The pair statistics run on the GPU; the groups and the coefficients are found on the host (a synchronisation: K is
+        small).  One channel and one process only."""
+        who = "merge_components"
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        if self.group is not None:
+            raise NotImplementedError(f"{who}: the model holds a shard of the frames (the trace sums would need an all-reduce)")
+        fp = self.fp
+        sz, P, K = fp.sz_list, fp.P, fp.K
+        with torch.no_grad():
+            C = self.C.detach().to(device, torch.float32).contiguous()
+            Ct = C
+            if traces is not None:
+                Ct = torch.as_tensor(traces).detach().to(device, torch.float32).contiguous()
+                if tuple(Ct.shape) != tuple(C.shape):
+                    raise ValueError(f"{who}: traces must be {tuple(C.shape)}, got {tuple(Ct.shape)}")
+            A_rows = fp._layout("rows", (), lambda: fp.A.reshape(P, K).t().contiguous())
+            boxes = ops.component_boxes(fp.A, sz, floor=floor, margin=margin)
+            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
+            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
+                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
+                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            stats = ops.component_pairs(A_rows, sz, boxes, Ct)
+            groups = ops.merge_groups(stats, K, thr, min_overlap)
+            merged = sum(len(g) >= 2 for g in groups)
+            result = dict(pairs=stats["pairs"], overlap=stats["overlap"], corr=stats["corr"], groups=groups, merged=merged,
+                          K=len(groups))
+            if dry_run or merged == 0:
+                self.last_merge = result
+                return result
+            rows = torch.tensor(sorted(k for g in groups if len(g) >= 2 for k in g), device=device)
+            Cm = C.index_select(0, rows)
+            if not bool((torch.isfinite(Cm) & (Cm >= 0)).all()):
+                raise ValueError(f"{who}: the traces of the components to merge ({rows.tolist()}) have negative or non-finite "
+                                 "entries: the rank-1 factor is defined for C >= 0")
+            gstats = ops.component_pairs(A_rows, sz, boxes, C, pairs=ops.merge_group_pairs(groups))
+            plan = ops.merge_plan(stats, K, thr, min_overlap, iters=iters, group_stats=gstats)
+            A_new, C_new = ops.merge_apply(fp.A.reshape(P, K), C, plan)
+            # what has one value per member: the weighted mean of pos, the dominant member's sigma and row of self.A
+            seg = torch.repeat_interleave(torch.arange(len(groups)), torch.as_tensor(np.diff(plan["offsets"]).astype(np.int64)))
+            wt = torch.from_numpy(plan["weight"])
+            members = torch.from_numpy(plan["members"].astype(np.int64))
+            pos_old = fp.pos.detach()
+            num = torch.zeros((len(groups), 3), dtype=torch.float64).index_add_(0, seg, wt[:, None] * pos_old.cpu().double()[members])
+            pos_new = num / torch.zeros(len(groups), dtype=torch.float64).index_add_(0, seg, wt)[:, None]
+            dom = torch.from_numpy(plan["dominant"])
+            single = torch.tensor([len(g) == 1 for g in groups])
+            pos_new = pos_new.to(pos_old.dtype)
+            pos_new[single] = pos_old.cpu()[dom[single]]              # an unmerged component keeps its bits
+            fp.A = A_new.reshape(*sz, len(groups))
+            fp.pos = pos_new.to(pos_old.device)
+            fp.sigma = fp.sigma.index_select(0, dom.to(fp.sigma.device))
+            self.C = C_new
+            self.A = self.A.index_select(0, dom.to(self.A.device))
+        if self.D is not None:
+            D = np.ascontiguousarray(self.D[..., plan["dominant"]])
+            lat = fp.flow_id.reshape(-1, 3).double()
+            for q in torch.nonzero(~single).reshape(-1).tolist():
+                d = torch.cdist(lat, fp.pos[q:q + 1].to(device).double())
+                D[..., q] = (1 - torch.exp(-.01 * d)).reshape(*sz).cpu().numpy()
+            self.D = D
+        fp.K = len(groups)
+        if hasattr(self, "K"):
+            self.K = fp.K
+        fp.invalidate_layouts()
+        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
+            setattr(self, name, None)
+        self.last_merge = result
+        return result
 
     def _background_refusals(self, loader, who):
         if self._nchan() != 1:

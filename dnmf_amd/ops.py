@@ -2002,6 +2002,201 @@ def component_stats(frames, sz, A_rows, boxes, C, w, sub=None, frame_ids=None, s
     return dict(sums=sums, foot=foot, frame_corr=frame_corr, raw=raw, image=image, r_values=r_values), state
 
 
+# ---- K26: merging duplicate components ---------------------------------------------------------------------------------------------
+MERGE_MAX_K = 4096                                                   # component_pairs forms (K, K) masks of the boxes
+PAIR_SUMS = ("saa", "n", "si", "sj", "sii", "sjj", "sij", "scc")     # the columns dnmf_component_pairs writes
+
+
+def candidate_pairs(boxes):
+    """(N, 2) int32 on the boxes' device: every (k, k) and every i < j whose inclusive boxes intersect, i ascending, then j."""
+    b = torch.as_tensor(boxes).long()
+    lo, hi = b[:, 0::2], b[:, 1::2]
+    meet = ((lo[:, None, :] <= hi[None, :, :]) & (lo[None, :, :] <= hi[:, None, :])).all(2)
+    return torch.nonzero(torch.triu(meet)).to(torch.int32).contiguous()      # nonzero's result may be column-major
+
+
+def component_pairs(A_rows, sz, boxes, C, pairs=None):
+    """K26.  The statistics of pairs of components, tests/merge_restatement.py (``pair_stats``) on the GPU.  ``A_rows`` (K, >= P)
+    fp32 CUDA, the footprints as rows; ``boxes`` (K, 6) int32 inclusive boxes of at most 4096 voxels (``component_boxes``); ``C``
+    (K, T) fp32 CUDA rows with unit inner stride, NaN allowed; ``pairs`` (N, 2) indices, i == j allowed -- None: every (k, k) and
+    every i < j whose boxes intersect (``candidate_pairs``).  Returns a dict of CUDA tensors, float64 (N,) but ``pairs`` (N, 2)
+    int32: ``saa`` = sum a_i a_j over the intersection of the boxes (0 where it is empty); over the frames where both traces are
+    finite ``n``, their number, ``si``, ``sj``, ``sii``, ``sjj``, ``sij``, the sums of d_i, d_j, d_i^2, d_j^2 and d_i d_j with d = c
+    - c[first such frame], and ``scc`` = sum c_i c_j; from them ``overlap`` = saa_ij / sqrt(saa_ii saa_jj) -- 0 where a norm is 0,
+    NaN where (i, i) or (j, j) is not among the pairs -- and ``corr``, Pearson's from the shifted sums, NaN where n < 2 or a
+    variance is not positive.  K <= 4096.  The boxes and the pairs are checked on the host before the launch: one synchronisation
+    where they come from the GPU.  float64 sums in a fixed order, no atomics: the same input gives the same bits."""
+    fn = "component_pairs"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if A_rows.dim() != 2:
+        raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
+    _rows(A_rows, fn, "A_rows", P, f" and rows of {P} floats")
+    K = A_rows.shape[0]
+    if K > MERGE_MAX_K:
+        raise ValueError(f"{fn}: K={K} components, at most {MERGE_MAX_K}")
+    dev = A_rows.device
+    _rows(C, fn, "C")
+    if C.dim() != 2 or C.shape[0] != K or C.device != dev:
+        raise ValueError(f"{fn}: C must be ({K}, T) on {dev}, got {tuple(C.shape)} on {C.device}")
+    T = C.shape[1]
+    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
+    if tuple(bh.shape) != (K, 6):
+        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
+    ph = candidate_pairs(bh) if pairs is None else torch.as_tensor(pairs).detach()
+    ph = ph.to("cpu", torch.int32).reshape(-1, 2).contiguous()
+    bd, pd = bh.to(dev), ph.to(dev)
+    N = ph.shape[0]
+    out = torch.empty((N, len(PAIR_SUMS)), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    with _timed("component_pairs"):
+        rc = lib.dnmf_component_pairs(A_rows.data_ptr(), _ld(A_rows, P), _int3((X, Y, Z)), bh.data_ptr(), bd.data_ptr(), K,
+                                      C.data_ptr(), _ld(C, T), T, ph.data_ptr(), pd.data_ptr(), N, out.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_component_pairs")
+    st = {name: out[:, q] for q, name in enumerate(PAIR_SUMS)}
+    pl = pd.long()
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    diag = nan.repeat(K)
+    on = pl[:, 0] == pl[:, 1]
+    diag[pl[on, 0]] = st["saa"][on]
+    den = diag[pl[:, 0]] * diag[pl[:, 1]]
+    st["overlap"] = torch.where(den > 0, st["saa"] / torch.sqrt(den), torch.where(den == 0, torch.zeros_like(den), nan))
+    n = st["n"]
+    va, vb = n * st["sii"] - st["si"] * st["si"], n * st["sjj"] - st["sj"] * st["sj"]
+    ok = (n >= 2) & (va > 0) & (vb > 0)
+    st["corr"] = torch.where(ok, (n * st["sij"] - st["si"] * st["sj"]) / torch.sqrt(torch.where(ok, va * vb, torch.ones_like(va))), nan)
+    st["pairs"] = pd
+    return st
+
+
+def _host64(stats):
+    import numpy as np
+    return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in stats.items()}
+
+
+def merge_groups(stats, K, thr, min_overlap):
+    """The groups of tests/merge_restatement.py (``groups_of``): the connected components of the edges ``corr >= thr and overlap
+    >= min_overlap`` (NaN fails) among the pairs of ``stats`` (``component_pairs``), as a list of lists of indices -- members
+    ascending, groups by their lowest member, so singletons keep their order.  On the host: a synchronisation."""
+    s = _host64(stats)
+    parent = list(range(int(K)))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    for (i, j), c, o in zip(s["pairs"].tolist(), s["corr"].tolist(), s["overlap"].tolist()):
+        if i != j and c >= thr and o >= min_overlap:
+            a, b = find(i), find(j)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    members = {}
+    for k in range(int(K)):
+        members.setdefault(find(k), []).append(k)
+    return [members[r] for r in sorted(members)]
+
+
+def merge_group_pairs(groups):
+    """(N, 2) int32 CPU: every i <= j of every group of two members or more -- the pairs whose ``saa`` and ``scc`` are the S and
+    Q of ``merge_plan``, whether or not the boxes intersect."""
+    out = [(g[a], g[b]) for g in groups if len(g) >= 2 for a in range(len(g)) for b in range(a, len(g))]
+    return torch.tensor(out, dtype=torch.int32).reshape(-1, 2)
+
+
+def merge_plan(stats, K, thr, min_overlap, iters=10, group_stats=None):
+    """Which components merge, and with which coefficients (tests/merge_restatement.py: ``plan``).  Float64 numpy on the host, a
+    documented synchronisation: K is small, as in ``select_components``.  ``stats``: what ``component_pairs`` returned (the
+    edges); ``group_stats``: a ``component_pairs`` result that lists every ``merge_group_pairs(groups)`` pair -- its ``saa`` and
+    ``scc`` are the S and Q of the groups (None: ``stats`` itself, a ValueError where a pair is missing).  A group of m >= 2
+    members becomes a' = sum u_k a_k, c' = sum w_k c_k, the rank-1 factor of sum_k a_k c_k^T in coefficient space: from u_k =
+    sqrt(Q_kk), ``iters`` rounds of w = S u / (u^T S u), u = Q w / (w^T Q w); then u is scaled so that u^T S u = S_dd of the
+    dominant member d (the largest sqrt(S_kk Q_kk)) and w inversely.  Returns a dict: ``groups`` (list of lists), ``offsets``
+    (K' + 1) and ``members`` int32 (the CSR table of ``merge_apply``), ``u``, ``w`` and ``weight`` = sqrt(S_kk Q_kk) float64, one
+    per member (1 for a singleton), ``dominant`` (K') int64 old indices, ``merged`` the number of groups with m >= 2."""
+    import numpy as np
+    groups = merge_groups(stats, K, thr, min_overlap)
+    gs = _host64(stats if group_stats is None else group_stats)
+    at = {(int(i), int(j)): p for p, (i, j) in enumerate(gs["pairs"].tolist())}
+
+    def block(g, name):
+        B = np.zeros((len(g), len(g)))
+        for a in range(len(g)):
+            for b in range(a, len(g)):
+                p = at.get((g[a], g[b]), at.get((g[b], g[a])))
+                if p is None:
+                    raise ValueError(f"merge_plan: the pair ({g[a]}, {g[b]}) of the group {g} is not among the statistics "
+                                     "(group_stats = component_pairs(..., pairs=merge_group_pairs(groups)))")
+                B[a, b] = B[b, a] = gs[name][p]
+        return B
+
+    u_all, w_all, weight_all, dominant = [], [], [], []
+    for g in groups:
+        if len(g) == 1:
+            u_all.append(np.ones(1)), w_all.append(np.ones(1)), weight_all.append(np.ones(1)), dominant.append(g[0])
+            continue
+        S, Q = block(g, "saa"), block(g, "scc")
+        u = np.sqrt(np.diag(Q))
+        w = np.zeros_like(u)
+        for _ in range(int(iters)):
+            w = S @ u / (u @ S @ u)
+            u = Q @ w / (w @ Q @ w)
+        weight = np.sqrt(np.diag(S) * np.diag(Q))
+        d = int(np.argmax(weight))
+        scale = np.sqrt(S[d, d] / (u @ S @ u))
+        u, w = u * scale, w / scale
+        if not (np.isfinite(u).all() and np.isfinite(w).all()):
+            raise ValueError(f"merge_plan: the group {g} has no finite rank-1 factor (a footprint or a trace that is zero?)")
+        u_all.append(u), w_all.append(w), weight_all.append(weight), dominant.append(g[d])
+    sizes = [len(g) for g in groups]
+    return dict(groups=groups, offsets=np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32),
+                members=np.asarray([k for g in groups for k in g], dtype=np.int32), u=np.concatenate(u_all), w=np.concatenate(w_all),
+                weight=np.concatenate(weight_all), dominant=np.asarray(dominant, dtype=np.int64), merged=sum(m >= 2 for m in sizes))
+
+
+def merge_apply(A, C, plan, A_out=None, C_out=None):
+    """K26.  The merged model of ``plan`` (``merge_plan``) in one launch: ``A`` (P, >= K) fp32 CUDA rows, the model's footprints
+    with K fastest (``fp.A.reshape(P, K)``), ``C`` (K, >= T) fp32 CUDA rows -> ``(A_out (P, K'), C_out (K', T))`` fp32, A_out[v, g]
+    = sum_k u_k A[v, k] and C_out[g, t] = sum_k w_k C[k, t] over the members of group g in their order, in float64, rounded once;
+    a singleton with u = w = 1 comes out bit for bit.  ``A_out`` / ``C_out``: rows to write into (any row stride; floats past a
+    row's extent are left alone), which may not overlap the inputs."""
+    import numpy as np
+    fn = "merge_apply"
+    for name, t in (("A", A), ("C", C)):
+        _rows(t, fn, name)
+        if t.dim() != 2:
+            raise ValueError(f"{fn}: {name} are rows, got {tuple(t.shape)}")
+    P, K = A.shape
+    T = C.shape[1]
+    dev = A.device
+    if C.shape[0] != K or C.device != dev:
+        raise ValueError(f"{fn}: C must be ({K}, T) on {dev}, got {tuple(C.shape)} on {C.device}")
+    off = torch.from_numpy(np.ascontiguousarray(plan["offsets"], dtype=np.int32))
+    mem = torch.from_numpy(np.ascontiguousarray(plan["members"], dtype=np.int32))
+    Kout = off.numel() - 1
+    u = torch.from_numpy(np.ascontiguousarray(plan["u"], dtype=np.float64)).to(dev)
+    w = torch.from_numpy(np.ascontiguousarray(plan["w"], dtype=np.float64)).to(dev)
+    if Kout < 1 or mem.numel() != int(off[-1]) or u.numel() != mem.numel() or w.numel() != mem.numel():
+        raise ValueError(f"{fn}: the plan's offsets, members, u and w do not belong together")
+    if A_out is None:
+        A_out = torch.empty((P, Kout), dtype=torch.float32, device=dev)
+    if C_out is None:
+        C_out = torch.empty((Kout, T), dtype=torch.float32, device=dev)
+    for name, t, shape in (("A_out", A_out, (P, Kout)), ("C_out", C_out, (Kout, T))):
+        _rows(t, fn, name)
+        if tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"{fn}: {name} must be {shape} on {dev}, got {tuple(t.shape)} on {t.device}")
+    od, md = off.to(dev), mem.to(dev)
+    lib = _lib.load()
+    with _timed("merge_apply"):
+        rc = lib.dnmf_merge_apply(A.data_ptr(), _ld(A, K), P, K, C.data_ptr(), _ld(C, T), T, off.data_ptr(), mem.data_ptr(),
+                                  od.data_ptr(), md.data_ptr(), Kout, u.data_ptr(), w.data_ptr(), A_out.data_ptr(), _ld(A_out, Kout),
+                                  C_out.data_ptr(), _ld(C_out, T), _stream())
+    _lib.check(rc, "dnmf_merge_apply")
+    return A_out, C_out
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -4,6 +4,7 @@ plots, against this repository's drop-in ``Demix.dNMF``.  Prints how well the re
 truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
+                                        [--evaluate] [--merge]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -11,6 +12,8 @@ print the median correlation of the simulator's traces with ``C`` and with the c
 correlation of the simulator's traces with ``C`` and with ``b + c``, and the median estimated decay beside the simulator's e^-0.3.
 ``--match``: also put the traces in the simulator's units (``DeformableNMF.match_traces``, K25) and print the median over neurons
 of the RMS difference between the simulator's traces and ``C`` before and after, beside the correlation, which the map leaves alone.
+``--merge``: last of all, merge the components that sit on one cell (``DeformableNMF.merge_components``, K26) and print the groups
+and K before and after.
 """
 import argparse
 import os
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--deconvolve", action="store_true")
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
+    ap.add_argument("--merge", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -95,6 +99,14 @@ def main():
         print("component evaluation over %d active frames each: r_values %s" % (ev["n_active"], ev["r_values"].cpu().numpy()))
         print("snr %s" % ev["snr"].cpu().numpy())
         print("keep %s  (%d of %d)" % (ev["keep"].int().cpu().numpy(), int(ev["keep"].sum()), K))
+    if a.merge:
+        out = dnmf.merge_components()
+        off = out["pairs"][:, 0] != out["pairs"][:, 1]
+        print("merge: %d candidate pairs, largest trace correlation %.3f, largest footprint overlap %.3f"
+              % (int(off.sum()), float(out["corr"][off].nan_to_num(-1.0).max()) if bool(off.any()) else float("nan"),
+                 float(out["overlap"][off].max()) if bool(off.any()) else float("nan")))
+        print("groups %s" % out["groups"])
+        print("K %d -> %d  (%d merged groups)" % (K, out["K"], out["merged"]))
     return corr
 
 

@@ -949,6 +949,46 @@ int dnmf_component_stats(const float *frames, long ldf, const float *sub, long l
 int dnmf_histogram_match(const float *a, long lda, int Ta, const float *b, long ldb, int Tb, int K, int nbins, int nonneg, float *out,
                          long ldo, double *beta, double *distance, int *info, double *qa, double *qb, dnmf_stream_t stream);
 
+/* ---- K26: merging duplicate components: the statistics of pairs of components, and the merged model (csrc/merge_components.hip) ------
+ * tests/merge_restatement.py is the definition in float64.  Two components that sit on one cell overlap in space and are correlated
+ * in time; dnmf_component_pairs measures both for N listed pairs, the host decides the groups and their coefficients (ops.merge_plan:
+ * K is small), and dnmf_merge_apply writes the merged model.
+ *
+ * dnmf_component_pairs.  A = K rows of lda >= P floats, the footprints as rows (voxel p = (x Y + y) Z + z), boxes (K, 6) int32 =
+ * (x0, x1, y0, y1, z0, z1) inclusive, as in K24; C = K rows of ldc >= T floats, the traces, NaN or inf allowed; pairs (N, 2) int32,
+ * (i, j) in any order, i == j allowed.  Per pair, out[p] = 8 doubles:
+ *   saa                     sum a_i a_j over the intersection of the two boxes, 0 where it is empty ((k, k): sum a_k^2 on the box);
+ *   n                       the frames where both traces are finite; t0 the first of them;
+ *   si, sj, sii, sjj, sij   sum d_i, d_j, d_i^2, d_j^2, d_i d_j over those frames, d = c - c[t0] (K18's shift: a constant trace has a
+ *                           variance of exactly 0);
+ *   scc                     sum c_i c_j over those frames, not shifted.
+ * One workgroup of 256 lanes per pair: a lane takes the voxels of the intersection (x slowest, z fastest), then the frames, at lane,
+ * lane + 256, .. in that order; t0 comes from a min-reduction on the frame index; the sums are reduced by block_sum0
+ * (csrc/block_ops.hpp) in its fixed order.  float64, no atomics, no workspace: the same input gives the same bits.  One launch, no host
+ * synchronisation.
+ *   boxes, pairs          on the HOST: checked before anything is launched;
+ *   boxes_dev, pairs_dev  the same arrays on the device: what the kernel reads.
+ * DNMF_E_NULL: a NULL argument;  DNMF_E_SHAPE: a size, K, T or N < 1, lda < P, ldc < T, a pair index outside [0, K), a box that is
+ * empty or reaches outside the volume or holds more than 4096 voxels (K24's limit);  DNMF_E_UNSUPPORTED: 2^31 voxels or more.
+ *
+ * dnmf_merge_apply.  The groups as a CSR table: group g has the members members[offsets[g] .. offsets[g + 1]), indices into the K old
+ * components; u and w hold one double per entry of members.  A = P rows of lda >= K floats (the (P, K) layout of the model's
+ * footprints, K fastest), C = K rows of ldc >= T floats:
+ *   A_out[v ldao + g] = (float) sum_m u[m] (double)A[v lda + members[m]]        P rows of ldao >= Kout floats
+ *   C_out[g ldco + t] = (float) sum_m w[m] (double)C[members[m] ldc + t]        Kout rows of ldco >= T floats
+ * the sums over a group's members in their order, in float64, rounded once; floats beyond a row's extent are left alone.  The first
+ * term is taken as it is, so a group of one member with u = w = 1 comes out bit for bit.  One launch, one thread per entry written.
+ *   offsets, members          on the HOST (Kout + 1 and offsets[Kout] ints): checked before anything is launched;
+ *   offsets_dev, members_dev  the same on the device;  u, w: device doubles.
+ * DNMF_E_NULL: a NULL argument;  DNMF_E_SHAPE: P, K, T or Kout < 1, Kout > K, lda < K, ldao < Kout, ldc or ldco < T, offsets that do
+ * not start at 0 or do not increase or pass K, a member outside [0, K), A_out or C_out overlapping A, C or each other;
+ * DNMF_E_UNSUPPORTED: 2^39 entries or more.  Nothing is launched on an error. */
+int dnmf_component_pairs(const float *A, long lda, const int *sz, const int *boxes, const int *boxes_dev, int K, const float *C,
+                         long ldc, int T, const int *pairs, const int *pairs_dev, int N, double *out, dnmf_stream_t stream);
+int dnmf_merge_apply(const float *A, long lda, long P, int K, const float *C, long ldc, int T, const int *offsets, const int *members,
+                     const int *offsets_dev, const int *members_dev, int Kout, const double *u, const double *w, float *A_out, long ldao,
+                     float *C_out, long ldco, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
