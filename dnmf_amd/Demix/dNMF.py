@@ -555,6 +555,7 @@ class DeformableNMF:
         # trace problem on the solver's float64 state, before self.C is rounded to float32 (float64 CPU tensor; zero at the
         # NNLS solution); None after a solver='mu' call
         self.last_temporal_kkt = None
+        self.last_spatial_kkt = None   # (K,) float64 after a spatial_step(solver='hals'), None after a 'mu' step
         # update_motion evaluates a whole epoch per launch when the caller's optimiser is a plain
         # torch.optim.Adam on [fp.beta] and the loader is a ResidentLoader (same result, see _motion_epoch)
         self.fused_motion = True
@@ -668,10 +669,16 @@ class DeformableNMF:
         return _mu_temporal(G, r, C0, gamma, iters).cpu().numpy()
 
     @staticmethod
-    def update_spatial(A, C, Y_i, D=None, gamma=None):
+    def update_spatial(A, C, Y_i, D=None, gamma=None, solver='mu', sweeps=1, boxes=None):
         """One multiplicative update of un-warped footprints (reference :151-160): numpy in, float64 numpy out.
         ``A`` (..., K), ``C`` (K,T), ``Y_i`` (..., T), ``D`` None or like ``A``; the leading axes are the voxels
-        (the reference's einsum strings accept two of them, any number works here).  K5 + K6, fp32 MFMA."""
+        (the reference's einsum strings accept two of them, any number works here).  K5 + K6, fp32 MFMA.
+        ``solver='hals'`` (extension): the dense K5, then ``sweeps`` sweeps of the exact solver K6h (``ops.hals_spatial``)
+        instead of the one multiplicative update; ``boxes`` (K,6) restricts neuron k to its box of the volume ``A.shape[:-1]``
+        (up to three axes), None leaves every voxel free."""
+        _check_solver(solver)
+        if solver == 'mu' and (boxes is not None or sweeps != 1):
+            raise ValueError("update_spatial: sweeps and boxes belong to solver='hals'")
         A, C, Y_i = np.asarray(A), np.asarray(C), np.asarray(Y_i)
         K, T = C.shape
         dev = torch.device(device)
@@ -681,23 +688,45 @@ class DeformableNMF:
         D_dev = None if D is None else torch.from_numpy(np.ascontiguousarray(np.asarray(D).reshape(-1, K))).to(dev, torch.float32)
         A1, Cs = torch.empty_like(A_dev), torch.empty((K, K), dtype=torch.float32, device=dev)
         DeformableNMF._spatial_accum_dense(Y_dev, C_dev, A1, Cs, None, None)
-        ops.mu_spatial(A_dev, A1, Cs, D_dev, gamma)
+        if solver == 'hals':
+            sz = None
+            if boxes is not None:
+                if A.ndim > 4:
+                    raise ValueError(f"update_spatial: boxes need at most three voxel axes, A is {A.shape}")
+                sz = tuple(A.shape[:-1]) + (1,) * (4 - A.ndim)
+            ops.hals_spatial(A_dev, A1, Cs, D_dev, gamma, sweeps=sweeps, boxes=boxes, sz=sz)
+        else:
+            ops.mu_spatial(A_dev, A1, Cs, D_dev, gamma)
         return A_dev.double().cpu().numpy().reshape(A.shape)
 
-    def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
+    def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None, solver='mu', sweeps=1, grow=0):
         """One multiplicative update of ``fp.A`` from the registered frames this process holds (the update the
         reference leaves commented out at :174, on the flattened voxel axis): K5 on the local frames, ONE all-reduce
         (sum) of the buffer that holds ``A1`` (P,K) and ``C_s`` (K,K) over ``self.group`` when the T axis is sharded,
         then K6 -- every rank ends with the same footprints.  ``registered`` (>=T_local,P) fp32 CUDA rows, frame b in
         row ``frame_ids[b]`` (None: b) with trace column ``times[b]`` (None: ``frame_ids[b]``, else b); ``D`` None or
         (X,Y,Z,K).  ``self.last_spatial_ms`` receives (K5, all-reduce, K6) HIP-event times when ``self.time_spatial``
-        is set."""
+        is set.
+
+        ``solver='hals'`` (extension): the same K5, all-reduce and ``_scale_Cs``, then ``sweeps`` sweeps of the exact
+        solver K6h in one launch -- cyclic coordinate descent on the non-negative least-squares problem of every voxel, which
+        the multiplicative update only approaches, can revive a zero and takes sums of any sign.  The support of neuron k is
+        the box of its non-zero values grown by ``grow`` voxels (an int or (gx, gy, gz)) and clipped to the volume; with
+        ``grow != 0`` the tile lists of K5 and K6h are made from the grown boxes (the cached lists of the 'mu' path are left
+        alone), and the dense form takes the same boxes, so the result does not depend on the form.
+        ``self.last_spatial_kkt`` (K,) float64 then holds, per neuron, how far the float64 state was from the solution after
+        the last sweep (largest projected-gradient entry); it is None after a 'mu' step."""
+        _check_spatial_solver(solver, sweeps, grow, "spatial_step")
         fp = self.fp
         P, K = fp.P, fp.K
         C = self.C.to(device, torch.float32).contiguous()
         if times is None:
             times = frame_ids
-        sl = self._spatial_lists()
+        hals = solver == 'hals'
+        if hals:
+            boxes, sl = self._spatial_support(grow)
+        else:
+            sl = self._spatial_lists()
         # A1 and C_s live in one buffer so that the exchange is a single collective; with compact footprints A1 exists
         # only for (tile, listed neuron) pairs -- a few floats per voxel instead of K (3 MB instead of 105 MB at cfg 3)
         n1 = sl["total"] if sl is not None else P * K
@@ -709,14 +738,53 @@ class DeformableNMF:
         self._scale_Cs(Cs)
         A2 = fp.A.reshape(P, K).contiguous()
         Dd = self._device_D(D)
-        if sl is not None:
+        kkt = None
+        if hals and sl is not None:
+            _, kkt = ops.hals_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma, sweeps=sweeps,
+                                            kkt=True, bbox=boxes)
+        elif hals:
+            _, kkt = ops.hals_spatial(A2, A1, Cs, Dd, gamma, sweeps=sweeps, boxes=boxes, kkt=True, sz=fp.sz_list)
+        elif sl is not None:
             # the values and boxes of the true A (not the floored lists of K3n): a sub-floor value is updated like any other
             ops.mu_spatial_lists(A2, fp.packed_lists(floor=0.0), sl, A1, Cs, fp.sz_list, Dd, gamma)
         else:
             ops.mu_spatial(A2, A1, Cs, Dd, gamma)
+        self.last_spatial_kkt = None if kkt is None else kkt.cpu()
         fp.A = A2.view(*fp.sz_list, K)
         self._footprints_written()
         return fp.A
+
+    def _spatial_support(self, grow):
+        """``(boxes, sl)`` of a 'hals' spatial_step: the (K,6) int32 boxes of the non-zero values of ``fp.A`` grown by ``grow``
+        and clipped to the volume, and the tile lists made from them (None: the dense form, by the rule of ``_spatial_lists``).
+        ``grow == 0``: the lists are the cached ones of the 'mu' path; else they are made here and kept nowhere."""
+        fp = self.fp
+        sz = fp.sz_list
+        if fp.K <= LISTS_MAX_K:
+            boxes = fp.packed_lists(floor=0.0)["bbox"]
+        else:   # no list layout holds this many neurons: the same boxes from the values
+            nz = fp.A.reshape(*sz, fp.K) != 0
+            cols = []
+            for ax in range(3):
+                hit = nz.any(dim=tuple(a for a in range(3) if a != ax))      # (dim, K)
+                at = torch.arange(sz[ax], device=hit.device)[:, None]
+                cols += [torch.where(hit, at, sz[ax]).amin(0), torch.where(hit, at, -1).amax(0)]   # empty: lo > hi
+            boxes = torch.stack(cols, 1).to(torch.int32).contiguous()
+        g = [int(v) for v in grow] if hasattr(grow, "__len__") else [int(grow)] * 3
+        if not any(g):
+            return boxes, self._spatial_lists()
+        boxes = ops.dilate_boxes(boxes, sz, g)
+        if fp.P * 32 >= 2 ** 31 or sz[1] * sz[2] < 4:
+            return boxes, None
+        ext = (boxes[:, 1::2] - boxes[:, 0::2] + 1).clamp_min(0).long()
+        if lists_verdict(self.spatial_kernel, fp.K, float(ext.prod(1).sum()) / fp.P) is not None:
+            return boxes, None
+        sl = ops.spatial_lists_setup({"bbox": boxes}, fp.K, sz)
+        if sl["total"] <= 0:
+            if self.spatial_kernel == 'lists':
+                raise ValueError("spatial_kernel='lists': a tile lists more than 32 neurons (or none at all)")
+            return boxes, None
+        return boxes, sl
 
     def _spatial_numerator(self, registered, C, sl, A1, Cs, frame_ids, times):
         """K5 of spatial_step: the numerator into ``A1`` (compact sums at the listed entries when ``sl`` is given, else
@@ -1212,7 +1280,7 @@ class DeformableNMF:
         return out
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
-                          live_spatial=False, iter_a=1, solver='mu', registered='nearest'):
+                          live_spatial=False, iter_a=1, solver='mu', registered='nearest', spatial_solver='mu', grow=0):
         """Reference :163-179: ``iter_c`` multiplicative updates of ``self.C`` under the current warp.
 
         ``solver='hals'`` (extension) runs ``iter_c`` sweeps of the exact solver K4h instead, from the same ``self.C``, on
@@ -1232,6 +1300,9 @@ class DeformableNMF:
         1e-32)`` (``spatial_step``: K5, one all-reduce over ``self.group``, K6) with the ``D`` of the constructor
         flattened over the voxels -- the reference's commented lines update an unrelated random ``self.A`` with
         mismatched shapes (:131, :169-176); here the update acts on the footprints the model uses.
+        ``spatial_solver='hals'`` (extension): ONE ``spatial_step(solver='hals', sweeps=iter_a, grow=grow)`` instead -- one
+        registration and one K5 pass over the movie, then ``iter_a`` sweeps of the exact solver K6h on supports grown by
+        ``grow`` voxels; ``self.last_spatial_kkt`` (K,) holds its per-neuron distance from the solution (None after 'mu').
 
         ``registered='linear'`` (extension) registers with K17 (``ops.warp_pullback``: trilinear, true voxel coordinates,
         without the reference's ``sz``-for-``sz - 1`` quirk -- not a parity path) instead of K7, both for the ``live_spatial``
@@ -1240,6 +1311,7 @@ class DeformableNMF:
         K, P = fp.K, fp.P
         _check_solver(solver)
         _check_registered(registered, "update_footprints")
+        _check_spatial_solver(spatial_solver, iter_a if spatial_solver == 'hals' else 1, grow, "update_footprints")
         hals = solver == 'hals'
         if hals:
             _hals_refuse_shards(gamma_c, self.group)
@@ -1279,8 +1351,14 @@ class DeformableNMF:
                     ops.warp_pullback(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
                 else:
                     ops.image_iwarp(frames, None, fp.sz_list, fp.beta.detach(), order, out=self._reg_buf, nchan=nch)
-                for _ in range(iter_a):
-                    self.spatial_step(self._reg_buf, D=self.D, gamma=gamma_a, times=order)
+                if spatial_solver == 'hals':
+                    self.spatial_step(self._reg_buf, D=self.D, gamma=gamma_a, times=order, solver='hals', sweeps=iter_a, grow=grow)
+                    if self.verbose:
+                        print('Spatial KKT: max %.3e median %.3e' % (float(self.last_spatial_kkt.max()),
+                                                                     float(self.last_spatial_kkt.median())))
+                else:
+                    for _ in range(iter_a):
+                        self.spatial_step(self._reg_buf, D=self.D, gamma=gamma_a, times=order)
             if return_dense is None:
                 return_dense = 8 * P * K * T_loc <= DENSE_RETURN_LIMIT
             if not return_dense:
@@ -1892,7 +1970,7 @@ class DeformableNMF:
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
-            background=0, background_rank=1, motion_order=None):
+            background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, motion_order=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
@@ -1904,7 +1982,9 @@ class DeformableNMF:
         because a background fitted before the model explains anything would take the neurons' mean light with it.  0: no
         background term, the path of a call without the argument.  ``background_rank=R``, 2 .. 8 (K23): those updates fit R
         images with R time courses (``update_background_rank``); 1: the rank-1 term.  ``motion_order`` is the model's
-        ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``)."""
+        ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``).
+        ``spatial_solver``, ``grow`` and ``iter_a`` are ``update_footprints``' (``'hals'``: the exact footprint solver K6h,
+        ``iter_a`` sweeps on supports grown by ``grow`` voxels; with ``verbose`` its max and median KKT are printed)."""
         _check_motion_solver(motion_solver, "fit")
         kept, kept_order = self.motion_smooth, self.motion_order
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
@@ -1925,7 +2005,8 @@ class DeformableNMF:
             for sweep in range(outer):
                 self.update_motion(train, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
                 out = self.update_footprints(test, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
-                                             iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered)
+                                             iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered,
+                                             spatial_solver=spatial_solver, grow=grow, iter_a=iter_a)
                 if background:
                     if background_rank == 1:
                         self.update_background(testloader, iters=background)
@@ -1985,7 +2066,7 @@ class MultiChannelDNMF(DeformableNMF):
         return self.colours.shape[0]
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=False,
-                          live_spatial=False, iter_a=1, solver='mu', registered='nearest'):
+                          live_spatial=False, iter_a=1, solver='mu', registered='nearest', spatial_solver='mu', grow=0):
         """As DeformableNMF.update_footprints on the channel sums; the dense ``A_t`` return is not offered.  With
         ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel;
         ``registered='linear'``: one K17 call, one solve per lattice point) and ``fp.A`` takes ``iter_a`` steps of
@@ -1994,9 +2075,10 @@ class MultiChannelDNMF(DeformableNMF):
             raise NotImplementedError("MultiChannelDNMF.update_footprints: return_dense")
         return super().update_footprints(testloader, batch_size, sz, gamma_c=gamma_c, gamma_a=gamma_a, iter_c=iter_c,
                                          return_dense=False, live_spatial=live_spatial, iter_a=iter_a, solver=solver,
+                                         spatial_solver=spatial_solver, grow=grow,
                                          registered=registered)
 
-    def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None):
+    def spatial_step(self, registered, D=None, gamma=None, frame_ids=None, times=None, solver='mu', sweeps=1, grow=0):
         """One multiplicative update of the (uncoloured) footprints ``fp.A`` from the registered frames of ALL channels
         (rows of NC * P floats).  With channel c showing neuron k as ``colours[c,k] A[:,k]`` the update of the shared ``A``
         that the reference's formula (``Demix/dNMF.py:151-160``) becomes is
@@ -2008,11 +2090,13 @@ class MultiChannelDNMF(DeformableNMF):
         form folds the colours into one channel K5 launch (``dnmf_spatial_accum_lists_channels``), the dense form runs K5
         per channel (by groups of 128 neurons beyond K = 128).  One all-reduce of the A1 | C_s buffer over ``self.group``
         like the single-channel step.  Not in the reference (no channel axis there): checked against this formula in
-        float64 and, for one channel of colour 1, against ``DeformableNMF.spatial_step``."""
+        float64 and, for one channel of colour 1, against ``DeformableNMF.spatial_step``.  ``solver='hals'``, ``sweeps``,
+        ``grow``: the exact solver K6h on the same fused sums (see ``DeformableNMF.spatial_step``)."""
         NC, P = self.colours.shape[0], self.fp.P
         if registered.shape[1] != NC * P:
             raise ValueError(f"MultiChannelDNMF.spatial_step: rows of {registered.shape[1]} floats, expected {NC} x {P}")
-        return super().spatial_step(registered, D=D, gamma=gamma, frame_ids=frame_ids, times=times)
+        return super().spatial_step(registered, D=D, gamma=gamma, frame_ids=frame_ids, times=times, solver=solver, sweeps=sweeps,
+                                    grow=grow)
 
     def _spatial_numerator(self, registered, C, sl, A1, Cs, frame_ids, times):
         fp = self.fp
@@ -2070,6 +2154,20 @@ SOLVERS = ('mu', 'hals')
 def _check_solver(solver):
     if solver not in SOLVERS:
         raise ValueError(f"solver={solver!r}: expected one of {SOLVERS}")
+
+
+def _check_spatial_solver(solver, sweeps, grow, who):
+    """The footprint solver's arguments: 'mu' (K6) takes one update and no growth; 'hals' (K6h) ``sweeps`` >= 1 and
+    ``grow`` >= 0 voxels, one number or (gx, gy, gz)."""
+    _check_solver(solver)
+    g = list(grow) if hasattr(grow, "__len__") else [grow] * 3
+    if len(g) != 3 or any(int(v) != v or v < 0 for v in g):
+        raise ValueError(f"{who}: grow={grow!r}, a whole number of voxels >= 0 or three of them")
+    if int(sweeps) != sweeps or sweeps < 1:
+        raise ValueError(f"{who}: sweeps={sweeps!r}, a whole number >= 1")
+    if solver == 'mu' and (any(g) or sweeps != 1):
+        raise ValueError(f"{who}: grow and sweeps belong to the 'hals' footprint solver (the multiplicative update keeps "
+                         "every zero: it cannot use a grown support)")
 
 
 def _check_registered(registered, who):

@@ -77,6 +77,10 @@ SIGNATURES = {
     "dnmf_spatial_accum_lists_channels": (_i, [_vp, _l, _l, _i, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _vp, _l, _vp, _vp,
                                                 _vp, _sz, _vp]),
     "dnmf_mu_spatial_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _vp]),
+    "dnmf_hals_spatial": (_i, [_vp, _vp, _vp, _vp, _d, _l, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "dnmf_hals_spatial_kkt": (_i, [_vp, _vp, _vp, _vp, _d, _l, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "dnmf_hals_spatial_lists_workspace": (_sz, [_i, _i, _i]),
+    "dnmf_hals_spatial_lists": (_i, [_vp, _vp, _vp, _vp, _vp, _d, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "dnmf_register_patches_grid": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "dnmf_register_patches_workspace": (_sz, [_i, _i, _i, _vp, _vp, _i]),
     "dnmf_register_patches": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, C.c_float, _vp, _vp, _vp, _sz, _i, _vp]),

@@ -407,6 +407,218 @@ __global__ __launch_bounds__(256) void mu_spatial_scatter_kernel(float *__restri
     }
 }
 
+// ---- K6h: exact NNLS footprint update (HALS / cyclic coordinate descent) on the sums of K5 -----------------------------
+// Given A1 and Cs the footprint problem separates by voxel: min 1/2 a^T Cs a - A1[p]^T a + gamma D[p]^T a, a >= 0, over
+// the neurons whose box holds p.  One sweep, k ascending over those neurons:
+//   g = sum_l a_l Cs[l,k] - A1[p,k] + gamma D[p,k]   (l over the same neurons, ascending, current values)
+//   a_k <- max(0, a_k - g / Cs[k,k])                  (Cs[k,k] <= 0 or not finite: a_k stays)
+// State and g are float64; all sweeps run in one launch and the state is rounded to fp32 once.  A voxel is one lane's
+// business from start to end (its state a column of LDS that no other lane touches), so nothing is exchanged but the KKT
+// maxima, and those are maxima: the same bits on every run.  Both forms walk the same neurons in the same order through
+// the same two functions below, so they agree bit for bit on the same sums.  The products and sums are separate, rounded
+// operations (the build does not contract them): a float64 restatement in plain numpy gives the same bits.
+__device__ __forceinline__ bool hs_in_box(const int *__restrict__ bb, int x, int y, int z) {
+    return x >= bb[0] && x <= bb[1] && y >= bb[2] && y <= bb[3] && z >= bb[4] && z <= bb[5];
+}
+__device__ __forceinline__ double hs_gradient(double dot, float a1, const float *__restrict__ D, long e, double gamma) {
+    double g = dot - (double)a1;
+    if (D) g += gamma * (double)D[e];
+    return g;
+}
+__device__ __forceinline__ double hs_step(double a, double g, double d) {
+    return (d > 0.0 && d < (double)INFINITY) ? fmax(0.0, a - g / d) : a;
+}
+__device__ __forceinline__ double hs_projected(double a, double g) { return fabs(a > 0.0 ? g : fmin(g, 0.0)); }
+__device__ __forceinline__ double hs_wave_max(double m) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off, 64));
+    return m;
+}
+// orders the LDS traffic of the lanes of one wave (as hals_temporal.hip does)
+__device__ __forceinline__ void hs_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// List form: one wave per tile, two tiles per workgroup.  Per wave in LDS: the tile's n x n block of Cs (fp32 as stored,
+// widened on use; every lane reads the same address), the n <= 32 float64 values of one voxel per lane (slot-major: the
+// 64 lanes of a slot are consecutive, no bank conflict) -- one of the lane's four voxels at a time -- and the KKT maxima
+// of the 32 slots.  A1c in = the sums, out = the new values (0 where the voxel is outside the neuron's box); the scatter
+// kernel of K6 then writes them into A (P,K).  kkt_work (ntiles, 32) or NULL.
+constexpr int HS_WAVES = 2;
+__global__ __launch_bounds__(64 * HS_WAVES) void hals_spatial_lists_kernel(const float *__restrict__ At, long Pp, int rowf,
+                                                                           float *__restrict__ A1c, const float *__restrict__ Cs,
+                                                                           const float *__restrict__ D, double gamma, int K, SlGeom g,
+                                                                           const int *__restrict__ tile_n, const int *__restrict__ tile_off,
+                                                                           const int *__restrict__ tile_list, const int *__restrict__ bbox,
+                                                                           int sweeps, double *__restrict__ kkt_work) {
+    __shared__ double state_all[HS_WAVES][SL_MAXL * 64];
+    __shared__ double kmax_all[HS_WAVES][SL_MAXL];
+    __shared__ float cs_all[HS_WAVES][SL_MAXL * SL_MAXL];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * HS_WAVES + wave;
+    if (q >= g.ntiles) return;      // no workgroup barrier below
+    const int n = tile_n[q];
+    if (n <= 0) return;
+    double *st = state_all[wave] + lane, *kmax = kmax_all[wave];
+    float *cs = cs_all[wave];
+    const int qu = q % g.nu, qx = q / g.nu;
+    const int x = 4 * qx + (lane >> 4), u = 64 * qu + 4 * (lane & 15);
+    const int *lst = tile_list + (long)q * SL_MAXL;
+    float *ent = A1c + tile_off[q] + 4 * lane;
+    for (int e = lane; e < n * n; e += 64) {
+        const int j = e / n, i = e - j * n;
+        cs[j * SL_MAXL + i] = Cs[(long)lst[j] * K + lst[i]];
+    }
+    if (lane < SL_MAXL) kmax[lane] = 0.0;
+    hs_wave_sync();
+    for (int v = 0; v < 4; ++v) {
+        const bool inside = x < g.X && u + v < g.YZ;
+        const int y = (u + v) / g.Z, z = (u + v) - y * g.Z;
+        const long hp = (long)(x + HALO) * rowf + (long)HALO * g.Z + u + v;      // halo index of the voxel
+        const long p = (long)x * g.YZ + u + v;
+        unsigned m = 0;             // slots whose box holds the voxel
+        for (int i = 0; i < n; ++i) {
+            const int ki = lst[i];
+            const bool in = inside && hs_in_box(bbox + 6 * ki, x, y, z);
+            m |= in ? 1u << i : 0u;
+            st[i * 64] = in ? (double)At[(long)ki * Pp + hp] : 0.0;
+        }
+        for (int s = 0; s <= sweeps; ++s) {     // the pass after the last sweep only measures
+            const bool last = s == sweeps;
+            if (last && !kkt_work) break;
+            for (int i = 0; i < n; ++i) {
+                const bool in = (m >> i) & 1u;
+                double pg = 0.0;
+                if (in) {
+                    double dot = 0.0;
+                    for (int j = 0; j < n; ++j)
+                        if ((m >> j) & 1u) dot = dot + st[j * 64] * (double)cs[j * SL_MAXL + i];
+                    const double gr = hs_gradient(dot, ent[256 * i + v], D, p * K + lst[i], gamma);
+                    if (last)
+                        pg = hs_projected(st[i * 64], gr);
+                    else
+                        st[i * 64] = hs_step(st[i * 64], gr, (double)cs[i * SL_MAXL + i]);
+                }
+                if (last) {
+                    pg = hs_wave_max(pg);
+                    if (lane == 0) kmax[i] = fmax(kmax[i], pg);
+                }
+            }
+        }
+        if (inside)
+            for (int i = 0; i < n; ++i) ent[256 * i + v] = (float)st[i * 64];
+    }
+    if (kkt_work) {
+        hs_wave_sync();
+        if (lane < n) kkt_work[(long)q * SL_MAXL + lane] = kmax[lane];
+    }
+}
+
+// kkt[k] = the largest of the (tile, slot) maxima of neuron k: one wave per neuron, tiles strided over the lanes
+__global__ __launch_bounds__(64) void hals_spatial_kkt_reduce_kernel(const double *__restrict__ kkt_work, int ntiles,
+                                                                     const int *__restrict__ tile_n, const int *__restrict__ tile_list,
+                                                                     double *__restrict__ kkt) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    double m = 0.0;
+    for (int q = lane; q < ntiles; q += 64) {
+        const int n = tile_n[q];
+        for (int i = 0; i < n; ++i)
+            if (tile_list[(long)q * SL_MAXL + i] == k) m = fmax(m, kkt_work[(long)q * SL_MAXL + i]);
+    }
+    m = hs_wave_max(m);
+    if (lane == 0) kkt[k] = m;
+}
+
+// Dense form: A, A1, D as (P,K); one lane per voxel, `nv` <= 64 voxels per one-wave workgroup (as many as the LDS holds).
+// Per lane in LDS the neurons whose box holds the voxel (all K without boxes), ascending, and their float64 values
+// (entry-major: the lanes of an entry are consecutive).  sweeps == 0 measures only (write == 0: A is not written).
+// kkt_bits (K) or NULL: the maxima as the bit patterns of non-negative doubles, which order like unsigned integers --
+// an integer maximum per workgroup in LDS, then one per neuron in memory; zeroed by the caller.
+__global__ __launch_bounds__(64) void hals_spatial_kernel(float *__restrict__ A, const float *__restrict__ A1,
+                                                          const float *__restrict__ Cs, const float *__restrict__ D, double gamma,
+                                                          long P, int K, int sweeps, const int *__restrict__ boxes, int YZ, int Z,
+                                                          int nv, unsigned long long *__restrict__ kkt_bits, int write) {
+    extern __shared__ double hs_lds[];
+    const int lane = threadIdx.x;
+    const long p = (long)blockIdx.x * nv + lane;
+    const bool active = lane < nv && p < P;
+    double *st = hs_lds + lane;                                                  // K x nv
+    unsigned long long *kmax = reinterpret_cast<unsigned long long *>(hs_lds + (size_t)K * nv);   // K
+    unsigned short *idx = reinterpret_cast<unsigned short *>(kmax + K) + lane;   // K x nv
+    if (kkt_bits) {
+        for (int k = lane; k < K; k += 64) kmax[k] = 0ull;
+        hs_wave_sync();
+    }
+    int cnt = 0;
+    if (active) {
+        const int x = (int)(p / YZ), u = (int)(p - (long)x * YZ);
+        const int y = u / Z, z = u - y * Z;
+        for (int l = 0; l < K; ++l) {
+            if (!boxes || hs_in_box(boxes + 6 * l, x, y, z)) {
+                idx[cnt * nv] = (unsigned short)l;
+                st[cnt * nv] = (double)A[p * K + l];
+                ++cnt;
+            } else if (write) {
+                A[p * K + l] = 0.0f;
+            }
+        }
+    }
+    for (int s = 0; s <= sweeps; ++s) {         // the pass after the last sweep only measures
+        const bool last = s == sweeps;
+        if (last && !kkt_bits) break;
+        for (int i = 0; i < cnt; ++i) {
+            const int k = idx[i * nv];
+            double dot = 0.0;
+            for (int j = 0; j < cnt; ++j) dot = dot + st[j * nv] * (double)Cs[(long)idx[j * nv] * K + k];
+            const double gr = hs_gradient(dot, A1[p * K + k], D, p * K + k, gamma);
+            if (last) {
+                const double pg = hs_projected(st[i * nv], gr);
+                if (pg == pg) atomicMax(&kmax[k], (unsigned long long)__double_as_longlong(pg));
+            } else {
+                st[i * nv] = hs_step(st[i * nv], gr, (double)Cs[(long)k * K + k]);
+            }
+        }
+    }
+    if (write)
+        for (int i = 0; i < cnt; ++i) A[p * K + idx[i * nv]] = (float)st[i * nv];
+    if (kkt_bits) {
+        hs_wave_sync();
+        for (int k = lane; k < K; k += 64)
+            if (kmax[k]) atomicMax(&kkt_bits[k], kmax[k]);
+    }
+}
+
+// voxels per workgroup of the dense form and its LDS bytes (0 voxels: K too large)
+static int hs_dense_voxels(int K, size_t *bytes) {
+    const size_t budget = 60 * 1024, per = (size_t)K * (sizeof(double) + sizeof(unsigned short)), fixed = (size_t)K * 8 + 16;
+    int nv = fixed >= budget ? 0 : (int)((budget - fixed) / per);
+    nv = nv > 64 ? 64 : nv;
+    *bytes = (size_t)nv * K * sizeof(double) + (size_t)K * 8 + (size_t)nv * K * sizeof(unsigned short);
+    return nv;
+}
+
+static int hs_dense_run(const char *who, float *A, const float *A1, const float *Cs, const float *D, double gamma, long P, int K,
+                        int sweeps, const int *boxes, int X, int Y, int Z, double *kkt, int write, dnmf_stream_t stream) {
+    DNMF_REQUIRE(A && A1 && Cs, DNMF_E_NULL, "%s: NULL buffer", who);
+    DNMF_REQUIRE(P > 0 && K > 0 && K <= 65535, DNMF_E_SHAPE, "%s: P=%ld K=%d", who, P, K);
+    DNMF_REQUIRE(!boxes || (X > 0 && Y > 0 && Z > 0 && (long)X * Y * Z == P), DNMF_E_SHAPE, "%s: boxes need X Y Z = P, got %d x %d x %d, P=%ld",
+                 who, X, Y, Z, P);
+    size_t lds = 0;
+    const int nv = hs_dense_voxels(K, &lds);
+    DNMF_REQUIRE(nv >= 1, DNMF_E_UNSUPPORTED, "%s: K=%d too large", who, K);
+    hipStream_t st = (hipStream_t)stream;
+    if (kkt) {
+        hipError_t e = hipMemsetAsync(kkt, 0, (size_t)K * sizeof(double), st);
+        DNMF_REQUIRE(e == hipSuccess, (int)e, "%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+    }
+    if (!boxes) Y = 1, Z = 1, X = 1;     // the coordinates are not used
+    hipLaunchKernelGGL(hals_spatial_kernel, dim3((unsigned)((P + nv - 1) / nv)), dim3(64), lds, st, A, A1, Cs, D, gamma, P, K, sweeps,
+                       boxes, boxes ? Y * Z : 1, boxes ? Z : 1, nv, reinterpret_cast<unsigned long long *>(kkt), write);
+    return check_launch(who);
+}
+
 template <int NB>
 static void launch_accum(const float *Y, long ldy, const int *frame_ids, const float *C, long ldc, const float *Ct, long ldct,
                          const int *times, int T, long P, int K, float *A1, int accumulate, hipStream_t st) {
@@ -559,6 +771,51 @@ int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs
                        tile_off, tile_list);
     hipLaunchKernelGGL(mu_spatial_scatter_kernel, grid, dim3(256), 0, st, A, A1c, K, g, tile_n, tile_off, tile_list);
     return check_launch("dnmf_mu_spatial_lists");
+}
+
+// ---- K6h (see the kernels above) ----
+int dnmf_hals_spatial(float *A, const float *A1, const float *Cs, const float *D, double gamma, long P, int K, int sweeps,
+                      const int *boxes, int X, int Y, int Z, double *kkt, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(sweeps >= 1, DNMF_E_SHAPE, "dnmf_hals_spatial: sweeps=%d < 1", sweeps);
+    return hs_dense_run("dnmf_hals_spatial", A, A1, Cs, D, gamma, P, K, sweeps, boxes, X, Y, Z, kkt, 1, stream);
+}
+
+int dnmf_hals_spatial_kkt(const float *A, const float *A1, const float *Cs, const float *D, double gamma, long P, int K,
+                          const int *boxes, int X, int Y, int Z, double *kkt, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(kkt, DNMF_E_NULL, "dnmf_hals_spatial_kkt: NULL buffer");
+    // sweeps == 0, write == 0: the kernel reads A and writes kkt only
+    return hs_dense_run("dnmf_hals_spatial_kkt", const_cast<float *>(A), A1, Cs, D, gamma, P, K, 0, boxes, X, Y, Z, kkt, 0, stream);
+}
+
+size_t dnmf_hals_spatial_lists_workspace(int X, int Y, int Z) {
+    if (X <= 0 || Y <= 0 || Z <= 0) return 0;
+    return (size_t)dnmf::sl_geom(X, Y, Z).ntiles * dnmf::SL_MAXL * sizeof(double);
+}
+
+int dnmf_hals_spatial_lists(float *A, const float *At, float *A1c, const float *Cs, const float *D, double gamma, int X, int Y, int Z,
+                            int K, const int *tables, const int *bbox, int sweeps, double *kkt, void *workspace,
+                            size_t workspace_bytes, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(A && At && A1c && Cs && tables && bbox, DNMF_E_NULL, "dnmf_hals_spatial_lists: NULL buffer");
+    DNMF_REQUIRE(X > 0 && Y > 0 && Z > 0 && K > 0 && sweeps >= 1, DNMF_E_SHAPE, "dnmf_hals_spatial_lists: X=%d Y=%d Z=%d K=%d sweeps=%d",
+                 X, Y, Z, K, sweeps);
+    const SlGeom g = sl_geom(X, Y, Z);
+    const size_t need = (size_t)g.ntiles * SL_MAXL * sizeof(double);
+    DNMF_REQUIRE(!kkt || (workspace && workspace_bytes >= need), DNMF_E_WORKSPACE, "dnmf_hals_spatial_lists: workspace %zu < %zu bytes",
+                 workspace_bytes, need);
+    const HaloLayout hl = make_halo_layout(X, Y, Z);
+    const int *tile_n = tables, *tile_off = tables + g.ntiles, *tile_list = tables + 2 * g.ntiles + 2;
+    hipStream_t st = (hipStream_t)stream;
+    double *work = kkt ? static_cast<double *>(workspace) : nullptr;
+    hipLaunchKernelGGL(hals_spatial_lists_kernel, dim3((unsigned)((g.ntiles + HS_WAVES - 1) / HS_WAVES)), dim3(64 * HS_WAVES), 0, st, At,
+                       hl.Pp, hl.rowf, A1c, Cs, D, gamma, K, g, tile_n, tile_off, tile_list, bbox, sweeps, work);
+    hipLaunchKernelGGL(mu_spatial_scatter_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, st, A, A1c, K, g, tile_n, tile_off,
+                       tile_list);
+    if (kkt)
+        hipLaunchKernelGGL(hals_spatial_kkt_reduce_kernel, dim3((unsigned)K), dim3(64), 0, st, work, g.ntiles, tile_n, tile_list, kkt);
+    return check_launch("dnmf_hals_spatial_lists");
 }
 
 }  // extern "C"

@@ -726,6 +726,119 @@ def mu_spatial_lists(A, layout, sl, A1c, Cs, sz, D=None, gamma=0.0):
     return A
 
 
+def _hals_spatial_boxes(fn, boxes, K, sz, dev):
+    """``boxes`` (K,6) as an int32 tensor on ``dev`` with ``sz``; a box that is not empty must lie inside the volume."""
+    if sz is None:
+        raise ValueError(f"{fn}: boxes need the volume sz=(X, Y, Z)")
+    sz = tuple(int(s) for s in sz)
+    b = torch.as_tensor(boxes)
+    if b.is_floating_point() or b.dim() != 2 or tuple(b.shape) != (K, 6):
+        raise ValueError(f"{fn}: boxes must be integers of shape (K={K}, 6), got {b.dtype} {tuple(b.shape)}")
+    b = b.to(device=dev, dtype=torch.int32).contiguous()
+    lo, hi = b[:, 0::2].long(), b[:, 1::2].long()
+    full = (lo <= hi).all(1, keepdim=True)
+    dims = torch.tensor(sz, device=dev)
+    if bool((full & ((lo < 0) | (hi >= dims))).any()):
+        raise ValueError(f"{fn}: a box reaches outside the volume {sz}")
+    return b, sz
+
+
+def _hals_spatial_sums(fn, A, A1, Cs, D):
+    for t, n in ((A, "A"), (A1, "A1"), (Cs, "Cs")):
+        _f32(t, n)
+    if A.dim() != 2 or A1.shape != A.shape or tuple(Cs.shape) != (A.shape[1], A.shape[1]):
+        raise ValueError(f"{fn}: A {tuple(A.shape)} (P,K), A1 {tuple(A1.shape)} (P,K) and Cs {tuple(Cs.shape)} (K,K) do not match")
+    if D is not None and _f32(D, "D").shape != A.shape:
+        raise ValueError(f"{fn}: D {tuple(D.shape)} is not like A {tuple(A.shape)}")
+    return A.shape
+
+
+def _sweeps(fn, sweeps):
+    if int(sweeps) != sweeps or sweeps < 1:
+        raise ValueError(f"{fn}: sweeps={sweeps!r}, a whole number >= 1")
+    return int(sweeps)
+
+
+def hals_spatial(A, A1, Cs, D=None, gamma=0.0, sweeps=1, boxes=None, kkt=False, sz=None):
+    """K6h, dense form.  A (P,K) fp32 updated in place by ``sweeps`` sweeps of cyclic coordinate descent (k ascending) on
+    ``1/2 a^T Cs a - A1[p]^T a + gamma D[p]^T a, a >= 0`` per voxel, over the neurons whose box holds it: ``boxes`` (K,6)
+    integers (xlo, xhi, ylo, yhi, zlo, zhi), inclusive, with the volume ``sz`` -- values outside become 0 -- or None: every
+    voxel is free.  ``kkt=True``: returns ``(A, kkt)``, kkt (K) float64 = the largest projected-gradient entry per neuron
+    of the float64 state after the last sweep (zero at the NNLS solution)."""
+    P, K = _hals_spatial_sums("hals_spatial", A, A1, Cs, D)
+    sweeps = _sweeps("hals_spatial", sweeps)
+    b, (X, Y, Z) = (None, (0, 0, 0)) if boxes is None else _hals_spatial_boxes("hals_spatial", boxes, K, sz, A.device)
+    if b is not None and X * Y * Z != P:
+        raise ValueError(f"hals_spatial: sz={sz} does not hold the P={P} voxels of A")
+    out = torch.empty((K,), dtype=torch.float64, device=A.device) if kkt else None
+    with _timed("hals_spatial"):
+        rc = _lib.load().dnmf_hals_spatial(A.data_ptr(), A1.data_ptr(), Cs.data_ptr(), _ptr(D), float(gamma or 0.0), P, K, sweeps,
+                                           _ptr(b), X, Y, Z, _ptr(out), _stream())
+    _lib.check(rc, "dnmf_hals_spatial")
+    return (A, out) if kkt else A
+
+
+def hals_spatial_kkt(A, A1, Cs, D=None, gamma=0.0, boxes=None, sz=None):
+    """(K) float64: the largest projected-gradient entry per neuron of the stored fp32 footprints A (P,K) for the sums
+    ``A1``, ``Cs`` (the measure ``hals_spatial(..., kkt=True)`` returns, for any stored state); nothing is written."""
+    P, K = _hals_spatial_sums("hals_spatial_kkt", A, A1, Cs, D)
+    b, (X, Y, Z) = (None, (0, 0, 0)) if boxes is None else _hals_spatial_boxes("hals_spatial_kkt", boxes, K, sz, A.device)
+    if b is not None and X * Y * Z != P:
+        raise ValueError(f"hals_spatial_kkt: sz={sz} does not hold the P={P} voxels of A")
+    out = torch.empty((K,), dtype=torch.float64, device=A.device)
+    with _timed("hals_spatial_kkt"):
+        rc = _lib.load().dnmf_hals_spatial_kkt(A.data_ptr(), A1.data_ptr(), Cs.data_ptr(), _ptr(D), float(gamma or 0.0), P, K,
+                                               _ptr(b), X, Y, Z, out.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_hals_spatial_kkt")
+    return out
+
+
+def hals_spatial_lists(A, layout, sl, A1c, Cs, sz, D=None, gamma=0.0, sweeps=1, kkt=False, bbox=None):
+    """K6h, list form, with the arguments of ``mu_spatial_lists``: A (P,K) updated in place at the entries the tiles list
+    from the halo copy ``layout["At"]``; A1c in = the sums, out = the new values.  The boxes are ``layout["bbox"]``, or
+    ``bbox`` (K,6) where the tile lists ``sl`` were made from other (dilated) boxes.  ``kkt`` as in ``hals_spatial``."""
+    X, Y, Z = (int(s) for s in sz)
+    for t, n in ((A, "A"), (A1c, "A1c"), (Cs, "Cs")):
+        _f32(t, n)
+    if A.dim() != 2 or A.shape[0] != X * Y * Z or tuple(Cs.shape) != (A.shape[1], A.shape[1]):
+        raise ValueError(f"hals_spatial_lists: A {tuple(A.shape)} (P,K), Cs {tuple(Cs.shape)} (K,K) do not match sz={tuple(sz)}")
+    if sl["total"] <= 0 or A1c.numel() < sl["total"]:
+        raise ValueError(f"hals_spatial_lists: A1c holds {A1c.numel()} floats, the tile lists {sl['total']} (<= 0: no list form)")
+    if D is not None and _f32(D, "D").shape != A.shape:
+        raise ValueError(f"hals_spatial_lists: D {tuple(D.shape)} is not like A {tuple(A.shape)}")
+    sweeps = _sweeps("hals_spatial_lists", sweeps)
+    K = A.shape[1]
+    b, _ = _hals_spatial_boxes("hals_spatial_lists", layout["bbox"] if bbox is None else bbox, K, sz, A.device)
+    lib = _lib.load()
+    out = ws = None
+    if kkt:
+        out = torch.empty((K,), dtype=torch.float64, device=A.device)
+        ws = torch.empty((_need(lib, "dnmf_hals_spatial_lists_workspace", X, Y, Z) // 8,), dtype=torch.float64, device=A.device)
+    with _timed("hals_spatial_lists"):
+        rc = lib.dnmf_hals_spatial_lists(A.data_ptr(), layout["At"].data_ptr(), A1c.data_ptr(), Cs.data_ptr(), _ptr(D),
+                                         float(gamma or 0.0), X, Y, Z, K, sl["tables"].data_ptr(), b.data_ptr(), sweeps, _ptr(out),
+                                         _ptr(ws), _nbytes(ws), _stream())
+    _lib.check(rc, "dnmf_hals_spatial_lists")
+    return (A, out) if kkt else A
+
+
+def dilate_boxes(bbox, sz, grow):
+    """(K,6) int32 boxes grown by ``grow`` voxels -- an int or (gx, gy, gz) -- on every side and clipped to the volume; an
+    empty box (lo > hi on an axis) stays as it is."""
+    g = [int(v) for v in grow] if hasattr(grow, "__len__") else [int(grow)] * 3
+    if len(g) != 3 or min(g) < 0:
+        raise ValueError(f"grow={grow!r}: a number of voxels >= 0 or three of them")
+    b = bbox.to(torch.int32)
+    lo, hi = b[:, 0::2], b[:, 1::2]
+    full = (lo <= hi).all(1, keepdim=True)
+    gt = torch.tensor(g, dtype=torch.int32, device=b.device)
+    top = torch.tensor([int(s) - 1 for s in sz], dtype=torch.int32, device=b.device)
+    out = torch.empty_like(b)
+    out[:, 0::2] = torch.where(full, (lo - gt).clamp_min(0), lo)
+    out[:, 1::2] = torch.where(full, torch.minimum(hi + gt, top), hi)
+    return out.contiguous()
+
+
 def pack_footprints_lists(A, sz):
     """Layout of K3n: dict(At (K,P), bbox (K,6) int32, pair_slot (K,K) int32, nslot int, boxfrac) -- ``boxfrac`` is
     the summed volume of the footprint boxes over the volume, i.e. the mean number of listed neurons per voxel."""

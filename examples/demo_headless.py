@@ -4,7 +4,7 @@ plots, against this repository's drop-in ``Demix.dNMF``.  Prints how well the re
 truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
-                                        [--evaluate] [--merge]
+                                        [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -14,6 +14,9 @@ correlation of the simulator's traces with ``C`` and with ``b + c``, and the med
 of the RMS difference between the simulator's traces and ``C`` before and after, beside the correlation, which the map leaves alone.
 ``--merge``: last of all, merge the components that sit on one cell (``DeformableNMF.merge_components``, K26) and print the groups
 and K before and after.
+``--spatial-solver hals``: also update the footprints after every temporal update (``update_footprints(live_spatial=True)``) with
+the exact solver K6h: ``--iter-a`` sweeps (default 5) on supports grown by ``--grow`` voxels (default 0), one K5 pass each time;
+``--spatial-solver mu``: ``--iter-a`` multiplicative updates (K6) instead.  Prints the per-neuron KKT figure of the last step.
 """
 import argparse
 import os
@@ -39,6 +42,9 @@ def main():
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--spatial-solver", choices=("mu", "hals"), default=None)
+    ap.add_argument("--grow", type=int, default=0)
+    ap.add_argument("--iter-a", type=int, default=5)
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -55,7 +61,12 @@ def main():
     optimizer = optim.Adam([dnmf.fp.beta], lr=1e-5)
     for _ in range(a.outer):
         dnmf.update_motion(dataloader, optimizer, gamma=1, epochs=a.epochs)
-        A_t, Y_i, Y = dnmf.update_footprints(testloader, batch_size, sz, gamma_c=0, iter_c=a.iter_c)
+        spatial = {} if a.spatial_solver is None else dict(live_spatial=True, spatial_solver=a.spatial_solver, iter_a=a.iter_a,
+                                                           grow=a.grow)
+        A_t, Y_i, Y = dnmf.update_footprints(testloader, batch_size, sz, gamma_c=0, iter_c=a.iter_c, **spatial)
+    if a.spatial_solver == "hals":
+        print("footprint KKT after the last step: max %.3e  median %.3e"
+              % (float(dnmf.last_spatial_kkt.max()), float(dnmf.last_spatial_kkt.median())))
     C = dnmf.C.cpu().numpy()
     corr = [np.corrcoef(C[k], dataset.traces[k])[0, 1] for k in range(K)]
     print("A_t", A_t.shape, "Y_i", Y_i.shape, "Y", Y.shape)

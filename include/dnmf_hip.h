@@ -408,6 +408,32 @@ int dnmf_spatial_accum_lists_channels(const float *Y, long ldy, long ldyc, int n
 int dnmf_mu_spatial_lists(float *A, const float *At, float *A1c, const float *Cs, const float *D, double gamma, int X, int Y, int Z,
                           int K, const int *tables, dnmf_stream_t stream);
 
+/* ---- K6h: exact NNLS footprint update (HALS / cyclic coordinate descent), beside the multiplicative update K6 ---------
+ * Not in the reference.  On the sums of K5 the footprint problem separates by voxel:
+ *   min 1/2 a^T Cs a - A1[p]^T a + gamma D[p]^T a ,  a >= 0 ,  over the neurons whose box holds voxel p
+ * (summed over p: 1/2 |Y_i - A C|^2 + gamma sum D o A up to a constant).  One sweep, k ascending over those neurons:
+ *   g = sum_l a_l Cs[l,k] - A1[p,k] + gamma D[p,k]  (l over the same neurons, ascending, current values)
+ *   a_k <- max(0, a_k - g / Cs[k,k])                (Cs[k,k] <= 0 or not finite: a_k stays)
+ * A box is (xlo, xhi, ylo, yhi, zlo, zhi), inclusive (the bbox of dnmf_pack_footprints_lists, possibly dilated); a value
+ * outside its neuron's box is zero and stays zero.  State and g are float64, `sweeps` >= 1 sweeps run in one launch and
+ * the state is rounded to fp32 once; no floating-point atomics, the same bits on every run, and the two forms give the
+ * same bits on the same sums.  kkt (K) float64 or NULL: per neuron the largest |pg| over its box, pg = g where a > 0,
+ * else min(g, 0), of the float64 state after the last sweep (zero exactly at the solution).
+ * dnmf_hals_spatial: A, A1, D (or NULL) as (P,K), in place; boxes (K,6) or NULL (every voxel free; X, Y, Z then unused,
+ *   else X Y Z = P); values outside the boxes are written as 0.
+ * dnmf_hals_spatial_kkt: kkt of a stored fp32 A for the given sums; A is only read.
+ * dnmf_hals_spatial_lists: the arguments of dnmf_mu_spatial_lists plus bbox (K,6), the boxes the tables were made from;
+ *   A1c in = the sums, out = the new values.  With kkt a workspace of dnmf_hals_spatial_lists_workspace bytes holds the
+ *   per-(tile, slot) maxima a second launch reduces per neuron. */
+int dnmf_hals_spatial(float *A, const float *A1, const float *Cs, const float *D, double gamma, long P, int K, int sweeps,
+                      const int *boxes, int X, int Y, int Z, double *kkt, dnmf_stream_t stream);
+int dnmf_hals_spatial_kkt(const float *A, const float *A1, const float *Cs, const float *D, double gamma, long P, int K,
+                          const int *boxes, int X, int Y, int Z, double *kkt, dnmf_stream_t stream);
+size_t dnmf_hals_spatial_lists_workspace(int X, int Y, int Z);
+int dnmf_hals_spatial_lists(float *A, const float *At, float *A1c, const float *Cs, const float *D, double gamma, int X, int Y, int Z,
+                            int K, const int *tables, const int *bbox, int sweeps, double *kkt, void *workspace,
+                            size_t workspace_bytes, dnmf_stream_t stream);
+
 /* ---- K8: position initialiser ----------------------------------------------------------------------
  * Reference: Demix/MotionCorrect.py -- MotionCorrect.motion_correct_pwrigid :260-328 -> tile_and_correct_3d :1518-1608
  * (per frame: rigid shift, then one shift per patch inside rigid +- max_deviation_rigid; register_translation_3d :648-797 with
