@@ -614,6 +614,8 @@ class DeformableNMF:
         self.last_evaluation = None
         # after merge_components: pairs, overlap, corr, groups, merged and K of that call
         self.last_merge = None
+        # after clean_footprints: the eight per-neuron statistics and the boxes of that call
+        self.last_footprint_clean = None
         self._warned = set()
 
     @classmethod
@@ -1139,6 +1141,59 @@ class DeformableNMF:
         for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
             setattr(self, name, None)
         self.last_merge = result
+        return result
+
+    def clean_footprints(self, method='nrg', nrgthr=0.9999, maxthr=0.2, median=True, closing=True, values='filtered', floor=1e-3,
+                         margin=1, dry_run=False):
+        """Clean the learned footprints (K27; tests/footprint_clean_restatement.py is the definition, and ``ops.clean_footprints``
+        has its bits).  An exact spatial solve (``spatial_solver='hals'`` with ``grow``) revives any voxel of a neuron's box
+        where the noise happens to follow the trace: a learned footprint is then a cell plus isolated voxels, pinholes and
+        sometimes a piece of a neighbour.  Per neuron, on its box (``ops.component_boxes(fp.A, sz, floor, margin)``; margin 1
+        keeps the dilation from being clipped): the 3 x 3 x 3 median (``median``), the cut (``method='nrg'``: the largest values
+        holding ``nrgthr`` of the energy; ``'max'``: above ``maxthr`` times the maximum), the closing (``closing``) and the
+        largest face-connected part; the result holds the median (``values='filtered'``) or the learned values
+        (``'original'``) on that part and 0 elsewhere.  Call it between sweeps, before ``evaluate_components`` or
+        ``merge_components``.
+        A neuron that cannot be cleaned -- no positive value or a non-finite one (it gets a one-voxel box), a negative value in
+        its box, nothing left by the cut -- keeps its column bit for bit and has ``ok = 0``: the step never deletes a component.
+        A box of more than 4096 voxels of a neuron with a positive value is a ValueError.
+        ``fp.A`` is replaced in place; every packed layout, K-shaped cache and ``last_*`` result is forgotten as in
+        ``select_components``; ``C``, ``pos``, ``sigma``, ``D`` and the warp stay.  Returns, and stores in
+        ``self.last_footprint_clean``, a dict of (K,) CUDA tensors: int32 ``ok``, ``n_box``, ``n_cut``, ``n_closed``, ``n_parts``,
+        ``n_kept``, float64 ``threshold`` and ``energy``, and ``boxes`` (K, 6) int32.  ``dry_run=True`` computes the dict and
+        leaves the model bit for bit, ``last_footprint_clean`` included.  One channel and one process only."""
+        who = "clean_footprints"
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        if self.group is not None:
+            raise NotImplementedError(f"{who}: the model holds a shard of the frames (every rank would have to clean alike)")
+        fp = self.fp
+        sz, P, K = fp.sz_list, fp.P, fp.K
+        with torch.no_grad():
+            if not fp.A.is_contiguous():
+                fp.A = fp.A.contiguous()
+            A = fp.A.detach().view(P, K)
+            boxes = ops.component_boxes(fp.A.detach(), sz, floor=floor, margin=margin)
+            # a column that cannot be cleaned gets a one-voxel box that says so: its first value that is not finite, else, where
+            # none is positive, the voxel 0
+            odd = ~torch.isfinite(A)
+            at = torch.where(odd.any(0), odd.to(torch.uint8).argmax(0), 0)
+            hopeless = odd.any(0) | ~(A > 0).any(0)
+            one = torch.stack((at // (sz[1] * sz[2]), at // sz[2] % sz[1], at % sz[2]), 1).repeat_interleave(2, 1).to(torch.int32)
+            boxes = torch.where(hopeless[:, None], one, boxes)
+            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
+            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
+                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
+                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            A_new, stats = ops.clean_footprints(A, sz, boxes, method=method, nrgthr=nrgthr, maxthr=maxthr, median=median,
+                                                closing=closing, values=values, out=None if dry_run else A)
+        result = dict(stats, boxes=boxes)
+        if dry_run:
+            return result
+        fp.invalidate_layouts()
+        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
+            setattr(self, name, None)
+        self.last_footprint_clean = result
         return result
 
     def _background_refusals(self, loader, who):

@@ -1,4 +1,4 @@
-// What the analysis kernels (K11 .. K13, K18 .. K26) share: wave and workgroup reductions in a fixed order, order statistics on
+// What the analysis kernels (K11 .. K13, K18 .. K27) share: wave and workgroup reductions in a fixed order, order statistics on
 // the monotone 64-bit key of a float64 (one by bisection, many by a workgroup sort), and the host-side plan of a call whose frames
 // go in segments.  The hot path (K2, K3*, K4*,
 // K7, K16) keeps its own fp32 reductions (common.hpp: wave_sum_last).

@@ -2310,6 +2310,76 @@ def merge_apply(A, C, plan, A_out=None, C_out=None):
     return A_out, C_out
 
 
+# ---- K27: cleaning the footprints ---------------------------------------------------------------------------------------------------
+CLEAN_METHODS = {"nrg": 0, "max": 1}              # the method and values arguments of dnmf_clean_footprints
+CLEAN_VALUES = {"filtered": 0, "original": 1}
+CLEAN_STATS = ("ok", "n_box", "n_cut", "n_closed", "n_parts", "n_kept")     # the int32 columns it writes
+
+
+def clean_footprints(A, sz, boxes, method='nrg', nrgthr=0.9999, maxthr=0.2, median=True, closing=True, values='filtered', out=None):
+    """K27.  Clean every footprint on its box, tests/footprint_clean_restatement.py on the GPU, bit for bit: the 3 x 3 x 3 median of
+    the volume (``median``; 3 x 3 x 1 at Z = 1, coordinates clamped), the cut -- ``method='nrg'``: the largest values that hold
+    ``nrgthr`` of the box's energy, every tie of the threshold kept; ``'max'``: the values above ``maxthr`` times the maximum --,
+    the morphological closing by the full 3 x 3 x 3 element (``closing``), and of what is left the largest face-connected part
+    by voxel count, a tie to the part with the lowest linear index.  On that part the result is the median (``values=
+    'filtered'``) or the input (``'original'``), 0 on the rest of the column.  ``A`` (P, K) or (X, Y, Z, K) fp32 CUDA, K fastest;
+    ``boxes`` (K, 6) int32 inclusive boxes of at most 4096 voxels (``component_boxes``), checked on the host before the launch:
+    one synchronisation where they come from the GPU.  Returns ``(A_out, stats)``: ``A_out`` in the shape of ``A`` -- ``out``
+    when given, which may be ``A`` itself -- and a dict of (K,) CUDA tensors: int32 ``ok``, ``n_box``, ``n_cut``, ``n_closed``,
+    ``n_parts``, ``n_kept``, float64 ``threshold`` and ``energy`` (NaN for 'max').  A neuron whose box holds a negative or
+    non-finite value or no positive one, or of which the cut keeps nothing, is refused, not deleted: ``ok = 0``, its column
+    comes back bit for bit, its other counts are 0 and its threshold NaN.  No floating-point atomics and one sequential
+    float64 sum: the same input gives the same bits."""
+    fn = "clean_footprints"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if method not in CLEAN_METHODS or values not in CLEAN_VALUES:
+        raise ValueError(f"{fn}: method is one of {sorted(CLEAN_METHODS)} and values one of {sorted(CLEAN_VALUES)}, got {method!r} "
+                         f"and {values!r}")
+    if method == 'nrg' and not 0.0 < float(nrgthr) <= 1.0:
+        raise ValueError(f"{fn}: nrgthr={nrgthr} outside (0, 1]")
+    if method == 'max' and not float(maxthr) >= 0.0:
+        raise ValueError(f"{fn}: maxthr={maxthr}, not >= 0")
+    if not torch.is_tensor(A) or A.dim() not in (2, 4):
+        raise ValueError(f"{fn}: A is a (P, K) or (X, Y, Z, K) tensor")
+    _f32(A, f"{fn}: A")
+    K = A.shape[-1]
+    if K < 1 or A.numel() != P * K or (A.dim() == 4 and tuple(A.shape[:3]) != (X, Y, Z)):
+        raise ValueError(f"{fn}: A must be ({P}, K) or ({X}, {Y}, {Z}, K), got {tuple(A.shape)}")
+    dev = A.device
+    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
+    if tuple(bh.shape) != (K, 6):
+        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
+    lo, hi = bh[:, 0::2].long(), bh[:, 1::2].long()
+    limit = torch.tensor([X, Y, Z])
+    wrong = ((lo < 0) | (hi >= limit) | (lo > hi)).any(1)
+    if bool(wrong.any()):
+        k = int(torch.nonzero(wrong)[0])
+        raise ValueError(f"{fn}: box {k} = {bh[k].tolist()} is empty or outside the volume {X}x{Y}x{Z}")
+    n = (hi - lo + 1).prod(1)
+    if int(n.max()) > COMPONENT_MAX_VOXELS:
+        raise ValueError(f"{fn}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most {COMPONENT_MAX_VOXELS}")
+    if out is None:
+        out = torch.empty_like(A)
+    else:
+        _f32(out, f"{fn}: out")
+        if tuple(out.shape) != tuple(A.shape) or out.device != dev:
+            raise ValueError(f"{fn}: out must be {tuple(A.shape)} on {dev}, got {tuple(out.shape)} on {out.device}")
+    bd = bh.to(dev)
+    istats = torch.empty((K, len(CLEAN_STATS)), dtype=torch.int32, device=dev)
+    dstats = torch.empty((K, 2), dtype=torch.float64, device=dev)
+    lib = _lib.load()
+    ws = _workspace(None, _need(lib, "dnmf_clean_footprints_workspace", K), dev)
+    with _timed("clean_footprints"):
+        rc = lib.dnmf_clean_footprints(A.data_ptr(), K, _int3((X, Y, Z)), bh.data_ptr(), bd.data_ptr(), K, CLEAN_METHODS[method],
+                                       float(nrgthr), float(maxthr), 1 if median else 0, 1 if closing else 0, CLEAN_VALUES[values],
+                                       out.data_ptr(), K, istats.data_ptr(), dstats.data_ptr(), ws.data_ptr(), _nbytes(ws), _stream())
+    _lib.check(rc, "dnmf_clean_footprints")
+    stats = {name: istats[:, q] for q, name in enumerate(CLEAN_STATS)}
+    stats["threshold"], stats["energy"] = dstats[:, 0], dstats[:, 1]
+    return out, stats
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -5,6 +5,7 @@ truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
                                         [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
+                                        [--clean-footprints]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -12,6 +13,8 @@ print the median correlation of the simulator's traces with ``C`` and with the c
 correlation of the simulator's traces with ``C`` and with ``b + c``, and the median estimated decay beside the simulator's e^-0.3.
 ``--match``: also put the traces in the simulator's units (``DeformableNMF.match_traces``, K25) and print the median over neurons
 of the RMS difference between the simulator's traces and ``C`` before and after, beside the correlation, which the map leaves alone.
+``--clean-footprints``: after the fit, clean the footprints (``DeformableNMF.clean_footprints``, K27: median, energy cut, closing,
+largest part) and print each neuron's box, kept voxels and parts.
 ``--merge``: last of all, merge the components that sit on one cell (``DeformableNMF.merge_components``, K26) and print the groups
 and K before and after.
 ``--spatial-solver hals``: also update the footprints after every temporal update (``update_footprints(live_spatial=True)``) with
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--clean-footprints", action="store_true")
     ap.add_argument("--spatial-solver", choices=("mu", "hals"), default=None)
     ap.add_argument("--grow", type=int, default=0)
     ap.add_argument("--iter-a", type=int, default=5)
@@ -67,6 +71,13 @@ def main():
     if a.spatial_solver == "hals":
         print("footprint KKT after the last step: max %.3e  median %.3e"
               % (float(dnmf.last_spatial_kkt.max()), float(dnmf.last_spatial_kkt.median())))
+    if a.clean_footprints:
+        before = (dnmf.fp.A > 0).reshape(-1, K).sum(0).tolist()
+        fc = dnmf.clean_footprints()
+        print("clean_footprints: %d of %d neurons cleaned" % (int(fc["ok"].sum()), K))
+        for k in range(K):
+            print("  neuron %2d: n_box %4d  n_kept %4d  n_parts %2d  (voxels > 0 before: %d)"
+                  % (k, int(fc["n_box"][k]), int(fc["n_kept"][k]), int(fc["n_parts"][k]), before[k]))
     C = dnmf.C.cpu().numpy()
     corr = [np.corrcoef(C[k], dataset.traces[k])[0, 1] for k in range(K)]
     print("A_t", A_t.shape, "Y_i", Y_i.shape, "Y", Y.shape)

@@ -1015,6 +1015,38 @@ int dnmf_merge_apply(const float *A, long lda, long P, int K, const float *C, lo
                      const int *offsets_dev, const int *members_dev, int Kout, const double *u, const double *w, float *A_out, long ldao,
                      float *C_out, long ldco, dnmf_stream_t stream);
 
+/* ---- K27: cleaning the footprints: median, energy cut, closing, largest part (csrc/footprint_clean.hip) -----------------------------
+ * tests/footprint_clean_restatement.py is the definition; every output is an integer or a bit pattern, and an implementation has
+ * exactly these bits.  A = P rows of lda >= K floats (the (P, K) layout of the model's footprints, K fastest; voxel p = (x Y + y) Z +
+ * z), boxes (K, 6) int32 = (x0, x1, y0, y1, z0, z1) inclusive, as in K24.  Per neuron k, on its box (n voxels):
+ *   1  refused (ok = 0, the column of out = the column of A bit for bit) when a box value is not finite or is negative, when none is
+ *      positive, when a median of step 2 is such a value (possible only through taps outside the box), or when step 3 keeps nothing;
+ *   2  median = 1: m = the median of the 3 x 3 x 3 (Z == 1: 3 x 3 x 1) neighbourhood in the VOLUME, coordinates clamped to it
+ *      (scipy.ndimage.median_filter(mode='nearest')), the values ordered as IEEE totalOrder; median = 0: m = a;
+ *   3  method 0 ('nrg'): v = the box values of m, descending, cum[j] = the float64 sum of (double)v[i]^2 for i <= j added in that order,
+ *      j* = the first j with cum[j] >= nrgthr cum[n - 1], threshold = v[j*], keep = m >= threshold and m > 0 (every tie kept), energy =
+ *      cum[j*] / cum[n - 1];  method 1 ('max'): threshold = maxthr (double)max m, keep = (double)m > threshold, energy = NaN;
+ *   4  closing = 1: dilation by the full 3 x 3 x 3 element with 0 outside the box, then erosion with 1 outside the box;
+ *   5  the largest face-connected (6 neighbours) part by voxel count, a tie to the part that holds the lowest linear index;
+ *   6  out = m (values 0, 'filtered') or a (values 1, 'original') on that part, 0 on the rest of the column.
+ *   istats  (K, 6) int32: ok, n_box, n_cut, n_closed, n_parts, n_kept (the last four 0 with ok = 0)
+ *   dstats  (K, 2) doubles: threshold, energy (both NaN with ok = 0)
+ * Two launches, no host synchronisation: one workgroup of 256 lanes per neuron with the box in LDS (56 KiB) writes a compact (K, 4096)
+ * buffer in the workspace and the statistics; one thread per entry of out then writes the (P, K) result, K fastest.  The cumulative
+ * sum is formed by one lane in the order above (np.cumsum's additions); the parts by minimum-label propagation with a pointer jump,
+ * at most n rounds, whose fixed point does not depend on the schedule; sizes by integer LDS atomics.  No floating-point atomics: the
+ * same input gives the same bits.  out may be A itself (same pointer and row stride), and may not overlap it otherwise.
+ *   boxes      on the HOST: checked before anything is launched;  boxes_dev: the same array on the device
+ *   workspace  dnmf_clean_footprints_workspace(K) bytes (0: K < 1), 4-byte aligned
+ * DNMF_E_NULL: a NULL argument;  DNMF_E_SHAPE: a size or K < 1, lda or ldo < K, a switch outside {0, 1}, nrgthr outside (0, 1] (method
+ * 0), maxthr < 0 (method 1), a box that is empty or reaches outside the volume or holds more than 4096 voxels, out overlapping A;
+ * DNMF_E_WORKSPACE: a short or misaligned workspace;  DNMF_E_UNSUPPORTED: 2^31 voxels or 2^39 entries or more.  Nothing is launched on
+ * an error. */
+size_t dnmf_clean_footprints_workspace(int K);
+int dnmf_clean_footprints(const float *A, long lda, const int *sz, const int *boxes, const int *boxes_dev, int K, int method,
+                          double nrgthr, double maxthr, int median, int closing, int values, float *out, long ldo, int *istats,
+                          double *dstats, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
