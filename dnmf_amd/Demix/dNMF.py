@@ -616,6 +616,8 @@ class DeformableNMF:
         self.last_merge = None
         # after clean_footprints: the eight per-neuron statistics and the boxes of that call
         self.last_footprint_clean = None
+        # after add_components: centres, boxes, explained, energy, ok, kept, added and K of that call
+        self.last_add = None
         self._warned = set()
 
     @classmethod
@@ -1011,6 +1013,13 @@ class DeformableNMF:
     # what select_components forgets, with every last_* result: the caches and workspaces with a K-shaped extent
     _K_SHAPED = ("_ws_k2", "_ws_k3", "_S_bufs", "_S_zero", "_gram_nbr", "_sl", "_ws_k5", "_spatial_buf", "_ws_mg", "_D_dev")
 
+    def _forget_k_shaped(self):
+        """The tail of every call that changes the components: the packed layouts of ``fp.A``, the caches and workspaces with a
+        K-shaped extent and every ``last_*`` result of an earlier call are forgotten."""
+        self.fp.invalidate_layouts()
+        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
+            setattr(self, name, None)
+
     def select_components(self, keep):
         """Shrink the model in place to the neurons ``keep`` -- a bool mask (K,) or indices, e.g. ``evaluate_components(...)
         ['keep']`` -- in the order given (a mask: ascending): ``fp.A``, ``fp.pos``, ``fp.sigma``, ``fp.K``, ``C``, ``D`` and
@@ -1045,9 +1054,7 @@ class DeformableNMF:
         fp.K = int(sel.numel())
         if hasattr(self, "K"):
             self.K = fp.K
-        fp.invalidate_layouts()
-        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
-            setattr(self, name, None)
+        self._forget_k_shaped()
         return fp.K
 
     def merge_components(self, thr=0.85, min_overlap=0.1, floor=1e-3, margin=0, traces=None, iters=10, dry_run=False):
@@ -1137,9 +1144,7 @@ class DeformableNMF:
         fp.K = len(groups)
         if hasattr(self, "K"):
             self.K = fp.K
-        fp.invalidate_layouts()
-        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
-            setattr(self, name, None)
+        self._forget_k_shaped()
         self.last_merge = result
         return result
 
@@ -1190,10 +1195,152 @@ class DeformableNMF:
         result = dict(stats, boxes=boxes)
         if dry_run:
             return result
-        fp.invalidate_layouts()
-        for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
-            setattr(self, name, None)
+        self._forget_k_shaped()
         self.last_footprint_clean = result
+        return result
+
+    def add_components(self, loader, n, image='corr', registered='linear', shape_std=None, half=None, min_distance=None,
+                       threshold=0.0, iters=5, min_explained=0.5, centres=None, dry_run=False):
+        """Grow the model by the neurons it has no component for (K28; tests/add_restatement.py is the definition).  ``K`` is
+        fixed at construction: a neuron that ``detect_positions`` missed on the template never enters the fit, and shows as a
+        blob in ``summary_images(source='residual')``.  This call closes the loop without rebuilding the model.
+        Candidates: up to ``n`` centres found by K14 (``ops.detect_neurons`` with ``shape_std`` -- default the median of
+        ``fp.sigma`` --, ``min_distance`` -- default 2 ``shape_std`` -- and ``threshold``) in the residual summary image
+        ``image`` (``'corr'``, ``'mean'``, ``'std'`` or ``'max'`` of ``summary_images(loader, 'residual', registered)``; a voxel
+        that is NaN there gets the image's median); those within ``min_distance`` of an existing ``fp.pos`` are dropped.
+        ``centres`` (M, 3) skips the detection and the drop: the caller's centres are taken as they are.
+        Fit: the box of a candidate is its centre +- ``half`` voxels (``ops.candidate_boxes``; default ceil(2 ``shape_std``) per
+        axis, 0 along an axis of extent 1), the start the model's Gaussian exp(-|u - centre|^2 / shape_std^2) on the box.  The
+        frames ``loader`` serves go through K28a (``ops.residual_boxes``) in pieces of at most 1 GiB, registered first as in
+        ``evaluate_components`` (``registered``), with the model's prediction ``fp.recon_image`` subtracted; K28b
+        (``ops.rank1_nmf``, ``iters`` rounds) then factors every box's residual in one launch (candidates in batches whose
+        residual stays within 1 GiB).  All candidates are fitted on the same residual, independently of each other -- not the
+        sequential pick, fit, subtract of the greedy initialisers: two picks on one cell both come out as that cell and are
+        left to ``merge_components``.
+        A candidate is kept when its ``ok`` is set and ``explained / energy >= min_explained``: the share of its box's residual
+        energy that a c^T takes off.  ``min_explained`` is a parameter, not a tolerance: its default sits in the gap that a
+        planted video leaves (tests/test_add_host.py measures it, 24 x 20 x {1, 2}, T = 40, three seeds): the two cells the
+        model lacks score 0.782 to 0.947 (their learned footprints correlate with the planted ones at 0.990 or more, the
+        Gaussian start at 0.93), a box on nothing 0.076 or less.  A weak pick whose box takes in part of a missing cell is no
+        box on nothing: it scores like the cell (0.89 and 0.90 measured where a noise peak lay 6 voxels from one), and is the
+        case ``threshold`` or a following ``merge_components`` is for.
+        For each candidate kept the model grows in place: ``fp.A`` gets a column (a scattered into a zero volume), ``fp.pos``
+        the centre of mass of a, ``fp.sigma`` ``shape_std``, ``C`` a row (c at the times of the frames served; 0 at the others
+        and on a frame with a sample that is not finite in the box), the unused ``self.A`` a zero row, ``D`` (when not None)
+        the constructor's 1 - exp(-0.01 distance) in float64; ``fp.K`` and ``K`` go up, ``fp.beta`` stays.  Every packed
+        layout, K-shaped cache and ``last_*`` result is forgotten as in ``select_components``.
+        Returns, and stores in ``self.last_add``, a dict: ``centres`` (M, 3) float32 and ``boxes`` (M, 6) int32, float64
+        ``explained`` and ``energy`` (M,), int32 ``ok`` (M,), bool ``kept`` (M,) -- CUDA tensors --, ``added`` their number and
+        ``K`` the component count with them.  ``dry_run=True`` computes the dict and leaves the model bit for bit
+        (``last_add`` apart); so does a call that keeps nothing.  One channel and one process only."""
+        who = "add_components"
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
+            raise NotImplementedError(f"{who}: the model or the loader holds a shard of the frames (every rank would have to add "
+                                      "alike)")
+        if int(n) < 1:
+            raise ValueError(f"{who}: n={n!r} candidates, at least 1")
+        if image not in ('corr', 'mean', 'std', 'max'):
+            raise ValueError(f"{who}: image must be 'corr', 'mean', 'std' or 'max', got {image!r}")
+        if registered is not None:
+            _check_registered(registered, who)
+        fp = self.fp
+        sz, P, K = fp.sz_list, fp.P, fp.K
+        sigma = float(fp.sigma.median()) if shape_std is None else float(shape_std)
+        if not (sigma > 0.0 and math.isfinite(sigma)):
+            raise ValueError(f"{who}: shape_std={shape_std!r} must be positive and finite")
+        md = 2.0 * sigma if min_distance is None else float(min_distance)
+        if half is None:
+            half = [0 if s == 1 else int(math.ceil(2.0 * sigma)) for s in sz]
+        with torch.no_grad():
+            if centres is None:
+                img = self.summary_images(loader, 'residual', registered)[image]
+                img = torch.where(torch.isnan(img), torch.nanmedian(img), img).to(torch.float32).contiguous()
+                pos, _, count = ops.detect_neurons(img, sz, int(n), shape_std=sigma, min_distance=md, threshold=threshold)
+                cand = pos[:int(count)]
+                if cand.shape[0]:
+                    far = torch.cdist(cand.double(), fp.pos.detach().to(device).double()).amin(1) > md
+                    cand = cand[far]
+            else:
+                cand = torch.as_tensor(centres).detach().to(device, torch.float32).reshape(-1, 3)
+            M = cand.shape[0]
+            f64 = dict(dtype=torch.float64, device=device)
+            result = dict(centres=cand.contiguous(), boxes=torch.zeros((0, 6), dtype=torch.int32, device=device),
+                          explained=torch.zeros(0, **f64), energy=torch.zeros(0, **f64),
+                          ok=torch.zeros(0, dtype=torch.int32, device=device), kept=torch.zeros(0, dtype=torch.bool, device=device),
+                          added=0, K=K)
+            if M == 0:
+                self.last_add = result
+                return result
+            boxes = ops.candidate_boxes(cand, sz, half)
+            bh = boxes.cpu().numpy()
+            ch = cand.cpu().numpy().astype(np.float64)
+            nvox = (bh[:, 1::2] - bh[:, 0::2] + 1).astype(np.int64).prod(1)
+            vmax = int(nvox.max())
+            if vmax > ops.COMPONENT_MAX_VOXELS:
+                raise ValueError(f"{who}: the box of candidate {int(nvox.argmax())} holds {vmax} voxels, at most "
+                                 f"{ops.COMPONENT_MAX_VOXELS} (lower half)")
+            # the start and the box coordinates on the host: M and vmax are small, and the centres had to come here anyway
+            coords, a0 = [], np.zeros((M, vmax), dtype=np.float32)
+            for m, b in enumerate(bh):
+                g = np.meshgrid(*(np.arange(b[2 * d], b[2 * d + 1] + 1) for d in range(3)), indexing="ij")
+                u = np.stack(g, -1).reshape(-1, 3).astype(np.float64)
+                coords.append(u)
+                a0[m, :u.shape[0]] = np.exp(-((u - ch[m][None, :]) ** 2).sum(1) / sigma ** 2)
+            frames, order = self._gather_frames(loader)
+            if not bool((order[1:] > order[:-1]).all()):
+                at = torch.argsort(order.long())
+                frames, order = frames.index_select(0, at), order[at]
+            T = frames.shape[0]
+            if T > ops.ADD_MAX_FRAMES:
+                raise ValueError(f"{who}: the loader serves {T} frames, at most {ops.ADD_MAX_FRAMES}")
+            C = self.C.to(device, torch.float32).contiguous()
+            step = max(1, min(T, (1 << 30) // (4 * P)))
+            batch = max(1, min(M, (1 << 30) // (4 * T * vmax)))
+            fits = []
+            for m0 in range(0, M, batch):
+                E = torch.empty((min(batch, M - m0), T, vmax), dtype=torch.float32, device=device)
+                for s in range(0, T, step):
+                    fr, tt = frames[s:s + step], order[s:s + step]
+                    sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
+                    if registered is not None:
+                        fr = fp.registered_video(fr, times=tt, interpolation=registered)
+                    ops.residual_boxes(fr, sz, boxes[m0:m0 + batch], sub=sub, out=E, t0=s, n_total=T)
+                fits.append(ops.rank1_nmf(E, nvox[m0:m0 + batch], torch.from_numpy(a0[m0:m0 + batch]).to(device), iters=iters))
+                del E
+            fit = {name: torch.cat([f[name] for f in fits], 0) for name in fits[0]}
+            kept = (fit["ok"] == 1) & (fit["explained"] / fit["energy"] >= float(min_explained))     # a NaN compares False
+            idx = torch.nonzero(kept).reshape(-1).tolist()
+            result.update(boxes=boxes, explained=fit["explained"], energy=fit["energy"], ok=fit["ok"], kept=kept, added=len(idx),
+                          K=K + len(idx))
+            if dry_run or not idx:
+                self.last_add = result
+                return result
+            ah = fit["a"].cpu().numpy()
+            cols = torch.zeros((P, len(idx)), dtype=torch.float32, device=device)
+            rows = torch.zeros((len(idx), C.shape[1]), dtype=torch.float32, device=device)
+            com = np.zeros((len(idx), 3), dtype=np.float64)
+            for q, m in enumerate(idx):
+                am = ah[m, :nvox[m]].astype(np.float64)
+                com[q] = (am[:, None] * coords[m]).sum(0) / am.sum()
+                u = torch.from_numpy(coords[m].astype(np.int64)).to(device)
+                cols[(u[:, 0] * sz[1] + u[:, 1]) * sz[2] + u[:, 2], q] = fit["a"][m, :nvox[m]]
+                rows[q, order.long()] = torch.nan_to_num(fit["c"][m], nan=0.0)
+            pos_new = torch.from_numpy(com).to(fp.pos.dtype)
+            fp.A = torch.cat((fp.A.detach().reshape(P, K), cols), 1).reshape(*sz, K + len(idx)).contiguous()
+            fp.pos = torch.cat((fp.pos.detach(), pos_new.to(fp.pos.device)), 0)
+            fp.sigma = torch.cat((fp.sigma, torch.full((len(idx),), sigma, dtype=fp.sigma.dtype, device=fp.sigma.device)), 0)
+            self.C = torch.cat((C, rows), 0).to(self.C.dtype)
+            self.A = torch.cat((self.A, torch.zeros((len(idx),) + tuple(self.A.shape[1:]), dtype=self.A.dtype, device=self.A.device)), 0)
+            if self.D is not None:
+                d = torch.cdist(fp.flow_id.reshape(-1, 3).double(), pos_new.to(device).double())
+                self.D = np.concatenate((self.D, (1 - torch.exp(-.01 * d)).reshape(*sz, len(idx)).cpu().numpy()), -1)
+        fp.K = K + len(idx)
+        if hasattr(self, "K"):
+            self.K = fp.K
+        self._forget_k_shaped()
+        self.last_add = result
         return result
 
     def _background_refusals(self, loader, who):

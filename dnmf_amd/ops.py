@@ -2380,6 +2380,133 @@ def clean_footprints(A, sz, boxes, method='nrg', nrgthr=0.9999, maxthr=0.2, medi
     return out, stats
 
 
+# ---- K28: new components from the residual -----------------------------------------------------------------------------------------
+ADD_MAX_CANDIDATES = 4096      # the limits of dnmf_residual_boxes / dnmf_rank1_nmf; a box holds at most COMPONENT_MAX_VOXELS
+ADD_MAX_FRAMES = 18432
+
+
+def candidate_boxes(centres, sz, half):
+    """(M, 6) int32 ``(x0, x1, y0, y1, z0, z1)``, inclusive, on the centres' device (the CPU for a list): per centre (M, 3) the voxel
+    floor(centre + 0.5), moved into the volume, +- ``half`` voxels (one number or one per axis), cut to the volume -- the boxes
+    ``residual_boxes`` takes."""
+    X, Y, Z = (int(s) for s in sz)
+    c = torch.as_tensor(centres).detach()
+    if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] < 1:
+        raise ValueError(f"candidate_boxes: centres must be (M, 3), got {tuple(c.shape)}")
+    if not bool(torch.isfinite(c.double()).all()):
+        raise ValueError("candidate_boxes: a centre is not finite")
+    h = [int(half)] * 3 if isinstance(half, (int, float)) else [int(v) for v in half]
+    if len(h) != 3 or min(h) < 0:
+        raise ValueError(f"candidate_boxes: half={half!r} is one number >= 0 or one per axis")
+    vox = torch.floor(c.double() + 0.5).long()
+    boxes = torch.empty((c.shape[0], 6), dtype=torch.int32, device=c.device)
+    for d, S in enumerate((X, Y, Z)):
+        v = vox[:, d].clamp(0, S - 1)
+        boxes[:, 2 * d] = (v - h[d]).clamp_min(0)
+        boxes[:, 2 * d + 1] = (v + h[d]).clamp_max(S - 1)
+    return boxes
+
+
+def _candidate_boxes(fn, boxes, sz):
+    """The host copy of ``boxes`` (M, 6), checked, and the voxels of each."""
+    X, Y, Z = (int(s) for s in sz)
+    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
+    if bh.dim() != 2 or bh.shape[1] != 6 or bh.shape[0] < 1:
+        raise ValueError(f"{fn}: boxes must be (M, 6), got {tuple(bh.shape)}")
+    if bh.shape[0] > ADD_MAX_CANDIDATES:
+        raise ValueError(f"{fn}: {bh.shape[0]} candidates, at most {ADD_MAX_CANDIDATES}")
+    lo, hi = bh[:, 0::2].long(), bh[:, 1::2].long()
+    wrong = ((lo < 0) | (hi >= torch.tensor([X, Y, Z])) | (lo > hi)).any(1)
+    if bool(wrong.any()):
+        m = int(torch.nonzero(wrong)[0])
+        raise ValueError(f"{fn}: box {m} = {bh[m].tolist()} is empty or outside the volume {X}x{Y}x{Z}")
+    n = (hi - lo + 1).prod(1)
+    if int(n.max()) > COMPONENT_MAX_VOXELS:
+        raise ValueError(f"{fn}: box {int(n.argmax())} holds {int(n.max())} voxels, at most {COMPONENT_MAX_VOXELS}")
+    return bh, n
+
+
+def residual_boxes(frames, sz, boxes, sub=None, frame_ids=None, out=None, t0=0, n_total=None):
+    """K28a.  The residual on candidate boxes -> ``E (M, n_total, vmax)`` fp32 CUDA: ``E[m, t0 + f, j] = frames_f(v_j) -
+    sub_f(v_j)`` (one fp32 subtraction; the frame itself without ``sub``) for the voxels v_j of box m, x slowest as K24 numbers
+    them; 0 for j past the box's voxels; a sample that is not finite is copied as it is.  ``frames`` (rows, ld >= P) fp32 CUDA
+    rows in footprint coordinates, ``frame_ids``: the rows to take; ``sub`` (B, ld >= P): what the model predicts, row f for the
+    f-th frame of the call; ``boxes`` (M, 6) int32 inclusive boxes inside the volume, of at most 4096 voxels
+    (``candidate_boxes``).  A movie larger than one buffer goes in pieces: ``out`` = the E of the earlier calls, ``t0`` the first
+    frame this call writes, ``n_total`` the frames of the movie (default: t0 + this call's); vmax = ``out.shape[2]``, else the
+    largest box.  At most 4096 boxes and 18 432 frames."""
+    fn = "residual_boxes"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
+    dev = frames.device
+    bh, nvox = _candidate_boxes(fn, boxes, sz)
+    M, t0 = bh.shape[0], int(t0)
+    n = t0 + B if n_total is None else int(n_total)
+    if B < 1 or t0 < 0 or t0 + B > n:
+        raise ValueError(f"{fn}: {B} frames at t0={t0} do not fit the {n} frames of E")
+    if n > ADD_MAX_FRAMES:
+        raise ValueError(f"{fn}: {n} frames, at most {ADD_MAX_FRAMES}")
+    if out is None:
+        out = torch.empty((M, n, int(nvox.max())), dtype=torch.float32, device=dev)
+    else:
+        _f32(out, f"{fn}: out")
+        if out.dim() != 3 or tuple(out.shape[:2]) != (M, n) or out.shape[2] < int(nvox.max()) or out.device != dev:
+            raise ValueError(f"{fn}: out must be ({M}, {n}, >= {int(nvox.max())}) on {dev}, got {tuple(out.shape)} on {out.device}")
+    vmax = out.shape[2]
+    if vmax > COMPONENT_MAX_VOXELS:
+        raise ValueError(f"{fn}: vmax={vmax}, at most {COMPONENT_MAX_VOXELS}")
+    bd = bh.to(dev)
+    lib = _lib.load()
+    with _timed("residual_boxes"):
+        rc = lib.dnmf_residual_boxes(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
+                                     _int3((X, Y, Z)), B, bh.data_ptr(), bd.data_ptr(), M, out.data_ptr(), n, vmax, t0, _stream())
+    _lib.check(rc, "dnmf_residual_boxes")
+    return out
+
+
+def rank1_nmf(E, nvox, a0, iters=5, workspace=None):
+    """K28b.  Per candidate the non-negative rank-1 factor of its residual, tests/add_restatement.py (``rank1_nmf``) on the GPU.
+    ``E`` (M, n, vmax) fp32 CUDA (``residual_boxes``), ``nvox`` (M,) the voxels of each box, ``a0`` (M, vmax) fp32 CUDA the start.
+    Over the frames V whose ``nvox[m]`` samples are all finite, ``iters`` rounds of c_t = max(<a, e_t>, 0) / |a|^2 and a_j =
+    max(sum_t c_t e_tj, 0) / |c|^2, then a scaled to |a0| and one more c-step.  Returns a dict of CUDA tensors: ``a`` (M, vmax)
+    fp32, 0 past a box's voxels; ``c`` (M, n) fp32, NaN outside V; float64 ``energy`` = sum_{V, j} e^2, ``explained`` = 2 sum_t c_t
+    <a, e_t> - |a|^2 |c|^2, ``saa`` = |a|^2 and ``scc`` = |c|^2 (M,); int32 ``n_valid`` and ``ok`` (M,).  A candidate whose |a|^2
+    or |c|^2 becomes 0 or whose V is empty has ``ok = 0`` and NaN rows; nothing is raised.  float64 inside, sums in a fixed order,
+    one rounding to fp32, no atomics: the same input gives the same bits.  vmax <= 4096, M <= 4096, n <= 18 432, iters >= 1."""
+    fn = "rank1_nmf"
+    _f32(E, f"{fn}: E")
+    if E.dim() != 3:
+        raise ValueError(f"{fn}: E must be (M, n, vmax), got {tuple(E.shape)}")
+    M, n, vmax = E.shape
+    dev = E.device
+    if M < 1 or n < 1 or vmax < 1:
+        raise ValueError(f"{fn}: E must be (M, n, vmax) with every extent >= 1, got {tuple(E.shape)}")
+    if vmax > COMPONENT_MAX_VOXELS or M > ADD_MAX_CANDIDATES or n > ADD_MAX_FRAMES:
+        raise ValueError(f"{fn}: E {tuple(E.shape)} above the limits ({ADD_MAX_CANDIDATES}, {ADD_MAX_FRAMES}, {COMPONENT_MAX_VOXELS})")
+    if int(iters) < 1:
+        raise ValueError(f"{fn}: iters={iters} must be at least 1")
+    _f32(a0, f"{fn}: a0")
+    if tuple(a0.shape) != (M, vmax) or a0.device != dev:
+        raise ValueError(f"{fn}: a0 must be ({M}, {vmax}) on {dev}, got {tuple(a0.shape)} on {a0.device}")
+    nh = torch.as_tensor(nvox).detach().to("cpu", torch.int32).reshape(-1)
+    if nh.numel() != M or int(nh.min()) < 1 or int(nh.max()) > vmax:
+        raise ValueError(f"{fn}: nvox must hold {M} counts in [1, {vmax}]")
+    nd = nh.to(dev)
+    lib = _lib.load()
+    workspace = _workspace(workspace, _need(lib, "dnmf_rank1_nmf_workspace", M, n), dev)
+    a = torch.empty((M, vmax), dtype=torch.float32, device=dev)
+    c = torch.empty((M, n), dtype=torch.float32, device=dev)
+    stats = torch.empty((M, 4), dtype=torch.float64, device=dev)
+    info = torch.empty((2, M), dtype=torch.int32, device=dev)
+    with _timed("rank1_nmf"):
+        rc = lib.dnmf_rank1_nmf(E.data_ptr(), M, n, vmax, nd.data_ptr(), a0.data_ptr(), int(iters), a.data_ptr(), c.data_ptr(),
+                                stats.data_ptr(), info[0].data_ptr(), info[1].data_ptr(), workspace.data_ptr(), _nbytes(workspace),
+                                _stream())
+    _lib.check(rc, "dnmf_rank1_nmf")
+    return dict(a=a, c=c, energy=stats[:, 0], explained=stats[:, 1], saa=stats[:, 2], scc=stats[:, 3], n_valid=info[0], ok=info[1])
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

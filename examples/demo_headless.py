@@ -5,7 +5,7 @@ truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
                                         [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
-                                        [--clean-footprints]
+                                        [--clean-footprints] [--add N]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -15,6 +15,8 @@ correlation of the simulator's traces with ``C`` and with ``b + c``, and the med
 of the RMS difference between the simulator's traces and ``C`` before and after, beside the correlation, which the map leaves alone.
 ``--clean-footprints``: after the fit, clean the footprints (``DeformableNMF.clean_footprints``, K27: median, energy cut, closing,
 largest part) and print each neuron's box, kept voxels and parts.
+``--add N``: after the fit, look for up to N neurons the model has no component for in the residual (``DeformableNMF.add_components``,
+K28) and print each candidate's explained / energy and K before and after.
 ``--merge``: last of all, merge the components that sit on one cell (``DeformableNMF.merge_components``, K26) and print the groups
 and K before and after.
 ``--spatial-solver hals``: also update the footprints after every temporal update (``update_footprints(live_spatial=True)``) with
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--merge", action="store_true")
+    ap.add_argument("--add", type=int, default=0, metavar="N")
     ap.add_argument("--clean-footprints", action="store_true")
     ap.add_argument("--spatial-solver", choices=("mu", "hals"), default=None)
     ap.add_argument("--grow", type=int, default=0)
@@ -121,6 +124,13 @@ def main():
         print("component evaluation over %d active frames each: r_values %s" % (ev["n_active"], ev["r_values"].cpu().numpy()))
         print("snr %s" % ev["snr"].cpu().numpy())
         print("keep %s  (%d of %d)" % (ev["keep"].int().cpu().numpy(), int(ev["keep"].sum()), K))
+    if a.add:
+        out = dnmf.add_components(testloader, a.add)
+        np.set_printoptions(precision=3, suppress=True, linewidth=160)
+        print("add: %d candidates, explained/energy %s" % (len(out["kept"]), (out["explained"] / out["energy"]).cpu().numpy()))
+        print("kept %s" % out["kept"].int().cpu().numpy())
+        print("K %d -> %d  (%d added)" % (K, out["K"], out["added"]))
+        K = out["K"]
     if a.merge:
         out = dnmf.merge_components()
         off = out["pairs"][:, 0] != out["pairs"][:, 1]

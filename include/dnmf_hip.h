@@ -1047,6 +1047,45 @@ int dnmf_clean_footprints(const float *A, long lda, const int *sz, const int *bo
                           double nrgthr, double maxthr, int median, int closing, int values, float *out, long ldo, int *istats,
                           double *dstats, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K28: new components from the residual: the residual on candidate boxes and its rank-1 factor (csrc/add_components.hip) ---------
+ * tests/add_restatement.py is the definition in float64.  M candidates, each a box boxes[m] = (x0, x1, y0, y1, z0, z1) inclusive, as in
+ * K24, of n_m voxels v_j in the order x slowest, z fastest; a movie of n frames in footprint coordinates.
+ *
+ * dnmf_residual_boxes (K28a).  For the B frames of the call (rows of ldf >= P floats; row frame_ids[f] of frames, or f; row f of sub,
+ * lds >= P floats, or NULL: nothing is subtracted) and every box
+ *     E[(m n + t0 + f) vmax + j] = frames_f(v_j) - sub_f(v_j)        one fp32 subtraction; frames_f(v_j) itself without sub
+ * for j < n_m, and 0 for n_m <= j < vmax: E is a compact (M, n, vmax) fp32 buffer of which this call writes the frames t0 .. t0 + B - 1,
+ * so a movie larger than one buffer goes through in pieces.  A sample that is not finite is copied as it is.  One launch, one workgroup
+ * per (box, run of 8 frames); the lanes read the z-rows of the box and write consecutive j.
+ *   boxes      (M, 6) int32 on the HOST: checked before anything is launched;  boxes_dev: the same on the device
+ * DNMF_E_NULL: frames, sz, boxes, boxes_dev or E NULL;  DNMF_E_SHAPE: a size, M, n, vmax or B < 1, t0 < 0 or t0 + B > n, ldf or lds <
+ * P, a box that is empty, reaches outside the volume or holds more than vmax voxels;  DNMF_E_UNSUPPORTED: vmax > 4096, M > 4096, n >
+ * 18 432, 2^31 voxels or more.
+ *
+ * dnmf_rank1_nmf (K28b).  Per candidate the non-negative rank-1 factor a c^T of E[m] (n rows of vmax floats, of which the first
+ * nvox[m] = n_m count), from the start a0 (M rows of vmax floats).  The valid frames V are those whose n_m samples are all finite.
+ *     repeat iters times:   c_t = max(sum_j a_j e_tj, 0) / sum_j a_j^2  (t in V);   a_j = max(sum_{t in V} c_t e_tj, 0) / sum_{t in V} c_t^2
+ *     finish:               a *= sqrt(sum a0^2 / sum a^2), then the c-step once more
+ *   a        (M, vmax) fp32: the footprint on the box, 0 for j >= n_m
+ *   c        (M, n) fp32: the trace, NaN on the frames outside V
+ *   stats    (M, 4) float64: energy = sum_{V, j} e^2;  explained = 2 sum_{t in V} c_t <a, e_t> - |a|^2 |c|^2 (what a c^T takes off the
+ *            energy);  |a|^2;  |c|^2 -- of the float64 a and c before they are rounded
+ *   n_valid  (M) int32: the frames in V;   ok (M) int32
+ * A candidate whose sum a^2 or sum c^2 is not a positive finite number at any step, or whose V is empty, is refused: ok = 0, its a
+ * (j < n_m) and c are NaN, explained and the two norms NaN; energy and n_valid are still those of its frames.  So is one whose
+ * nvox[m] is outside [1, vmax] (energy 0, n_valid 0).  Nothing is raised.
+ * Products of the fp32 samples are taken in float64 and summed in float64 in a fixed order (csrc/add_components.hip states it); a
+ * and c stay in float64 between the steps -- a in LDS, c in the workspace -- and are rounded to fp32 once.  One launch runs every
+ * iteration, one workgroup of 512 lanes per candidate; no atomics: the same input gives the same bits.  No host synchronisation.
+ *   workspace  dnmf_rank1_nmf_workspace(M, n) bytes (0 on bad arguments), 8-byte aligned
+ * DNMF_E_NULL: a NULL argument;  DNMF_E_SHAPE: M, n, vmax or iters < 1;  DNMF_E_UNSUPPORTED: vmax > 4096, M > 4096, n > 18 432;
+ * DNMF_E_WORKSPACE: a short or misaligned workspace.  Nothing is launched on an error. */
+int dnmf_residual_boxes(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const int *sz, int B,
+                        const int *boxes, const int *boxes_dev, int M, float *E, int n, int vmax, int t0, dnmf_stream_t stream);
+size_t dnmf_rank1_nmf_workspace(int M, int n);
+int dnmf_rank1_nmf(const float *E, int M, int n, int vmax, const int *nvox, const float *a0, int iters, float *a, float *c,
+                   double *stats, int *n_valid, int *ok, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
