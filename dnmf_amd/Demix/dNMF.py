@@ -2172,7 +2172,7 @@ class DeformableNMF:
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
-            background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, motion_order=None):
+            background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, learn_colours=0, motion_order=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
@@ -2186,7 +2186,9 @@ class DeformableNMF:
         images with R time courses (``update_background_rank``); 1: the rank-1 term.  ``motion_order`` is the model's
         ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``).
         ``spatial_solver``, ``grow`` and ``iter_a`` are ``update_footprints``' (``'hals'``: the exact footprint solver K6h,
-        ``iter_a`` sweeps on supports grown by ``grow`` voxels; with ``verbose`` its max and median KKT are printed)."""
+        ``iter_a`` sweeps on supports grown by ``grow`` voxels; with ``verbose`` its max and median KKT are printed).
+        ``learn_colours=n > 0`` (K29, ``MultiChannelDNMF`` only): every sweep ends with ``update_colours(testloader, sweeps=n)``
+        on the frames the sweep's other steps read; 0: the colours stay, the path of a call without the argument."""
         _check_motion_solver(motion_solver, "fit")
         kept, kept_order = self.motion_smooth, self.motion_order
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
@@ -2197,6 +2199,10 @@ class DeformableNMF:
             raise ValueError(f"fit: background is a number of alternations >= 0, got {background!r}")
         if int(background_rank) != background_rank or not 1 <= background_rank <= ops.BACKGROUND_RANKS[1]:
             raise ValueError(f"fit: background_rank={background_rank!r} (1 .. {ops.BACKGROUND_RANKS[1]})")
+        if int(learn_colours) != learn_colours or learn_colours < 0:
+            raise ValueError(f"fit: learn_colours is a number of sweeps >= 0, got {learn_colours!r}")
+        if learn_colours and not hasattr(self, "update_colours"):
+            raise ValueError("fit: learn_colours needs a MultiChannelDNMF (a single-channel model has no colours)")
         if background:
             self._background_refusals(dataloader, "fit(background=)")
             self._background_refusals(testloader, "fit(background=)")
@@ -2209,6 +2215,8 @@ class DeformableNMF:
                 out = self.update_footprints(test, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
                                              iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered,
                                              spatial_solver=spatial_solver, grow=grow, iter_a=iter_a)
+                if learn_colours:
+                    self.update_colours(test, sweeps=int(learn_colours))
                 if background:
                     if background_rank == 1:
                         self.update_background(testloader, iters=background)
@@ -2249,6 +2257,8 @@ class MultiChannelDNMF(DeformableNMF):
         self.colours = colours
         self._chan_fp = None
         self._chan_key = None
+        # after update_colours: colours and kkt before / after, ok, ok_channel, scale, objective before / after of that call
+        self.last_colours = None
 
     def _channels(self):
         import copy
@@ -2315,6 +2325,82 @@ class MultiChannelDNMF(DeformableNMF):
 
     def _scale_Cs(self, Cs):
         Cs.mul_(self.colours.T @ self.colours)
+
+    def update_colours(self, loader, sweeps=10, normalise=True, dry_run=False):
+        """Learns ``self.colours`` from the frames ``loader`` serves, with ``fp.A``, ``fp.beta`` and ``self.C`` fixed (K29;
+        tests/colours_restatement.py is the definition).  With A_t the UNCOLOURED warped footprints of frame t, G_t = A_t^T A_t
+        and r_t^c = A_t^T y_t^c, the squared error of channel c is the quadratic 1/2 x^T M x - b_c^T x in x = colours[c, :],
+        M[k, l] = sum_t G_t[k, l] C[k, t] C[l, t], b[c, k] = sum_t r_t^c[k] C[k, t]; each channel takes ``sweeps`` cyclic
+        coordinate sweeps of the non-negative solver from its current colours (``ops.colour_normal_eqs``, ``ops.colour_solve``:
+        float64).  ``sweeps`` is a parameter of the algorithm, not a tolerance; ``kkt`` in the result says how far from the
+        solution the sweeps ended.  ``normalise``: colours[:, k] s with C[k, :] / s is the same model, so the largest colour of
+        every neuron is then set to 1 and its trace rescaled.  A neuron whose trace is zero on these frames (M[k, k] = 0), or
+        whose new colours are all zero or not finite, keeps its colours and its trace (``ok[k] = 0``): the step never kills a
+        component.  A channel whose sums are not finite keeps its row (``ok_channel[c] = 0``).
+        The frames go through in time order in pieces of at most 1 GiB; per piece and channel the Gram kernel that
+        ``gram_kernel`` selects runs on the uncoloured ``fp`` (G is the same for every channel and is kept from the first).
+        ``self.colours`` is replaced by a new tensor and ``self.C`` by a rescaled one; ``fp.A`` and its layouts stay.  Returns,
+        and keeps in ``self.last_colours``, a dict of CUDA tensors: ``colours_before`` / ``colours`` (NC, K) fp32,
+        ``kkt_before`` / ``kkt`` (NC) float64, ``ok`` (K) and ``ok_channel`` (NC) bool, ``scale`` (K) float64 the factor each
+        trace was multiplied by, and the floats ``objective_before`` / ``objective`` = sum_c 1/2 x^T M x - b_c^T x, half the
+        squared error up to a constant.  ``dry_run=True`` returns the same and leaves the model bit for bit as it was."""
+        who = "update_colours"
+        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
+            raise NotImplementedError(f"{who}: the loader holds a shard of the frames (M and b would need an all-reduce)")
+        fp = self.fp
+        NC, K = self.colours.shape
+        P = fp.P
+        if NC > ops.COLOUR_MAX_NC or K > ops.COLOUR_MAX_K:
+            raise ValueError(f"{who}: NC={NC} channels (<= {ops.COLOUR_MAX_NC}), K={K} neurons (<= {ops.COLOUR_MAX_K})")
+        if int(sweeps) != sweeps or sweeps < 1:
+            raise ValueError(f"{who}: sweeps={sweeps!r}, a whole number >= 1")
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            if frames.dim() != 2 or frames.shape[1] != NC * P:
+                raise ValueError(f"{who}: rows of {frames.shape[-1]} floats, expected {NC} x {P}")
+            if not bool((order[1:] > order[:-1]).all()):
+                at = torch.argsort(order.long())
+                frames, order = frames.index_select(0, at), order[at]
+            T = frames.shape[0]
+            C = self.C.to(device, torch.float32)
+            Cs = C[:, order.long()].contiguous()                     # the traces of the frames served, in time order
+            step = max(1, min(T, (1 << 30) // (4 * max(NC * P, K * K))))
+            nbr, state, M, b = self._gram_nbr, None, None, None
+            for s in range(0, T, step):
+                fr, tt = frames[s:s + step], order[s:s + step]
+                G, rs = None, []
+                for c in range(NC):
+                    Gc, rc = self._gram_rhs_one(fp, fr[:, c * P:(c + 1) * P], tt)
+                    if G is None:
+                        G = Gc                                       # A_t^T A_t does not depend on the frames' values
+                    rs.append(rc)
+                    del Gc
+                M, b, state = ops.colour_normal_eqs(G, torch.stack(rs), Cs[:, s:s + step], state=state, first=s == 0,
+                                                    finish=s + step >= T)
+            self._gram_nbr = nbr                                     # the pattern of the last COLOURED Gram matrices, for K4
+            old = self.colours.contiguous()
+            kkt0 = ops.colour_kkt(M, b, old)
+            sol = ops.colour_solve(M, b, old, sweeps=int(sweeps))
+            okc = sol["ok"] != 0
+            new = sol["colours"].double()
+            diag = torch.diagonal(M)
+            top = new.max(0).values
+            ok = torch.isfinite(new).all(0) & (top > 0) & torch.isfinite(diag) & (diag > 0)
+            scale = torch.where(ok & bool(normalise), top, torch.ones_like(top))
+            colours = torch.where(ok[None, :], new / scale[None, :], old.double()).float()
+
+            def objective(x):
+                x = x.double()
+                return float((0.5 * torch.einsum("ck,kl,cl->c", x, M, x) - (b * x).sum(1)).sum())
+
+            out = dict(colours_before=old, colours=colours, kkt_before=kkt0, kkt=sol["kkt"], ok=ok, ok_channel=okc, scale=scale,
+                       objective_before=objective(old), objective=objective(sol["colours"]))
+            if not dry_run:
+                self.colours = colours
+                self.C = (C.double() * scale[:, None]).float()
+                self._chan_fp = None
+                self.last_colours = out
+        return out
 
     def _footprints_written(self):
         super()._footprints_written()

@@ -2507,6 +2507,107 @@ def rank1_nmf(E, nvox, a0, iters=5, workspace=None):
     return dict(a=a, c=c, energy=stats[:, 0], explained=stats[:, 1], saa=stats[:, 2], scc=stats[:, 3], n_valid=info[0], ok=info[1])
 
 
+# ---- K29: the colours of a multi-channel model ------------------------------------------------------------------------------------
+COLOUR_MAX_K, COLOUR_MAX_NC = 4096, 16          # the limits of dnmf_colour_normal_eqs / dnmf_colour_solve
+COLOUR_LDS_MAX_K = 128                          # K29b holds M in LDS up to here and reads it from global memory beyond
+
+
+def _colour_limits(fn, K, NC):
+    if not (1 <= K <= COLOUR_MAX_K and 1 <= NC <= COLOUR_MAX_NC):
+        raise ValueError(f"{fn}: K={K} neurons (1 .. {COLOUR_MAX_K}), NC={NC} channels (1 .. {COLOUR_MAX_NC})")
+
+
+def _colour_system(fn, M, b, colours):
+    """The checks of the two calls that read ``M`` (K, K), ``b`` (NC, K) float64 and ``colours`` (NC, K) fp32 -> (K, NC)."""
+    _f32(colours, f"{fn}: colours")
+    if colours.dim() != 2:
+        raise ValueError(f"{fn}: colours must be (NC, K), got {tuple(colours.shape)}")
+    NC, K = colours.shape
+    _colour_limits(fn, K, NC)
+    for name, t, shape in (("M", M, (K, K)), ("b", b, (NC, K))):
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == colours.device):
+            raise ValueError(f"{fn}: {name} must be a contiguous float64 tensor {shape} on {colours.device}, got {t.dtype} "
+                             f"{tuple(t.shape)} on {t.device}")
+    return K, NC
+
+
+def colour_normal_eqs(G, r, C, state=None, first=True, finish=True, out=None):
+    """K29a.  The normal equations of the colours, tests/colours_restatement.py (``normal_eqs``) on the GPU -> ``(M, b, state)``.
+    ``G`` (B, K, K) and ``r`` (NC, B, K) fp32 CUDA, contiguous: the Gram matrices of the UNCOLOURED warped footprints and their
+    products with each channel of the B frames of the call; ``C`` (K, B) fp32 CUDA rows, the traces of those frames.  ``M`` (K, K)
+    = sum_t G_t[k, l] C[k, t] C[l, t] and ``b`` (NC, K) = sum_t r_t^c[k] C[k, t], float64 CUDA (``out = (M, b)``: written there),
+    over every frame since the state was reset -- both None with ``finish=False``.  A movie larger than one buffer goes in several
+    calls, as in ``summary_images``: ``first=True`` resets ``state``, the last call has ``finish=True``; a later call may not be
+    larger than the first.  The terms are formed in float64 and added in a fixed order that does not depend on the pieces: the
+    same movie gives the same bits however it is cut.  No atomics.  K <= 4096, NC <= 16."""
+    fn = "colour_normal_eqs"
+    _f32(G, f"{fn}: G"), _f32(r, f"{fn}: r")
+    if G.dim() != 3 or G.shape[1] != G.shape[2] or G.shape[0] < 1:
+        raise ValueError(f"{fn}: G must be (B, K, K), got {tuple(G.shape)}")
+    B, K, _ = G.shape
+    if r.dim() != 3 or r.shape[1:] != (B, K) or r.device != G.device:
+        raise ValueError(f"{fn}: r must be (NC, {B}, {K}) on {G.device}, got {tuple(r.shape)} on {r.device}")
+    NC = r.shape[0]
+    _colour_limits(fn, K, NC)
+    _rows(C, fn, "C", B, f" and rows of {B} floats")
+    if C.dim() != 2 or C.shape[0] != K or C.device != G.device:
+        raise ValueError(f"{fn}: C must be ({K}, {B}) on {G.device}, got {tuple(C.shape)} on {C.device}")
+    dev = G.device
+    lib = _lib.load()
+    state = _stream_state(fn, state, _need(lib, "dnmf_colour_normal_eqs_workspace", K, NC, B), first, dev)
+    M = b = None
+    if finish:
+        if out is None:
+            M = torch.empty((K, K), dtype=torch.float64, device=dev)
+            b = torch.empty((NC, K), dtype=torch.float64, device=dev)
+        else:
+            M, b = out
+            for name, t, shape in (("M", M, (K, K)), ("b", b, (NC, K))):
+                if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                    raise ValueError(f"{fn}: out {name} must be a contiguous float64 tensor {shape} on {dev}")
+    with _timed("colour_normal_eqs"):
+        rc = lib.dnmf_colour_normal_eqs(G.data_ptr(), r.data_ptr(), C.data_ptr(), _ld(C, B), K, NC, B, 1 if first else 0,
+                                        1 if finish else 0, state.data_ptr(), _nbytes(state), _ptr(M), _ptr(b), _stream())
+    _lib.check(rc, "dnmf_colour_normal_eqs")
+    return M, b, state
+
+
+def colour_solve(M, b, colours, sweeps=10):
+    """K29b.  ``sweeps`` cyclic coordinate sweeps on ``1/2 x^T M x - b_c^T x, x >= 0`` per channel c from x = ``colours[c]``,
+    tests/colours_restatement.py (``solve``) on the GPU.  ``M`` (K, K) and ``b`` (NC, K) float64 CUDA (``colour_normal_eqs``),
+    ``colours`` (NC, K) fp32 CUDA, left as it is.  Returns a dict of CUDA tensors: ``colours`` (NC, K) fp32, a new tensor, x
+    rounded once; ``kkt`` (NC) float64, the largest projected-gradient entry after the last sweep (zero at the solution); ``ok``
+    (NC) int32, 0 for a channel whose ``b``, or ``M``, holds an entry that is not finite: it keeps its row and its kkt is NaN.
+    A coordinate whose M[k, k] is not a positive finite number is left alone.  float64 inside, one workgroup per channel, M in
+    LDS up to K = 128 and in global memory beyond; the same input gives the same bits.  K <= 4096, NC <= 16, sweeps >= 1."""
+    fn = "colour_solve"
+    K, NC = _colour_system(fn, M, b, colours)
+    sweeps = _sweeps(fn, sweeps)
+    dev = colours.device
+    out = torch.empty((NC, K), dtype=torch.float32, device=dev)
+    kkt = torch.empty((NC,), dtype=torch.float64, device=dev)
+    ok = torch.empty((NC,), dtype=torch.int32, device=dev)
+    with _timed("colour_solve"):
+        rc = _lib.load().dnmf_colour_solve(M.data_ptr(), b.data_ptr(), colours.data_ptr(), K, NC, sweeps, out.data_ptr(),
+                                           kkt.data_ptr(), ok.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_colour_solve")
+    return dict(colours=out, kkt=kkt, ok=ok)
+
+
+def colour_kkt(M, b, colours):
+    """(NC) float64: the largest projected-gradient entry of ``1/2 x^T M x - b_c^T x, x >= 0`` at x = ``colours[c]`` (the measure
+    ``colour_solve`` reports, for any colours); NaN for a channel whose ``b``, or ``M``, holds an entry that is not finite."""
+    fn = "colour_kkt"
+    K, NC = _colour_system(fn, M, b, colours)
+    kkt = torch.empty((NC,), dtype=torch.float64, device=colours.device)
+    ok = torch.empty((NC,), dtype=torch.int32, device=colours.device)
+    with _timed("colour_kkt"):
+        rc = _lib.load().dnmf_colour_solve(M.data_ptr(), b.data_ptr(), colours.data_ptr(), K, NC, 0, 0, kkt.data_ptr(),
+                                           ok.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_colour_solve")
+    return kkt
+
+
 def pack_footprints_sparse(A, order):
     """A (..., K) and a neuron order -> (Aps (P,Ks), row_mask (P) uint8) for the zero-skipping Gram kernel."""
     K = A.shape[-1]

@@ -1086,6 +1086,44 @@ size_t dnmf_rank1_nmf_workspace(int M, int n);
 int dnmf_rank1_nmf(const float *E, int M, int n, int vmax, const int *nvox, const float *a0, int iters, float *a, float *c,
                    double *stats, int *n_valid, int *ok, void *workspace, size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K29: the channel colours of a multi-channel model: normal equations and their non-negative solve (csrc/colours.hip) -----------
+ * tests/colours_restatement.py is the definition in float64.  Channel c of a frame is modelled as sum_k colours[c, k] A_k(q_t) C[k, t];
+ * with A_t the UNCOLOURED warped footprints of frame t, G_t = A_t^T A_t and r_t^c = A_t^T y_t^c, the squared error of channel c is the
+ * quadratic 1/2 x^T M x - b_c^T x (+ a constant) in x = colours[c, :], with
+ *     M[k, l] = sum_t G_t[k, l] C[k, t] C[l, t]   (K, K), the same for every channel       b[c, k] = sum_t r_t^c[k] C[k, t]   (NC, K)
+ *
+ * dnmf_colour_normal_eqs (K29a).  G (B, K, K) and r (NC, B, K) fp32, contiguous, of the B frames of the call; C = K rows of ldc >= B
+ * floats, the traces of those frames.  A term is (double)G ((double)C[k, t] (double)C[l, t]) -- the inner product is exact, so a
+ * symmetric G gives a symmetric M bit for bit -- and (double)r (double)C[k, t]; the terms of an entry are added in float64 in the order
+ * of t within a segment of 32 frames, from 0.0, and the segments in their order, from 0.0.  The segments are cut on the count of
+ * frames since the state was reset, which the state keeps with the sum of the closed segments and the open one: a movie fed in pieces
+ * of ANY sizes (first = 1 resets the state, the last call has finish = 1 and writes M and b; both may be NULL without it) gives the
+ * bits of one call.  One streaming read of G: a workgroup owns 16 x 64 entries (k, l), a lane 4 of them with consecutive lanes on
+ * consecutive l, and one segment, whose traces it stages in LDS once.  Three launches, no floating-point atomics, no host
+ * synchronisation; nothing is launched on an error.
+ *   state   dnmf_colour_normal_eqs_workspace(K, NC, B) bytes (0 on bad arguments), 8-byte aligned; it grows with B, so the state of the
+ *           largest call serves every call
+ * DNMF_E_NULL: G, r, C or state NULL, M or b NULL with finish;  DNMF_E_SHAPE: K, NC or B < 1, ldc < B;  DNMF_E_UNSUPPORTED: K > 4096,
+ * NC > 16, more than 65534 segments;  DNMF_E_WORKSPACE: a short or misaligned state.
+ *
+ * dnmf_colour_solve (K29b).  Per channel c, from x = (double)colours[c, :] and h = M x (the terms of h[l] added in the order of k),
+ * `sweeps` sweeps of k = 0 .. K - 1:
+ *     d = M[k, k];  d > 0 and finite:  x_k' = fmax(0, x_k + (b[c, k] - h[k]) / d),  h += (x_k' - x_k) M[k, :]  (skipped when nothing moves)
+ * and a coordinate with any other d is left alone.  M[k, :] stands for column k: M is taken as symmetric.  Then
+ *   out    (NC, K) fp32: x rounded once (not written with sweeps = 0, and may then be NULL)
+ *   kkt    (NC) float64: max_k |pg_k|, pg_k = (h - b_c)[k] where x_k > 0, else min((h - b_c)[k], 0): zero exactly at the solution
+ *   ok     (NC) int32: 0 for a channel whose b, or the shared M, holds an entry that is not finite; its row of out = its row of
+ *          colours bit for bit and its kkt is NaN
+ * One launch, one workgroup of 256 lanes per channel, float64 throughout.  M is held in LDS where K <= 128 (8 K^2 = 128 KiB of the CU's
+ * 160) and read from global memory, a row ahead, beyond that.  The same input gives the same bits.
+ * DNMF_E_NULL: M, b, colours, kkt or ok NULL, out NULL with sweeps > 0;  DNMF_E_SHAPE: K or NC < 1, sweeps < 0;  DNMF_E_UNSUPPORTED:
+ * K > 4096, NC > 16.  Nothing is launched on an error. */
+size_t dnmf_colour_normal_eqs_workspace(int K, int NC, int B);
+int dnmf_colour_normal_eqs(const float *G, const float *r, const float *C, long ldc, int K, int NC, int B, int first, int finish,
+                           void *state, size_t state_bytes, double *M, double *b, dnmf_stream_t stream);
+int dnmf_colour_solve(const double *M, const double *b, const float *colours, int K, int NC, int sweeps, float *out, double *kkt,
+                      int *ok, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
