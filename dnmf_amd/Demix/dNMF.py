@@ -47,6 +47,11 @@ def _sz_list(sz):
     return [int(s) for s in (sz.tolist() if isinstance(sz, torch.Tensor) else sz)]
 
 
+def _gib_rows(n, P):
+    """How many of ``n`` rows of ``P`` fp32 values go through at a time: what 1 GiB holds, at least one."""
+    return max(1, min(n, (1 << 30) // (4 * P)))
+
+
 def lists_verdict(mode, K, boxfrac=None, nslot=None, has_nbr=None):
     """The one rule for "the neuron-list kernel forms apply", on plain values: None when they do, else the first reason they
     do not -- 'mode' (the kernel choice is neither 'auto' nor 'lists'), 'K', 'slots' (the pattern of G has too many), 'boxes'
@@ -538,14 +543,7 @@ class DeformableNMF:
         self.C = torch.rand((K, T)).to(device)
         self.A = torch.rand((K, _sz_list(sz)[0], _sz_list(sz)[1])).to(device)  # unused in the reference too (:131)
         self.verbose = True
-        if positions is not None:
-            # D = 1 - exp(-0.01 * distance(voxel, centre_k)), float64 (reference :133-137)
-            lat = self.fp.flow_id.reshape(-1, 3).double()
-            d = torch.cdist(lat, positions.to(device).double())
-            X, Y, Z = _sz_list(sz)
-            self.D = (1 - torch.exp(-.01 * d)).reshape(X, Y, Z, K).cpu().numpy()
-        else:
-            self.D = None
+        self.D = None if positions is None else self._distance_prior(positions).reshape(*_sz_list(sz), K)
         self._ws_k2 = None
         self._ws_k3 = None
         self._S_bufs = None
@@ -890,6 +888,56 @@ class DeformableNMF:
             idx.append(torch.as_tensor(data[1]).to(device, torch.int32).reshape(-1))
         return torch.cat(fr, 0).contiguous(), torch.cat(idx, 0)
 
+    def _frames_in_time_order(self, loader):
+        """``_gather_frames`` with the frames sorted by their times where the loader did not serve them so."""
+        frames, order = self._gather_frames(loader)
+        if not bool((order[1:] > order[:-1]).all()):
+            at = torch.argsort(order.long())
+            frames, order = frames.index_select(0, at), order[at]
+        return frames, order
+
+    def _residual_pieces(self, frames, order, C, registered, P):
+        """The frames in pieces of at most 1 GiB -> per piece ``(s, fr, tt, sub)``: its first row, its frames (registered under
+        the current ``fp.beta`` where ``registered`` says how), their times and the model's prediction ``fp.recon_image(C, tt)``
+        as rows of ``P`` floats (None without ``C``)."""
+        fp = self.fp
+        step = _gib_rows(frames.shape[0], P)
+        for s in range(0, frames.shape[0], step):
+            fr, tt = frames[s:s + step], order[s:s + step]
+            sub = None if C is None else ops.halo_interior(fp.recon_image(C, tt), fp.sz_list).reshape(fr.shape[0], P)
+            if registered is not None:
+                fr = fp.registered_video(fr, times=tt, interpolation=registered)
+            yield s, fr, tt, sub
+
+    def _single_model_only(self, who, loader=None, shard_reason=None):
+        """The refusals of a step written for one channel and, with ``shard_reason`` (the text after ``who``), for a model and a
+        loader that hold every frame."""
+        if self._nchan() != 1:
+            raise NotImplementedError(f"{who}: one channel only")
+        sharded = self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None)
+        if shard_reason is not None and sharded:
+            raise NotImplementedError(f"{who}: {shard_reason}")
+
+    def _box_sizes(self, who, boxes, what="neuron", hint="raise floor or lower margin"):
+        """The voxels of each box (K,) int64; ValueError where one holds more than the box kernels take."""
+        n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
+        if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
+            raise ValueError(f"{who}: the box of {what} {int(n.argmax())} holds {int(n.max())} voxels, at most "
+                             f"{ops.COMPONENT_MAX_VOXELS} ({hint})")
+        return n
+
+    def _component_boxes(self, who, floor, margin):
+        """``ops.component_boxes`` of the footprints, none larger than the box kernels take."""
+        boxes = ops.component_boxes(self.fp.A.detach(), self.fp.sz_list, floor=floor, margin=margin)
+        self._box_sizes(who, boxes)
+        return boxes
+
+    def _distance_prior(self, pos):
+        """D = 1 - exp(-0.01 * distance(voxel, centre_k)) for the centres ``pos`` (n, 3), float64 numpy (P, n) (reference
+        :133-137)."""
+        d = torch.cdist(self.fp.flow_id.reshape(-1, 3).double(), pos.to(device).double())
+        return (1 - torch.exp(-.01 * d)).cpu().numpy()
+
     def registered_video(self, loader, interpolation='linear', fill=None):
         """The motion-corrected movie of every frame ``loader`` serves, under the current ``fp.beta``: (T_loc, nchan*P) fp32
         CUDA rows in the loader's order (``ExponentialFP.registered_video``: ``'linear'`` = K17, trilinear in true voxel
@@ -915,26 +963,16 @@ class DeformableNMF:
             raise ValueError(f"summary_images: source must be 'video' or 'residual', got {source!r}")
         if registered is not None:
             _check_registered(registered, "summary_images")
-        if self._nchan() != 1:
-            raise NotImplementedError("summary_images: one channel only")
-        fp = self.fp
-        sz = fp.sz_list
-        P = sz[0] * sz[1] * sz[2]
+        self._single_model_only("summary_images")
+        sz = self.fp.sz_list
         with torch.no_grad():
-            frames, order = self._gather_frames(loader)
+            frames, order = self._gather_frames(loader)      # in the loader's order, not sorted
             T = frames.shape[0]
-            step = max(1, min(T, (1 << 30) // (4 * P)))
             C = self.C.to(device, torch.float32).contiguous() if source == 'residual' else None
             state = images = None
-            for s in range(0, T, step):
-                fr, tt = frames[s:s + step], order[s:s + step]
-                sub = None
-                if C is not None:
-                    sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
-                if registered is not None:
-                    fr = fp.registered_video(fr, times=tt, interpolation=registered)
+            for s, fr, _, sub in self._residual_pieces(frames, order, C, registered, sz[0] * sz[1] * sz[2]):
                 images, state = ops.summary_images(fr, sz, sub=sub, neighbours=neighbours, state=state, first=s == 0,
-                                                   finish=s + step >= T)
+                                                   finish=s + fr.shape[0] >= T)
         return images
 
     def evaluate_components(self, loader, registered='linear', active=0.25, margin=2, floor=1e-3, min_r=0.5, min_snr=1.0):
@@ -964,43 +1002,29 @@ class DeformableNMF:
         who = "evaluate_components"
         if registered is not None:
             _check_registered(registered, who)
-        if self._nchan() != 1:
-            raise NotImplementedError(f"{who}: one channel only")
-        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
-            raise NotImplementedError(f"{who}: the loader holds a shard of the frames (the mean images would need an all-reduce)")
+        self._single_model_only(who, loader, "the loader holds a shard of the frames (the mean images would need an all-reduce)")
         if not 0 < active <= 1:
             raise ValueError(f"{who}: active={active!r} is the fraction of the frames that count as active, in (0, 1]")
         fp = self.fp
         sz, P, K = fp.sz_list, fp.P, fp.K
         with torch.no_grad():
-            frames, order = self._gather_frames(loader)
-            if not bool((order[1:] > order[:-1]).all()):
-                at = torch.argsort(order.long())
-                frames, order = frames.index_select(0, at), order[at]
+            frames, order = self._frames_in_time_order(loader)
             T = frames.shape[0]
             C = self.C.to(device, torch.float32).contiguous()
             Cs = C[:, order.long()].contiguous()                     # the traces of the frames served, in time order
             A_rows = fp._layout("rows", (), lambda: fp.A.reshape(P, K).t().contiguous())
-            boxes = ops.component_boxes(fp.A, sz, floor=floor, margin=margin)
-            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
-            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
-                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
-                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            boxes = self._component_boxes(who, floor, margin)
             score = Cs.double()
             if T > 1:
                 score = torch.cat((Cs[:, 1:2], 0.5 * (Cs[:, :-2].double() + Cs[:, 2:].double()), Cs[:, -2:-1]), 1).double()
             n_active = min(T, max(1, int(math.ceil(active * T))))
             top = torch.sort(score, dim=1, descending=True, stable=True).indices[:, :n_active]
             w = torch.zeros((K, T), dtype=torch.float32, device=device).scatter_(1, top, 1.0)
-            step = max(1, min(T, (1 << 30) // (4 * P)))
             state, raw, corr = None, [], []
-            for s in range(0, T, step):
-                fr, tt = frames[s:s + step], order[s:s + step]
-                sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
-                if registered is not None:
-                    fr = fp.registered_video(fr, times=tt, interpolation=registered)
-                out, state = ops.component_stats(fr, sz, A_rows, boxes, Cs[:, s:s + step], w[:, s:s + step], sub=sub, state=state,
-                                                 first=s == 0, finish=s + step >= T)
+            for s, fr, _, sub in self._residual_pieces(frames, order, C, registered, P):
+                e = s + fr.shape[0]
+                out, state = ops.component_stats(fr, sz, A_rows, boxes, Cs[:, s:e], w[:, s:e], sub=sub, state=state, first=s == 0,
+                                                 finish=e >= T)
                 raw.append(out["raw"])
                 corr.append(out["frame_corr"])
             raw, corr = torch.cat(raw, 1), torch.cat(corr, 1)
@@ -1019,6 +1043,14 @@ class DeformableNMF:
         self.fp.invalidate_layouts()
         for name in self._K_SHAPED + tuple(n for n in vars(self) if n.startswith("last_")):
             setattr(self, name, None)
+
+    def _components_changed(self, K):
+        """The model now holds ``K`` components: ``fp.K`` and ``K`` say so, and what ``_forget_k_shaped`` names is forgotten."""
+        self.fp.K = K
+        if hasattr(self, "K"):
+            self.K = K
+        self._forget_k_shaped()
+        return K
 
     def select_components(self, keep):
         """Shrink the model in place to the neurons ``keep`` -- a bool mask (K,) or indices, e.g. ``evaluate_components(...)
@@ -1040,8 +1072,7 @@ class DeformableNMF:
             raise ValueError("select_components: the selection is empty")
         if int(sel.min()) < 0 or int(sel.max()) >= K:
             raise ValueError(f"select_components: index out of range for K={K}: {sel.tolist()}")
-        if self._nchan() != 1:
-            raise NotImplementedError("select_components: one channel only")
+        self._single_model_only("select_components")
         with torch.no_grad():
             at = sel.to(fp.A.device)
             fp.A = fp.A.index_select(3, at).contiguous()
@@ -1051,11 +1082,7 @@ class DeformableNMF:
             self.A = self.A.index_select(0, at.to(self.A.device))
         if self.D is not None:
             self.D = np.ascontiguousarray(self.D[..., sel.numpy()])
-        fp.K = int(sel.numel())
-        if hasattr(self, "K"):
-            self.K = fp.K
-        self._forget_k_shaped()
-        return fp.K
+        return self._components_changed(int(sel.numel()))
 
     def merge_components(self, thr=0.85, min_overlap=0.1, floor=1e-3, margin=0, traces=None, iters=10, dry_run=False):
         """Merge the components that sit on one cell (K26; tests/merge_restatement.py is the definition).  The proposal step
@@ -1083,10 +1110,7 @@ class DeformableNMF:
         The pair statistics run on the GPU; the groups and the coefficients are found on the host (a synchronisation: K is
         small).  One channel and one process only."""
         who = "merge_components"
-        if self._nchan() != 1:
-            raise NotImplementedError(f"{who}: one channel only")
-        if self.group is not None:
-            raise NotImplementedError(f"{who}: the model holds a shard of the frames (the trace sums would need an all-reduce)")
+        self._single_model_only(who, None, "the model holds a shard of the frames (the trace sums would need an all-reduce)")
         fp = self.fp
         sz, P, K = fp.sz_list, fp.P, fp.K
         with torch.no_grad():
@@ -1097,11 +1121,7 @@ class DeformableNMF:
                 if tuple(Ct.shape) != tuple(C.shape):
                     raise ValueError(f"{who}: traces must be {tuple(C.shape)}, got {tuple(Ct.shape)}")
             A_rows = fp._layout("rows", (), lambda: fp.A.reshape(P, K).t().contiguous())
-            boxes = ops.component_boxes(fp.A, sz, floor=floor, margin=margin)
-            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
-            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
-                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
-                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            boxes = self._component_boxes(who, floor, margin)
             stats = ops.component_pairs(A_rows, sz, boxes, Ct)
             groups = ops.merge_groups(stats, K, thr, min_overlap)
             merged = sum(len(g) >= 2 for g in groups)
@@ -1136,15 +1156,10 @@ class DeformableNMF:
             self.A = self.A.index_select(0, dom.to(self.A.device))
         if self.D is not None:
             D = np.ascontiguousarray(self.D[..., plan["dominant"]])
-            lat = fp.flow_id.reshape(-1, 3).double()
             for q in torch.nonzero(~single).reshape(-1).tolist():
-                d = torch.cdist(lat, fp.pos[q:q + 1].to(device).double())
-                D[..., q] = (1 - torch.exp(-.01 * d)).reshape(*sz).cpu().numpy()
+                D[..., q] = self._distance_prior(fp.pos[q:q + 1]).reshape(*sz)
             self.D = D
-        fp.K = len(groups)
-        if hasattr(self, "K"):
-            self.K = fp.K
-        self._forget_k_shaped()
+        self._components_changed(len(groups))
         self.last_merge = result
         return result
 
@@ -1168,10 +1183,7 @@ class DeformableNMF:
         ``n_kept``, float64 ``threshold`` and ``energy``, and ``boxes`` (K, 6) int32.  ``dry_run=True`` computes the dict and
         leaves the model bit for bit, ``last_footprint_clean`` included.  One channel and one process only."""
         who = "clean_footprints"
-        if self._nchan() != 1:
-            raise NotImplementedError(f"{who}: one channel only")
-        if self.group is not None:
-            raise NotImplementedError(f"{who}: the model holds a shard of the frames (every rank would have to clean alike)")
+        self._single_model_only(who, None, "the model holds a shard of the frames (every rank would have to clean alike)")
         fp = self.fp
         sz, P, K = fp.sz_list, fp.P, fp.K
         with torch.no_grad():
@@ -1186,10 +1198,7 @@ class DeformableNMF:
             hopeless = odd.any(0) | ~(A > 0).any(0)
             one = torch.stack((at // (sz[1] * sz[2]), at // sz[2] % sz[1], at % sz[2]), 1).repeat_interleave(2, 1).to(torch.int32)
             boxes = torch.where(hopeless[:, None], one, boxes)
-            n = (boxes[:, 1::2] - boxes[:, 0::2] + 1).long().prod(1)
-            if int(n.max()) > ops.COMPONENT_MAX_VOXELS:
-                raise ValueError(f"{who}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most "
-                                 f"{ops.COMPONENT_MAX_VOXELS} (raise floor or lower margin)")
+            self._box_sizes(who, boxes)
             A_new, stats = ops.clean_footprints(A, sz, boxes, method=method, nrgthr=nrgthr, maxthr=maxthr, median=median,
                                                 closing=closing, values=values, out=None if dry_run else A)
         result = dict(stats, boxes=boxes)
@@ -1234,11 +1243,7 @@ class DeformableNMF:
         ``K`` the component count with them.  ``dry_run=True`` computes the dict and leaves the model bit for bit
         (``last_add`` apart); so does a call that keeps nothing.  One channel and one process only."""
         who = "add_components"
-        if self._nchan() != 1:
-            raise NotImplementedError(f"{who}: one channel only")
-        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
-            raise NotImplementedError(f"{who}: the model or the loader holds a shard of the frames (every rank would have to add "
-                                      "alike)")
+        self._single_model_only(who, loader, "the model or the loader holds a shard of the frames (every rank would have to add alike)")
         if int(n) < 1:
             raise ValueError(f"{who}: n={n!r} candidates, at least 1")
         if image not in ('corr', 'mean', 'std', 'max'):
@@ -1276,11 +1281,8 @@ class DeformableNMF:
             boxes = ops.candidate_boxes(cand, sz, half)
             bh = boxes.cpu().numpy()
             ch = cand.cpu().numpy().astype(np.float64)
-            nvox = (bh[:, 1::2] - bh[:, 0::2] + 1).astype(np.int64).prod(1)
+            nvox = self._box_sizes(who, boxes, "candidate", "lower half").cpu().numpy()
             vmax = int(nvox.max())
-            if vmax > ops.COMPONENT_MAX_VOXELS:
-                raise ValueError(f"{who}: the box of candidate {int(nvox.argmax())} holds {vmax} voxels, at most "
-                                 f"{ops.COMPONENT_MAX_VOXELS} (lower half)")
             # the start and the box coordinates on the host: M and vmax are small, and the centres had to come here anyway
             coords, a0 = [], np.zeros((M, vmax), dtype=np.float32)
             for m, b in enumerate(bh):
@@ -1288,24 +1290,16 @@ class DeformableNMF:
                 u = np.stack(g, -1).reshape(-1, 3).astype(np.float64)
                 coords.append(u)
                 a0[m, :u.shape[0]] = np.exp(-((u - ch[m][None, :]) ** 2).sum(1) / sigma ** 2)
-            frames, order = self._gather_frames(loader)
-            if not bool((order[1:] > order[:-1]).all()):
-                at = torch.argsort(order.long())
-                frames, order = frames.index_select(0, at), order[at]
+            frames, order = self._frames_in_time_order(loader)
             T = frames.shape[0]
             if T > ops.ADD_MAX_FRAMES:
                 raise ValueError(f"{who}: the loader serves {T} frames, at most {ops.ADD_MAX_FRAMES}")
             C = self.C.to(device, torch.float32).contiguous()
-            step = max(1, min(T, (1 << 30) // (4 * P)))
-            batch = max(1, min(M, (1 << 30) // (4 * T * vmax)))
+            batch = _gib_rows(M, T * vmax)
             fits = []
             for m0 in range(0, M, batch):
                 E = torch.empty((min(batch, M - m0), T, vmax), dtype=torch.float32, device=device)
-                for s in range(0, T, step):
-                    fr, tt = frames[s:s + step], order[s:s + step]
-                    sub = ops.halo_interior(fp.recon_image(C, tt), sz).reshape(fr.shape[0], P)
-                    if registered is not None:
-                        fr = fp.registered_video(fr, times=tt, interpolation=registered)
+                for s, fr, _, sub in self._residual_pieces(frames, order, C, registered, P):
                     ops.residual_boxes(fr, sz, boxes[m0:m0 + batch], sub=sub, out=E, t0=s, n_total=T)
                 fits.append(ops.rank1_nmf(E, nvox[m0:m0 + batch], torch.from_numpy(a0[m0:m0 + batch]).to(device), iters=iters))
                 del E
@@ -1334,20 +1328,13 @@ class DeformableNMF:
             self.C = torch.cat((C, rows), 0).to(self.C.dtype)
             self.A = torch.cat((self.A, torch.zeros((len(idx),) + tuple(self.A.shape[1:]), dtype=self.A.dtype, device=self.A.device)), 0)
             if self.D is not None:
-                d = torch.cdist(fp.flow_id.reshape(-1, 3).double(), pos_new.to(device).double())
-                self.D = np.concatenate((self.D, (1 - torch.exp(-.01 * d)).reshape(*sz, len(idx)).cpu().numpy()), -1)
-        fp.K = K + len(idx)
-        if hasattr(self, "K"):
-            self.K = fp.K
-        self._forget_k_shaped()
+                self.D = np.concatenate((self.D, self._distance_prior(pos_new).reshape(*sz, len(idx))), -1)
+        self._components_changed(K + len(idx))
         self.last_add = result
         return result
 
     def _background_refusals(self, loader, who):
-        if self._nchan() != 1:
-            raise NotImplementedError(f"{who}: one channel only")
-        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
-            raise NotImplementedError(f"{who}: the loader holds a shard of the frames (the b step would need an all-reduce)")
+        self._single_model_only(who, loader, "the loader holds a shard of the frames (the b step would need an all-reduce)")
 
     def update_background(self, loader, iters=3):
         """Fit the rank-1 background of the frames ``loader`` serves on what the current model leaves: Y_t ~ M_t + b f_t, with
@@ -1375,16 +1362,12 @@ class DeformableNMF:
         fp = self.fp
         sz, P = fp.sz_list, fp.P
         with torch.no_grad():
-            frames, order = self._gather_frames(loader)
-            if rank > 1:
-                if rank > order.numel():
-                    raise ValueError(f"{who}: rank={rank} for the {order.numel()} frames served")
-                if not bool((order[1:] > order[:-1]).all()):
-                    at = torch.argsort(order.long())
-                    frames, order = frames.index_select(0, at), order[at]
+            frames, order = self._frames_in_time_order(loader) if rank > 1 else self._gather_frames(loader)
+            if rank > max(1, order.numel()):
+                raise ValueError(f"{who}: rank={rank} for the {order.numel()} frames served")
             C = self.C.to(device, torch.float32).contiguous()
             beta = fp.beta.detach()
-            piece = max(1, min(frames.shape[0], (1 << 30) // (4 * P), K2_MAX_FRAMES))
+            piece = min(_gib_rows(frames.shape[0], P), K2_MAX_FRAMES)
             zeros = torch.zeros((piece, P), dtype=torch.float32, device=device)
 
             def predict(s, e):
@@ -2355,16 +2338,13 @@ class MultiChannelDNMF(DeformableNMF):
         if int(sweeps) != sweeps or sweeps < 1:
             raise ValueError(f"{who}: sweeps={sweeps!r}, a whole number >= 1")
         with torch.no_grad():
-            frames, order = self._gather_frames(loader)
+            frames, order = self._frames_in_time_order(loader)
             if frames.dim() != 2 or frames.shape[1] != NC * P:
                 raise ValueError(f"{who}: rows of {frames.shape[-1]} floats, expected {NC} x {P}")
-            if not bool((order[1:] > order[:-1]).all()):
-                at = torch.argsort(order.long())
-                frames, order = frames.index_select(0, at), order[at]
             T = frames.shape[0]
             C = self.C.to(device, torch.float32)
             Cs = C[:, order.long()].contiguous()                     # the traces of the frames served, in time order
-            step = max(1, min(T, (1 << 30) // (4 * max(NC * P, K * K))))
+            step = _gib_rows(T, max(NC * P, K * K))
             nbr, state, M, b = self._gram_nbr, None, None, None
             for s in range(0, T, step):
                 fr, tt = frames[s:s + step], order[s:s + step]

@@ -16,34 +16,16 @@
 //           ceil(n / NM_WAVES)) in their order; the NM_WAVES partial sums of a voxel meet in LDS and are added in wave order.
 // Both read E[m] along j: coalesced.  Every sum has a fixed order and there are no atomics: the same input gives the same bits.
 #include "block_ops.hpp"
+#include "boxes.hpp"
 
 namespace dnmf {
 namespace {
 
-constexpr int AC_MAX_VOXELS = 4096;     // K24's limit on a box
 constexpr int AC_MAX_BOXES = 4096;
 constexpr int AC_MAX_FRAMES = 18432;
 
 constexpr int RB_THREADS = 256;
 constexpr int RB_FRAMES = 8;            // frames a workgroup gathers: the offsets of a lane's voxels are worked out once per run
-
-struct Box {
-    int x0, y0, z0, ey, ez, n;
-};
-
-__device__ __forceinline__ Box load_box(const int *b) {
-    Box q;
-    q.x0 = b[0], q.y0 = b[2], q.z0 = b[4];
-    q.ey = b[3] - b[2] + 1, q.ez = b[5] - b[4] + 1;
-    q.n = (b[1] - b[0] + 1) * q.ey * q.ez;
-    return q;
-}
-
-// voxel i of the box (x slowest, z fastest) -> its offset inside a frame
-__device__ __forceinline__ int box_offset(const Box &q, int i, int Y, int Z) {
-    const int bz = i % q.ez, r = i / q.ez, by = r % q.ey, bx = r / q.ey;
-    return ((q.x0 + bx) * Y + q.y0 + by) * Z + q.z0 + bz;
-}
 
 struct GatherArgs {
     const float *frames, *sub;
@@ -156,7 +138,7 @@ __device__ __forceinline__ void a_step(const float *Em, double *a, const double 
 }
 
 __global__ __launch_bounds__(NM_THREADS) void rank1_nmf_kernel(NmfArgs g) {
-    __shared__ double a[AC_MAX_VOXELS];
+    __shared__ double a[BOX_MAX_VOXELS];
     __shared__ double part[NM_WAVES * 64];
     __shared__ double red[NM_WAVES];
     const int tid = threadIdx.x, m = blockIdx.x;
@@ -212,7 +194,7 @@ __global__ __launch_bounds__(NM_THREADS) void rank1_nmf_kernel(NmfArgs g) {
 
 int nmf_limits(const char *fn, int M, int n, int vmax) {
     DNMF_REQUIRE(M >= 1 && n >= 1 && vmax >= 1, DNMF_E_SHAPE, "%s: M=%d candidates, n=%d frames, vmax=%d voxels", fn, M, n, vmax);
-    DNMF_REQUIRE(vmax <= AC_MAX_VOXELS, DNMF_E_UNSUPPORTED, "%s: vmax=%d voxels a box, at most %d", fn, vmax, AC_MAX_VOXELS);
+    DNMF_REQUIRE(vmax <= BOX_MAX_VOXELS, DNMF_E_UNSUPPORTED, "%s: vmax=%d voxels a box, at most %d", fn, vmax, BOX_MAX_VOXELS);
     DNMF_REQUIRE(M <= AC_MAX_BOXES, DNMF_E_UNSUPPORTED, "%s: M=%d candidates, at most %d", fn, M, AC_MAX_BOXES);
     DNMF_REQUIRE(n <= AC_MAX_FRAMES, DNMF_E_UNSUPPORTED, "%s: n=%d frames, at most %d", fn, n, AC_MAX_FRAMES);
     return DNMF_OK;
@@ -235,15 +217,8 @@ int dnmf_residual_boxes(const float *frames, long ldf, const float *sub, long ld
     if (rc != DNMF_OK) return rc;
     DNMF_REQUIRE(B >= 1 && t0 >= 0 && (long)t0 + B <= n, DNMF_E_SHAPE, "%s: B=%d frames at t0=%d of n=%d", fn, B, t0, n);
     DNMF_REQUIRE(ldf >= P && (!sub || lds >= P), DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld below a row of P=%ld", fn, ldf, lds, P);
-    for (int m = 0; m < M; ++m) {
-        const int *b = boxes + 6 * (long)m;
-        const bool inside = b[0] >= 0 && b[1] < sz[0] && b[2] >= 0 && b[3] < sz[1] && b[4] >= 0 && b[5] < sz[2];
-        DNMF_REQUIRE(inside && b[0] <= b[1] && b[2] <= b[3] && b[4] <= b[5], DNMF_E_SHAPE,
-                     "%s: box %d = x %d..%d, y %d..%d, z %d..%d is empty or outside the volume %dx%dx%d", fn, m, b[0], b[1], b[2], b[3],
-                     b[4], b[5], sz[0], sz[1], sz[2]);
-        const long nb = (long)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) * (b[5] - b[4] + 1);
-        DNMF_REQUIRE(nb <= vmax, DNMF_E_SHAPE, "%s: box %d holds %ld voxels, vmax=%d", fn, m, nb, vmax);
-    }
+    const int rb = check_boxes(fn, sz, boxes, M, vmax, DNMF_E_SHAPE, "vmax=");
+    if (rb != DNMF_OK) return rb;
     GatherArgs a;
     a.frames = frames, a.sub = sub, a.ldf = ldf, a.lds = lds, a.frame_ids = frame_ids, a.boxes = boxes_dev;
     a.Y = sz[1], a.Z = sz[2], a.B = B, a.n = n, a.vmax = vmax, a.t0 = t0, a.E = E;

@@ -12,12 +12,12 @@
 // the segments of a neuron in their order (no floating-point atomics: the same input gives the same bits) and forms the
 // per-frame and per-neuron figures.
 #include "block_ops.hpp"
+#include "boxes.hpp"
 
 namespace dnmf {
 namespace {
 
 constexpr int CS_THREADS = 256, CS_WAVES = CS_THREADS / 64;
-constexpr int CS_MAX_VOXELS = 4096;     // K13's limit: 16 voxels a lane
 constexpr int CS_MIN_SEGMENT = 16;      // frames: below this the partial image sums cost more traffic than the frames
 constexpr int CS_TARGET_BLOCKS = 2048;
 
@@ -37,17 +37,8 @@ int component_plan(const char *fn, const int *sz, const int *boxes, int K, int B
     g.P = (long)g.X * g.Y * g.Z;
     DNMF_REQUIRE(g.P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, g.P);
     DNMF_REQUIRE(K <= (1 << 20), DNMF_E_UNSUPPORTED, "%s: K=%d neurons", fn, K);
-    g.vmax = 0;
-    for (int k = 0; k < K; ++k) {
-        const int *b = boxes + 6 * (long)k;
-        const bool inside = b[0] >= 0 && b[1] < g.X && b[2] >= 0 && b[3] < g.Y && b[4] >= 0 && b[5] < g.Z;
-        DNMF_REQUIRE(inside && b[0] <= b[1] && b[2] <= b[3] && b[4] <= b[5], DNMF_E_SHAPE,
-                     "%s: box %d = x %d..%d, y %d..%d, z %d..%d is empty or outside the volume %dx%dx%d", fn, k, b[0], b[1], b[2], b[3],
-                     b[4], b[5], g.X, g.Y, g.Z);
-        const long n = (long)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) * (b[5] - b[4] + 1);
-        DNMF_REQUIRE(n <= CS_MAX_VOXELS, DNMF_E_UNSUPPORTED, "%s: box %d holds %ld voxels, at most %d", fn, k, n, CS_MAX_VOXELS);
-        if ((int)n > g.vmax) g.vmax = (int)n;
-    }
+    const int rb = check_boxes(fn, sz, boxes, K, BOX_MAX_VOXELS, DNMF_E_UNSUPPORTED, "at most ", &g.vmax);
+    if (rb != DNMF_OK) return rb;
     const int per_lane = (g.vmax + CS_THREADS - 1) / CS_THREADS;
     g.slots = 1;
     while (g.slots < per_lane) g.slots *= 2;
@@ -73,24 +64,6 @@ struct ComponentArgs {
     double *part_w;        // (K, cap)
     size_t cap, vstride;
 };
-
-struct Box {
-    int x0, y0, z0, ey, ez, n;
-};
-
-__device__ __forceinline__ Box load_box(const int *b) {
-    Box q;
-    q.x0 = b[0], q.y0 = b[2], q.z0 = b[4];
-    q.ey = b[3] - b[2] + 1, q.ez = b[5] - b[4] + 1;
-    q.n = (b[1] - b[0] + 1) * q.ey * q.ez;
-    return q;
-}
-
-// voxel i of the box (x slowest, z fastest) -> its offset inside a frame
-__device__ __forceinline__ int box_offset(const Box &q, int i, int Y, int Z) {
-    const int bz = i % q.ez, r = i / q.ez, by = r % q.ey, bx = r / q.ey;
-    return ((q.x0 + bx) * Y + q.y0 + by) * Z + q.z0 + bz;
-}
 
 // The sums of three values over the workgroup behind one barrier, in every lane, in block_reduce's order (block_ops.hpp).  red:
 // CS_WAVES x 3 doubles of LDS that no lane still reads.

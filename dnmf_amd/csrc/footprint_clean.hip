@@ -3,7 +3,7 @@
 // is an integer or a bit pattern; the kernel's only floating-point arithmetic is the sequential float64 sum of squares of the cut
 // and two float64 products.
 //
-// Clean.  One workgroup of FC_THREADS lanes per neuron, its box (at most FC_MAX_VOXELS voxels, x slowest) in LDS; a lane takes the
+// Clean.  One workgroup of FC_THREADS lanes per neuron, its box (at most BOX_MAX_VOXELS voxels, x slowest) in LDS; a lane takes the
 // box voxels lane, lane + FC_THREADS, ...
 //   median    27 (Z == 1: 9) taps from global memory, as 32-bit keys in IEEE totalOrder, sorted in registers by an odd-even
 //             transposition network of constant indices; the middle key is the median;
@@ -15,20 +15,20 @@
 //             every lane writes) until a block-wide flag stays clear -- at most n rounds; labels only decrease and are indices of
 //             voxels of the same part, so the fixed point is the part's lowest index under any schedule.  Sizes by integer LDS
 //             atomics; the largest part, a tie to the lowest index, by a max-reduction of (size, ~index).
-// The result goes to a compact (K, FC_MAX_VOXELS) buffer, the statistics to (K, 6) ints and (K, 2) doubles.
+// The result goes to a compact (K, BOX_MAX_VOXELS) buffer, the statistics to (K, 6) ints and (K, 2) doubles.
 //
 // Scatter.  One thread per entry of the (P, K) output, K fastest: the compact value inside the neuron's box, 0 outside, the input's
 // own bits for a neuron that was refused (ok = 0).  An entry is read and written by the same thread: out may be A itself.
 //
 // No floating-point atomics, no scratch.
 #include "block_ops.hpp"
+#include "boxes.hpp"
 
 namespace dnmf {
 namespace {
 
 constexpr int FC_THREADS = 256, FC_WAVES = FC_THREADS / 64;
-constexpr int FC_MAX_VOXELS = 4096;                                // K24's limit on a box
-constexpr int FC_PER_LANE = FC_MAX_VOXELS / FC_THREADS;
+constexpr int FC_PER_LANE = BOX_MAX_VOXELS / FC_THREADS;
 constexpr int FC_ISTATS = 6, FC_DSTATS = 2;                        // ok, n_box, n_cut, n_closed, n_parts, n_kept; threshold, energy
 constexpr int FC_NONE = 0x7fffffff;                                // the label of a voxel outside the mask
 
@@ -39,7 +39,7 @@ struct CleanArgs {
     int X, Y, Z;
     int method, median, closing, values;
     double nrgthr, maxthr;
-    float *comp;            // (K, FC_MAX_VOXELS)
+    float *comp;            // (K, BOX_MAX_VOXELS)
     int *istats;            // (K, FC_ISTATS)
     double *dstats;         // (K, FC_DSTATS)
 };
@@ -90,20 +90,21 @@ __device__ __forceinline__ uint64_t judge(float v) {
 }
 
 __global__ __launch_bounds__(FC_THREADS) void clean_footprints_kernel(CleanArgs g) {
-    __shared__ float m[FC_MAX_VOXELS];
-    __shared__ uint64_t key[FC_MAX_VOXELS];              // the sort of the cut; after it the labels and the part sizes
-    __shared__ uint8_t keep[FC_MAX_VOXELS], closed[FC_MAX_VOXELS];
+    __shared__ float m[BOX_MAX_VOXELS];
+    __shared__ uint64_t key[BOX_MAX_VOXELS];              // the sort of the cut; after it the labels and the part sizes
+    __shared__ uint8_t keep[BOX_MAX_VOXELS], closed[BOX_MAX_VOXELS];
     __shared__ uint64_t red[FC_WAVES];
     __shared__ double cut[2];                            // threshold, energy
-    int *lab = reinterpret_cast<int *>(key), *cnt = lab + FC_MAX_VOXELS;
+    int *lab = reinterpret_cast<int *>(key), *cnt = lab + BOX_MAX_VOXELS;
     uint8_t *dil = reinterpret_cast<uint8_t *>(cnt);
 
     const int tid = threadIdx.x;
     const long k = blockIdx.x;
     const int *b = g.boxes + 6 * k;
+    // all three extents are needed below (the closing and the parts walk the box itself), so not boxes.hpp's Box
     const int x0 = b[0], y0 = b[2], z0 = b[4];
     const int ex = b[1] - x0 + 1, ey = b[3] - y0 + 1, ez = b[5] - z0 + 1;
-    const int n = ex * ey * ez;                          // the host has checked the boxes: 1 <= n <= FC_MAX_VOXELS, inside the volume
+    const int n = ex * ey * ez;                          // the host has checked the boxes: 1 <= n <= BOX_MAX_VOXELS, inside the volume
     const float *col = g.A + k;
     int *ist = g.istats + FC_ISTATS * k;
     double *dst = g.dstats + FC_DSTATS * k;
@@ -247,15 +248,15 @@ __global__ __launch_bounds__(FC_THREADS) void clean_footprints_kernel(CleanArgs 
     for (int v = tid; v < n; v += FC_THREADS)
         if (closed[v] && lab[v] == v) {
             ++n_parts;
-            const uint64_t cand = ((uint64_t)cnt[v] << 32) | (uint32_t)(FC_MAX_VOXELS - v);    // larger size, then lower index
+            const uint64_t cand = ((uint64_t)cnt[v] << 32) | (uint32_t)(BOX_MAX_VOXELS - v);    // larger size, then lower index
             top = cand > top ? cand : top;
         }
     n_parts = block_reduce<FC_THREADS>(n_parts, OpSum(), red);
     top = block_reduce<FC_THREADS>(top, OpMaxKey(), red);
-    const int winner = FC_MAX_VOXELS - (int)(uint32_t)top, n_kept = (int)(top >> 32);
+    const int winner = BOX_MAX_VOXELS - (int)(uint32_t)top, n_kept = (int)(top >> 32);
 
     // 6. the values
-    float *comp = g.comp + FC_MAX_VOXELS * k;
+    float *comp = g.comp + BOX_MAX_VOXELS * k;
     for (int v = tid; v < n; v += FC_THREADS) {
         float a = 0.0f;
         if (closed[v] && lab[v] == winner) {
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(FC_THREADS) void scatter_footprints_kernel(ScatterA
         const int z = (int)(p % g.Z), r = (int)(p / g.Z), y = r % g.Y, x = r / g.Y;
         const int *b = g.boxes + 6 * k;
         const bool inside = x >= b[0] && x <= b[1] && y >= b[2] && y <= b[3] && z >= b[4] && z <= b[5];
-        a = inside ? g.comp[(long)FC_MAX_VOXELS * k + ((x - b[0]) * (b[3] - b[2] + 1) + y - b[2]) * (b[5] - b[4] + 1) + z - b[4]] : 0.0f;
+        a = inside ? g.comp[(long)BOX_MAX_VOXELS * k + ((x - b[0]) * (b[3] - b[2] + 1) + y - b[2]) * (b[5] - b[4] + 1) + z - b[4]] : 0.0f;
     }
     g.out[p * g.ldo + k] = a;
 }
@@ -308,7 +309,7 @@ size_t dnmf_clean_footprints_workspace(int K) {
         dnmf::fail(DNMF_E_SHAPE, "dnmf_clean_footprints_workspace: K=%d neurons", K);
         return 0;
     }
-    return sizeof(float) * dnmf::FC_MAX_VOXELS * (size_t)K;
+    return sizeof(float) * dnmf::BOX_MAX_VOXELS * (size_t)K;
 }
 
 int dnmf_clean_footprints(const float *A, long lda, const int *sz, const int *boxes, const int *boxes_dev, int K, int method,
@@ -328,15 +329,8 @@ int dnmf_clean_footprints(const float *A, long lda, const int *sz, const int *bo
                  DNMF_E_SHAPE, "%s: method=%d, median=%d, closing=%d, values=%d: each is 0 or 1", fn, method, median, closing, values);
     DNMF_REQUIRE(method == 1 || (nrgthr > 0.0 && nrgthr <= 1.0), DNMF_E_SHAPE, "%s: nrgthr=%g outside (0, 1]", fn, nrgthr);
     DNMF_REQUIRE(method == 0 || maxthr >= 0.0, DNMF_E_SHAPE, "%s: maxthr=%g, not >= 0", fn, maxthr);
-    for (int k = 0; k < K; ++k) {
-        const int *b = boxes + 6 * (long)k;
-        const bool inside = b[0] >= 0 && b[1] < X && b[2] >= 0 && b[3] < Y && b[4] >= 0 && b[5] < Z;
-        DNMF_REQUIRE(inside && b[0] <= b[1] && b[2] <= b[3] && b[4] <= b[5], DNMF_E_SHAPE,
-                     "%s: box %d = x %d..%d, y %d..%d, z %d..%d is empty or outside the volume %dx%dx%d", fn, k, b[0], b[1], b[2], b[3],
-                     b[4], b[5], X, Y, Z);
-        const long n = (long)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) * (b[5] - b[4] + 1);
-        DNMF_REQUIRE(n <= FC_MAX_VOXELS, DNMF_E_SHAPE, "%s: box %d holds %ld voxels, at most %d", fn, k, n, FC_MAX_VOXELS);
-    }
+    const int rb = check_boxes(fn, sz, boxes, K, BOX_MAX_VOXELS, DNMF_E_SHAPE);
+    if (rb != DNMF_OK) return rb;
     const size_t need = dnmf_clean_footprints_workspace(K);
     DNMF_REQUIRE(workspace_bytes >= need, DNMF_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu", fn, workspace_bytes, need);
     DNMF_REQUIRE(((size_t)workspace & 3) == 0, DNMF_E_WORKSPACE, "%s: workspace must be 4-byte aligned", fn);

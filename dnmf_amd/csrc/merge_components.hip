@@ -11,12 +11,12 @@
 // Apply.  One launch, one thread per entry of the new model: A_out[v, g] = sum over the members k of group g of u_k A[v, k] and
 // C_out[g, t] = sum_k w_k C[k, t], in member order, in float64, rounded once.
 #include "block_ops.hpp"
+#include "boxes.hpp"
 
 namespace dnmf {
 namespace {
 
 constexpr int MC_THREADS = 256, MC_WAVES = MC_THREADS / 64;
-constexpr int MC_MAX_VOXELS = 4096;     // K24's limit on a box
 constexpr int MC_SUMS = 8;              // saa, n, si, sj, sii, sjj, sij, scc
 
 struct PairArgs {
@@ -38,12 +38,12 @@ __global__ __launch_bounds__(MC_THREADS) void component_pairs_kernel(PairArgs g)
     const int y0 = max(bi[2], bj[2]), y1 = min(bi[3], bj[3]);
     const int z0 = max(bi[4], bj[4]), z1 = min(bi[5], bj[5]);
     const int ey = y1 - y0 + 1, ez = z1 - z0 + 1;
-    const int n = (x1 >= x0 && ey > 0 && ez > 0) ? (x1 - x0 + 1) * ey * ez : 0;   // inside both boxes: at most MC_MAX_VOXELS
+    const int n = (x1 >= x0 && ey > 0 && ez > 0) ? (x1 - x0 + 1) * ey * ez : 0;   // inside both boxes: at most BOX_MAX_VOXELS
+    const Box q = {x0, y0, z0, ey, ez, n};
     const float *Ai = g.A + (long)i * g.lda, *Aj = g.A + (long)j * g.lda;
     double saa = 0.0;
     for (int v = tid; v < n; v += MC_THREADS) {
-        const int bz = v % ez, r = v / ez, by = r % ey, bx = r / ey;
-        const int off = ((x0 + bx) * g.Y + y0 + by) * g.Z + z0 + bz;
+        const int off = box_offset(q, v, g.Y, g.Z);
         saa = fma((double)Ai[off], (double)Aj[off], saa);
     }
 
@@ -146,15 +146,8 @@ int dnmf_component_pairs(const float *A, long lda, const int *sz, const int *box
     DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, P);
     DNMF_REQUIRE(lda >= P, DNMF_E_SHAPE, "%s: lda=%ld below a row of P=%ld", fn, lda, P);
     DNMF_REQUIRE(ldc >= T, DNMF_E_SHAPE, "%s: ldc=%ld below a row of T=%d", fn, ldc, T);
-    for (int k = 0; k < K; ++k) {
-        const int *b = boxes + 6 * (long)k;
-        const bool inside = b[0] >= 0 && b[1] < X && b[2] >= 0 && b[3] < Y && b[4] >= 0 && b[5] < Z;
-        DNMF_REQUIRE(inside && b[0] <= b[1] && b[2] <= b[3] && b[4] <= b[5], DNMF_E_SHAPE,
-                     "%s: box %d = x %d..%d, y %d..%d, z %d..%d is empty or outside the volume %dx%dx%d", fn, k, b[0], b[1], b[2], b[3],
-                     b[4], b[5], X, Y, Z);
-        const long n = (long)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) * (b[5] - b[4] + 1);
-        DNMF_REQUIRE(n <= MC_MAX_VOXELS, DNMF_E_SHAPE, "%s: box %d holds %ld voxels, at most %d", fn, k, n, MC_MAX_VOXELS);
-    }
+    const int rb = check_boxes(fn, sz, boxes, K, BOX_MAX_VOXELS, DNMF_E_SHAPE);
+    if (rb != DNMF_OK) return rb;
     for (long p = 0; p < N; ++p)
         DNMF_REQUIRE(pairs[2 * p] >= 0 && pairs[2 * p] < K && pairs[2 * p + 1] >= 0 && pairs[2 * p + 1] < K, DNMF_E_SHAPE,
                      "%s: pair %ld = (%d, %d) outside [0, %d)", fn, p, pairs[2 * p], pairs[2 * p + 1], K);

@@ -2019,7 +2019,35 @@ def high_pass_frames(frames, sz, gSig, frame_ids=None, out=None, taps=None):
     return out
 
 
-COMPONENT_MAX_VOXELS = 4096   # the largest box of K24 (K13's limit)
+COMPONENT_MAX_VOXELS = 4096   # the largest box of K24, K26, K27 and K28 (csrc/boxes.hpp: BOX_MAX_VOXELS)
+
+
+def _boxes(fn, boxes, sz, n=None, limit=COMPONENT_MAX_VOXELS, noun="box", dev=None, check=True):
+    """``boxes`` (``n``, 6) -- None: (M, 6), M >= 1 -- as the box kernels take them -> (the host int32 copy, its copy on ``dev``,
+    the voxels of each box, int64).  With ``check`` every box lies inside the volume ``sz``, is not empty and holds at most
+    ``limit`` voxels, ``noun`` naming it in that message; without, the library's own check of the host copy speaks."""
+    X, Y, Z = (int(s) for s in sz)
+    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
+    if (bh.dim() != 2 or bh.shape[1] != 6 or bh.shape[0] < 1) if n is None else tuple(bh.shape) != (n, 6):
+        raise ValueError(f"{fn}: boxes must be ({'M' if n is None else n}, 6), got {tuple(bh.shape)}")
+    lo, hi = bh[:, 0::2].long(), bh[:, 1::2].long()
+    nvox = (hi - lo + 1).prod(1)
+    if check:
+        wrong = ((lo < 0) | (hi >= torch.tensor([X, Y, Z])) | (lo > hi)).any(1)
+        if bool(wrong.any()):
+            k = int(torch.nonzero(wrong)[0])
+            raise ValueError(f"{fn}: box {k} = {bh[k].tolist()} is empty or outside the volume {X}x{Y}x{Z}")
+        if int(nvox.max()) > limit:
+            raise ValueError(f"{fn}: {noun} {int(nvox.argmax())} holds {int(nvox.max())} voxels, at most {limit}")
+    return bh, (bh if dev is None else bh.to(dev)), nvox
+
+
+def _a_rows(fn, A_rows, P):
+    """The footprints as fp32 CUDA rows (K, >= ``P``) -> K."""
+    if A_rows.dim() != 2:
+        raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
+    _rows(A_rows, fn, "A_rows", P, f" and rows of {P} floats")
+    return A_rows.shape[0]
 
 
 def component_boxes(A, sz, floor=1e-3, margin=2):
@@ -2081,25 +2109,18 @@ def component_stats(frames, sz, A_rows, boxes, C, w, sub=None, frame_ids=None, s
     P = X * Y * Z
     fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
     dev = frames.device
-    if A_rows.dim() != 2:
-        raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
-    _rows(A_rows, fn, "A_rows", P, f" and rows of {P} floats")
-    K = A_rows.shape[0]
+    K = _a_rows(fn, A_rows, P)
     for name, t in (("C", C), ("w", w)):
         _rows(t, fn, name, B, f" and rows of {B} floats")
         if t.dim() != 2 or t.shape[0] != K:
             raise ValueError(f"{fn}: {name} must be ({K}, {B}), got {tuple(t.shape)}")
-    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
-    if tuple(bh.shape) != (K, 6):
-        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
-    bd = bh.to(dev)
+    bh, bd, nvox = _boxes(fn, boxes, sz, K, dev=dev, check=False)     # the workspace entry below checks them
     lib = _lib.load()
     sz3 = _int3((X, Y, Z))
     need = _need(lib, "dnmf_component_stats_workspace", sz3, bh.data_ptr(), K, B, int(segment))
     # the boxes may change between the calls, and with them the bytes: the library judges a later call's state
     state = _stream_state(fn, state, need, first, dev, sized=False)
-    ext = bh[:, 1::2] - bh[:, 0::2] + 1
-    vmax = int(ext.prod(1).max())
+    vmax = int(nvox.max())
     f64 = dict(dtype=torch.float64, device=dev)
     sums, foot = torch.empty((K, B, 3), **f64), torch.empty((K, 3), **f64)
     frame_corr, raw = torch.empty((K, B), **f64), torch.empty((K, B), **f64)
@@ -2142,10 +2163,7 @@ def component_pairs(A_rows, sz, boxes, C, pairs=None):
     fn = "component_pairs"
     X, Y, Z = (int(s) for s in sz)
     P = X * Y * Z
-    if A_rows.dim() != 2:
-        raise ValueError(f"{fn}: A_rows are rows (K, ld), got {tuple(A_rows.shape)}")
-    _rows(A_rows, fn, "A_rows", P, f" and rows of {P} floats")
-    K = A_rows.shape[0]
+    K = _a_rows(fn, A_rows, P)
     if K > MERGE_MAX_K:
         raise ValueError(f"{fn}: K={K} components, at most {MERGE_MAX_K}")
     dev = A_rows.device
@@ -2153,12 +2171,10 @@ def component_pairs(A_rows, sz, boxes, C, pairs=None):
     if C.dim() != 2 or C.shape[0] != K or C.device != dev:
         raise ValueError(f"{fn}: C must be ({K}, T) on {dev}, got {tuple(C.shape)} on {C.device}")
     T = C.shape[1]
-    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
-    if tuple(bh.shape) != (K, 6):
-        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
+    bh, bd, _ = _boxes(fn, boxes, sz, K, dev=dev, check=False)        # the library checks them, with the pairs
     ph = candidate_pairs(bh) if pairs is None else torch.as_tensor(pairs).detach()
     ph = ph.to("cpu", torch.int32).reshape(-1, 2).contiguous()
-    bd, pd = bh.to(dev), ph.to(dev)
+    pd = ph.to(dev)
     N = ph.shape[0]
     out = torch.empty((N, len(PAIR_SUMS)), dtype=torch.float64, device=dev)
     lib = _lib.load()
@@ -2347,25 +2363,13 @@ def clean_footprints(A, sz, boxes, method='nrg', nrgthr=0.9999, maxthr=0.2, medi
     if K < 1 or A.numel() != P * K or (A.dim() == 4 and tuple(A.shape[:3]) != (X, Y, Z)):
         raise ValueError(f"{fn}: A must be ({P}, K) or ({X}, {Y}, {Z}, K), got {tuple(A.shape)}")
     dev = A.device
-    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
-    if tuple(bh.shape) != (K, 6):
-        raise ValueError(f"{fn}: boxes must be ({K}, 6), got {tuple(bh.shape)}")
-    lo, hi = bh[:, 0::2].long(), bh[:, 1::2].long()
-    limit = torch.tensor([X, Y, Z])
-    wrong = ((lo < 0) | (hi >= limit) | (lo > hi)).any(1)
-    if bool(wrong.any()):
-        k = int(torch.nonzero(wrong)[0])
-        raise ValueError(f"{fn}: box {k} = {bh[k].tolist()} is empty or outside the volume {X}x{Y}x{Z}")
-    n = (hi - lo + 1).prod(1)
-    if int(n.max()) > COMPONENT_MAX_VOXELS:
-        raise ValueError(f"{fn}: the box of neuron {int(n.argmax())} holds {int(n.max())} voxels, at most {COMPONENT_MAX_VOXELS}")
+    bh, bd, _ = _boxes(fn, boxes, sz, K, noun="the box of neuron", dev=dev)
     if out is None:
         out = torch.empty_like(A)
     else:
         _f32(out, f"{fn}: out")
         if tuple(out.shape) != tuple(A.shape) or out.device != dev:
             raise ValueError(f"{fn}: out must be {tuple(A.shape)} on {dev}, got {tuple(out.shape)} on {out.device}")
-    bd = bh.to(dev)
     istats = torch.empty((K, len(CLEAN_STATS)), dtype=torch.int32, device=dev)
     dstats = torch.empty((K, 2), dtype=torch.float64, device=dev)
     lib = _lib.load()
@@ -2407,25 +2411,6 @@ def candidate_boxes(centres, sz, half):
     return boxes
 
 
-def _candidate_boxes(fn, boxes, sz):
-    """The host copy of ``boxes`` (M, 6), checked, and the voxels of each."""
-    X, Y, Z = (int(s) for s in sz)
-    bh = torch.as_tensor(boxes).detach().to("cpu", torch.int32).contiguous()
-    if bh.dim() != 2 or bh.shape[1] != 6 or bh.shape[0] < 1:
-        raise ValueError(f"{fn}: boxes must be (M, 6), got {tuple(bh.shape)}")
-    if bh.shape[0] > ADD_MAX_CANDIDATES:
-        raise ValueError(f"{fn}: {bh.shape[0]} candidates, at most {ADD_MAX_CANDIDATES}")
-    lo, hi = bh[:, 0::2].long(), bh[:, 1::2].long()
-    wrong = ((lo < 0) | (hi >= torch.tensor([X, Y, Z])) | (lo > hi)).any(1)
-    if bool(wrong.any()):
-        m = int(torch.nonzero(wrong)[0])
-        raise ValueError(f"{fn}: box {m} = {bh[m].tolist()} is empty or outside the volume {X}x{Y}x{Z}")
-    n = (hi - lo + 1).prod(1)
-    if int(n.max()) > COMPONENT_MAX_VOXELS:
-        raise ValueError(f"{fn}: box {int(n.argmax())} holds {int(n.max())} voxels, at most {COMPONENT_MAX_VOXELS}")
-    return bh, n
-
-
 def residual_boxes(frames, sz, boxes, sub=None, frame_ids=None, out=None, t0=0, n_total=None):
     """K28a.  The residual on candidate boxes -> ``E (M, n_total, vmax)`` fp32 CUDA: ``E[m, t0 + f, j] = frames_f(v_j) -
     sub_f(v_j)`` (one fp32 subtraction; the frame itself without ``sub``) for the voxels v_j of box m, x slowest as K24 numbers
@@ -2440,8 +2425,10 @@ def residual_boxes(frames, sz, boxes, sub=None, frame_ids=None, out=None, t0=0, 
     P = X * Y * Z
     fid, B = _frame_rows(fn, frames, sub, frame_ids, P)
     dev = frames.device
-    bh, nvox = _candidate_boxes(fn, boxes, sz)
+    bh, bd, nvox = _boxes(fn, boxes, sz, dev=dev)
     M, t0 = bh.shape[0], int(t0)
+    if M > ADD_MAX_CANDIDATES:
+        raise ValueError(f"{fn}: {M} candidates, at most {ADD_MAX_CANDIDATES}")
     n = t0 + B if n_total is None else int(n_total)
     if B < 1 or t0 < 0 or t0 + B > n:
         raise ValueError(f"{fn}: {B} frames at t0={t0} do not fit the {n} frames of E")
@@ -2456,7 +2443,6 @@ def residual_boxes(frames, sz, boxes, sub=None, frame_ids=None, out=None, t0=0, 
     vmax = out.shape[2]
     if vmax > COMPONENT_MAX_VOXELS:
         raise ValueError(f"{fn}: vmax={vmax}, at most {COMPONENT_MAX_VOXELS}")
-    bd = bh.to(dev)
     lib = _lib.load()
     with _timed("residual_boxes"):
         rc = lib.dnmf_residual_boxes(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),

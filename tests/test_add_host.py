@@ -256,7 +256,10 @@ def test_ops_and_driver_refuse_before_the_gpu():
                             "min_explained", "centres", "dry_run"]
     assert params["image"].default == 'corr' and params["centres"].default is None and params["dry_run"].default is False
     assert "self.last_add = None" in inspect.getsource(dNMF.DeformableNMF.__init__)
-    assert "_forget_k_shaped()" in inspect.getsource(dNMF.DeformableNMF.select_components)
+    # select_components ends in the shared tail of every change of the component count, and that tail forgets
+    assert "_components_changed(" in inspect.getsource(dNMF.DeformableNMF.select_components)
+    assert "_forget_k_shaped()" in inspect.getsource(dNMF.DeformableNMF._components_changed)
+    assert "_components_changed(" in inspect.getsource(dNMF.DeformableNMF.add_components)
     doc = dNMF.DeformableNMF.add_components.__doc__
     assert "merge_components" in doc and "tests/test_add_host.py" in doc
 
