@@ -192,9 +192,12 @@ def warp_gather(A: torch.Tensor, beta: torch.Tensor, times, want_A_t=True, want_
 
 
 def recon_image(Apk: torch.Tensor, K: int, sz, C: torch.Tensor, times, out: torch.Tensor | None = None) -> torch.Tensor:
-    """S[b] = sum_k C[k,times[b]] A[:,k] in the halo layout.  Apk (P,Kp), C (K,T) -> (B, halo_voxels(sz))."""
+    """S[b] = sum_k C[k,times[b]] A[:,k] in the halo layout.  Apk (P,Kp), C (K,T) with any row stride (a column window of
+    a longer trace table) -> (B, halo_voxels(sz))."""
     X, Y, Z = (int(s) for s in sz)
-    _f32(Apk, "Apk"), _f32(C, "C")
+    _f32(Apk, "Apk"), _rows(C, "recon_image", "C")
+    if C.dim() != 2 or C.shape[0] < K:
+        raise ValueError(f"recon_image: C must be (K, T) with K = {K} rows, got {tuple(C.shape)}")
     P, Kp = Apk.shape
     if P != X * Y * Z:
         raise ValueError(f"recon_image: Apk has {P} rows, the volume {X}x{Y}x{Z} has {X * Y * Z} voxels")
@@ -595,7 +598,7 @@ def render_frames(positions, traces, sz, shape_std, t0=0, T=None, out=None):
     if out is None:
         out = torch.empty((T, P), dtype=torch.float32, device=pos.device)
     lib = _lib.load()
-    amp = float(traces.max())
+    amp = float(traces.abs().max())   # the kernel's cut-off is sized for the largest magnitude: a negative trace counts
     for s in range(0, T, 32768):
         n = min(32768, T - s)
         _lib.check(lib.dnmf_render_frames(pos.data_ptr(), traces.data_ptr(), K, T_total, t0 + s, n, X, Y, Z,
