@@ -530,6 +530,29 @@ class ExponentialFP(nn.Module):
         pos, amp, _ = ops.track_neurons(rows, sz, pred, shape_std=shape_std, search=search, threshold=threshold, background=background)
         return (pos, amp) if on_gpu else (pos.cpu().numpy(), amp.cpu().numpy())
 
+    @staticmethod
+    def follow_positions(video, points, shape_std=3, search=(3, 3, 1), anchor=0, momentum=0.0, max_gap=5, threshold=0.0, background=None):
+        """The neurons followed through ``video`` (what ``track_positions`` takes) from their centres ``points`` (K,3) in the
+        frame ``anchor``, forwards and backwards, by K15c (``ops.follow_neurons``): ``(P_T (K,3,T) float64, amplitudes (K,T),
+        info)``, ``info`` a dict ``predicted (K,3,T), peaks (K,T), lost_at (K,2)``.  Unlike ``track_positions`` frame t is
+        chained on frame t -+ 1: it is searched within ``search`` voxels of the last position found plus ``momentum`` times
+        the last step, so a neuron that moves little per frame and far in total is followed with a small window -- the
+        guard against capture by a brighter neighbour -- and ``momentum=1`` follows one that moves further per frame than
+        the window is wide.  NaN = not found; after more than ``max_gap`` such frames in a row the chain is lost from
+        ``lost_at[k]`` (forward, backward; -1: never) on.  ``P_T`` feeds ``init_motion``, ``positions`` and ``roi_signals``
+        as tracks from anywhere.  The T steps of a chain are sequential and there is still no exclusion between neurons: a
+        neuron within about 2 shape_std of a brighter one can be captured by it.  numpy or CPU-torch in, numpy out; a CUDA
+        ``video`` gives CUDA tensors.  The reference has no counterpart."""
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "follow_positions")
+        pts = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points))
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError(f"follow_positions: points must be (K, 3), got {tuple(pts.shape)}")
+        out = ops.follow_neurons(rows, sz, pts.double().to(device), shape_std=shape_std, search=search, anchor=anchor, momentum=momentum,
+                                 max_gap=max_gap, threshold=threshold, background=background)
+        if not on_gpu:
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+        return out["positions"], out["amplitudes"], dict(predicted=out["predicted"], peaks=out["peaks"], lost_at=out["lost_at"])
+
 
 class DeformableNMF:
     """Reference ``Demix/dNMF.py:124-194``: owns the spatial model ``fp`` and the traces ``C`` (K,T)."""
@@ -608,6 +631,8 @@ class DeformableNMF:
         self.last_deconv = None
         # after match_traces: beta (K, 2), distance (K,), ok (K,) of that call (CUDA tensors)
         self.last_match = None
+        # after follow: (P_T (K,3,T), amplitudes (K,T), info) of that call
+        self.last_follow = None
         # after evaluate_components: r_values, snr, frame_corr, raw, images, boxes, n_active and keep of that call
         self.last_evaluation = None
         # after merge_components: pairs, overlap, corr, groups, merged and K of that call
@@ -1753,6 +1778,18 @@ class DeformableNMF:
                 raise ValueError(f"track: predict must be None, 'model' or positions, got {predict!r}")
             predict = self.positions()
         return ExponentialFP.track_positions(frames, self.fp.pos, shape_std=float(self.fp.sigma[0]), search=search, predict=predict, **kw)
+
+    def follow(self, frames, anchor=0, start=None, search=(3, 3, 1), **kw):
+        """The model's neurons followed through ``frames`` from the frame ``anchor``, forwards and backwards, each frame
+        searched around what the frame before gave (K15c, ``ExponentialFP.follow_positions``, with the model's width
+        ``fp.sigma``): ``(P_T (K,3,T) float64, amplitudes (K,T), info)``, also kept in ``self.last_follow``.  ``start`` (K,3):
+        the centres in the anchor frame; None takes the model's centres there under the current warp,
+        ``self.positions(times=[anchor])``.  ``kw``: ``momentum``, ``max_gap``, ``threshold``, ``background``.  Neurons are not
+        excluded from one another: one within about 2 sigma of a brighter one can be captured by it."""
+        if start is None:
+            start = self.positions(times=[int(anchor)])[:, :, 0]
+        self.last_follow = ExponentialFP.follow_positions(frames, start, shape_std=float(self.fp.sigma[0]), search=search, anchor=anchor, **kw)
+        return self.last_follow
 
     def positions(self, points=None, times=None, start=None, tol=1e-6):
         """``fp.positions``: where the fitted warp puts the neurons in every frame, (K,3,T) float64 numpy."""

@@ -1465,6 +1465,67 @@ def track_neurons(frames, sz, predict, shape_std=3, search=(6, 6, 1), threshold=
     return positions, amplitudes, peaks
 
 
+def follow_neurons(frames, sz, start, shape_std=3, search=(3, 3, 1), anchor=0, momentum=0.0, max_gap=5, threshold=0.0, background=None,
+                   times=None):
+    """K15c.  frames as ``track_neurons`` takes them, start (K,3) fp32 / fp64 CUDA: the centres in frame ``anchor`` -> a dict of
+    CUDA tensors ``positions (K,3,T) fp64, amplitudes (K,T) fp32, peaks (K,T) fp32, predicted (K,3,T) fp64, lost_at (K,2)
+    int32``: every neuron followed from the anchor frame to the last and to the first frame of ``times`` (None: every row;
+    ``anchor`` counts its slots) by K15's search chained on itself (include/dnmf_hip.h): frame j is searched within ``search``
+    voxels of ``predicted[k, :, j]`` = the last position found + ``momentum`` x the last step x the frames since.  A frame
+    without a result is NaN and the chain coasts; after more than ``max_gap`` such frames in a row it is lost: ``lost_at[k]``
+    (forward, backward) holds that frame (-1: never lost) and the frames after it are NaN.  A start row that is not finite gives
+    NaN rows and ``lost_at = anchor``.  ``shape_std``, ``threshold``, ``background`` as in ``track_neurons``.  The T steps of a
+    chain are sequential and only 2 K workgroups run; there is still no exclusion between neurons: a neuron within about
+    2 shape_std of a brighter one can be captured by it, and both chains then follow the same blob."""
+    X, Y, Z = (int(s) for s in sz)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2
+            and frames.stride(1) == 1 and frames.stride(0) >= X * Y * Z and frames.shape[1] >= X * Y * Z):
+        raise ValueError("follow_neurons: frames must be float32 CUDA (T, ld) rows with unit inner stride and ld >= X Y Z")
+    dev = frames.device
+    if not (isinstance(start, torch.Tensor) and start.is_cuda and start.dtype in (torch.float32, torch.float64) and start.dim() == 2
+            and start.shape[1] == 3 and start.shape[0] >= 1):
+        raise ValueError("follow_neurons: start must be a (K,3) float32 or float64 CUDA tensor with K >= 1")
+    start = start.double().contiguous()
+    K = start.shape[0]
+    tt = None
+    if times is not None:
+        tt = _i32(times, dev)
+        if tt.numel() < 1 or int(tt.min()) < 0 or int(tt.max()) >= frames.shape[0]:
+            raise ValueError(f"follow_neurons: times must be at least one row index in [0, {frames.shape[0]})")
+    T = tt.numel() if tt is not None else frames.shape[0]
+    w = [int(v) for v in search]
+    if len(w) != 3 or min(w) < 0:
+        raise ValueError(f"follow_neurons: search must be three integers >= 0, got {search}")
+    sigma = float(shape_std)
+    if not (sigma > 0.0 and sigma != float("inf")):
+        raise ValueError(f"follow_neurons: shape_std={shape_std} must be positive and finite")
+    anchor, max_gap, momentum = int(anchor), int(max_gap), float(momentum)
+    if not 0 <= anchor < T:
+        raise ValueError(f"follow_neurons: anchor={anchor} outside [0, {T})")
+    if not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"follow_neurons: momentum={momentum} must lie in [0, 1]")
+    if max_gap < 0:
+        raise ValueError(f"follow_neurons: max_gap={max_gap} must not be negative")
+    bg = None
+    if background is not None:
+        if isinstance(background, torch.Tensor) or hasattr(background, "__len__"):
+            bg = torch.as_tensor(background).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if bg.numel() != T:
+                raise ValueError(f"follow_neurons: background of {bg.numel()} values for {T} frames")
+        else:
+            bg = torch.full((T,), float(background), dtype=torch.float32, device=dev)
+    out = dict(positions=torch.empty((K, 3, T), dtype=torch.float64, device=dev),
+               amplitudes=torch.empty((K, T), dtype=torch.float32, device=dev), peaks=torch.empty((K, T), dtype=torch.float32, device=dev),
+               predicted=torch.empty((K, 3, T), dtype=torch.float64, device=dev), lost_at=torch.empty((K, 2), dtype=torch.int32, device=dev))
+    with _timed("follow_neurons"):
+        rc = _lib.load().dnmf_follow_neurons(frames.data_ptr(), frames.stride(0), _int3((X, Y, Z)), T, _ptr(tt), start.data_ptr(), K, sigma,
+                                             _int3(w), anchor, momentum, max_gap, float(threshold), _ptr(bg), out["positions"].data_ptr(),
+                                             out["amplitudes"].data_ptr(), out["peaks"].data_ptr(), out["predicted"].data_ptr(),
+                                             out["lost_at"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_follow_neurons")
+    return out
+
+
 NEIGHBOURS = {"face": 0, "full": 1}   # DNMF_NEIGHBOURS_* of include/dnmf_hip.h
 
 

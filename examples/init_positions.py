@@ -5,7 +5,7 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track] [--follow]
                                       [--gn [--motion-smooth S] [--motion-order ORDER]]
                                       [--detect-image {template,corr,max,std}]
 
@@ -22,6 +22,10 @@ which averages over time.  The same three numbers are printed for the chosen ima
 peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
 printed for both sets of tracks.
 
+``--follow``: the centres of frame 0 are followed through the video by the chained tracker (``ExponentialFP.follow_positions``,
+K15c: every frame searched within ``--search`` voxels of what the frame before gave, no registration involved) and the same
+three numbers are printed with ``init_motion`` fed from those tracks; the numbers with it are unmeasured.
+
 ``--gn``: every fit is repeated with the Gauss-Newton motion solver (``fit(..., motion_solver='gn')``: K16 + Levenberg-Marquardt
 steps per frame, ``--gn-iters`` of them, no learning rate) and its three numbers are printed beside Adam's.  ``--motion-smooth S``
 gives that fit the temporal prior (``fit(..., motion_smooth=S)``, K16s: S in mean squared error per squared voxel of
@@ -37,7 +41,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from Demix.dNMF import DeformableNMF, SimulatedVideoDataset  # noqa: E402
+from Demix.dNMF import DeformableNMF, ExponentialFP, SimulatedVideoDataset  # noqa: E402
 from Demix.MotionCorrect import MotionCorrect  # noqa: E402
 
 
@@ -55,13 +59,15 @@ def main():
     ap.add_argument("--detect-image", choices=("template", "corr", "max", "std"), default=None,
                     help="--detect on this image: the registration template or a summary image (K18) of the corrected movie")
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
+    ap.add_argument("--follow", action="store_true", help="follow the centres of frame 0 frame to frame (K15c) and start a fit from those tracks")
+    ap.add_argument("--momentum", type=float, default=0.0, help="--follow: share of the last step the next search is moved by")
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
     ap.add_argument("--gn-iters", type=int, default=10, help="--gn: Levenberg-Marquardt iterations per frame")
     ap.add_argument("--motion-smooth", type=float, default=0.0, help="--gn: weight of the temporal smoothness prior (0: none)")
     ap.add_argument("--motion-order", choices=("translation", "affine", "quadratic", "graded"), default="quadratic",
                     help="--gn: the coefficients the fit moves; graded: translation, then affine, then all")
     ap.add_argument("--gsig", type=float, default=None, help="register on high-pass-filtered frames: gSig_filt=(S, S) (K22)")
-    ap.add_argument("--search", type=int, default=3, help="--track: voxels searched in x and y around the initialiser's track")
+    ap.add_argument("--search", type=int, default=3, help="--track, --follow: voxels searched in x and y around the prediction")
     a = ap.parse_args()
     a.detect = a.detect or a.detect_image is not None
     if a.motion_smooth and not a.gn:
@@ -117,6 +123,14 @@ def main():
               f"centres {np.nanmean(np.abs(refined[sel, :2, :] - truth[tr, :2, :])):.2f} voxels with the tracker, {err:.2f} with "
               f"the initialiser alone")
         starts["tracker"] = refined
+    if a.follow:
+        chained, _, info = ExponentialFP.follow_positions(video, pts, shape_std=3, search=(a.search, a.search, 1), anchor=0,
+                                                          momentum=a.momentum)
+        lost = np.isnan(chained).any(1)
+        print(f"follow_positions: {int((~lost).sum())} of {lost.size} (neuron, frame) pairs found, {int((info['lost_at'] >= 0).sum())} "
+              f"chains lost; mean |x, y error| of the per-frame centres {np.nanmean(np.abs(chained[sel, :2, :] - truth[tr, :2, :])):.2f} "
+              f"voxels chained, {err:.2f} with the initialiser alone")
+        starts["chained"] = chained
     for start, tracks in starts.items():
         for solver in ("adam", "gn") if a.gn else ("adam",):
             torch.manual_seed(1)

@@ -609,6 +609,33 @@ int dnmf_track_neurons(const float *frames, long ldf, const int *sz, int T, cons
                        int predict_per_frame, int K, double sigma, const int *search, double threshold, const float *background,
                        double *positions, float *amplitudes, float *peaks, dnmf_stream_t stream);
 
+/* ---- K15c: chained neuron tracking -- K15's search, frame after frame ----------------------------------------------------
+ * Every neuron k < K is carried from the anchor frame through the T frames by two independent chains: the forward one visits
+ * the frames anchor, anchor + 1, ..., T - 1, the backward one anchor, anchor - 1, ..., 0 (it repeats the anchor search and
+ * writes nothing for the anchor frame).  tests/follow_restatement.py is the definition in float64.  A chain starts with
+ * last = start[k], vel = 0, n = 0, miss = 0 and does, per visited frame j:
+ *   predict  pred = last + (momentum * vel) * n, float64, every operation rounded once in the order written (no fused
+ *            multiply-add); predicted[k, :, j] = pred;
+ *   search   K15's search of frame j around pred, unchanged: window, pick, refinement, amplitude and NaN rules;
+ *   found    if n > 0: vel = (p^ - last) / n;  last = p^ (as stored: fp32 widened), n = 1, miss = 0; the row is written;
+ *   missed   the row is NaN; n += 1, miss += 1; if miss > max_gap the chain is lost: lost_at[k, direction] = j, and every later
+ *            frame of the chain gets NaN rows and a NaN predicted.
+ * A start row that is not finite loses both chains before their first search: lost_at = anchor and every frame is NaN, predicted
+ * included.  momentum = 0 searches around the last position found; momentum = 1 extrapolates the last step, which follows a
+ * neuron that moves further per frame than the window is wide.  There is still no exclusion between neurons: a neuron within
+ * about 2 sigma of a brighter one can be captured by it, and two chains may then follow the same blob.
+ * frames, ldf, sz, times (T device row indices, NULL: 0..T-1; anchor counts slots of times), search, threshold, background: as
+ * K15's.  start (K,3) fp64 on the device.  positions, predicted (K,3,T) fp64; amplitudes, peaks (K,T) fp32, either may be NULL;
+ * lost_at (K,2) int, forward then backward, -1 for a chain that was never lost.  One launch of 2 K workgroups, one per (neuron,
+ * direction), each of which walks its frames one after the other with its state in registers: the T steps of a chain are
+ * sequential, so the call has the parallelism of 2 K workgroups only.  Every output element is written by exactly one
+ * workgroup; no atomics, no host synchronisation, no workspace.  LDS as K15's.
+ * DNMF_E_NULL: frames, sz, start, search, positions, predicted or lost_at NULL;  DNMF_E_SHAPE: K15's, anchor outside [0, T),
+ * momentum outside [0, 1] or not finite, max_gap < 0;  DNMF_E_UNSUPPORTED: K15's.  Nothing is launched on an error. */
+int dnmf_follow_neurons(const float *frames, long ldf, const int *sz, int T, const int *times, const double *start, int K, double sigma,
+                        const int *search, int anchor, double momentum, int max_gap, double threshold, const float *background,
+                        double *positions, float *amplitudes, float *peaks, double *predicted, int *lost_at, dnmf_stream_t stream);
+
 /* ---- K16: per-frame normal equations of the motion fit, and the Levenberg-Marquardt step -----------------------------------
  * The motion loss is a sum over frames and frame t only sees beta[:, :, t]: 30 unknowns (12 at Z == 1) against P residuals.
  * With r(v) = A_tC(v) - y(v) and g_d(v) = d A_tC / d q_d (v) exactly as K2 forms them (same warp, same taps, out-of-bounds
