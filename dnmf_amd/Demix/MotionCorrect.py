@@ -440,8 +440,8 @@ class MotionCorrect(object):
         """``points`` (K,3) followed through ``video`` (T, X, Y, Z) by ``ExponentialFP.track_positions`` (K15): ``(P_T (K,3,T)
         float64, amplitudes (K,T))``, numpy.  The search of every frame is centred on ``apply_shifts_points(video, points)``
         when piecewise shifts are stored -- the patch grid's coarse track, refined per neuron -- else on the points
-        themselves; ``search`` defaults to ``max_shifts``; ``kw``: ``threshold``, ``background``.  A neuron within about 2
-        shape_std of a brighter one can be captured by it: ``search`` is the guard.  The reference has no counterpart."""
+        themselves; ``search`` defaults to ``max_shifts``; ``kw``: ``threshold``, ``background``, ``exclude``.  A neuron within
+        about 2 shape_std of a brighter one can be captured by it: ``search`` is the guard, ``exclude=R`` (K15x) the remedy.  The reference has no counterpart."""
         if not self.is3D:
             raise NotImplementedError("MotionCorrect.track_points is a 3-D function like apply_shifts_points; register 2-D "
                                       "videos as (T, X, Y, 1) with is3D=True")

@@ -506,7 +506,7 @@ class ExponentialFP(nn.Module):
         return (b, f) if on_gpu else (b.cpu().numpy(), f.cpu().numpy())
 
     @staticmethod
-    def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None):
+    def track_positions(video, points, shape_std=3, search=(6, 6, 1), predict=None, threshold=0.0, background=None, **kw):
         """Where the neurons are in every frame of ``video`` -- (T, X, Y, Z) values, or frames that already live on the GPU as
         ``(rows (T, P), sz)`` or a ``ResidentLoader``: ``(P_T (K,3,T) float64, amplitudes (K,T))`` by K15
         (``ops.track_neurons``): per neuron and frame the sub-voxel peak of the frame's matched-filter score (K14's, with
@@ -516,8 +516,18 @@ class ExponentialFP(nn.Module):
         on frame t - 1.  NaN = not found (the "not tracked" of ``init_motion``): the prediction is not finite, the window
         misses the volume, or the peak is not above ``threshold``.  ``background``: None (0), a number or T values taken off
         the frames.  The searches are independent and neighbouring neurons are not removed from the score: a neuron within
-        about 2 shape_std of a brighter one can be captured by it, and ``search`` is the guard against that.  numpy or
-        CPU-torch in, numpy out; a CUDA ``video`` gives CUDA tensors.  The reference has no counterpart."""
+        about 2 shape_std of a brighter one can be captured by it, and ``search`` is the guard against that -- unless the
+        one further keyword ``exclude=R`` (default 0: the call as described) is R >= 1: K15 then runs once for the peaks, each
+        frame's neurons are ordered by them (descending, stable, NaN last) and K15x (``ops.track_neurons_exclusive``)
+        searches them in that order, every neuron on the frame less the model footprints of those already placed, in R
+        rounds -- the brighter neuron no longer hides the dimmer one.  Two neurons that K15 finds on the same voxel have
+        equal peaks and keep the order of their indices.  ``follow_positions`` has no such mode.  numpy or CPU-torch in,
+        numpy out; a CUDA ``video`` gives CUDA tensors.  The reference has no counterpart."""
+        exclude = int(kw.pop("exclude", 0))
+        if kw:
+            raise TypeError(f"track_positions: unexpected keyword arguments {sorted(kw)}")
+        if exclude < 0:
+            raise ValueError(f"track_positions: exclude={exclude} must not be negative")
         rows, sz, on_gpu = ExponentialFP._video_rows(video, "track_positions")
         pred = points if predict is None else predict
         pred = pred if isinstance(pred, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pred))
@@ -527,7 +537,11 @@ class ExponentialFP(nn.Module):
         K = len(points)
         if pred.dim() not in (2, 3) or pred.shape[0] != K or pred.shape[1] != 3:
             raise ValueError(f"track_positions: predict must be ({K}, 3, T) or ({K}, 3), got {tuple(pred.shape)}")
-        pos, amp, _ = ops.track_neurons(rows, sz, pred, shape_std=shape_std, search=search, threshold=threshold, background=background)
+        pos, amp, peaks = ops.track_neurons(rows, sz, pred, shape_std=shape_std, search=search, threshold=threshold, background=background)
+        if exclude:
+            order = torch.argsort(torch.nan_to_num(peaks, nan=float("-inf")), dim=0, descending=True, stable=True).int()
+            pos, amp, _, _ = ops.track_neurons_exclusive(rows, sz, pred, order, shape_std=shape_std, search=search, rounds=exclude,
+                                                         threshold=threshold, background=background)
         return (pos, amp) if on_gpu else (pos.cpu().numpy(), amp.cpu().numpy())
 
     @staticmethod
@@ -1771,8 +1785,9 @@ class DeformableNMF:
         the model's own centres ``fp.pos`` and width ``fp.sigma`` (K15): ``(P_T (K,3,T) float64, amplitudes (K,T))``, tracks
         that feed ``init_motion`` unchanged.  ``predict``: None looks around ``fp.pos`` in every frame, ``'model'`` around
         ``self.positions()`` -- tracking around the current warp -- and a (K,3,T) or (K,3) array around itself; ``kw``:
-        ``threshold``, ``background``.  Neighbouring neurons are not removed from the score, so a neuron within about
-        2 sigma of a brighter one can be captured by it: ``search`` is the guard."""
+        ``threshold``, ``background``, ``exclude``.  Neighbouring neurons are not removed from the score, so a neuron within
+        about 2 sigma of a brighter one can be captured by it: ``search`` is the guard, and ``exclude=R`` (K15x, R rounds) the
+        remedy."""
         if isinstance(predict, str):
             if predict != 'model':
                 raise ValueError(f"track: predict must be None, 'model' or positions, got {predict!r}")

@@ -99,6 +99,7 @@ SIGNATURES = {
     "dnmf_detect_neurons": (_i, [_vp, _vp, _i, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dnmf_track_neurons": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _d, _vp, _d, _vp, _vp, _vp, _vp, _vp]),
     "dnmf_follow_neurons": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _d, _vp, _i, _d, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dnmf_track_neurons_exclusive": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _d, _vp, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dnmf_warp_normal_eqs_workspace": (_sz, [_i, _i, _i, _i]),
     "dnmf_warp_normal_eqs": (_i, [_vp, _l, _vp, _vp, _l, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "dnmf_lm_step": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp]),

@@ -1,4 +1,4 @@
-// The search K15 (track_neurons.hip) and K15c (follow_neurons.hip) share: one workgroup of TK_THREADS threads looks for the
+// The search K15 (track_neurons.hip), K15c (follow_neurons.hip) and K15x (track_exclusive.hip) share: one workgroup of TK_THREADS threads looks for the
 // peak of one frame's K14 score inside the window around one predicted position (tests/track_restatement.py is the
 // definition, in float64; everything here is fp32), and the host-side geometry that sizes its LDS.
 //
@@ -87,14 +87,28 @@ struct TrackLds {
     float *e2;     // 3
 };
 
+// What a search does to the region as it stages it.  K15 and K15c stage the frame as it is; K15x (track_exclusive.hip) takes the
+// placed neighbours off.  begin: the region is known -- the box of extents (c0, c1, c2) whose first voxel is (q0, q1, q2) -- and
+// nothing of it is staged yet; operator(): the value to store for the voxel (l0, l1, l2) of the box, given frame - background;
+// finish: every thread has stored its values in buf (voxel e = tid, tid + TK_THREADS, ...), the barrier that ends the
+// staging has not been reached.  begin and finish are called by the whole workgroup and may hold barriers.
+struct StageAsIs {
+    __device__ __forceinline__ void begin(int, int, int, int, int, int, int) {}
+    __device__ __forceinline__ float operator()(float v, int, int, int) const { return v; }
+    __device__ __forceinline__ void finish(float *, int) {}
+};
+
 // One search of the frame row `fr` (background `bg` taken off) around `pred`, by the whole workgroup; every argument, and so
 // the result and every branch around a barrier, is the same in every thread.  The caller has filled L.tap / L.c2 (fill_taps;
 // the first barrier here orders them) and no thread may still read L of an earlier search of a kind that this one writes: the
 // barriers of a search order bufA, bufB, wv and wi against the search before; e2 and c2 are read by thread 0 after the last
 // barrier and written again only after the first barriers of the next search.
-// True: p^ in phat (every thread), the score at the picked voxel in peak (every thread), the amplitude in amp (thread 0 only).
-__device__ __forceinline__ bool track_search(const float *__restrict__ fr, float bg, const TrackGeom &g, double px, double py, double pz,
-                                             const TrackLds &L, int tid, float (&phat)[3], float &amp, float &peak) {
+// True: p^ in phat (every thread), the score at the picked voxel in peak (every thread), the amplitude in amp (thread 0 only),
+// p* in pick (every thread).
+template <typename Stage>
+__device__ __forceinline__ bool track_search_staged(const float *__restrict__ fr, float bg, const TrackGeom &g, double px, double py,
+                                                    double pz, const TrackLds &L, int tid, float (&phat)[3], float &amp, float &peak,
+                                                    int (&pick)[3], Stage &stage) {
     const float *tap = L.tap, *c2 = L.c2;
     float *bufA = L.bufA, *bufB = L.bufB;
     const int lane = tid & 63, wave = tid >> 6;
@@ -111,10 +125,12 @@ __device__ __forceinline__ bool track_search(const float *__restrict__ fr, float
     int c0 = ihi[0] - ilo[0] + 1, c1 = ihi[1] - ilo[1] + 1, c2e = ihi[2] - ilo[2] + 1;
     int q0 = ilo[0], q1 = ilo[1], q2 = ilo[2];
     const int nin = c0 * c1 * c2e;
+    stage.begin(q0, q1, q2, c0, c1, c2e, tid);
     for (int e = tid; e < nin; e += TK_THREADS) {
         const int l2 = e % c2e, l1 = (e / c2e) % c1, l0 = e / (c2e * c1);
-        bufA[e] = fr[((long)(q0 + l0) * g.Y + (q1 + l1)) * g.Z + (q2 + l2)] - bg;
+        bufA[e] = stage(fr[((long)(q0 + l0) * g.Y + (q1 + l1)) * g.Z + (q2 + l2)] - bg, l0, l1, l2);
     }
+    stage.finish(bufA, tid);
     __syncthreads();
     filter_pass(bufA, bufB, tap, c2, r, g.o0, pick3(g.o0, slo[0], slo[1], slo[2]), pick3(g.o0, shi[0], shi[1], shi[2]),
                 pick3(g.o0, g.X, g.Y, g.Z), c0, c1, c2e, q0, q1, q2, tid);
@@ -178,9 +194,17 @@ __device__ __forceinline__ bool track_search(const float *__restrict__ fr, float
     __syncthreads();
     if (tid == 0) amp = footprint_amplitude(refined_score(bv, adj[0], adj[1], adj[2]), c2, r, S, L.e2[0], L.e2[1], L.e2[2]);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) phat[d] = (float)p[d] + dl[d];
+    for (int d = 0; d < 3; ++d) phat[d] = (float)p[d] + dl[d], pick[d] = p[d];
     peak = bv;
     return true;
+}
+
+// The search of K15 and K15c: the frame as it is.
+__device__ __forceinline__ bool track_search(const float *__restrict__ fr, float bg, const TrackGeom &g, double px, double py, double pz,
+                                             const TrackLds &L, int tid, float (&phat)[3], float &amp, float &peak) {
+    StageAsIs stage;
+    int pick[3];
+    return track_search_staged(fr, bg, g, px, py, pz, L, tid, phat, amp, peak, pick, stage);
 }
 
 // 0 ok, else the error already recorded.  Everything that can be checked without the device.

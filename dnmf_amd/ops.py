@@ -1465,6 +1465,75 @@ def track_neurons(frames, sz, predict, shape_std=3, search=(6, 6, 1), threshold=
     return positions, amplitudes, peaks
 
 
+def track_neurons_exclusive(frames, sz, predict, order, shape_std=3, search=(6, 6, 1), rounds=2, threshold=0.0, background=None,
+                            times=None):
+    """K15x.  ``track_neurons`` with exclusion between the neurons of a frame: frames, predict, shape_std, search, threshold,
+    background, times as there, order (K,T) int32 CUDA, a permutation of 0..K-1 per frame -> ``(positions (K,3,T) fp64,
+    amplitudes (K,T) fp32, peaks (K,T) fp32, n_subtracted (K,T) int32)``.  Per frame the neurons are searched in the sequence
+    ``order[:, t]``, each on the frame less the model footprints -- amplitude x exp(-|x - p^|^2 / shape_std^2) within
+    ceil(3 shape_std) voxels of the pick -- of the neurons already placed in that frame, so a neuron within about 2 shape_std
+    of a brighter one that is searched first is no longer captured by it; rounds 2 .. ``rounds`` search every neuron again
+    with all others taken off at their latest result (include/dnmf_hip.h).  A neuron without a result is NaN and is not taken
+    off.  ``n_subtracted``: the neighbours whose footprint met the searched region in the last round.  One workgroup per frame
+    walks its K rounds searches in sequence; K <= 1024."""
+    X, Y, Z = (int(s) for s in sz)
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.float32 and frames.dim() == 2
+            and frames.stride(1) == 1 and frames.stride(0) >= X * Y * Z and frames.shape[1] >= X * Y * Z):
+        raise ValueError("track_neurons_exclusive: frames must be float32 CUDA (T, ld) rows with unit inner stride and ld >= X Y Z")
+    dev = frames.device
+    per_frame = isinstance(predict, torch.Tensor) and predict.dim() == 3
+    if per_frame:
+        predict = _tracks(predict, "track_neurons_exclusive")
+    elif not (isinstance(predict, torch.Tensor) and predict.is_cuda and predict.dtype in (torch.float32, torch.float64)
+              and predict.dim() == 2 and predict.shape[1] == 3 and predict.shape[0] >= 1):
+        raise ValueError("track_neurons_exclusive: predict must be a (K,3,T) or (K,3) float32 or float64 CUDA tensor with K >= 1")
+    predict = predict.contiguous()
+    K = predict.shape[0]
+    tt = None
+    if times is not None:
+        tt = _i32(times, dev)
+        if tt.numel() < 1 or int(tt.min()) < 0 or int(tt.max()) >= frames.shape[0]:
+            raise ValueError(f"track_neurons_exclusive: times must be at least one row index in [0, {frames.shape[0]})")
+    T = tt.numel() if tt is not None else (predict.shape[2] if per_frame else frames.shape[0])
+    if per_frame and predict.shape[2] != T:
+        raise ValueError(f"track_neurons_exclusive: predict of {predict.shape[2]} frames for {T} frames")
+    if tt is None and frames.shape[0] < T:
+        raise ValueError(f"track_neurons_exclusive: {frames.shape[0]} frames for a prediction of {T} frames")
+    w = [int(v) for v in search]
+    if len(w) != 3 or min(w) < 0:
+        raise ValueError(f"track_neurons_exclusive: search must be three integers >= 0, got {search}")
+    sigma = float(shape_std)
+    if not (sigma > 0.0 and sigma != float("inf")):
+        raise ValueError(f"track_neurons_exclusive: shape_std={shape_std} must be positive and finite")
+    rounds = int(rounds)
+    if rounds < 1:
+        raise ValueError(f"track_neurons_exclusive: rounds={rounds} must be at least 1")
+    if not (isinstance(order, torch.Tensor) and order.is_cuda and order.dtype == torch.int32 and tuple(order.shape) == (K, T)):
+        raise ValueError(f"track_neurons_exclusive: order must be a ({K}, {T}) int32 CUDA tensor")
+    order = order.contiguous()
+    if not bool((order.sort(dim=0).values == torch.arange(K, dtype=torch.int32, device=dev)[:, None]).all()):
+        raise ValueError("track_neurons_exclusive: order must hold every neuron 0..K-1 once per frame (a permutation per column)")
+    bg = None
+    if background is not None:
+        if isinstance(background, torch.Tensor) or hasattr(background, "__len__"):
+            bg = torch.as_tensor(background).to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+            if bg.numel() != T:
+                raise ValueError(f"track_neurons_exclusive: background of {bg.numel()} values for {T} frames")
+        else:
+            bg = torch.full((T,), float(background), dtype=torch.float32, device=dev)
+    positions = torch.empty((K, 3, T), dtype=torch.float64, device=dev)
+    amplitudes = torch.empty((K, T), dtype=torch.float32, device=dev)
+    peaks = torch.empty((K, T), dtype=torch.float32, device=dev)
+    n_subtracted = torch.empty((K, T), dtype=torch.int32, device=dev)
+    with _timed("track_neurons_exclusive"):
+        rc = _lib.load().dnmf_track_neurons_exclusive(frames.data_ptr(), frames.stride(0), _int3((X, Y, Z)), T, _ptr(tt), predict.data_ptr(),
+                                                      int(predict.dtype == torch.float64), int(per_frame), K, order.data_ptr(), rounds,
+                                                      sigma, _int3(w), float(threshold), _ptr(bg), positions.data_ptr(),
+                                                      amplitudes.data_ptr(), peaks.data_ptr(), n_subtracted.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_track_neurons_exclusive")
+    return positions, amplitudes, peaks, n_subtracted
+
+
 def follow_neurons(frames, sz, start, shape_std=3, search=(3, 3, 1), anchor=0, momentum=0.0, max_gap=5, threshold=0.0, background=None,
                    times=None):
     """K15c.  frames as ``track_neurons`` takes them, start (K,3) fp32 / fp64 CUDA: the centres in frame ``anchor`` -> a dict of

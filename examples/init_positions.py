@@ -5,7 +5,7 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 ``DeformableNMF`` from those tracks (``init_motion``), fit, and read the tracks (``positions``) and the traces back.  Needs an
 MI355X.
 
-    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track] [--follow]
+    python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track [--exclude R]] [--follow]
                                       [--gn [--motion-smooth S] [--motion-order ORDER]]
                                       [--detect-image {template,corr,max,std}]
 
@@ -20,7 +20,9 @@ which averages over time.  The same three numbers are printed for the chosen ima
 
 ``--track``: the initialiser's tracks are refined per neuron and frame by the tracker (``MotionCorrect.track_points``, K15: the
 peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
-printed for both sets of tracks.
+printed for both sets of tracks.  ``--exclude R`` (with ``--track``): the tracker takes the neurons already placed in a frame off
+the data before it looks for the next one, in R rounds (K15x, ``track_positions(..., exclude=R)``), so a neuron next to a
+brighter one is not captured by it; the numbers with it are unmeasured.
 
 ``--follow``: the centres of frame 0 are followed through the video by the chained tracker (``ExponentialFP.follow_positions``,
 K15c: every frame searched within ``--search`` voxels of what the frame before gave, no registration involved) and the same
@@ -59,6 +61,7 @@ def main():
     ap.add_argument("--detect-image", choices=("template", "corr", "max", "std"), default=None,
                     help="--detect on this image: the registration template or a summary image (K18) of the corrected movie")
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
+    ap.add_argument("--exclude", type=int, default=0, help="--track: rounds of exclusive tracking (K15x); 0: K15 as it is")
     ap.add_argument("--follow", action="store_true", help="follow the centres of frame 0 frame to frame (K15c) and start a fit from those tracks")
     ap.add_argument("--momentum", type=float, default=0.0, help="--follow: share of the last step the next search is moved by")
     ap.add_argument("--gn", action="store_true", help="repeat every fit with the Gauss-Newton motion solver")
@@ -117,7 +120,7 @@ def main():
 
     starts = {"identity": None, "tracks": P_T}
     if a.track:
-        refined, _ = mc.track_points(video, pts, search=(a.search, a.search, 1), shape_std=3)
+        refined, _ = mc.track_points(video, pts, search=(a.search, a.search, 1), shape_std=3, exclude=a.exclude)
         lost = np.isnan(refined).any(1)
         print(f"track_points: {int((~lost).sum())} of {lost.size} (neuron, frame) pairs found; mean |x, y error| of the per-frame "
               f"centres {np.nanmean(np.abs(refined[sel, :2, :] - truth[tr, :2, :])):.2f} voxels with the tracker, {err:.2f} with "

@@ -636,6 +636,31 @@ int dnmf_follow_neurons(const float *frames, long ldf, const int *sz, int T, con
                         const int *search, int anchor, double momentum, int max_gap, double threshold, const float *background,
                         double *positions, float *amplitudes, float *peaks, double *predicted, int *lost_at, dnmf_stream_t stream);
 
+/* ---- K15x: exclusive neuron tracking -- K15's search with the placed neighbours taken off -------------------------------------
+ * K15 with exclusion between the neurons of a frame.  tests/track_exclusive_restatement.py is the definition in float64; all
+ * arithmetic here is fp32.  Every frame j < T on its own; order[:, j] ((K,T) device ints, a permutation of 0..K-1 per frame) is
+ * the sequence of its searches.  A placed neuron i is its latest result (p*_i, p^_i, a_i); its footprint is
+ * a_i prod_d exp(-(x_d - p^_{i,d})^2 / sigma^2) at the voxels of the volume with |x_d - p*_{i,d}| <= r on every axis, 0 elsewhere.
+ *   round 1   for k in order[:, j]: K15's search of (k, j) -- window around predict, pick, refinement, amplitude, threshold and
+ *             NaN rules unchanged -- on frame_j - background_j - the footprints of the neurons placed so far in this frame.  A
+ *             search with a result places k; one without leaves it unplaced, and it is never subtracted;
+ *   rounds    2 .. rounds, the same order: k is searched again with all other placed neurons at their latest result taken off;
+ *             the new result replaces the old one; without a result k's row becomes NaN and k is unplaced.
+ * The outputs are those of the last round.  n_subtracted[k, j]: how many placed neighbours' +-r boxes met the region that (k, j)'s
+ * last search staged (0 without a window).  A frame's K rounds searches depend on one another and run in sequence.  Chaining
+ * on the frame before (K15c) with exclusion would need all K chains in lock-step per frame: not provided.
+ * frames, ldf, sz, times, predict, predict_f64, predict_per_frame, sigma, search, threshold, background, positions, amplitudes,
+ * peaks: as K15's.  order is not verified (it is device data): an entry outside [0, K) is skipped, and the rows of a neuron that
+ * a frame's order leaves out are not written.  n_subtracted (K,T) int or NULL.  One launch of T workgroups, one per frame; the
+ * placed list (9 words per neuron) and 16 neighbour tables lie in LDS beside K15's region: K <= 1024, and all of it within
+ * 48 KiB.  The same input gives the same bits; no atomics, no host synchronisation, no workspace.
+ * DNMF_E_NULL: frames, sz, predict, order, search or positions NULL;  DNMF_E_SHAPE: K15's, rounds < 1;  DNMF_E_UNSUPPORTED: K15's,
+ * K > 1024, LDS over 48 KiB (the message names the parts).  Nothing is launched on an error. */
+int dnmf_track_neurons_exclusive(const float *frames, long ldf, const int *sz, int T, const int *times, const void *predict, int predict_f64,
+                                 int predict_per_frame, int K, const int *order, int rounds, double sigma, const int *search,
+                                 double threshold, const float *background, double *positions, float *amplitudes, float *peaks,
+                                 int *n_subtracted, dnmf_stream_t stream);
+
 /* ---- K16: per-frame normal equations of the motion fit, and the Levenberg-Marquardt step -----------------------------------
  * The motion loss is a sum over frames and frame t only sees beta[:, :, t]: 30 unknowns (12 at Z == 1) against P residuals.
  * With r(v) = A_tC(v) - y(v) and g_d(v) = d A_tC / d q_d (v) exactly as K2 forms them (same warp, same taps, out-of-bounds
