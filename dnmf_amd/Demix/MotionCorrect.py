@@ -378,6 +378,36 @@ class MotionCorrect(object):
             images, state = ops.summary_images(rows, sz, neighbours=neighbours, state=state, first=n == 0, finish=n == len(pieces) - 1)
         return {k: v.cpu().numpy() for k, v in images.items()}
 
+    def _stored_pieces(self, who):
+        """``(pieces, sz)`` of the stored corrected movie -- ``mc_els`` when the piecewise pass kept one, else ``mc``; several
+        videos count as one movie: ``pieces()`` yields it as (rows, P) fp32 CUDA tensors of at most 1 GiB, in order."""
+        movies = getattr(self, "mc_els", None) or getattr(self, "mc", None)
+        if not movies:
+            raise ValueError(f"MotionCorrect.{who}: no video given and no corrected movie stored; construct with "
+                             "save_corrected=True and call motion_correct() first")
+        sz = [int(n) for n in movies[0].shape[:3]]
+        P = sz[0] * sz[1] * sz[2]
+        limit = max(1, (1 << 30) // (4 * P))
+
+        def pieces():
+            for m in movies:
+                for s in range(0, m.shape[3], limit):
+                    e = min(m.shape[3], s + limit)
+                    yield torch.from_numpy(np.ascontiguousarray(np.moveaxis(m[..., s:e], 3, 0))).to(device, torch.float32).reshape(e - s, P)
+        return pieces, sz
+
+    def robust_images(self, video=None, **kw):
+        """The order-statistic images (K30, ``ExponentialFP.robust_images``; ``kw``: ``percentiles``, ``noise``) of a
+        (T, X, Y, Z) ``video`` or, without one, of the stored corrected movie, as ``summary_images`` takes it: a dict
+        ``median / max / mad / noise / pnr / n / percentile`` of (X, Y, Z) numpy images (CUDA tensors for a CUDA ``video``).
+        The stored movie goes to the GPU in pieces of at most 1 GiB, once per pass of the selection.  Samples the
+        correction left NaN are left out of their voxel's statistics (``n`` counts the others)."""
+        from .dNMF import ExponentialFP, _images_to_numpy
+        if video is not None:
+            return ExponentialFP.robust_images(video, **kw)
+        pieces, sz = self._stored_pieces("robust_images")
+        return _images_to_numpy(ops.robust_images(pieces, sz, **kw))
+
     def detect_points(self, K, shape_std=3, **kw):
         """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
         made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,
@@ -388,7 +418,11 @@ class MotionCorrect(object):
 
         ``image`` (keyword, default ``'template'``: the above, unchanged): ``'corr'``, ``'max'`` or ``'std'`` search that summary
         image of the stored corrected movie (``summary_images()``, K18; needs ``save_corrected=True``) -- the template averages
-        over time and hides neurons that are dim on average but active; an (X, Y, Z) array is searched as given.  NaNs (the
+        over time and hides neurons that are dim on average but active; ``'temporal_median'`` and ``'pnr'`` search that image
+        of ``robust_images()`` (K30) and ``'corr_pnr'`` the product of K18's ``corr`` and ``pnr``, the usual seed image: pnr
+        shows an active cell however narrow and however dark its surroundings, where ``max`` and ``std`` show what is bright
+        and noisy (the temporal median is not called ``'median'``: that spelling stays an error, as it has been); an
+        (X, Y, Z) array is searched as given.  NaNs (the
         border strips the correction leaves, voxels without a valid neighbour) are replaced by the image's finite minimum,
         as the template's are."""
         if not self.is3D:
@@ -398,10 +432,15 @@ class MotionCorrect(object):
         from .dNMF import ExponentialFP
         if not isinstance(image, str) or image != "template":
             if isinstance(image, str):
-                if image not in ("corr", "max", "std"):
-                    raise ValueError(f"MotionCorrect.detect_points: image must be 'template', 'corr', 'max', 'std' or an (X, Y, Z) "
-                                     f"array, got {image!r}")
-                img = self.summary_images()[image]
+                if image not in ("corr", "max", "std", "temporal_median", "pnr", "corr_pnr"):
+                    raise ValueError(f"MotionCorrect.detect_points: image must be 'template', 'corr', 'max', 'std', "
+                                     f"'temporal_median', 'pnr', 'corr_pnr' or an (X, Y, Z) array, got {image!r}")
+                if image in ("corr", "max", "std"):
+                    img = self.summary_images()[image]
+                elif image == "corr_pnr":
+                    img = self.summary_images()["corr"] * self.robust_images()["pnr"]
+                else:
+                    img = self.robust_images()["median" if image == "temporal_median" else image]
             else:
                 img = image.detach().cpu().numpy() if torch.is_tensor(image) else np.asarray(image)
                 if img.ndim != 3:

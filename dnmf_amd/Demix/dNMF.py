@@ -43,6 +43,11 @@ STAGE_LIMIT = 96 << 30      # a host loader's frames are staged on the GPU once 
 GN_CHUNK_BYTES = 1 << 30    # update_motion(solver='gn') builds the reconstruction images of this many bytes of frames at a time
 
 
+def _images_to_numpy(images):
+    """A dict of CUDA images, one level of nesting allowed, as numpy."""
+    return {k: _images_to_numpy(v) if isinstance(v, dict) else v.cpu().numpy() for k, v in images.items()}
+
+
 def _sz_list(sz):
     return [int(s) for s in (sz.tolist() if isinstance(sz, torch.Tensor) else sz)]
 
@@ -481,6 +486,21 @@ class ExponentialFP(nn.Module):
         rows, sz, on_gpu = ExponentialFP._video_rows(video, "summary_images")
         images, _ = ops.summary_images(rows, sz, neighbours=neighbours)
         return images if on_gpu else {k: v.cpu().numpy() for k, v in images.items()}
+
+    @staticmethod
+    def robust_images(video, percentiles=(), noise='diff'):
+        """The order-statistic images of ``video`` -- (T, X, Y, Z) values, ``(rows (T, P), sz)`` or a ``ResidentLoader``, as
+        ``summary_images`` takes it -- by K30 (``ops.robust_images``, exact selection, the same bits on every run): a dict of
+        (X, Y, Z) float64 images ``median``, ``max``, ``mad`` (median |y - median|), ``noise`` (``'diff'``: the median absolute
+        difference of adjacent frames x 1.4826 / sqrt(2), what ``deconvolve`` estimates per trace; ``'mad'``: 1.4826 mad),
+        ``pnr`` = (max - median) / noise, ``n`` (int32: the finite samples of the voxel; the others are left out) and
+        ``percentile`` {p: image} for every p of ``percentiles`` (8 gives an F0 image).  ``median`` is a baseline no transient
+        pulls up; ``pnr`` shows a cell that is dim on average but active, however narrow, where ``max`` and ``std`` show what is
+        bright and noisy; ``corr`` x ``pnr`` is the usual seed image.  pnr is NaN where noise is 0 or not finite or n < 2.
+        numpy or CPU-torch in, numpy out; CUDA frames give CUDA tensors."""
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "robust_images")
+        images = ops.robust_images(rows, sz, percentiles, noise)
+        return images if on_gpu else _images_to_numpy(images)
 
     @staticmethod
     def background(video, iters=3):
@@ -1013,6 +1033,22 @@ class DeformableNMF:
                 images, state = ops.summary_images(fr, sz, sub=sub, neighbours=neighbours, state=state, first=s == 0,
                                                    finish=s + fr.shape[0] >= T)
         return images
+
+    def robust_images(self, loader, registered=None, **kw):
+        """The order-statistic images (``ExponentialFP.robust_images``, K30; ``kw``: ``percentiles``, ``noise``) of every frame
+        ``loader`` serves, in the loader's order: a dict of (X, Y, Z) float64 CUDA images.  ``registered='linear'`` (K17) or
+        ``'nearest'`` (K7) registers the frames under the current ``fp.beta`` first, as ``summary_images`` does.  The selection
+        sees the movie 9 times per group of quantiles (27 times in all with the defaults): the frames go through in pieces of at
+        most 1 GiB each time, and registered frames are made anew each time.  One channel, and a loader that holds every frame."""
+        if registered is not None:
+            _check_registered(registered, "robust_images")
+        self._single_model_only("robust_images", loader, "the loader holds a shard of the frames (a voxel's order statistics "
+                                                         "need all of its samples)")
+        sz = self.fp.sz_list
+        with torch.no_grad():
+            frames, order = self._gather_frames(loader)
+            P = sz[0] * sz[1] * sz[2]
+            return ops.robust_images(lambda: (fr for _, fr, _, _ in self._residual_pieces(frames, order, None, registered, P)), sz, **kw)
 
     def evaluate_components(self, loader, registered='linear', active=0.25, margin=2, floor=1e-3, min_r=0.5, min_snr=1.0):
         """Which of the K components explain anything (K24, ``ops.component_stats``): one pass over the registered frames

@@ -140,6 +140,10 @@ SIGNATURES = {
     "dnmf_colour_normal_eqs_workspace": (_sz, [_i, _i, _i]),
     "dnmf_colour_normal_eqs": (_i, [_vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "dnmf_colour_solve": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "dnmf_temporal_select_passes": (_i, []),
+    "dnmf_temporal_select_workspace": (_sz, [_vp, _i]),
+    "dnmf_temporal_select_pass": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _l, _i, _vp, _sz, _vp]),
+    "dnmf_temporal_select_finish": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

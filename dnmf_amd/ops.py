@@ -4,7 +4,9 @@ libdnmf_hip.so."""
 from __future__ import annotations
 
 import ctypes
+import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1637,6 +1639,182 @@ def summary_images(frames, sz, sub=None, frame_ids=None, neighbours='full', stat
     if not finish:
         return None, state
     return dict(mean=images[0], std=images[1], max=images[2], corr=images[3]), state
+
+
+SELECT_SOURCES = {"value": 0, "absdev": 1, "absdiff": 2}   # DNMF_SELECT_* of include/dnmf_hip.h
+TEMPORAL_MAX_QUANTILES = 4
+
+
+def temporal_quantiles_passes():
+    """How often ``temporal_quantiles`` has to see the whole movie: a movie fed in pieces is fed this many times."""
+    return _lib.load().dnmf_temporal_select_passes()
+
+
+class TemporalSelectState:
+    """What ``temporal_quantiles`` keeps between the pieces and the passes of one selection: ``buffer``, the device state of
+    K30 (``dnmf_temporal_select_workspace``: (8 + 76 Q) bytes a voxel, whatever the number of frames), the arguments the
+    selection was started with, ``pass_index``, ``rows`` (fed in this pass so far) and ``rows_per_pass`` (of pass 0, None while
+    that one runs)."""
+
+    def __init__(self, buffer, sz, q, source):
+        self.buffer, self.sz, self.q, self.source = buffer, tuple(sz), tuple(q), source
+        self.pass_index, self.rows, self.rows_per_pass = 0, 0, None
+
+
+def _interpolated_quantiles(lo, hi, n, q):
+    """numpy's ``method='linear'`` in float64 on the two order statistics: the line a_lo + (h - lo)(a_hi - a_lo), h = q (n - 1),
+    evaluated from the upper end where h - lo >= 0.5, as numpy does -- (Q, X, Y, Z) float64, NaN where n = 0."""
+    qv = torch.tensor(q, dtype=torch.float64, device=lo.device).reshape(-1, 1, 1, 1)
+    h = qv * (n.double() - 1.0)[None]
+    t = h - torch.floor(h)
+    a, b = lo.double(), hi.double()
+    d = b - a
+    return torch.where(t >= 0.5, b - d * (1.0 - t), a + d * t)
+
+
+def temporal_quantiles(frames, sz, q, source='value', centre=None, frame_ids=None, state=None, first=True, finish=True, segment=0):
+    """K30.  frames (rows, ld >= X Y Z) fp32 CUDA rows -> ``(result, state)``: per voxel the exact quantiles ``q`` (1 to 4
+    numbers in [0, 1], one call shares every pass over the movie among them) over time of
+
+    * ``source='value'``: the samples themselves;
+    * ``'absdev'``: ``|y - centre|`` with ``centre`` an fp32 image of X Y Z voxels (one fp32 subtraction);
+    * ``'absdiff'``: ``|y_{t+1} - y_t|`` in the order of the rows (``frame_ids`` order), one term fewer than rows.
+
+    Samples that are not finite are left out.  ``result`` is a dict of CUDA tensors: ``n`` (X, Y, Z) int32, the samples kept;
+    ``lo`` and ``hi`` (Q, X, Y, Z) fp32, the kept samples of ranks floor(h) and min(floor(h) + 1, n - 1), h = q (n - 1) --
+    input samples, bit for bit (-0 comes back as +0), NaN where n = 0; ``value`` (Q, X, Y, Z) float64, the two interpolated
+    like ``np.nanquantile(method='linear')``.  ``frame_ids``: the rows of ``frames`` to take (None: all, in order).
+
+    The selection sees the movie ``temporal_quantiles_passes()`` = 9 times.  With ``first=True, finish=True`` the rows are the
+    whole movie and one call does it all.  A movie larger than one buffer goes in pieces, once per pass: the first piece of
+    pass 0 has ``first=True`` (``state``: None for a new one, or one to reuse), every later call passes the returned state with
+    ``first=False``, and the last piece of each pass has ``finish=True``; ``result`` is None until the last piece of the last
+    pass.  Every pass must bring the same rows in the same order, cut in any way: the state counts them, and a pass that
+    brings more or fewer rows than pass 0 is refused.  Integer counts only: the same bits on every run and however the movie
+    is cut.  State: (8 + 76 Q) bytes a voxel (80 MiB for 512 x 512 x 2 and two quantiles).  ``segment``: frames per workgroup
+    (0: the kernel's choice)."""
+    fn = "temporal_quantiles"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    qs = [float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64)).ravel()]
+    if not 1 <= len(qs) <= TEMPORAL_MAX_QUANTILES:
+        raise ValueError(f"{fn}: {len(qs)} quantiles, 1 to {TEMPORAL_MAX_QUANTILES} a call")
+    if not all(0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f"{fn}: q must lie in [0, 1], got {qs}")
+    if source not in SELECT_SOURCES:
+        raise ValueError(f"{fn}: source must be 'value', 'absdev' or 'absdiff', got {source!r}")
+    fid, B = _frame_rows(fn, frames, None, frame_ids, P)
+    if B < 1:
+        raise ValueError(f"{fn}: no rows")
+    if fid is not None and (int(fid.min()) < 0 or int(fid.max()) >= frames.shape[0]):
+        raise ValueError(f"{fn}: frame_ids must be row indices in [0, {frames.shape[0]})")
+    dev = frames.device
+    if source == "absdev":
+        if centre is None:
+            raise ValueError(f"{fn}: source='absdev' needs centre, an fp32 image of {P} voxels")
+        if not (isinstance(centre, torch.Tensor) and centre.is_cuda and centre.dtype == torch.float32 and centre.numel() == P
+                and centre.is_contiguous()):
+            raise ValueError(f"{fn}: centre must be a contiguous float32 CUDA image of {P} voxels")
+    else:
+        centre = None
+    lib = _lib.load()
+    need = _need(lib, "dnmf_temporal_select_workspace", _int3((X, Y, Z)), len(qs))
+    if first:
+        buf = state.buffer if isinstance(state, TemporalSelectState) else None
+        state = TemporalSelectState(_workspace(buf, need, dev), (X, Y, Z), qs, source)
+    else:
+        if not isinstance(state, TemporalSelectState):
+            raise ValueError(f"{fn}: first=False needs the state of the earlier calls")
+        if (state.sz, state.q, state.source) != ((X, Y, Z), tuple(qs), source):
+            raise ValueError(f"{fn}: the selection was started with sz={state.sz}, q={state.q}, source={state.source!r}")
+    npass = lib.dnmf_temporal_select_passes()
+    if state.pass_index >= npass:
+        raise ValueError(f"{fn}: the selection is finished; start another with first=True")
+    whole = first and finish
+    if state.rows_per_pass is not None and state.rows + B > state.rows_per_pass:
+        raise ValueError(f"{fn}: pass {state.pass_index} brings {state.rows + B} rows so far, pass 0 had {state.rows_per_pass}: "
+                         f"every pass must bring the same rows")
+    if finish and state.rows_per_pass is not None and state.rows + B != state.rows_per_pass:
+        raise ValueError(f"{fn}: pass {state.pass_index} ends after {state.rows + B} rows, pass 0 had {state.rows_per_pass}: "
+                         f"every pass must bring the same rows")
+    qarr = (ctypes.c_double * len(qs))(*qs)
+    with _timed(fn):
+        for p in (range(npass) if whole else [state.pass_index]):
+            rc = lib.dnmf_temporal_select_pass(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3((X, Y, Z)), B, SELECT_SOURCES[source],
+                                               _ptr(centre), qarr, len(qs), p, 0 if whole else state.rows, int(segment),
+                                               state.buffer.data_ptr(), _nbytes(state.buffer), _stream())
+            _lib.check(rc, "dnmf_temporal_select_pass")
+    if whole:
+        state.pass_index, state.rows, state.rows_per_pass = npass, 0, B
+    else:
+        state.rows += B
+        if finish:
+            state.rows_per_pass = state.rows
+            state.pass_index, state.rows = state.pass_index + 1, 0
+    if state.pass_index < npass:
+        return None, state
+    Q = len(qs)
+    lo = torch.empty((Q, X, Y, Z), dtype=torch.float32, device=dev)
+    hi = torch.empty((Q, X, Y, Z), dtype=torch.float32, device=dev)
+    n = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
+    rc = lib.dnmf_temporal_select_finish(_int3((X, Y, Z)), Q, state.buffer.data_ptr(), _nbytes(state.buffer), lo.data_ptr(), hi.data_ptr(),
+                                         n.data_ptr(), _stream())
+    _lib.check(rc, "dnmf_temporal_select_finish")
+    return dict(lo=lo, hi=hi, n=n, value=_interpolated_quantiles(lo, hi, n, qs)), state
+
+
+NOISE_DIFF_SCALE = 1.4826 / math.sqrt(2.0)   # K21's estimate of a trace's noise from its adjacent differences (deconvolve_traces)
+NOISE_MAD_SCALE = 1.4826
+
+
+def _quantiles_of_pieces(pieces, sz, q, source='value', centre=None):
+    """``temporal_quantiles`` of a movie that ``pieces()`` serves as an iterable of row tensors, once per pass."""
+    state = result = None
+    for p in range(temporal_quantiles_passes()):
+        prev = None
+        for rows in pieces():
+            if prev is not None:
+                _, state = temporal_quantiles(prev, sz, q, source, centre, state=state, first=p == 0 and state is None, finish=False)
+            prev = rows
+        if prev is None:
+            raise ValueError("robust_images: no frames")
+        result, state = temporal_quantiles(prev, sz, q, source, centre, state=state, first=p == 0 and state is None, finish=True)
+        if result is not None:       # the last pass, or a movie of one piece, which one call takes through every pass
+            return result
+
+
+def robust_images(pieces, sz, percentiles=(), noise='diff'):
+    """The order-statistic images of a movie (K30, ``temporal_quantiles``; tests/robust_restatement.py R6): a dict of float64
+    CUDA images (X, Y, Z) -- ``median``, ``max``, ``mad`` = median |y - fp32(median)|, ``noise`` ('diff': median |y_{t+1} - y_t|
+    x 1.4826 / sqrt(2), the constants of the estimate ``deconvolve_traces`` makes per trace; 'mad': 1.4826 mad),
+    ``pnr`` = (max - median) / noise (NaN where noise is 0 or not finite, or n < 2), ``n`` int32 (the finite samples) and
+    ``percentile`` {p: image} for every p of ``percentiles`` (in [0, 100]).  ``pieces``: fp32 CUDA rows (T, ld >= X Y Z), or
+    a callable that returns an iterable of such pieces, in the same order at every call -- it is called once per pass, 9
+    passes for every selection: one for median, max and the first two percentiles, one per further four percentiles, one
+    for mad and, with noise='diff', one for the noise."""
+    if noise not in ("diff", "mad"):
+        raise ValueError(f"robust_images: noise must be 'diff' or 'mad', got {noise!r}")
+    ps = list(percentiles)
+    if not all(0.0 <= float(p) <= 100.0 for p in ps):
+        raise ValueError(f"robust_images: percentiles must lie in [0, 100], got {ps}")
+    if isinstance(pieces, torch.Tensor):
+        rows = pieces
+        pieces = lambda: (rows,)     # noqa: E731
+    qs = [0.5, 1.0] + [float(p) / 100.0 for p in ps]
+    values, n = [], None
+    for s in range(0, len(qs), TEMPORAL_MAX_QUANTILES):
+        r = _quantiles_of_pieces(pieces, sz, qs[s:s + TEMPORAL_MAX_QUANTILES])
+        values.extend(r["value"])
+        n = r["n"] if n is None else n
+    median, mx = values[0], values[1]
+    mad = _quantiles_of_pieces(pieces, sz, [0.5], 'absdev', median.float().contiguous())["value"][0]
+    if noise == "diff":
+        sigma = _quantiles_of_pieces(pieces, sz, [0.5], 'absdiff')["value"][0] * NOISE_DIFF_SCALE
+    else:
+        sigma = NOISE_MAD_SCALE * mad
+    ok = torch.isfinite(sigma) & (sigma != 0) & (n >= 2)
+    pnr = torch.where(ok, (mx - median) / sigma, torch.full_like(sigma, float("nan")))
+    return dict(median=median, max=mx, mad=mad, noise=sigma, pnr=pnr, n=n, percentile={p: values[2 + i] for i, p in enumerate(ps)})
 
 
 def background_state(sz, B, segment=0, device="cuda"):

@@ -7,7 +7,7 @@ MI355X.
 
     python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track [--exclude R]] [--follow]
                                       [--gn [--motion-smooth S] [--motion-order ORDER]]
-                                      [--detect-image {template,corr,max,std}]
+                                      [--detect-image {template,corr,max,std,temporal_median,pnr,corr_pnr}]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
 ground truth of frame 0; the model is built on the detected centres alone, as many neurons as were found.  The simulator's
@@ -16,7 +16,9 @@ when that is within sigma (one centre per neuron), and the errors and correlatio
 
 ``--detect-image corr | max | std`` (implies ``--detect``): the centres come from that summary image of the corrected movie
 (``MotionCorrect.summary_images``, K18; the registration then keeps its movie, ``save_corrected=True``) instead of the template,
-which averages over time.  The same three numbers are printed for the chosen image.
+which averages over time.  ``temporal_median | pnr | corr_pnr`` take the temporal median, the peak-to-noise image
+(``MotionCorrect.robust_images``, K30) or K18's ``corr`` times it, the usual seed image.  The same three numbers are printed for
+the chosen image; with the three K30 images they are unmeasured (the example has not been run with them).
 
 ``--track``: the initialiser's tracks are refined per neuron and frame by the tracker (``MotionCorrect.track_points``, K15: the
 peak of the matched-filter score within 3 voxels of the patch grid's track) before ``init_motion``; the same three numbers are
@@ -58,8 +60,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--batch", type=int, default=10)
     ap.add_argument("--detect", action="store_true", help="find the centres in the template instead of taking the simulator's")
-    ap.add_argument("--detect-image", choices=("template", "corr", "max", "std"), default=None,
-                    help="--detect on this image: the registration template or a summary image (K18) of the corrected movie")
+    ap.add_argument("--detect-image", choices=("template", "corr", "max", "std", "temporal_median", "pnr", "corr_pnr"), default=None,
+                    help="--detect on this image: the registration template, a summary image (K18) or an order-statistic image (K30) "
+                         "of the corrected movie")
     ap.add_argument("--track", action="store_true", help="refine the initialiser's tracks with the tracker (K15) before init_motion")
     ap.add_argument("--exclude", type=int, default=0, help="--track: rounds of exclusive tracking (K15x); 0: K15 as it is")
     ap.add_argument("--follow", action="store_true", help="follow the centres of frame 0 frame to frame (K15c) and start a fit from those tracks")

@@ -1176,6 +1176,48 @@ int dnmf_colour_normal_eqs(const float *G, const float *r, const float *C, long 
 int dnmf_colour_solve(const double *M, const double *b, const float *colours, int K, int NC, int sweeps, float *out, double *kkt,
                       int *ok, dnmf_stream_t stream);
 
+/* ---- K30: exact order statistics over time, per voxel: the samples behind the median, noise and percentile images ------------------
+ * (csrc/robust_images.hip; tests/robust_restatement.py is the definition.)  For the rows y[t, p] of a movie of a volume (X, Y, Z) (rows
+ * of ldf >= P floats, voxel p = (x Y + y) Z + z; row frame_ids[j] of frames, or j, for the j-th row of the call) the sequence of a
+ * voxel is, by source,
+ *   DNMF_SELECT_VALUE    x_t = y_t;
+ *   DNMF_SELECT_ABSDEV   x_t = |y_t - centre[p]|, centre a (P) fp32 image: one fp32 subtraction rounded to nearest, then the sign off;
+ *   DNMF_SELECT_ABSDIFF  x_t = |y_{t+1} - y_t| in the order the rows are given, the same arithmetic: one term fewer than the movie has
+ *                        rows.  The last row of a piece is kept in the state, so a cut between two pieces loses no term.
+ * Samples that are not finite are left out; n[p] counts the others.  For each of the nq <= 4 quantiles q[i] in [0, 1] (a HOST array)
+ * h = q (n - 1) in float64, lo = floor(h), hi = min(lo + 1, n - 1), and the results are the kept samples of ranks lo and hi in
+ * ascending order (from 0; -0 and +0 are one value, returned as +0): input samples, comparable for equality.  Where n = 0 both are NaN.
+ * The interpolation between the two is the caller's, in float64.
+ * A radix select on the order-preserving 32-bit key of a float, 4 bits a pass: dnmf_temporal_select_passes() = 9 passes (8 digits from
+ * the top, then one that counts the samples <= a_lo and takes the least sample above it, which settles a_hi).  EVERY pass streams the
+ * whole movie once, in any number of calls (pieces) of any sizes, the same rows in the same order in every pass:
+ *   for pass in 0 .. 8:  for every piece:  dnmf_temporal_select_pass(piece, .., pass, rows_before = rows of the earlier pieces, ..)
+ *   dnmf_temporal_select_finish(..)
+ * rows_before == 0 opens the pass: a launch picks, per voxel and quantile, the digit of the pass before from its counters, and clears
+ * them.  The library does not know how many rows a pass had; feeding every pass the same rows is the caller's duty (ops.py keeps count
+ * and refuses).  A workgroup owns 256 contiguous voxels (every row is read in full lines) and a segment of frames (segment > 0: that
+ * many frames each; 0: the kernel's choice); a thread keeps its voxel's 16 counters per quantile in a column of LDS of its own and
+ * adds them to the state with integer atomics at the end -- integer sums do not depend on the order, no floating-point atomics: the
+ * same input gives the same bits on every run and however the movie is cut.  4 B per voxel and frame are read in each pass.
+ *   state    caller-owned, 4-byte aligned, dnmf_temporal_select_workspace(sz, nq) bytes (0 on bad arguments; it does not depend on
+ *            the number of frames): per voxel n and the carried row, per voxel and quantile lo, the remaining rank and the key prefix
+ *            (4 B each), and the 16 counters: (8 + 76 nq) B a voxel -- 80 MiB for 512 x 512 x 2 with 2 quantiles.
+ *   finish   writes lo (nq, P) fp32, hi (nq, P) fp32 and n (P) int32; valid after pass 8.
+ * No host synchronisation.  DNMF_E_NULL: frames, sz, q, state or an output NULL, centre NULL with DNMF_SELECT_ABSDEV;  DNMF_E_SHAPE: a
+ * size or B < 1, nq outside 1 .. 4, a q outside [0, 1] (NaN included), an unknown source, pass outside 0 .. 8, segment < 0, ldf < P;
+ * DNMF_E_UNSUPPORTED: 2^31 voxels or more, rows_before + B > 2^31 - 1 (the counters are 32 bits wide; nothing is ever truncated), more
+ * than 65535 segments;  DNMF_E_WORKSPACE: a short or misaligned state.  Nothing is launched on an error. */
+#define DNMF_SELECT_VALUE 0
+#define DNMF_SELECT_ABSDEV 1
+#define DNMF_SELECT_ABSDIFF 2
+int dnmf_temporal_select_passes(void);
+size_t dnmf_temporal_select_workspace(const int *sz, int nq);
+int dnmf_temporal_select_pass(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, int source,
+                              const float *centre, const double *q, int nq, int pass, long rows_before, int segment, void *state,
+                              size_t state_bytes, dnmf_stream_t stream);
+int dnmf_temporal_select_finish(const int *sz, int nq, const void *state, size_t state_bytes, float *lo, float *hi, int *n,
+                                dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
