@@ -874,12 +874,15 @@ class DeformableNMF:
     @staticmethod
     def _spatial_accum_dense(registered, C, A1, Cs, frame_ids, times):
         """Dense K5 into A1 (P,K) and Cs (K,K): one launch up to 128 neurons, else columns of A1 by groups of 128 (K5 holds
-        8 trace blocks per wave) and C C^T in float64 (it is tiny)."""
+        8 trace blocks per wave) and C C^T in float64 (it is tiny).  The frames of the call and their trace columns are
+        those of ``ops._ids`` in both forms: as many as ``times``, else as ``frame_ids`` with column b for frame b, else every
+        row of ``registered``."""
         K = C.shape[0]
         if K <= 128:
             ops.spatial_accum(registered, C, frame_ids=frame_ids, times=times, A1=A1, Cs=Cs, accumulate=False)
             return
-        Cl = C[:, :registered.shape[0]] if times is None else C[:, torch.as_tensor(times, device=C.device).long()]
+        _, tt, B = ops._ids(registered, frame_ids, times, C.device)
+        Cl = C[:, :B] if tt is None else C[:, tt.long()]
         for s0 in range(0, K, 128):
             part, _ = ops.spatial_accum(registered, C[s0:s0 + 128].contiguous(), frame_ids=frame_ids, times=times)
             A1[:, s0:s0 + 128] = part

@@ -637,9 +637,10 @@ def spatial_accum(Y, C, frame_ids=None, times=None, A1=None, Cs=None, accumulate
         Cs = torch.empty((K, K), dtype=torch.float32, device=dev)
         accumulate = False
     Ct = C.t().contiguous()   # frame-major copy of the traces (K T floats): the kernel's matrix operands in 64-byte runs
+    # (the transpose of a single trace column is contiguous as it stands and keeps stride 1: _ld, as for any single row)
     with _timed("spatial_accum"):
-        rc = _lib.load().dnmf_spatial_accum(Y.data_ptr(), Y.stride(0), _ptr(fid), C.data_ptr(), C.stride(0), Ct.data_ptr(),
-                                            Ct.stride(0), _ptr(tt), T, P, K, A1.data_ptr(), Cs.data_ptr(),
+        rc = _lib.load().dnmf_spatial_accum(Y.data_ptr(), _ld(Y, P), _ptr(fid), C.data_ptr(), _ld(C, C.shape[1]), Ct.data_ptr(),
+                                            _ld(Ct, K), _ptr(tt), T, P, K, A1.data_ptr(), Cs.data_ptr(),
                                             int(bool(accumulate)), _stream())
     _lib.check(rc, "dnmf_spatial_accum")
     return A1, Cs

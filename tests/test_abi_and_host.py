@@ -459,3 +459,24 @@ def test_spatial_lists_frame_splits_and_workspace(lib, X, Y, Z, T, ns, fps):
     # and the shape checks come first
     assert lib.dnmf_spatial_accum_lists(a, P - 1, None, a, T, None, T, X, Y, Z, K, a, total, a, a, None, 0, None) == -2
     assert lib.dnmf_spatial_accum_lists(None, P, None, a, T, None, T, X, Y, Z, K, a, total, a, a, None, 0, None) == -1
+
+
+def test_dense_footprint_update_refusals(lib):
+    """The dense K5 and K6 refuse, before any launch, what they cannot take: K5 more than 128 traces a call (the caller
+    goes by column groups), rows shorter than P, frame-major traces with rows shorter than K, a NULL output; K6 more
+    footprint rows than its 64 KiB of LDS hold (K = 1024 is the last it takes) and no voxels."""
+    buf = ctypes.create_string_buffer(64)
+    a = ctypes.addressof(buf)
+    P, T = 70, 21
+
+    def k5(Y=a, ldy=P, C=a, Ct=None, ldct=0, K=20, A1=a, Cs=a, T=T):
+        return lib.dnmf_spatial_accum(Y, ldy, None, C, T, Ct, ldct, None, T, P, K, A1, Cs, 0, None)
+
+    assert k5(K=129) == -3 and b"K=129" in lib.dnmf_last_error()
+    assert k5(ldy=P - 1) == -2 and b"ldy=69" in lib.dnmf_last_error()
+    assert k5(Ct=a, ldct=19) == -2 and b"ldct=19" in lib.dnmf_last_error()
+    assert k5(A1=None) == -1 and b"NULL" in lib.dnmf_last_error()
+    assert k5(Y=None) == -1 and k5(C=None) == -1 and k5(Cs=None) == -1 and k5(T=0) == -2
+    assert lib.dnmf_mu_spatial(a, a, a, None, 0.0, 17, 1025, None) == -3 and b"K=1025" in lib.dnmf_last_error()
+    assert lib.dnmf_mu_spatial(a, a, a, None, 0.0, 0, 20, None) == -2 and b"P=0" in lib.dnmf_last_error()
+    assert lib.dnmf_mu_spatial(None, a, a, None, 0.0, 17, 20, None) == -1
