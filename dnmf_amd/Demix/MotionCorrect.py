@@ -408,6 +408,33 @@ class MotionCorrect(object):
         pieces, sz = self._stored_pieces("robust_images")
         return _images_to_numpy(ops.robust_images(pieces, sz, **kw))
 
+    def dff_movie(self, video=None, **kw):
+        """The dF/F movie (K31, ``ExponentialFP.dff_movie``; ``kw``: ``window``, ``stride``, ``percentile``, ``mode``, ``offset``,
+        ``min_samples``) of a (T, X, Y, Z) ``video`` or, without one, of the stored corrected movie, as ``robust_images`` takes
+        it -> ``(movie, info)``: numpy float32 (T, X, Y, Z) and the knots of the running baseline (CUDA rows (T, P) for a CUDA
+        ``video``).  The stored movie is held on the GPU whole while the call runs, as the movie that comes back is; the kernels
+        take it in pieces of at most 1 GiB.  Samples the correction left NaN are left out of their windows and stay NaN in the
+        movie."""
+        from .dNMF import ExponentialFP
+        if video is not None:
+            return ExponentialFP.dff_movie(video, **kw)
+        pieces, sz = self._stored_pieces("dff_movie")
+        percentile = float(kw.pop("percentile", 8.0))
+        if not 0.0 <= percentile <= 100.0:
+            raise ValueError(f"MotionCorrect.dff_movie: percentile must lie in [0, 100], got {percentile!r}")
+        held = list(pieces())
+        edges = np.cumsum([0] + [p.shape[0] for p in held])
+
+        def rows_of(r0, r1):
+            first, last = np.searchsorted(edges, r0, side="right") - 1, np.searchsorted(edges, r1, side="left") - 1
+            if first == last:
+                return held[first][r0 - edges[first]:r1 - edges[first]]
+            return torch.cat([held[i][max(r0, edges[i]) - edges[i]:min(r1, edges[i + 1]) - edges[i]] for i in range(first, last + 1)])
+        T = int(edges[-1])
+        movie, info = ops.dff_rows(rows_of, T, sz, kw.pop("window"), kw.pop("stride", None), percentile / 100.0, **kw)
+        info = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()}
+        return movie.cpu().numpy().reshape(T, *sz), info
+
     def detect_points(self, K, shape_std=3, **kw):
         """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
         made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,

@@ -82,6 +82,38 @@ def deconvolveTraces(traces, fps=None, decay_time=None, g=None, penalty=None, ba
     return c.cpu().numpy(), s.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
 
 
+def detrend_df_f(traces, window, stride=None, percentile=8.0, mode='df', offset=0.0):
+    """Traces (K, T) or (T,) read against their own running baseline (K31, ``ops.running_quantile`` and ``ops.baseline_apply`` on
+    the traces as a movie of K voxels; tests/dff_restatement.py is the definition) -> ``(traces_out, baseline)``, both like
+    ``traces``.  The baseline is, per trace, the ``percentile`` of every window of ``window`` frames, one every ``stride`` frames
+    (None: a quarter of the window; 1: an exact running percentile filter), joined by straight lines between the window
+    centres and flat outside them; ``mode``: ``'df'`` y - F0, ``'dff'`` (y - F0) / (F0 + offset), ``'dfsqrtf'``, ``'baseline'``.
+    Frames that are not finite -- what ``cleanTraces`` masks -- are left out of their windows and stay NaN.  What CaImAn's
+    ``detrend_df_f`` does to its traces, with three differences: linear instead of cubic interpolation between the knots, windows
+    clamped at the two ends instead of padded, and an interpolated (``method='linear'``) percentile; the background ``b f`` is not
+    added to the baseline.  A numpy array comes back as float32 numpy arrays, a CUDA tensor as CUDA tensors; the input is not
+    modified."""
+    if not 0.0 <= float(percentile) <= 100.0:
+        raise ValueError(f"detrend_df_f: percentile must lie in [0, 100], got {percentile!r}")
+    tensors = isinstance(traces, torch.Tensor)
+    if tensors and not traces.is_cuda:
+        raise ValueError("detrend_df_f: a tensor must live on the GPU (numpy arrays are taken from the host)")
+    t = traces.float() if tensors else torch.from_numpy(np.ascontiguousarray(traces, dtype=np.float32)).cuda()
+    single = t.dim() == 1
+    if t.dim() not in (1, 2):
+        raise ValueError(f"detrend_df_f: traces are (K, T) or (T,), got {tuple(t.shape)}")
+    K, T = (1, t.shape[0]) if single else t.shape
+    rows = torch.empty((T, K), dtype=torch.float32, device=t.device)          # (T, K): a movie of K voxels
+    rows.copy_((t[None, :] if single else t).t())
+    sz = (K, 1, 1)
+    knots = ops.running_quantile(rows, sz, window, stride, float(percentile) / 100.0)
+    out = ops.baseline_apply(rows, sz, knots["value"], knots["centres"], mode, offset).t().contiguous()
+    base = ops.baseline_apply(rows, sz, knots["value"], knots["centres"], "baseline").t().contiguous()
+    if single:
+        out, base = out[0], base[0]
+    return (out, base) if tensors else (out.cpu().numpy(), base.cpu().numpy())
+
+
 def histogram_match(a, b, nbins, type):
     """The moving trace ``a`` rescaled so that its histogram resembles that of the reference trace ``b`` (K25,
     ``ops.histogram_match``; tests/histmatch_restatement.py is the definition) -> ``(atransform, distance)``.  The ``nbins``

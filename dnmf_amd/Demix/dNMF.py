@@ -503,6 +503,30 @@ class ExponentialFP(nn.Module):
         return images if on_gpu else _images_to_numpy(images)
 
     @staticmethod
+    def dff_movie(video, window, stride=None, percentile=8.0, mode='dff', offset=0.0, min_samples=1):
+        """``video`` -- (T, X, Y, Z) values, ``(rows (T, P), sz)`` or a ``ResidentLoader``, as ``robust_images`` takes it, its rows
+        in time order -- read against its own slowly moving baseline (K31, ``ops.running_quantile`` and ``ops.baseline_apply``;
+        tests/dff_restatement.py): per voxel the ``percentile`` of every window of ``window`` frames, one every ``stride`` frames
+        (None: a quarter of the window), exact and interpolated as ``np.nanquantile`` does, joined by straight lines between the
+        window centres and held flat outside them -> ``(movie, info)``.  ``mode``: ``'dff'`` (y - F0) / (F0 + offset), ``'df'``
+        y - F0, ``'dfsqrtf'`` (y - F0) / sqrt(F0 + offset), ``'baseline'`` F0 itself; NaN where the sample or the baseline is not
+        finite (a window with fewer than ``min_samples`` finite samples has none) or F0 + offset <= 0.  A session that bleaches
+        has no single F0: the one 8th percentile of ``robust_images`` sits at its end-of-session level.  ``info``: ``knots``
+        (J, X, Y, Z) float64, ``centres``, ``n`` (J, X, Y, Z), ``starts``, ``ends``.  CUDA frames give CUDA rows (T, P) and CUDA
+        ``knots`` / ``n``; numpy or CPU-torch in, numpy float32 (T, X, Y, Z) out.  Unlike CaImAn's ``detrend_df_f`` the knots are
+        joined linearly (not by a cubic zoom), the windows at the two ends are clamped to the movie (not padded), and the
+        percentile is interpolated (``method='linear'``), not the nearest rank."""
+        if not 0.0 <= float(percentile) <= 100.0:
+            raise ValueError(f"dff_movie: percentile must lie in [0, 100], got {percentile!r}")
+        rows, sz, on_gpu = ExponentialFP._video_rows(video, "dff_movie")
+        movie, info = ops.dff_rows(lambda r0, r1: rows[r0:r1], rows.shape[0], sz, window, stride, float(percentile) / 100.0, mode,
+                                   offset, min_samples)
+        if on_gpu:
+            return movie, info
+        info = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()}
+        return movie.cpu().numpy().reshape(rows.shape[0], *sz), info
+
+    @staticmethod
     def background(video, iters=3):
         """The rank-1 background of ``video`` as it is (K19, ``ops.background_fit``): ``(b (X, Y, Z), f (T,))`` fp32, both >= 0
         with mean(f) = 1, after ``iters`` alternations of the two exact coordinate steps of ``min |video - b f|^2`` from b = 1.
@@ -661,6 +685,9 @@ class DeformableNMF:
         self.background = None
         # after clean_traces: a, b, F0, fitted, n_outliers per neuron (CUDA tensors, (K,)) of that call
         self.last_clean = None
+        # after dff_movie: knots (J,X,Y,Z) float64, centres, n, starts, ends of that call; after detrend_traces: baseline (K,T)
+        self.last_dff = None
+        self.last_detrend = None
         # after deconvolve: g, penalty, baseline, noise, rss, n_valid, n_pools, ok per neuron (CUDA tensors, (K,)) of that call
         self.last_deconv = None
         # after match_traces: beta (K, 2), distance (K,), ok (K,) of that call (CUDA tensors)
@@ -1052,6 +1079,47 @@ class DeformableNMF:
             frames, order = self._gather_frames(loader)
             P = sz[0] * sz[1] * sz[2]
             return ops.robust_images(lambda: (fr for _, fr, _, _ in self._residual_pieces(frames, order, None, registered, P)), sz, **kw)
+
+    def dff_movie(self, loader, registered=None, **kw):
+        """The dF/F movie (``ExponentialFP.dff_movie``, K31; ``kw``: ``window``, ``stride``, ``percentile``, ``mode``, ``offset``,
+        ``min_samples``) of every frame ``loader`` serves, in the order of the frame times: (T, P) fp32 CUDA rows.
+        ``registered='linear'`` (K17) or ``'nearest'`` (K7) registers the frames under the current ``fp.beta`` first, as
+        ``robust_images`` does.  The frames go through in pieces of at most 1 GiB that overlap by up to window - stride frames
+        (registered frames of the overlap are made twice).  ``self.last_dff`` receives ``knots``, ``centres``, ``n``, ``starts``
+        and ``ends``.  One channel, and a loader that holds every frame."""
+        if registered is not None:
+            _check_registered(registered, "dff_movie")
+        self._single_model_only("dff_movie", loader, "the loader holds a shard of the frames (a running baseline needs the "
+                                                     "frames next to each other)")
+        percentile = float(kw.pop("percentile", 8.0))
+        if not 0.0 <= percentile <= 100.0:
+            raise ValueError(f"dff_movie: percentile must lie in [0, 100], got {percentile!r}")
+        fp = self.fp
+        with torch.no_grad():
+            frames, order = self._frames_in_time_order(loader)
+
+            def rows_of(r0, r1):
+                if registered is None:
+                    return frames[r0:r1]
+                return fp.registered_video(frames[r0:r1], times=order[r0:r1], interpolation=registered)
+            movie, info = ops.dff_rows(rows_of, frames.shape[0], fp.sz_list, kw.pop("window"), kw.pop("stride", None), percentile / 100.0,
+                                       **kw)
+        self.last_dff = info
+        return movie
+
+    def detrend_traces(self, window, traces=None, **kw):
+        """The traces read against their own running baseline (K31, ``Demix.Traces.detrend_df_f``; ``kw``: ``stride``,
+        ``percentile``, ``mode``, ``offset``): ``self.C``, or ``traces`` (K, T) -- e.g. what ``clean_traces`` returned, whose NaN
+        frames are left out of their windows -> (K, T) fp32 on the GPU.  ``self.C`` stays as it is; ``self.last_detrend``
+        receives the ``baseline`` (K, T) of the call."""
+        from .Traces import detrend_df_f
+        self._single_model_only("detrend_traces", None, "the model holds a shard of the frames (a running baseline needs the "
+                                                        "frames next to each other)")
+        with torch.no_grad():
+            C = (self.C if traces is None else torch.as_tensor(traces)).detach().to(device, torch.float32)
+            out, baseline = detrend_df_f(C, window, **kw)
+        self.last_detrend = dict(baseline=baseline)
+        return out
 
     def evaluate_components(self, loader, registered='linear', active=0.25, margin=2, floor=1e-3, min_r=0.5, min_snr=1.0):
         """Which of the K components explain anything (K24, ``ops.component_stats``): one pass over the registered frames

@@ -144,6 +144,9 @@ SIGNATURES = {
     "dnmf_temporal_select_workspace": (_sz, [_vp, _i]),
     "dnmf_temporal_select_pass": (_i, [_vp, _l, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _l, _i, _vp, _sz, _vp]),
     "dnmf_temporal_select_finish": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dnmf_running_windows": (_l, [_l, _i, _i]),
+    "dnmf_running_quantile": (_i, [_vp, _l, _vp, _vp, _i, _l, _l, _i, _i, _d, _i, _vp, _vp, _vp, _l, _vp, _vp]),
+    "dnmf_baseline_apply": (_i, [_vp, _l, _vp, _vp, _i, _l, _vp, _l, _vp, _i, _i, _d, _vp, _l, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

@@ -10,6 +10,7 @@
 // picks the digit and the remaining rank of every voxel and quantile and clears the counters; the pair pass counts the samples
 // <= a_lo and takes the least sample above it, which settles a_hi without a second selection.
 #include "block_ops.hpp"
+#include "key32.hpp"
 
 namespace dnmf {
 namespace {
@@ -46,14 +47,6 @@ int select_plan(const char *fn, const int *sz, int nq, SelectPlan &g) {
     g.bytes = g.off_hist + align256((size_t)nq * TS_BINS * P * 4);
     return DNMF_OK;
 }
-
-// value -> key with key(a) < key(b) <=> a < b for finite a, b; -0 and +0 share the key of +0
-__device__ __forceinline__ uint32_t to_key32(float v) {
-    const uint32_t u = v == 0.0f ? 0u : __float_as_uint(v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float from_key32(uint32_t k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); }
 
 struct SelectArgs {
     const float *frames, *centre, *carry;

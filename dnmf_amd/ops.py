@@ -1818,6 +1818,183 @@ def robust_images(pieces, sz, percentiles=(), noise='diff'):
     return dict(median=median, max=mx, mad=mad, noise=sigma, pnr=pnr, n=n, percentile={p: values[2 + i] for i, p in enumerate(ps)})
 
 
+RUNNING_MAX_WINDOW = 2048                                                # a window of K31a lives in LDS
+BASELINE_MODES = {"baseline": 0, "df": 1, "dff": 2, "dfsqrtf": 3}        # DNMF_BASELINE_* of include/dnmf_hip.h
+
+
+def _window_args(fn, window, stride):
+    if int(window) != window or int(window) < 1:
+        raise ValueError(f"{fn}: window={window!r}: a number of frames, at least 1")
+    window = int(window)
+    if window > RUNNING_MAX_WINDOW:
+        raise ValueError(f"{fn}: window={window} frames, at most {RUNNING_MAX_WINDOW} (a window lives in LDS; nothing is truncated)")
+    stride = max(1, window // 4) if stride is None else stride
+    if int(stride) != stride or not 1 <= int(stride) <= window:
+        raise ValueError(f"{fn}: stride={stride!r} outside [1, window={window}]")
+    return window, int(stride)
+
+
+def running_window_plan(T, window, stride=None):
+    """The windows K31 covers a movie of ``T`` frames with (tests/dff_restatement.py D1; host only, integers, the plan the kernel
+    uses): a dict ``J``, ``starts`` and ``ends`` (J,) int64 -- window j holds the frames [starts[j], ends[j]), starts[j] =
+    min(j stride, max(T - window, 0)), the last one ends at T -- and ``centres`` (J,) float64, (start + end - 1) / 2, where the
+    knots sit.  ``stride=None``: max(1, window // 4)."""
+    fn = "running_window_plan"
+    window, stride = _window_args(fn, window, stride)
+    if int(T) != T or int(T) < 1:
+        raise ValueError(f"{fn}: T={T!r} frames")
+    T = int(T)
+    J = 1 if T <= window else -((window - T) // stride) + 1
+    starts = np.minimum(np.arange(J, dtype=np.int64) * stride, max(T - window, 0))
+    ends = np.minimum(starts + window, T)
+    return dict(J=J, starts=starts, ends=ends, centres=(starts + ends - 1).astype(np.float64) / 2.0)
+
+
+def running_quantile(frames, sz, window, stride=None, q=0.08, frame_ids=None, min_samples=1, row0=0, T=None, run=0):
+    """K31a.  frames (rows, ld >= X Y Z) fp32 CUDA rows in time order -> per voxel the exact quantile ``q`` in [0, 1] of every
+    window of ``window`` frames, one every ``stride`` frames (None: max(1, window // 4)), of ``running_window_plan``: a dict of
+
+    * ``n`` (J, X, Y, Z) int32, the finite samples of the window (the others are left out, as in ``temporal_quantiles``);
+    * ``lo``, ``hi`` (J, X, Y, Z) fp32, the kept samples of ranks floor(h) and min(floor(h) + 1, n - 1), h = q (n - 1): input
+      samples, bit for bit (-0 comes back as +0), NaN where n = 0;
+    * ``value`` (J, X, Y, Z) float64, the two interpolated like ``np.nanquantile(method='linear')``, NaN where n < ``min_samples``;
+    * ``centres``, ``starts``, ``ends`` of the plan, and ``windows = (j0, j1)``.
+
+    The rows are the frames ``row0 .. row0 + rows - 1`` of a movie of ``T`` frames (None: the rows are the movie), taken in the
+    order of ``frame_ids`` where given.  Computed are exactly the windows j0 .. j1 - 1 that lie wholly inside the rows; the
+    others are NaN / 0 in the tables.  A movie that goes in pieces overlaps them by up to window - stride rows so that every
+    window is whole in some piece; the tables of the pieces, put together, equal those of one call bit for bit.  ``run``:
+    windows per workgroup (0: the kernel's choice); the result does not depend on it.  No workspace, integer counts only."""
+    fn = "running_quantile"
+    window, stride = _window_args(fn, window, stride)
+    q = float(q)
+    if not 0.0 <= q <= 1.0:
+        raise ValueError(f"{fn}: q must lie in [0, 1], got {q}")
+    if int(min_samples) < 1:
+        raise ValueError(f"{fn}: min_samples={min_samples!r}, at least 1")
+    if int(run) < 0:
+        raise ValueError(f"{fn}: run={run!r}: windows per workgroup, 0 for the kernel's choice")
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _frame_rows(fn, frames, None, frame_ids, P)
+    if B < 1:
+        raise ValueError(f"{fn}: no rows")
+    if fid is not None and (int(fid.min()) < 0 or int(fid.max()) >= frames.shape[0]):
+        raise ValueError(f"{fn}: frame_ids must be row indices in [0, {frames.shape[0]})")
+    row0 = int(row0)
+    T = row0 + B if T is None else int(T)
+    if row0 < 0 or row0 + B > T:
+        raise ValueError(f"{fn}: rows {row0} .. {row0 + B} of a movie of T={T} frames")
+    plan = running_window_plan(T, window, stride)
+    J, dev = plan["J"], frames.device
+    lo = torch.full((J, X, Y, Z), float("nan"), dtype=torch.float32, device=dev)
+    hi = torch.full((J, X, Y, Z), float("nan"), dtype=torch.float32, device=dev)
+    n = torch.zeros((J, X, Y, Z), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    win = (ctypes.c_long * 2)()
+    with _timed(fn):
+        rc = lib.dnmf_running_quantile(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3((X, Y, Z)), B, row0, T, window, stride, q,
+                                       int(run), lo.data_ptr(), hi.data_ptr(), n.data_ptr(), P, win, _stream())
+    _lib.check(rc, "dnmf_running_quantile")
+    value = _interpolated_quantiles(lo, hi, n, [q])[0]
+    if int(min_samples) > 1:
+        value = torch.where(n >= int(min_samples), value, torch.full_like(value, float("nan")))
+    return dict(lo=lo, hi=hi, n=n, value=value, centres=plan["centres"], starts=plan["starts"], ends=plan["ends"],
+                windows=(int(win[0]), int(win[1])))
+
+
+def _overlap(a, b):
+    """Whether the storages of two tensors share a byte."""
+    sa, sb = a.untyped_storage(), b.untyped_storage()
+    return sa.data_ptr() < sb.data_ptr() + sb.nbytes() and sb.data_ptr() < sa.data_ptr() + sa.nbytes()
+
+
+def baseline_apply(frames, sz, value, centres, mode='dff', offset=0.0, frame_ids=None, row0=0, out=None):
+    """K31b.  frames (rows, ld >= X Y Z) fp32 CUDA rows, the frames ``row0 .. row0 + rows - 1`` of the movie (in the order of
+    ``frame_ids`` where given), read against the baseline that runs through the knots ``value`` (J, X, Y, Z) float64 at the
+    frames ``centres`` (J,), strictly increasing -- what ``running_quantile`` returned: F0 is the first knot before the first
+    centre, the last one after the last, and between two centres their line, in float64 (tests/dff_restatement.py D3).
+    -> (rows, P) fp32 by ``mode``: ``'baseline'`` F0, ``'df'`` y - F0, ``'dff'`` (y - F0) / (F0 + offset), ``'dfsqrtf'``
+    (y - F0) / sqrt(F0 + offset), computed in float64 and rounded once; NaN where y or F0 is not finite and, in the last two,
+    where F0 + offset <= 0.  ``out``: rows to write (None: new ones); it may not share memory with ``frames``.  One streaming
+    launch."""
+    fn = "baseline_apply"
+    if mode not in BASELINE_MODES:
+        raise ValueError(f"{fn}: mode must be one of {sorted(BASELINE_MODES)}, got {mode!r}")
+    offset = float(offset)
+    if not math.isfinite(offset):
+        raise ValueError(f"{fn}: offset={offset} is not finite")
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    fid, B = _frame_rows(fn, frames, None, frame_ids, P)
+    if B < 1:
+        raise ValueError(f"{fn}: no rows")
+    if fid is not None and (int(fid.min()) < 0 or int(fid.max()) >= frames.shape[0]):
+        raise ValueError(f"{fn}: frame_ids must be row indices in [0, {frames.shape[0]})")
+    dev = frames.device
+    c = torch.from_numpy(np.array(centres.cpu() if isinstance(centres, torch.Tensor) else centres, dtype=np.float64).ravel())
+    J = c.numel()
+    if J < 1 or not bool((c[1:] > c[:-1]).all()) or not bool(torch.isfinite(c).all()):
+        raise ValueError(f"{fn}: centres must be at least one finite frame position, strictly increasing")
+    if not (isinstance(value, torch.Tensor) and value.is_cuda and value.dtype == torch.float64 and value.is_contiguous()
+            and value.numel() == J * P):
+        raise ValueError(f"{fn}: value must be a contiguous float64 CUDA tensor of {J} knots x {P} voxels")
+    if int(row0) < 0:
+        raise ValueError(f"{fn}: row0={row0!r}")
+    if out is not None and isinstance(out, torch.Tensor) and _overlap(out, frames):
+        raise ValueError(f"{fn}: out may not share memory with frames")
+    out = _out_rows(fn, out, B, P, dev)
+    lib, cdev = _lib.load(), c.to(dev)
+    with _timed(fn):
+        rc = lib.dnmf_baseline_apply(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3((X, Y, Z)), B, int(row0), value.data_ptr(), P,
+                                     cdev.data_ptr(), J, BASELINE_MODES[mode], offset, out.data_ptr(), _ld(out, P), _stream())
+    _lib.check(rc, "dnmf_baseline_apply")
+    return out[:B, :P]
+
+
+def _running_pieces(T, P, window, stride, limit=None):
+    """How a movie of ``T`` frames goes through K31 in pieces of at most 1 GiB (``limit`` rows; at least one window): a list of
+    ``(r0, r1, j0, j1)`` -- the rows [r0, r1) hold exactly the windows j0 .. j1 - 1 whole, consecutive pieces overlap by up to
+    window - stride rows, and every window is in one piece."""
+    plan = running_window_plan(T, window, stride)
+    starts, ends, J = plan["starts"], plan["ends"], plan["J"]
+    limit = max(int(ends[0] - starts[0]), (1 << 30) // (4 * P) if limit is None else int(limit))
+    pieces, j0 = [], 0
+    while j0 < J:
+        j1 = j0 + 1
+        while j1 < J and ends[j1] - starts[j0] <= limit:
+            j1 += 1
+        pieces.append((int(starts[j0]), int(ends[j1 - 1]), j0, j1))
+        j0 = j1
+    return plan, pieces
+
+
+def dff_rows(rows_of, T, sz, window, stride=None, q=0.08, mode='dff', offset=0.0, min_samples=1, limit=None, out=None):
+    """K31a then K31b on a movie of ``T`` frames that ``rows_of(r0, r1)`` serves as fp32 CUDA rows (r1 - r0, ld >= P) in time
+    order, in pieces of at most 1 GiB (``limit``: rows a piece, for tests) -> ``(movie (T, P) fp32 CUDA, info)`` with
+    ``info = dict(knots (J, X, Y, Z) float64, centres, n, starts, ends)``: the same bits however the movie is cut."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    window, stride = _window_args("dff_rows", window, stride)
+    plan, pieces = _running_pieces(T, P, window, stride, limit)
+    knots = n = None
+    for r0, r1, j0, j1 in pieces:
+        r = running_quantile(rows_of(r0, r1), sz, window, stride, q, min_samples=min_samples, row0=r0, T=T)
+        got0, got1 = r["windows"]
+        assert got0 <= j0 and j1 <= got1, (r["windows"], j0, j1)
+        if knots is None:
+            knots, n = r["value"], r["n"]
+        else:
+            knots[j0:j1], n[j0:j1] = r["value"][j0:j1], r["n"][j0:j1]
+    dev = knots.device
+    movie = _out_rows("dff_rows", out, T, P, dev)
+    step = max(1, min(T, (1 << 30) // (4 * P) if limit is None else int(limit)))
+    for r0 in range(0, T, step):
+        r1 = min(T, r0 + step)
+        baseline_apply(rows_of(r0, r1), sz, knots, plan["centres"], mode, offset, row0=r0, out=movie[r0:r1])
+    return movie[:T, :P], dict(knots=knots, centres=plan["centres"], n=n, starts=plan["starts"], ends=plan["ends"])
+
+
 def background_state(sz, B, segment=0, device="cuda"):
     """An empty state for ``background_accum`` calls of up to ``B`` frames each; pass it with ``first=True``."""
     X, Y, Z = (int(s) for s in sz)

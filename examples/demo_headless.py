@@ -5,10 +5,12 @@ truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
                                         [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
-                                        [--clean-footprints] [--add N]
+                                        [--clean-footprints] [--add N] [--dff W]
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
+``--dff W``: also read the traces against their running 8th-percentile baseline over windows of W frames
+(``DeformableNMF.detrend_traces``, K31) and print the median correlation of the simulator's traces with ``C`` and with the detrended ``C``.
 ``--deconvolve``: also deconvolve the traces (``DeformableNMF.deconvolve``, K21), everything estimated, and print the median
 correlation of the simulator's traces with ``C`` and with ``b + c``, and the median estimated decay beside the simulator's e^-0.3.
 ``--match``: also put the traces in the simulator's units (``DeformableNMF.match_traces``, K25) and print the median over neurons
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--iter-c", type=int, default=50)
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--clean", type=float, default=None, metavar="FPS")
+    ap.add_argument("--dff", type=int, default=0, metavar="W")
     ap.add_argument("--deconvolve", action="store_true")
     ap.add_argument("--match", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
@@ -98,6 +101,10 @@ def main():
         print("median trace correlation with ground truth at %g fps: C %.3f  cleaned C %.3f  (outliers removed: %d, curves fitted: %d of %d)"
               % (a.clean, median_corr(C), median_corr(cleaned), int(dnmf.last_clean["n_outliers"].sum()),
                  int(dnmf.last_clean["fitted"].sum()), K))
+    if a.dff:
+        detrended = dnmf.detrend_traces(a.dff).cpu().numpy().astype(np.float64)
+        print("median trace correlation with ground truth: C %.3f  C against its running baseline (window %d) %.3f"
+              % (float(np.median(corr)), a.dff, float(np.median([np.corrcoef(detrended[k], dataset.traces[k])[0, 1] for k in range(K)]))))
     if a.deconvolve:
         c, s, info = dnmf.deconvolve()
         ok = info["ok"].cpu().numpy()

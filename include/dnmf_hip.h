@@ -1218,6 +1218,52 @@ int dnmf_temporal_select_pass(const float *frames, long ldf, const int *frame_id
 int dnmf_temporal_select_finish(const int *sz, int nq, const void *state, size_t state_bytes, float *lo, float *hi, int *n,
                                 dnmf_stream_t stream);
 
+/* ---- K31: the running-percentile baseline of a movie, and the movie read against it (dF/F) ----------------------------------------
+ * (csrc/running_baseline.hip; tests/dff_restatement.py is the definition.)  A movie of T frames is covered by J windows of
+ * `window` = W frames, one every `stride` = S frames (1 <= S <= W <= 2048): J = 1 if T <= W, else ceil((T - W) / S) + 1
+ * (dnmf_running_windows; 0 on bad arguments); window j holds the frames [s_j, e_j), s_j = min(j S, max(T - W, 0)),
+ * e_j = min(s_j + W, T) -- the last window ends at T and is full-length whenever T >= W -- and its knot sits at c_j = (s_j + e_j - 1) / 2.
+ *
+ * K31a, dnmf_running_quantile.  frames: B rows of ldf >= P floats (row frame_ids[i] of frames, or i, for the i-th row of the call), the
+ * frames row0 .. row0 + B - 1 of the movie in time order.  Computed are exactly the windows that lie wholly inside these rows, j0 .. j1 - 1,
+ * and windows[0] = j0, windows[1] = j1 (windows: a HOST array of two longs, written before the call returns; j0 == j1: nothing is
+ * launched).  Per voxel p and window j, of the samples of the window that are finite (NaN and +-inf are left out, as in K30):
+ *   n[j ldk + p]    int32, their count;
+ *   lo, hi[j ldk + p]  fp32, those of ranks floor(h) and min(floor(h) + 1, n - 1) in ascending order, h = q (n - 1) in float64: input
+ *                   samples, bit for bit (-0 and +0 are one value, returned as +0); NaN where n = 0.
+ * Rows outside j0 .. j1 - 1 of the three tables are not touched; the interpolation between lo and hi is the caller's, in float64.
+ * A workgroup owns 64 contiguous voxels (32 for W > 512, 16 for W > 1024) and `run` consecutive windows (0: the kernel's choice --
+ * about 1024 workgroups, so that a movie of few voxels, a matrix of traces, still fills the machine).  It holds the window in LDS
+ * as K30's 32-bit keys in a ring of W rows, so that the step to the next window reads S new rows: within a run every sample is
+ * read from memory once, (W + (run - 1) S) rows per run.  Selection by bisection on the key, integer counts only: no floating-point
+ * atomics, no scratch, no workspace, and the same bits for every run, for every cut of the movie into calls and on every launch.
+ *
+ * K31b, dnmf_baseline_apply.  value (J, ldv >= P) float64: the knot values b_j per voxel; centres (J) float64 DEVICE, strictly
+ * increasing: their abscissae.  For row i of the call, frame t = row0 + i:  F0 = b_0 for t <= c_0, b_{J-1} for t >= c_{J-1}, else with
+ * c_j <= t < c_{j+1} and w = (t - c_j) / (c_{j+1} - c_j):  F0 = b_j if w == 0, else b_j + w (b_{j+1} - b_j), each operation rounded
+ * once in float64 (a NaN knot spreads through this arithmetic and nowhere else).  out[i ldo + p], from the fp32 sample y and F0 in
+ * float64, rounded once to fp32, by mode:
+ *   DNMF_BASELINE_F0  F0;   DNMF_BASELINE_DF  y - F0;   DNMF_BASELINE_DFF  (y - F0) / (F0 + offset);
+ *   DNMF_BASELINE_DFSQRTF  (y - F0) / sqrt(F0 + offset);
+ * NaN where y or F0 is not finite and, in the last two modes, where F0 + offset <= 0.  One streaming launch: 4 B read and 4 B written
+ * per voxel and frame, a thread keeps the two knot values of its interval in registers over 32 consecutive frames.  out may not
+ * overlap frames.
+ * No host synchronisation.  DNMF_E_NULL: a required pointer NULL;  DNMF_E_SHAPE: a size, B, J, T or window < 1, stride outside
+ * [1, window], q outside [0, 1] (NaN included), rows outside the movie, run < 0, an unknown mode, an offset that is not finite, a
+ * leading dimension below P, out overlapping frames;  DNMF_E_UNSUPPORTED: window > 2048, 2^31 voxels or more, more than 65535 runs.
+ * Nothing is launched on an error. */
+#define DNMF_BASELINE_F0 0
+#define DNMF_BASELINE_DF 1
+#define DNMF_BASELINE_DFF 2
+#define DNMF_BASELINE_DFSQRTF 3
+long dnmf_running_windows(long T, int window, int stride);
+int dnmf_running_quantile(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, long row0, long T, int window,
+                          int stride, double q, int run, float *lo, float *hi, int *n, long ldk, long *windows,
+                          dnmf_stream_t stream);
+int dnmf_baseline_apply(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, long row0, const double *value,
+                        long ldv, const double *centres, int J, int mode, double offset, float *out, long ldo,
+                        dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
