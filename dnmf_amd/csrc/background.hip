@@ -11,9 +11,15 @@
 //           caller's state in their order, a third writes b.
 // No floating-point atomics: the same input at the same addresses gives the same bits.
 //
-// K23, further down: the same two passes for R images and R time courses (2 <= R <= 8) with R sums where K19 has one, the R x R Gram
-// matrix of the factor held fixed from a launch of its own, and a per-frame (per-voxel) non-negative solve by coordinate sweeps in
-// the finishing launch; tests/background_rank_restatement.py is its definition.  K19's kernels are as they were.
+// K23: the same two passes for R images and R time courses (2 <= R <= 8) with R sums where K19 has one, the R x R Gram matrix of the
+// factor held fixed from a launch of its own, and a per-frame (per-voxel) non-negative solve by coordinate sweeps in the finishing
+// launch; tests/background_rank_restatement.py is its definition.
+//
+// One skeleton, two policies.  What walks the movie is written once: the workgroup prologues, the head / 16-byte body / tail walk of
+// a dots segment (segment_walk), the accumulate kernel (K19 runs its R = 1 instantiation), the reduction of the accumulate partials,
+// and the tile prologue, clamp, NaN row and store of the subtraction.  What the families do with a residual stays their own, because
+// it decides the bits: K19's dots keep four float64 sums a lane (head, body x y z w, tail) and sum b^2 beside them, K23's one sum per
+// component; K19 subtracts with one fp32 fmaf, K23 with float64 products added c ascending; K19 finishes in closed form, K23 by sweeps.
 #include <cstdint>
 
 #include "block_ops.hpp"
@@ -55,46 +61,78 @@ int dots_plan(const char *fn, long P, int B, DotsPlan &g) {
 
 struct DotsArgs {
     const float *frames, *sub, *b;
-    long ldf, lds, P, seglen;
+    long ldf, lds, ldb, P, seglen;   // ldb: between the R images of K23
     const int *frame_ids;
     int nseg;
-    double *part, *bbpart;
+    double *part, *bbpart;           // bbpart: K19
 };
 
-// One term b (y - m) added to `acc`; WITH_BB: b^2 to `q`.
-template <bool SUB, bool WITH_BB>
-__device__ __forceinline__ void dots_term(float y, float m, float b, double &acc, double &q) {
-    const double bd = (double)b;
-    const double r = SUB ? (double)y - (double)m : (double)y;
-    acc = fma(bd, r, acc);
-    if (WITH_BB) q = fma(bd, bd, q);
+// The work of a dots workgroup: frame j of the call, segment s of n voxels; y, m (NULL without SUB) and b at its first voxel.
+struct Segment {
+    int j, s;
+    long n;
+    const float *y, *m, *b;
+};
+
+template <bool SUB>
+__device__ __forceinline__ Segment dots_segment(const DotsArgs &a) {
+    const long bid = blockIdx.x;
+    Segment g;
+    g.j = (int)(bid / a.nseg), g.s = (int)(bid - (long)g.j * a.nseg);
+    const long p0 = (long)g.s * a.seglen;
+    g.n = (a.P - p0 < a.seglen ? a.P - p0 : a.seglen);
+    g.y = a.frames + (long)(a.frame_ids ? a.frame_ids[g.j] : g.j) * a.ldf + p0;
+    g.m = SUB ? a.sub + (long)g.j * a.lds + p0 : nullptr;
+    g.b = a.b + p0;
+    return g;
 }
 
-template <bool SUB, bool WITH_BB>
-__device__ __forceinline__ void dots_segment(const float *__restrict__ y, const float *__restrict__ m, const float *__restrict__ b,
-                                             long n, double &sum, double &sumq) {
+template <bool SUB>
+__device__ __forceinline__ double residual(float y, float m) { return SUB ? (double)y - (double)m : (double)y; }
+
+// The walk of a segment, the residuals r = y - m handed on in float64.  16-byte loads from the first voxel at which y, m and the R
+// rows of b (ldb floats apart) are all aligned; rows whose starts differ in phase (P % 4 != 0 against the aligned b) are read one
+// float at a time.  one(i, r, slot): voxel i of the segment, slot 0 before the 16-byte body and 1 behind it.  four(head, i, r0 .. r3):
+// the voxels head + 4 i .. head + 4 i + 3, for the caller's own 16-byte load of float4 i of every (b row + head).
+template <bool SUB, int R, typename One, typename Four>
+__device__ __forceinline__ void segment_walk(const Segment &g, long ldb, One &&one, Four &&four) {
     const int tid = threadIdx.x;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
-    // 16-byte loads from the first voxel at which y, m and b are all aligned; rows whose starts differ in phase (P % 4 != 0
-    // against the aligned b) are read one float at a time
+    const float *__restrict__ y = g.y, *__restrict__ m = g.m;
     const unsigned ph = word_phase(y);
-    const bool vec = word_phase(b) == ph && (!SUB || word_phase(m) == ph);
-    long head = vec ? (long)((4 - ph) & 3) : n;
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    for (long i = tid; i < head; i += BG_THREADS) dots_term<SUB, WITH_BB>(y[i], SUB ? m[i] : 0.0f, b[i], acc[0], q[0]);
-    const float4 *y4 = reinterpret_cast<const float4 *>(y + head), *b4 = reinterpret_cast<const float4 *>(b + head);
+    bool vec = !SUB || word_phase(m) == ph;
+#pragma unroll
+    for (int c = 0; c < R; ++c) vec = vec && word_phase(g.b + (long)c * ldb) == ph;
+    long head = vec ? (long)((4 - ph) & 3) : g.n;
+    if (head > g.n) head = g.n;
+    const long n4 = (g.n - head) >> 2;
+    for (long i = tid; i < head; i += BG_THREADS) one(i, residual<SUB>(y[i], SUB ? m[i] : 0.0f), 0);
+    const float4 *y4 = reinterpret_cast<const float4 *>(y + head);
     const float4 *m4 = SUB ? reinterpret_cast<const float4 *>(m + head) : nullptr;
 #pragma unroll 2
     for (long i = tid; i < n4; i += BG_THREADS) {
-        const float4 yv = y4[i], bv = b4[i];
+        const float4 yv = y4[i];
         const float4 mv = SUB ? m4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        dots_term<SUB, WITH_BB>(yv.x, mv.x, bv.x, acc[0], q[0]);
-        dots_term<SUB, WITH_BB>(yv.y, mv.y, bv.y, acc[1], q[1]);
-        dots_term<SUB, WITH_BB>(yv.z, mv.z, bv.z, acc[2], q[2]);
-        dots_term<SUB, WITH_BB>(yv.w, mv.w, bv.w, acc[3], q[3]);
+        four(head, i, residual<SUB>(yv.x, mv.x), residual<SUB>(yv.y, mv.y), residual<SUB>(yv.z, mv.z), residual<SUB>(yv.w, mv.w));
     }
-    for (long i = head + 4 * n4 + tid; i < n; i += BG_THREADS) dots_term<SUB, WITH_BB>(y[i], SUB ? m[i] : 0.0f, b[i], acc[1], q[1]);
+    for (long i = head + 4 * n4 + tid; i < g.n; i += BG_THREADS) one(i, residual<SUB>(y[i], SUB ? m[i] : 0.0f), 1);
+}
+
+// K19: four float64 sums a lane -- the head in slot 0, the body in slots x y z w, the tail in slot 1 -- as (a0 + a1) + (a2 + a3);
+// WITH_BB: b^2 beside them in the same way.
+template <bool SUB, bool WITH_BB>
+__device__ __forceinline__ void dots_sums(const Segment &g, double &sum, double &sumq) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
+    auto term = [&](float b, double r, int k) {
+        const double bd = (double)b;
+        acc[k] = fma(bd, r, acc[k]);
+        if (WITH_BB) q[k] = fma(bd, bd, q[k]);
+    };
+    segment_walk<SUB, 1>(
+        g, 0, [&](long i, double r, int slot) { term(g.b[i], r, slot); },
+        [&](long head, long i, double r0, double r1, double r2, double r3) {
+            const float4 bv = reinterpret_cast<const float4 *>(g.b + head)[i];
+            term(bv.x, r0, 0), term(bv.y, r1, 1), term(bv.z, r2, 2), term(bv.w, r3, 3);
+        });
     sum = (acc[0] + acc[1]) + (acc[2] + acc[3]);
     sumq = (q[0] + q[1]) + (q[2] + q[3]);
 }
@@ -102,23 +140,17 @@ __device__ __forceinline__ void dots_segment(const float *__restrict__ y, const 
 template <bool SUB>
 __global__ __launch_bounds__(BG_THREADS) void background_dots_kernel(DotsArgs a) {
     __shared__ double red[2 * BG_WAVES];
-    const long bid = blockIdx.x;
-    const int j = (int)(bid / a.nseg), s = (int)(bid - (long)j * a.nseg);
-    const long p0 = (long)s * a.seglen;
-    const long n = (a.P - p0 < a.seglen ? a.P - p0 : a.seglen);
-    const float *y = a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf + p0;
-    const float *m = SUB ? a.sub + (long)j * a.lds + p0 : nullptr;
-    const float *b = a.b + p0;
+    const Segment g = dots_segment<SUB>(a);
     double sum, sumq;
-    if (j == 0) {   // the first frame's workgroups also sum b^2 over their segment
-        dots_segment<SUB, true>(y, m, b, n, sum, sumq);
+    if (g.j == 0) {   // the first frame's workgroups also sum b^2 over their segment
+        dots_sums<SUB, true>(g, sum, sumq);
         const double tq = block_sum0<BG_THREADS>(sumq, red + BG_WAVES);
-        if (threadIdx.x == 0) a.bbpart[s] = tq;
+        if (threadIdx.x == 0) a.bbpart[g.s] = tq;
     } else {
-        dots_segment<SUB, false>(y, m, b, n, sum, sumq);
+        dots_sums<SUB, false>(g, sum, sumq);
     }
     const double t = block_sum0<BG_THREADS>(sum, red);
-    if (threadIdx.x == 0) a.part[bid] = t;
+    if (threadIdx.x == 0) a.part[blockIdx.x] = t;
 }
 
 // num_j = the segments of frame j in their order; bb = the segments of b^2 in their order (every thread the same sum)
@@ -157,15 +189,6 @@ int accum_plan(const char *fn, long P, int B, int segment, AccumPlan &g) {
     return DNMF_OK;
 }
 
-struct AccumArgs {
-    const float *frames, *sub, *f;
-    long ldf, lds, P;
-    const int *frame_ids;
-    int B, seglen;
-    double *part;
-    size_t stride;
-};
-
 // The `live` (1..4) floats at row + p, p a multiple of 4, zeros beyond: one 16-byte load where the row start allows it.
 __device__ __forceinline__ float4 load4(const float *__restrict__ row, long p, int live) {
     if (live == 4 && word_phase(row) == 0) return *reinterpret_cast<const float4 *>(row + p);
@@ -177,50 +200,68 @@ __device__ __forceinline__ float4 load4(const float *__restrict__ row, long p, i
     return v;
 }
 
-template <bool SUB>
-__global__ __launch_bounds__(BG_THREADS) void background_accum_kernel(AccumArgs a) {
+struct AccumRankArgs {
+    const float *frames, *sub, *f;
+    long ldf, lds, ldf_t, P;   // ldf_t: between the R time courses
+    const int *frame_ids;
+    int B, seglen;
+    double *part;
+    size_t stride;
+};
+
+// part[segment][c][p] = sum over the segment's frames of f_c[t] (y - m): four voxels a lane, 4 R float64 sums in registers.  Both
+// families: K19 is R = 1.
+template <int R, bool SUB>
+__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_kernel(AccumRankArgs a) {
     const long p = (long)blockIdx.x * BG_TILE + 4 * (long)threadIdx.x;
     if (p >= a.P) return;
     const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
     const int seg = blockIdx.y;
     const int f0 = seg * a.seglen, f1 = min(a.B, f0 + a.seglen);
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    double s[R][4];
+#pragma unroll
+    for (int c = 0; c < R; ++c) s[c][0] = s[c][1] = s[c][2] = s[c][3] = 0.0;
 #pragma unroll 2
     for (int j = f0; j < f1; ++j) {
         const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
-        const double fj = (double)a.f[j];
+        double r0 = (double)y.x, r1 = (double)y.y, r2 = (double)y.z, r3 = (double)y.w;
         if (SUB) {
             const float4 m = load4(a.sub + (long)j * a.lds, p, live);
-            s0 = fma(fj, (double)y.x - (double)m.x, s0);
-            s1 = fma(fj, (double)y.y - (double)m.y, s1);
-            s2 = fma(fj, (double)y.z - (double)m.z, s2);
-            s3 = fma(fj, (double)y.w - (double)m.w, s3);
-        } else {
-            s0 = fma(fj, (double)y.x, s0);
-            s1 = fma(fj, (double)y.y, s1);
-            s2 = fma(fj, (double)y.z, s2);
-            s3 = fma(fj, (double)y.w, s3);
+            r0 -= (double)m.x, r1 -= (double)m.y, r2 -= (double)m.z, r3 -= (double)m.w;
+        }
+#pragma unroll
+        for (int c = 0; c < R; ++c) {
+            const double fc = (double)a.f[(long)c * a.ldf_t + j];
+            s[c][0] = fma(fc, r0, s[c][0]);
+            s[c][1] = fma(fc, r1, s[c][1]);
+            s[c][2] = fma(fc, r2, s[c][2]);
+            s[c][3] = fma(fc, r3, s[c][3]);
         }
     }
-    double *out = a.part + (size_t)seg * a.stride + p;
-    out[0] = s0;
-    if (live > 1) out[1] = s1;
-    if (live > 2) out[2] = s2;
-    if (live > 3) out[3] = s3;
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+        double *out = a.part + ((size_t)seg * R + c) * a.stride + p;
+        out[0] = s[c][0];
+        if (live > 1) out[1] = s[c][1];
+        if (live > 2) out[2] = s[c][2];
+        if (live > 3) out[3] = s[c][3];
+    }
 }
 
-// sums = (first ? 0 : sums) + the segments in their order; ff = (first ? 0 : ff) + sum f^2 of the call (workgroup 0, fixed tree)
-__global__ __launch_bounds__(BG_THREADS) void background_accum_reduce_kernel(const double *__restrict__ part, size_t stride, int nseg, long P,
-                                                                             int first, const float *__restrict__ f, int B,
-                                                                             double *__restrict__ sums, double *__restrict__ ff) {
+// sums[c][p] = (first ? 0 : sums[c][p]) + the segments in their order; c rides on gridDim.y.  With f (K19, R = 1) workgroup 0 also
+// leaves ff = (first ? 0 : ff) + sum f^2 of the call (fixed tree); K23 passes NULL and has its Gram launch.
+__global__ __launch_bounds__(BG_THREADS) void background_accum_reduce_kernel(const double *__restrict__ part, size_t stride, int nseg, int R,
+                                                                             long P, int first, double *__restrict__ sums,
+                                                                             const float *__restrict__ f, int B, double *__restrict__ ff) {
     __shared__ double red[BG_WAVES];
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int c = blockIdx.y;
     if (i < P) {
-        double acc = first ? 0.0 : sums[i];
-        for (int s = 0; s < nseg; ++s) acc += part[(size_t)s * stride + i];
-        sums[i] = acc;
+        double acc = first ? 0.0 : sums[(size_t)c * stride + i];
+        for (int s = 0; s < nseg; ++s) acc += part[((size_t)s * R + c) * stride + i];
+        sums[(size_t)c * stride + i] = acc;
     }
-    if (blockIdx.x == 0) {
+    if (f && blockIdx.x == 0) {
         double q = 0.0;
         for (int j = threadIdx.x; j < B; j += BG_THREADS) {
             const double v = (double)f[j];
@@ -245,28 +286,14 @@ __global__ __launch_bounds__(BG_THREADS) void background_accum_finish_kernel(con
 // ---- subtract ------------------------------------------------------------------------------------------------------------------
 struct SubtractArgs {
     const float *frames, *b, *f;
-    long ldf, ldo, P, ntiles;
+    long ldf, ldo, ldb, ldf_t, P, ntiles;
     const int *frame_ids, *times;
-    int nf, clamp;
+    int nf, clamp, R;
     float *out;
 };
 
-__global__ __launch_bounds__(BG_THREADS) void background_subtract_kernel(SubtractArgs a) {
-    const long bid = blockIdx.x;
-    const int j = (int)(bid / a.ntiles);
-    const long p = (bid - (long)j * a.ntiles) * BG_TILE + 4 * (long)threadIdx.x;
-    if (p >= a.P) return;
-    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
-    const int t = a.times ? a.times[j] : j;
-    // a time f has no entry for: the row becomes NaN instead of reading beyond f
-    const float fj = (t >= 0 && t < a.nf) ? a.f[t] : __builtin_nanf("");
-    const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
-    const float4 b = load4(a.b, p, live);
-    float4 r;
-    r.x = fmaf(-b.x, fj, y.x), r.y = fmaf(-b.y, fj, y.y), r.z = fmaf(-b.z, fj, y.z), r.w = fmaf(-b.w, fj, y.w);
-    if (a.clamp) r.x = fmaxf(r.x, 0.0f), r.y = fmaxf(r.y, 0.0f), r.z = fmaxf(r.z, 0.0f), r.w = fmaxf(r.w, 0.0f);
-    if (t < 0 || t >= a.nf) r.x = r.y = r.z = r.w = fj;   // fmaxf drops a NaN
-    float *o = a.out + (long)j * a.ldo;
+// `live` (1..4) floats to o + p, p a multiple of 4: one 16-byte store where the row start allows it.
+__device__ __forceinline__ void store4(float *__restrict__ o, long p, int live, float4 r) {
     if (live == 4 && word_phase(o) == 0) {
         *reinterpret_cast<float4 *>(o + p) = r;
         return;
@@ -275,6 +302,39 @@ __global__ __launch_bounds__(BG_THREADS) void background_subtract_kernel(Subtrac
     if (live > 1) o[p + 1] = r.y;
     if (live > 2) o[p + 2] = r.z;
     if (live > 3) o[p + 3] = r.w;
+}
+
+// K19 (RANK false): out = fmaf(-b, f[t], y), one fp32 fused multiply-add.  K23: out = (float)((double)y - sum_c (double)b_c (double)f_c[t]),
+// the products added one by one, c ascending.
+template <bool RANK>
+__global__ __launch_bounds__(BG_THREADS) void background_subtract_kernel(SubtractArgs a) {
+    const long bid = blockIdx.x;
+    const int j = (int)(bid / a.ntiles);
+    const long p = (bid - (long)j * a.ntiles) * BG_TILE + 4 * (long)threadIdx.x;
+    if (p >= a.P) return;
+    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
+    const int t = a.times ? a.times[j] : j;
+    const bool known = t >= 0 && t < a.nf;
+    const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
+    float4 r;
+    if (RANK) {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        if (known)
+            for (int c = 0; c < a.R; ++c) {
+                const double fc = (double)a.f[(long)c * a.ldf_t + t];
+                const float4 b = load4(a.b + (long)c * a.ldb, p, live);
+                s0 = s0 + (double)b.x * fc, s1 = s1 + (double)b.y * fc, s2 = s2 + (double)b.z * fc, s3 = s3 + (double)b.w * fc;
+            }
+        r.x = (float)((double)y.x - s0), r.y = (float)((double)y.y - s1), r.z = (float)((double)y.z - s2), r.w = (float)((double)y.w - s3);
+    } else {
+        const float fj = known ? a.f[t] : 0.0f;
+        const float4 b = load4(a.b, p, live);
+        r.x = fmaf(-b.x, fj, y.x), r.y = fmaf(-b.y, fj, y.y), r.z = fmaf(-b.z, fj, y.z), r.w = fmaf(-b.w, fj, y.w);
+    }
+    if (a.clamp) r.x = fmaxf(r.x, 0.0f), r.y = fmaxf(r.y, 0.0f), r.z = fmaxf(r.z, 0.0f), r.w = fmaxf(r.w, 0.0f);
+    // a time f has no entry for: the row becomes NaN instead of reading beyond f (after the clamp: fmaxf drops a NaN)
+    if (!known) r.x = r.y = r.z = r.w = __builtin_nanf("");
+    store4(a.out + (long)j * a.ldo, p, live, r);
 }
 
 // ---- K23: rank R ---------------------------------------------------------------------------------------------------------------
@@ -351,64 +411,31 @@ __global__ __launch_bounds__(64) void background_gram_reduce_kernel(const double
     G[k] = s;
 }
 
-struct DotsRankArgs {
-    const float *frames, *sub, *b;
-    long ldf, lds, ldb, P, seglen;
-    const int *frame_ids;
-    int nseg;
-    double *part;
-};
-
-// part[(frame, segment)][c] = sum over the segment's voxels of b_c (y - m)
+// part[(frame, segment)][c] = sum over the segment's voxels of b_c (y - m): one float64 sum per component and lane
 template <int R, bool SUB>
-__global__ __launch_bounds__(BG_THREADS) void background_dots_rank_kernel(DotsRankArgs a) {
+__global__ __launch_bounds__(BG_THREADS) void background_dots_rank_kernel(DotsArgs a) {
     __shared__ double red[BG_WAVES][R];
     const int tid = threadIdx.x;
-    const long bid = blockIdx.x;
-    const int j = (int)(bid / a.nseg), s = (int)(bid - (long)j * a.nseg);
-    const long p0 = (long)s * a.seglen;
-    const long n = (a.P - p0 < a.seglen ? a.P - p0 : a.seglen);
-    const float *__restrict__ y = a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf + p0;
-    const float *__restrict__ m = SUB ? a.sub + (long)j * a.lds + p0 : nullptr;
-    const float *__restrict__ b = a.b + p0;
+    const Segment g = dots_segment<SUB>(a);
     double acc[R];
 #pragma unroll
     for (int c = 0; c < R; ++c) acc[c] = 0.0;
-    // as in K19: 16-byte loads from the first voxel at which y, m and every row of b are aligned, else float by float
-    const unsigned ph = word_phase(y);
-    bool vec = !SUB || word_phase(m) == ph;
+    segment_walk<SUB, R>(
+        g, a.ldb,
+        [&](long i, double r, int) {
 #pragma unroll
-    for (int c = 0; c < R; ++c) vec = vec && word_phase(b + (long)c * a.ldb) == ph;
-    long head = vec ? (long)((4 - ph) & 3) : n;
-    if (head > n) head = n;
-    const long n4 = (n - head) >> 2;
-    for (long i = tid; i < head; i += BG_THREADS) {
-        const double r = SUB ? (double)y[i] - (double)m[i] : (double)y[i];
+            for (int c = 0; c < R; ++c) acc[c] = fma((double)g.b[(long)c * a.ldb + i], r, acc[c]);
+        },
+        [&](long head, long i, double r0, double r1, double r2, double r3) {
 #pragma unroll
-        for (int c = 0; c < R; ++c) acc[c] = fma((double)b[(long)c * a.ldb + i], r, acc[c]);
-    }
-    const float4 *y4 = reinterpret_cast<const float4 *>(y + head);
-    const float4 *m4 = SUB ? reinterpret_cast<const float4 *>(m + head) : nullptr;
-#pragma unroll 2
-    for (long i = tid; i < n4; i += BG_THREADS) {
-        const float4 yv = y4[i];
-        const float4 mv = SUB ? m4[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const double r0 = SUB ? (double)yv.x - (double)mv.x : (double)yv.x, r1 = SUB ? (double)yv.y - (double)mv.y : (double)yv.y;
-        const double r2 = SUB ? (double)yv.z - (double)mv.z : (double)yv.z, r3 = SUB ? (double)yv.w - (double)mv.w : (double)yv.w;
-#pragma unroll
-        for (int c = 0; c < R; ++c) {
-            const float4 bv = reinterpret_cast<const float4 *>(b + (long)c * a.ldb + head)[i];
-            acc[c] = fma((double)bv.x, r0, acc[c]);
-            acc[c] = fma((double)bv.y, r1, acc[c]);
-            acc[c] = fma((double)bv.z, r2, acc[c]);
-            acc[c] = fma((double)bv.w, r3, acc[c]);
-        }
-    }
-    for (long i = head + 4 * n4 + tid; i < n; i += BG_THREADS) {
-        const double r = SUB ? (double)y[i] - (double)m[i] : (double)y[i];
-#pragma unroll
-        for (int c = 0; c < R; ++c) acc[c] = fma((double)b[(long)c * a.ldb + i], r, acc[c]);
-    }
+            for (int c = 0; c < R; ++c) {
+                const float4 bv = reinterpret_cast<const float4 *>(g.b + (long)c * a.ldb + head)[i];
+                acc[c] = fma((double)bv.x, r0, acc[c]);
+                acc[c] = fma((double)bv.y, r1, acc[c]);
+                acc[c] = fma((double)bv.z, r2, acc[c]);
+                acc[c] = fma((double)bv.w, r3, acc[c]);
+            }
+        });
 #pragma unroll
     for (int c = 0; c < R; ++c) {
         const double v = wave_sum(acc[c]);
@@ -419,7 +446,7 @@ __global__ __launch_bounds__(BG_THREADS) void background_dots_rank_kernel(DotsRa
         double t = 0.0;
 #pragma unroll
         for (int w = 0; w < BG_WAVES; ++w) t += red[w][tid];
-        a.part[bid * R + tid] = t;
+        a.part[(long)blockIdx.x * R + tid] = t;
     }
 }
 
@@ -448,64 +475,6 @@ __global__ __launch_bounds__(BG_THREADS) void background_dots_rank_finish_kernel
     for (int c = 0; c < R; ++c) f[(long)c * ldf_t + t] = (float)x[c];
 }
 
-struct AccumRankArgs {
-    const float *frames, *sub, *f;
-    long ldf, lds, ldf_t, P;
-    const int *frame_ids;
-    int B, seglen;
-    double *part;
-    size_t stride;
-};
-
-// part[segment][c][p] = sum over the segment's frames of f_c[t] (y - m): four voxels a lane, 4 R float64 sums in registers
-template <int R, bool SUB>
-__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_kernel(AccumRankArgs a) {
-    const long p = (long)blockIdx.x * BG_TILE + 4 * (long)threadIdx.x;
-    if (p >= a.P) return;
-    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
-    const int seg = blockIdx.y;
-    const int f0 = seg * a.seglen, f1 = min(a.B, f0 + a.seglen);
-    double s[R][4];
-#pragma unroll
-    for (int c = 0; c < R; ++c) s[c][0] = s[c][1] = s[c][2] = s[c][3] = 0.0;
-#pragma unroll 2
-    for (int j = f0; j < f1; ++j) {
-        const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
-        double r0 = (double)y.x, r1 = (double)y.y, r2 = (double)y.z, r3 = (double)y.w;
-        if (SUB) {
-            const float4 m = load4(a.sub + (long)j * a.lds, p, live);
-            r0 -= (double)m.x, r1 -= (double)m.y, r2 -= (double)m.z, r3 -= (double)m.w;
-        }
-#pragma unroll
-        for (int c = 0; c < R; ++c) {
-            const double fc = (double)a.f[(long)c * a.ldf_t + j];
-            s[c][0] = fma(fc, r0, s[c][0]);
-            s[c][1] = fma(fc, r1, s[c][1]);
-            s[c][2] = fma(fc, r2, s[c][2]);
-            s[c][3] = fma(fc, r3, s[c][3]);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < R; ++c) {
-        double *out = a.part + ((size_t)seg * R + c) * a.stride + p;
-        out[0] = s[c][0];
-        if (live > 1) out[1] = s[c][1];
-        if (live > 2) out[2] = s[c][2];
-        if (live > 3) out[3] = s[c][3];
-    }
-}
-
-// sums[c][p] = (first ? 0 : sums[c][p]) + the segments in their order; c rides on gridDim.y
-__global__ __launch_bounds__(BG_THREADS) void background_accum_rank_reduce_kernel(const double *__restrict__ part, size_t stride, int nseg, int R,
-                                                                                  long P, int first, double *__restrict__ sums) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int c = blockIdx.y;
-    if (i >= P) return;
-    double acc = first ? 0.0 : sums[(size_t)c * stride + i];
-    for (int s = 0; s < nseg; ++s) acc += part[((size_t)s * R + c) * stride + i];
-    sums[(size_t)c * stride + i] = acc;
-}
-
 // Per voxel: the sweeps from the voxel's current b with W in LDS; num is (R, P), w_out the Gram matrix
 template <int R>
 __global__ __launch_bounds__(BG_THREADS) void background_accum_rank_finish_kernel(const double *__restrict__ sums, size_t stride,
@@ -529,47 +498,16 @@ __global__ __launch_bounds__(BG_THREADS) void background_accum_rank_finish_kerne
     for (int c = 0; c < R; ++c) b[(long)c * ldb + p] = (float)x[c];
 }
 
-struct SubtractRankArgs {
-    const float *frames, *b, *f;
-    long ldf, ldo, ldb, ldf_t, P, ntiles;
-    const int *frame_ids, *times;
-    int nf, clamp, R;
-    float *out;
-};
+// ---- what the entries share ----------------------------------------------------------------------------------------------------
+unsigned lane_blocks(long n) { return (unsigned)((n + BG_THREADS - 1) / BG_THREADS); }   // workgroups of a launch with one element a lane
 
-// out = (float)((double)y - sum_c (double)b_c (double)f_c[t]), the products added one by one, c ascending
-__global__ __launch_bounds__(BG_THREADS) void background_subtract_rank_kernel(SubtractRankArgs a) {
-    const long bid = blockIdx.x;
-    const int j = (int)(bid / a.ntiles);
-    const long p = (bid - (long)j * a.ntiles) * BG_TILE + 4 * (long)threadIdx.x;
-    if (p >= a.P) return;
-    const int live = a.P - p >= 4 ? 4 : (int)(a.P - p);
-    const int t = a.times ? a.times[j] : j;
-    const bool known = t >= 0 && t < a.nf;
-    const float4 y = load4(a.frames + (long)(a.frame_ids ? a.frame_ids[j] : j) * a.ldf, p, live);
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    if (known)
-        for (int c = 0; c < a.R; ++c) {
-            const double fc = (double)a.f[(long)c * a.ldf_t + t];
-            const float4 b = load4(a.b + (long)c * a.ldb, p, live);
-            s0 = s0 + (double)b.x * fc, s1 = s1 + (double)b.y * fc, s2 = s2 + (double)b.z * fc, s3 = s3 + (double)b.w * fc;
-        }
-    float4 r;
-    r.x = (float)((double)y.x - s0), r.y = (float)((double)y.y - s1), r.z = (float)((double)y.z - s2), r.w = (float)((double)y.w - s3);
-    if (a.clamp) r.x = fmaxf(r.x, 0.0f), r.y = fmaxf(r.y, 0.0f), r.z = fmaxf(r.z, 0.0f), r.w = fmaxf(r.w, 0.0f);
-    if (!known) r.x = r.y = r.z = r.w = __builtin_nanf("");   // a time f has no entry for: the row becomes NaN
-    float *o = a.out + (long)j * a.ldo;
-    if (live == 4 && word_phase(o) == 0) {
-        *reinterpret_cast<float4 *>(o + p) = r;
-        return;
-    }
-    o[p] = r.x;
-    if (live > 1) o[p + 1] = r.y;
-    if (live > 2) o[p + 2] = r.z;
-    if (live > 3) o[p + 3] = r.w;
+// `what`: "workspace" or "state", as the entry's texts call it
+int check_workspace(const char *fn, const char *what, const void *ws, size_t bytes, size_t need) {
+    DNMF_REQUIRE(bytes >= need, DNMF_E_WORKSPACE, "%s: %s of %zu bytes, need %zu", fn, what, bytes, need);
+    DNMF_REQUIRE(((size_t)ws & 7) == 0, DNMF_E_WORKSPACE, "%s: %s must be 8-byte aligned", fn, what);
+    return DNMF_OK;
 }
 
-// ---- K23: the plans and the launches by R --------------------------------------------------------------------------------------
 int rank_check(const char *fn, int R, int inner) {
     DNMF_REQUIRE(R >= BGR_MIN && R <= BGR_MAX, DNMF_E_UNSUPPORTED, "%s: R=%d components (%d .. %d; one component is K19's entry)", fn, R, BGR_MIN,
                  BGR_MAX);
@@ -577,6 +515,34 @@ int rank_check(const char *fn, int R, int inner) {
     return DNMF_OK;
 }
 
+// Both subtractions: K19 is R = 1 with the one fmaf (RANK false: no rows of b or f in its texts), K23 checks its R first.
+template <bool RANK>
+int subtract(const char *fn, const float *frames, long ldf, const int *frame_ids, const float *b, long ldb, const float *f, long ldf_t, int R, int nf,
+             const int *times, long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream) {
+    DNMF_REQUIRE(frames && b && f && out, DNMF_E_NULL, "%s: NULL argument", fn);
+    if (RANK) {
+        const int rc = rank_check(fn, R, 1);
+        if (rc != DNMF_OK) return rc;
+    }
+    DNMF_REQUIRE(P >= 1 && B >= 1 && nf >= 1, DNMF_E_SHAPE, "%s: P=%ld voxels, B=%d frames, nf=%d", fn, P, B, nf);
+    if (RANK) {
+        DNMF_REQUIRE(ldf >= P && ldo >= P && ldb >= P, DNMF_E_SHAPE, "%s: ldf=%ld ldo=%ld ldb=%ld below a row of P=%ld", fn, ldf, ldo, ldb, P);
+        DNMF_REQUIRE(ldf_t >= nf, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of nf=%d", fn, ldf_t, nf);
+    } else {
+        DNMF_REQUIRE(ldf >= P && ldo >= P, DNMF_E_SHAPE, "%s: ldf=%ld ldo=%ld below a row of P=%ld", fn, ldf, ldo, P);
+    }
+    DNMF_REQUIRE(times || B <= nf, DNMF_E_SHAPE, "%s: B=%d frames but f has %d values and times is NULL", fn, B, nf);
+    DNMF_REQUIRE(out != frames || (!frame_ids && ldo == ldf), DNMF_E_SHAPE, "%s: in place (out == frames) needs frame_ids NULL and ldo == ldf", fn);
+    DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, P);
+    SubtractArgs a;
+    a.frames = frames, a.b = b, a.f = f, a.ldf = ldf, a.ldo = ldo, a.ldb = ldb, a.ldf_t = ldf_t, a.P = P, a.ntiles = (P + BG_TILE - 1) / BG_TILE;
+    a.frame_ids = frame_ids, a.times = times, a.nf = nf, a.clamp = clamp != 0, a.R = R, a.out = out;
+    DNMF_REQUIRE(a.ntiles * B < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld workgroups (split the call)", fn, a.ntiles * B);
+    hipLaunchKernelGGL(background_subtract_kernel<RANK>, dim3((unsigned)(a.ntiles * B)), dim3(BG_THREADS), 0, (hipStream_t)stream, a);
+    return check_launch(fn);
+}
+
+// ---- K23: the plans and the launches by R --------------------------------------------------------------------------------------
 size_t gram_bytes(long n, int R) { return align256((size_t)((n + BG_GRAM_CHUNK - 1) / BG_GRAM_CHUNK) * (R * (R + 1) / 2) * sizeof(double)); }
 
 struct DotsRankPlan {
@@ -621,29 +587,34 @@ void launch_gram(const float *x, long ld, long n, double *part, int first, doubl
 }
 
 template <int R>
-void launch_dots_rank(const DotsRankArgs &a, int B, int inner, float *f, long ldf_t, double *num, double *q, double *Q, double *gram,
+void launch_dots_rank(const DotsArgs &a, int B, int inner, float *f, long ldf_t, double *num, double *q, double *Q, double *gram,
                       hipStream_t st) {
     launch_gram<R>(a.b, a.ldb, a.P, gram, 1, Q, st);
     const dim3 grid((unsigned)((long)B * a.nseg));
     if (a.sub) hipLaunchKernelGGL((background_dots_rank_kernel<R, true>), grid, dim3(BG_THREADS), 0, st, a);
     else hipLaunchKernelGGL((background_dots_rank_kernel<R, false>), grid, dim3(BG_THREADS), 0, st, a);
-    hipLaunchKernelGGL(background_dots_rank_finish_kernel<R>, dim3((unsigned)((B + BG_THREADS - 1) / BG_THREADS)), dim3(BG_THREADS), 0, st,
-                       a.part, Q, a.nseg, B, inner, f, ldf_t, num, q);
+    hipLaunchKernelGGL(background_dots_rank_finish_kernel<R>, dim3(lane_blocks(B)), dim3(BG_THREADS), 0, st, a.part, Q, a.nseg, B, inner, f, ldf_t, num, q);
+}
+
+// The accumulate pass and the reduction of its partials, the first two launches of both b half-steps.  ff: K19's sum f^2, which
+// the reduction then keeps (NULL: K23).
+template <int R>
+void launch_accum(const AccumRankArgs &a, const AccumPlan &g, int first, double *sums, double *ff, hipStream_t st) {
+    const dim3 grid((unsigned)g.ntiles, (unsigned)g.nseg);
+    if (a.sub) hipLaunchKernelGGL((background_accum_rank_kernel<R, true>), grid, dim3(BG_THREADS), 0, st, a);
+    else hipLaunchKernelGGL((background_accum_rank_kernel<R, false>), grid, dim3(BG_THREADS), 0, st, a);
+    hipLaunchKernelGGL(background_accum_reduce_kernel, dim3(lane_blocks(a.P), (unsigned)R), dim3(BG_THREADS), 0, st, a.part, a.stride, g.nseg, R,
+                       a.P, first, sums, ff ? a.f : nullptr, a.B, ff);
 }
 
 template <int R>
 void launch_accum_rank(const AccumRankArgs &a, const AccumRankPlan &g, int first, int finish, int inner, double *W, double *sums, double *gram,
                        float *b, long ldb, double *num, double *w, hipStream_t st) {
-    const dim3 grid((unsigned)g.a.ntiles, (unsigned)g.a.nseg);
-    if (a.sub) hipLaunchKernelGGL((background_accum_rank_kernel<R, true>), grid, dim3(BG_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((background_accum_rank_kernel<R, false>), grid, dim3(BG_THREADS), 0, st, a);
-    const unsigned pblocks = (unsigned)((a.P + BG_THREADS - 1) / BG_THREADS);
-    hipLaunchKernelGGL(background_accum_rank_reduce_kernel, dim3(pblocks, (unsigned)R), dim3(BG_THREADS), 0, st, a.part, a.stride, g.a.nseg, R,
-                       a.P, first, sums);
+    launch_accum<R>(a, g.a, first, sums, nullptr, st);
     launch_gram<R>(a.f, a.ldf_t, (long)a.B, gram, first, W, st);
     if (finish)
-        hipLaunchKernelGGL(background_accum_rank_finish_kernel<R>, dim3(pblocks), dim3(BG_THREADS), 0, st, sums, a.stride, W, a.P, inner, b, ldb,
-                           num, w);
+        hipLaunchKernelGGL(background_accum_rank_finish_kernel<R>, dim3(lane_blocks(a.P)), dim3(BG_THREADS), 0, st, sums, a.stride, W, a.P, inner,
+                           b, ldb, num, w);
 }
 
 // R is a template parameter of the kernels: one case per supported value
@@ -672,26 +643,24 @@ size_t dnmf_background_dots_workspace(long P, int B) {
 int dnmf_background_dots(const float *frames, long ldf, const float *sub, long lds, const int *frame_ids, const float *b, long P, int B,
                          double *num, double *bb, float *f, void *workspace, size_t workspace_bytes, dnmf_stream_t stream) {
     using namespace dnmf;
-    DNMF_REQUIRE(frames && b && f && workspace, DNMF_E_NULL, "dnmf_background_dots: NULL argument");
+    const char *fn = "dnmf_background_dots";
+    DNMF_REQUIRE(frames && b && f && workspace, DNMF_E_NULL, "%s: NULL argument", fn);
     DotsPlan g;
-    const int rc = dots_plan("dnmf_background_dots", P, B, g);
+    int rc = dots_plan(fn, P, B, g);
     if (rc != DNMF_OK) return rc;
-    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P), DNMF_E_SHAPE, "dnmf_background_dots: ldf=%ld lds=%ld below a row of P=%ld", ldf, lds, P);
-    DNMF_REQUIRE(workspace_bytes >= g.bytes, DNMF_E_WORKSPACE, "dnmf_background_dots: workspace of %zu bytes, need %zu", workspace_bytes,
-                 g.bytes);
-    DNMF_REQUIRE(((size_t)workspace & 7) == 0, DNMF_E_WORKSPACE, "dnmf_background_dots: workspace must be 8-byte aligned");
+    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P), DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld below a row of P=%ld", fn, ldf, lds, P);
+    rc = check_workspace(fn, "workspace", workspace, workspace_bytes, g.bytes);
+    if (rc != DNMF_OK) return rc;
     char *w = static_cast<char *>(workspace);
     DotsArgs a;
-    a.frames = frames, a.sub = sub, a.b = b, a.ldf = ldf, a.lds = lds, a.P = P, a.seglen = g.seglen, a.frame_ids = frame_ids;
-    a.nseg = g.nseg;
-    a.part = reinterpret_cast<double *>(w), a.bbpart = reinterpret_cast<double *>(w + g.off_bb);
+    a.frames = frames, a.sub = sub, a.b = b, a.ldf = ldf, a.lds = lds, a.ldb = P, a.P = P, a.seglen = g.seglen, a.frame_ids = frame_ids;
+    a.nseg = g.nseg, a.part = reinterpret_cast<double *>(w), a.bbpart = reinterpret_cast<double *>(w + g.off_bb);
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((long)B * g.nseg));
     if (sub) hipLaunchKernelGGL(background_dots_kernel<true>, grid, dim3(BG_THREADS), 0, st, a);
     else hipLaunchKernelGGL(background_dots_kernel<false>, grid, dim3(BG_THREADS), 0, st, a);
-    hipLaunchKernelGGL(background_dots_finish_kernel, dim3((unsigned)((B + BG_THREADS - 1) / BG_THREADS)), dim3(BG_THREADS), 0, st, a.part,
-                       a.bbpart, g.nseg, B, num, bb, f);
-    return check_launch("dnmf_background_dots");
+    hipLaunchKernelGGL(background_dots_finish_kernel, dim3(lane_blocks(B)), dim3(BG_THREADS), 0, st, a.part, a.bbpart, g.nseg, B, num, bb, f);
+    return check_launch(fn);
 }
 
 size_t dnmf_background_accum_workspace(long P, int B, int segment) {
@@ -704,46 +673,29 @@ int dnmf_background_accum(const float *frames, long ldf, const float *sub, long 
                           int first, int finish, int segment, void *state, size_t state_bytes, float *b, double *num, double *ff,
                           dnmf_stream_t stream) {
     using namespace dnmf;
-    DNMF_REQUIRE(frames && f && state, DNMF_E_NULL, "dnmf_background_accum: NULL argument");
-    DNMF_REQUIRE(b || !finish, DNMF_E_NULL, "dnmf_background_accum: b is NULL with finish");
+    const char *fn = "dnmf_background_accum";
+    DNMF_REQUIRE(frames && f && state, DNMF_E_NULL, "%s: NULL argument", fn);
+    DNMF_REQUIRE(b || !finish, DNMF_E_NULL, "%s: b is NULL with finish", fn);
     AccumPlan g;
-    const int rc = accum_plan("dnmf_background_accum", P, B, segment, g);
+    int rc = accum_plan(fn, P, B, segment, g);
     if (rc != DNMF_OK) return rc;
-    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P), DNMF_E_SHAPE, "dnmf_background_accum: ldf=%ld lds=%ld below a row of P=%ld", ldf, lds, P);
-    DNMF_REQUIRE(state_bytes >= g.bytes, DNMF_E_WORKSPACE, "dnmf_background_accum: state of %zu bytes, need %zu", state_bytes, g.bytes);
-    DNMF_REQUIRE(((size_t)state & 7) == 0, DNMF_E_WORKSPACE, "dnmf_background_accum: state must be 8-byte aligned");
+    DNMF_REQUIRE(ldf >= P && (!sub || lds >= P), DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld below a row of P=%ld", fn, ldf, lds, P);
+    rc = check_workspace(fn, "state", state, state_bytes, g.bytes);
+    if (rc != DNMF_OK) return rc;
     char *w = static_cast<char *>(state);
     double *hdr = reinterpret_cast<double *>(w), *sums = reinterpret_cast<double *>(w + g.off_sums);
-    AccumArgs a;
-    a.frames = frames, a.sub = sub, a.f = f, a.ldf = ldf, a.lds = lds, a.P = P, a.frame_ids = frame_ids, a.B = B, a.seglen = g.seglen;
-    a.part = reinterpret_cast<double *>(w + g.off_part), a.stride = g.stride;
+    AccumRankArgs a;
+    a.frames = frames, a.sub = sub, a.f = f, a.ldf = ldf, a.lds = lds, a.ldf_t = B, a.P = P, a.frame_ids = frame_ids, a.B = B;
+    a.seglen = g.seglen, a.part = reinterpret_cast<double *>(w + g.off_part), a.stride = g.stride;
     const hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)g.ntiles, (unsigned)g.nseg);
-    if (sub) hipLaunchKernelGGL(background_accum_kernel<true>, grid, dim3(BG_THREADS), 0, st, a);
-    else hipLaunchKernelGGL(background_accum_kernel<false>, grid, dim3(BG_THREADS), 0, st, a);
-    const unsigned pblocks = (unsigned)((P + BG_THREADS - 1) / BG_THREADS);
-    hipLaunchKernelGGL(background_accum_reduce_kernel, dim3(pblocks), dim3(BG_THREADS), 0, st, a.part, g.stride, g.nseg, P, first != 0, f, B,
-                       sums, hdr);
-    if (finish) hipLaunchKernelGGL(background_accum_finish_kernel, dim3(pblocks), dim3(BG_THREADS), 0, st, sums, hdr, P, b, num, ff);
-    return check_launch("dnmf_background_accum");
+    launch_accum<1>(a, g, first != 0, sums, hdr, st);
+    if (finish) hipLaunchKernelGGL(background_accum_finish_kernel, dim3(lane_blocks(P)), dim3(BG_THREADS), 0, st, sums, hdr, P, b, num, ff);
+    return check_launch(fn);
 }
 
 int dnmf_background_subtract(const float *frames, long ldf, const int *frame_ids, const float *b, const float *f, int nf, const int *times,
                              long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream) {
-    using namespace dnmf;
-    DNMF_REQUIRE(frames && b && f && out, DNMF_E_NULL, "dnmf_background_subtract: NULL argument");
-    DNMF_REQUIRE(P >= 1 && B >= 1 && nf >= 1, DNMF_E_SHAPE, "dnmf_background_subtract: P=%ld voxels, B=%d frames, nf=%d", P, B, nf);
-    DNMF_REQUIRE(ldf >= P && ldo >= P, DNMF_E_SHAPE, "dnmf_background_subtract: ldf=%ld ldo=%ld below a row of P=%ld", ldf, ldo, P);
-    DNMF_REQUIRE(times || B <= nf, DNMF_E_SHAPE, "dnmf_background_subtract: B=%d frames but f has %d values and times is NULL", B, nf);
-    DNMF_REQUIRE(out != frames || (!frame_ids && ldo == ldf), DNMF_E_SHAPE,
-                 "dnmf_background_subtract: in place (out == frames) needs frame_ids NULL and ldo == ldf");
-    DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "dnmf_background_subtract: %ld voxels (32-bit offsets)", P);
-    SubtractArgs a;
-    a.frames = frames, a.b = b, a.f = f, a.ldf = ldf, a.ldo = ldo, a.P = P, a.ntiles = (P + BG_TILE - 1) / BG_TILE;
-    a.frame_ids = frame_ids, a.times = times, a.nf = nf, a.clamp = clamp != 0, a.out = out;
-    DNMF_REQUIRE(a.ntiles * B < (1L << 31), DNMF_E_UNSUPPORTED, "dnmf_background_subtract: %ld workgroups (split the call)", a.ntiles * B);
-    hipLaunchKernelGGL(background_subtract_kernel, dim3((unsigned)(a.ntiles * B)), dim3(BG_THREADS), 0, (hipStream_t)stream, a);
-    return check_launch("dnmf_background_subtract");
+    return dnmf::subtract<false>("dnmf_background_subtract", frames, ldf, frame_ids, b, P, f, nf, 1, nf, times, P, B, out, ldo, clamp, stream);
 }
 
 size_t dnmf_background_dots_rank_workspace(long P, int B, int R) {
@@ -765,12 +717,12 @@ int dnmf_background_dots_rank(const float *frames, long ldf, const float *sub, l
     if (rc != DNMF_OK) return rc;
     DNMF_REQUIRE(ldf >= P && (!sub || lds >= P) && ldb >= P, DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld ldb=%ld below a row of P=%ld", fn, ldf, lds, ldb, P);
     DNMF_REQUIRE(ldf_t >= B, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of B=%d", fn, ldf_t, B);
-    DNMF_REQUIRE(workspace_bytes >= g.bytes, DNMF_E_WORKSPACE, "%s: workspace of %zu bytes, need %zu", fn, workspace_bytes, g.bytes);
-    DNMF_REQUIRE(((size_t)workspace & 7) == 0, DNMF_E_WORKSPACE, "%s: workspace must be 8-byte aligned", fn);
+    rc = check_workspace(fn, "workspace", workspace, workspace_bytes, g.bytes);
+    if (rc != DNMF_OK) return rc;
     char *w = static_cast<char *>(workspace);
-    DotsRankArgs a;
+    DotsArgs a;
     a.frames = frames, a.sub = sub, a.b = b, a.ldf = ldf, a.lds = lds, a.ldb = ldb, a.P = P, a.seglen = g.d.seglen, a.frame_ids = frame_ids;
-    a.nseg = g.d.nseg, a.part = reinterpret_cast<double *>(w + g.off_part);
+    a.nseg = g.d.nseg, a.part = reinterpret_cast<double *>(w + g.off_part), a.bbpart = nullptr;
     double *Q = reinterpret_cast<double *>(w), *gram = reinterpret_cast<double *>(w + g.off_gram);
     const hipStream_t st = (hipStream_t)stream;
 #define DNMF_BG_CALL(N) launch_dots_rank<N>(a, B, inner, f, ldf_t, num, q, Q, gram, st)
@@ -800,8 +752,8 @@ int dnmf_background_accum_rank(const float *frames, long ldf, const float *sub, 
     DNMF_REQUIRE(ldf >= P && (!sub || lds >= P) && (!finish || ldb >= P), DNMF_E_SHAPE, "%s: ldf=%ld lds=%ld ldb=%ld below a row of P=%ld", fn, ldf,
                  lds, ldb, P);
     DNMF_REQUIRE(ldf_t >= B, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of B=%d", fn, ldf_t, B);
-    DNMF_REQUIRE(state_bytes >= g.bytes, DNMF_E_WORKSPACE, "%s: state of %zu bytes, need %zu", fn, state_bytes, g.bytes);
-    DNMF_REQUIRE(((size_t)state & 7) == 0, DNMF_E_WORKSPACE, "%s: state must be 8-byte aligned", fn);
+    rc = check_workspace(fn, "state", state, state_bytes, g.bytes);
+    if (rc != DNMF_OK) return rc;
     char *w = static_cast<char *>(state);
     double *W = reinterpret_cast<double *>(w), *sums = reinterpret_cast<double *>(w + g.off_sums);
     double *gram = reinterpret_cast<double *>(w + g.off_gram);
@@ -817,23 +769,8 @@ int dnmf_background_accum_rank(const float *frames, long ldf, const float *sub, 
 
 int dnmf_background_subtract_rank(const float *frames, long ldf, const int *frame_ids, const float *b, long ldb, const float *f, long ldf_t, int R,
                                   int nf, const int *times, long P, int B, float *out, long ldo, int clamp, dnmf_stream_t stream) {
-    using namespace dnmf;
-    const char *fn = "dnmf_background_subtract_rank";
-    DNMF_REQUIRE(frames && b && f && out, DNMF_E_NULL, "%s: NULL argument", fn);
-    const int rc = rank_check(fn, R, 1);
-    if (rc != DNMF_OK) return rc;
-    DNMF_REQUIRE(P >= 1 && B >= 1 && nf >= 1, DNMF_E_SHAPE, "%s: P=%ld voxels, B=%d frames, nf=%d", fn, P, B, nf);
-    DNMF_REQUIRE(ldf >= P && ldo >= P && ldb >= P, DNMF_E_SHAPE, "%s: ldf=%ld ldo=%ld ldb=%ld below a row of P=%ld", fn, ldf, ldo, ldb, P);
-    DNMF_REQUIRE(ldf_t >= nf, DNMF_E_SHAPE, "%s: ldf_t=%ld below a row of nf=%d", fn, ldf_t, nf);
-    DNMF_REQUIRE(times || B <= nf, DNMF_E_SHAPE, "%s: B=%d frames but f has %d values and times is NULL", fn, B, nf);
-    DNMF_REQUIRE(out != frames || (!frame_ids && ldo == ldf), DNMF_E_SHAPE, "%s: in place (out == frames) needs frame_ids NULL and ldo == ldf", fn);
-    DNMF_REQUIRE(P < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld voxels (32-bit offsets)", fn, P);
-    SubtractRankArgs a;
-    a.frames = frames, a.b = b, a.f = f, a.ldf = ldf, a.ldo = ldo, a.ldb = ldb, a.ldf_t = ldf_t, a.P = P, a.ntiles = (P + BG_TILE - 1) / BG_TILE;
-    a.frame_ids = frame_ids, a.times = times, a.nf = nf, a.clamp = clamp != 0, a.R = R, a.out = out;
-    DNMF_REQUIRE(a.ntiles * B < (1L << 31), DNMF_E_UNSUPPORTED, "%s: %ld workgroups (split the call)", fn, a.ntiles * B);
-    hipLaunchKernelGGL(background_subtract_rank_kernel, dim3((unsigned)(a.ntiles * B)), dim3(BG_THREADS), 0, (hipStream_t)stream, a);
-    return check_launch(fn);
+    return dnmf::subtract<true>("dnmf_background_subtract_rank", frames, ldf, frame_ids, b, ldb, f, ldf_t, R, nf, times, P, B, out, ldo, clamp,
+                                stream);
 }
 
 }  // extern "C"

@@ -1995,6 +1995,16 @@ def dff_rows(rows_of, T, sz, window, stride=None, q=0.08, mode='dff', offset=0.0
     return movie[:T, :P], dict(knots=knots, centres=plan["centres"], n=n, starts=plan["starts"], ends=plan["ends"])
 
 
+def _pass_rows(frames, sub, fid, P):
+    """What every pass over the movie is given first: frames, ldf, sub, lds, frame_ids as the library takes them."""
+    return frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid)
+
+
+def _scratch(need, dev):
+    """A workspace of ``need`` bytes that nothing outlives the call (float64: 8-byte aligned, as the passes ask)."""
+    return torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+
+
 def background_state(sz, B, segment=0, device="cuda"):
     """An empty state for ``background_accum`` calls of up to ``B`` frames each; pass it with ``first=True``."""
     X, Y, Z = (int(s) for s in sz)
@@ -2013,15 +2023,13 @@ def background_dots(frames, b, sub=None, frame_ids=None):
     fid, B = _frame_rows("background_dots", frames, sub, frame_ids, P)
     dev = frames.device
     lib = _lib.load()
-    need = _need(lib, "dnmf_background_dots_workspace", P, B)
-    ws =torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    ws = _scratch(_need(lib, "dnmf_background_dots_workspace", P, B), dev)
     num = torch.empty((B,), dtype=torch.float64, device=dev)
     bb = torch.empty((1,), dtype=torch.float64, device=dev)
     f = torch.empty((B,), dtype=torch.float32, device=dev)
     with _timed("background_dots"):
-        rc = lib.dnmf_background_dots(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
-                                      b.data_ptr(), P, B, num.data_ptr(), bb.data_ptr(), f.data_ptr(), ws.data_ptr(), _nbytes(ws),
-                                      _stream())
+        rc = lib.dnmf_background_dots(*_pass_rows(frames, sub, fid, P), b.data_ptr(), P, B, num.data_ptr(), bb.data_ptr(), f.data_ptr(),
+                                      ws.data_ptr(), _nbytes(ws), _stream())
     _lib.check(rc, "dnmf_background_dots")
     return f, num, bb
 
@@ -2049,9 +2057,8 @@ def background_accum(frames, f, sz, sub=None, frame_ids=None, state=None, first=
     num = torch.empty((X, Y, Z), dtype=torch.float64, device=dev) if finish else None
     ff = torch.empty((1,), dtype=torch.float64, device=dev) if finish else None
     with _timed("background_accum"):
-        rc = lib.dnmf_background_accum(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
-                                       f.data_ptr(), P, B, 1 if first else 0, 1 if finish else 0, int(segment), state.data_ptr(),
-                                       _nbytes(state), _ptr(b), _ptr(num), _ptr(ff), _stream())
+        rc = lib.dnmf_background_accum(*_pass_rows(frames, sub, fid, P), f.data_ptr(), P, B, 1 if first else 0, 1 if finish else 0,
+                                       int(segment), state.data_ptr(), _nbytes(state), _ptr(b), _ptr(num), _ptr(ff), _stream())
     _lib.check(rc, "dnmf_background_accum")
     return ((b, num, ff) if finish else None), state
 
@@ -2119,14 +2126,12 @@ def _dots_rank(frames, b, f, sub, fid, B, P, R, inner):
     """The launch of ``background_dots_rank`` on checked arguments; ``f`` (R, B) rows are the start and receive the result."""
     dev = frames.device
     lib = _lib.load()
-    need = _need(lib, "dnmf_background_dots_rank_workspace", P, B, R)
-    ws =torch.empty(((need + 7) // 8,), dtype=torch.float64, device=dev)
+    ws = _scratch(_need(lib, "dnmf_background_dots_rank_workspace", P, B, R), dev)
     num = torch.empty((R, B), dtype=torch.float64, device=dev)
     q = torch.empty((R, R), dtype=torch.float64, device=dev)
     with _timed("background_dots_rank"):
-        rc = lib.dnmf_background_dots_rank(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
-                                           b.data_ptr(), _ld(b, P), R, P, B, int(inner), f.data_ptr(), _ld(f, B), num.data_ptr(),
-                                           q.data_ptr(), ws.data_ptr(), _nbytes(ws), _stream())
+        rc = lib.dnmf_background_dots_rank(*_pass_rows(frames, sub, fid, P), b.data_ptr(), _ld(b, P), R, P, B, int(inner), f.data_ptr(),
+                                           _ld(f, B), num.data_ptr(), q.data_ptr(), ws.data_ptr(), _nbytes(ws), _stream())
     _lib.check(rc, "dnmf_background_dots_rank")
     return f, num, q
 
@@ -2180,9 +2185,9 @@ def background_accum_rank(frames, f, sz, b=None, sub=None, frame_ids=None, state
         num = torch.empty((R, X, Y, Z), dtype=torch.float64, device=dev)
         w = torch.empty((R, R), dtype=torch.float64, device=dev)
     with _timed("background_accum_rank"):
-        rc = lib.dnmf_background_accum_rank(frames.data_ptr(), _ld(frames, P), _ptr(sub), 0 if sub is None else _ld(sub, P), _ptr(fid),
-                                            f.data_ptr(), _ld(f, B), R, P, B, 1 if first else 0, 1 if finish else 0, int(segment),
-                                            int(inner), state.data_ptr(), _nbytes(state), _ptr(out), P, _ptr(num), _ptr(w), _stream())
+        rc = lib.dnmf_background_accum_rank(*_pass_rows(frames, sub, fid, P), f.data_ptr(), _ld(f, B), R, P, B, 1 if first else 0,
+                                            1 if finish else 0, int(segment), int(inner), state.data_ptr(), _nbytes(state), _ptr(out), P,
+                                            _ptr(num), _ptr(w), _stream())
     _lib.check(rc, "dnmf_background_accum_rank")
     return ((out, num, w) if finish else None), state
 
@@ -2280,13 +2285,10 @@ def background_fit(frames, sz, iters, sub_fn=None, piece=None):
     T = frames.shape[0]
     if int(iters) < 1:
         raise ValueError(f"background_fit: iters={iters}")
-    if piece is None:
-        piece = max(1, (1 << 30) // (4 * P))
-    piece = max(1, min(int(piece), T))
+    cuts = _pieces(P, T, piece)
     dev = frames.device
     b = torch.ones((X, Y, Z), dtype=torch.float32, device=dev)
     f = torch.empty((T,), dtype=torch.float32, device=dev)
-    cuts = [(s, min(T, s + piece)) for s in range(0, T, piece)]
     state = None
     for _ in range(int(iters)):
         for s, e in cuts:

@@ -173,6 +173,35 @@ def test_accum_in_two_pieces_through_the_state(ops, sz, R):
         ops.background_accum_rank(Yd, fd, sz, state=ops.background_state_rank(sz, 2, R, segment=3), first=False, segment=3)
 
 
+ONE_KERNEL_CASES = [(sz, segment, with_sub, 1) for sz in [(9, 7, 3), (1023, 1, 1)] for segment in (0, 5) for with_sub in (False, True)]
+ONE_KERNEL_CASES.append(((1023, 1, 1), 5, True, 3))
+
+
+@pytest.mark.parametrize("sz,segment,with_sub,pieces", ONE_KERNEL_CASES)
+def test_rank_one_and_rank_r_run_one_accumulate_kernel(ops, sz, segment, with_sub, pieces):
+    """K19's accumulate pass is the R = 1 instantiation of K23's: with a signed trace in row 0 of f and zeros in row 1, ``num[0]`` of
+    the rank-2 call is ``num`` of the rank-1 call bit for bit -- the same subtraction, the same fma, the same segments added in the
+    same order.  37 frames from rows padded by 3 (frames) and 5 (sub) floats, P % 4 != 0; once in three pieces through the states."""
+    n, P = 37, sz[0] * sz[1] * sz[2]
+    rng = np.random.RandomState(P + segment)
+    Y = padded(rng.uniform(0.0, 2.0, (n, P)).astype(np.float32), 3)
+    M = padded(rng.uniform(0.0, 1.5, (n, P)).astype(np.float32), 5) if with_sub else None
+    f2 = torch.zeros((2, n), dtype=torch.float32, device="cuda")
+    f2[0] = dev(rng.uniform(-1.0, 1.0, n))
+    step = -(-n // pieces)
+    state_r = ops.background_state_rank(sz, step, 2, segment=segment)
+    state_1 = ops.background_state(sz, step, segment=segment)
+    for s in range(0, n, step):
+        e = min(n, s + step)
+        sub = None if M is None else M[s:e]
+        rank, state_r = ops.background_accum_rank(Y[s:e], f2[:, s:e], sz, sub=sub, state=state_r, first=s == 0, finish=e == n, segment=segment)
+        one, state_1 = ops.background_accum(Y[s:e], f2[0, s:e], sz, sub=sub, state=state_1, first=s == 0, finish=e == n, segment=segment)
+    torch.cuda.synchronize()
+    assert rank[1].shape == (2, *sz) and one[1].shape == tuple(sz)
+    assert bool(one[1].abs().max() > 0)
+    assert torch.equal(rank[1][0], one[1]), f"{sz} segment={segment} sub={with_sub} pieces={pieces}"
+
+
 # ---- zero diagonals -------------------------------------------------------------------------------------------------------------
 def test_zero_diagonals_give_zero(ops):
     sz, R = (41, 25, 1), 3
