@@ -634,7 +634,10 @@ class DeformableNMF:
         # trace problem on the solver's float64 state, before self.C is rounded to float32 (float64 CPU tensor; zero at the
         # NNLS solution); None after a solver='mu' call
         self.last_temporal_kkt = None
-        self.last_spatial_kkt = None   # (K,) float64 after a spatial_step(solver='hals'), None after a 'mu' step
+        # after update_footprints(solver='ar1'): g, penalty, baseline, s, colour, n_colours, n_pools, n_weightless, F of that
+        # call (see there); None after another solver
+        self.last_temporal_ar = None
+        self.last_spatial_kkt = None  # (K,) float64 after a spatial_step(solver='hals'), None after a 'mu' step
         # update_motion evaluates a whole epoch per launch when the caller's optimiser is a plain
         # torch.optim.Adam on [fp.beta] and the loader is a ResidentLoader (same result, see _motion_epoch)
         self.fused_motion = True
@@ -1611,8 +1614,22 @@ class DeformableNMF:
         return out
 
     def update_footprints(self, testloader, batch_size, sz, gamma_c=1e-2, gamma_a=1e0, iter_c=10, return_dense=None,
-                          live_spatial=False, iter_a=1, solver='mu', registered='nearest', spatial_solver='mu', grow=0):
+                          live_spatial=False, iter_a=1, solver='mu', registered='nearest', spatial_solver='mu', grow=0,
+                          ar_g=None, ar_penalty=0.0, ar_baseline=0.0):
         """Reference :163-179: ``iter_c`` multiplicative updates of ``self.C`` under the current warp.
+
+        ``solver='ar1'`` (extension, K32) puts the calcium dynamics into the fit: ``iter_c`` sweeps of block coordinate descent
+        over the neurons from the same ``self.C``, on the same Gram data (the dense path, frames sorted by time), each row
+        replaced by the AR(1), non-negative deconvolution of its own residual trace weighted by ``G_t[k,k]``
+        (``ops.ar1_temporal``; tests/ar1_restatement.py is the definition).  ``ar_g``: the decay per frame, a number or (K,);
+        None estimates it per neuron from the current traces with K21's estimator, and a trace that cannot be treated gets 0,
+        the plain non-negative step.  ``ar_penalty`` >= 0 and ``ar_baseline``: a number or (K,).  Needs ``gamma_c == 0`` (the
+        AR model replaces that term), frame times that are a run of consecutive integers, at most 6144 of them, one channel and
+        a model and loader that hold every frame.  ``self.last_temporal_ar`` then holds ``g``, ``penalty``, ``baseline``, ``s``
+        (K, T; the spikes, in time order), ``colour``, ``n_colours``, ``n_pools``, ``n_weightless`` and ``F``, the objective
+        before the call and after it (float64, the state before ``self.C`` is rounded to float32; it does not rise from traces
+        that meet the constraints, while a start below the baseline or falling faster than ``g`` is no admissible point and may
+        lie lower); ``last_temporal_kkt`` is None.
 
         ``solver='hals'`` (extension) runs ``iter_c`` sweeps of the exact solver K4h instead, from the same ``self.C``, on
         the same Gram data: cyclic coordinate descent on the non-negative least-squares problem the multiplicative update
@@ -1640,17 +1657,22 @@ class DeformableNMF:
         input of ``spatial_step`` and for the returned ``Y_i``; the default ``'nearest'`` is the reference's."""
         fp = self.fp
         K, P = fp.K, fp.P
-        _check_solver(solver)
+        _check_trace_solver(solver)
         _check_registered(registered, "update_footprints")
         _check_spatial_solver(spatial_solver, iter_a if spatial_solver == 'hals' else 1, grow, "update_footprints")
-        hals = solver == 'hals'
+        hals, ar1 = solver == 'hals', solver == 'ar1'
         if hals:
             _hals_refuse_shards(gamma_c, self.group)
+        if ar1:
+            self._ar1_refusals(testloader, gamma_c)
         with torch.no_grad():
-            frames, order = self._gather_frames(testloader)
+            frames, order = self._frames_in_time_order(testloader) if ar1 else self._gather_frames(testloader)
+            if ar1 and not bool((order[1:] - order[:-1] == 1).all()):
+                raise ValueError("update_footprints(solver='ar1'): the frame times must be a run of consecutive integers "
+                                 "(the AR(1) model links every frame to the one before)")
             T_loc = frames.shape[0]
             Csel = self.C.to(device, torch.float32)[:, order.long()].contiguous()
-            ly = self._lists_layout_for_fused_update(gamma_c)
+            ly = None if ar1 else self._lists_layout_for_fused_update(gamma_c)
             kkt = None
             if ly is not None:
                 # K3n leaves its slot tables in the workspace and K4 / K4h reads them there: no dense (T,K,K) in between
@@ -1662,11 +1684,15 @@ class DeformableNMF:
                     Cnew = ops.mu_temporal_slots(ly, self._ws_k3, fp.sz_list, Csel.clone(), iter_c)
             else:
                 G, r = self._gram_rhs(frames, order)
-                if hals:
+                if ar1:
+                    Cnew = self._ar1_temporal(G, r, Csel, iter_c, ar_g, ar_penalty, ar_baseline)
+                elif hals:
                     Cnew, kkt = _hals_temporal(G, r, Csel, gamma_c, iter_c, group=self.group, nbr=self._gram_nbr)
                 else:
                     Cnew = _mu_temporal(G, r, Csel, gamma_c, iter_c, group=self.group, nbr=self._gram_nbr)
             self.last_temporal_kkt = None if kkt is None else kkt.cpu()
+            if not ar1:
+                self.last_temporal_ar = None
             if hals and self.verbose:
                 print('Temporal KKT: max %.3e median %.3e' % (float(self.last_temporal_kkt.max()),
                                                               float(self.last_temporal_kkt.median())))
@@ -1709,6 +1735,38 @@ class DeformableNMF:
                     yi = ops.image_iwarp(frames, order[s:s + 256], fp.sz_list, fp.beta.detach(), order[s:s + 256])
                 Yi[..., s:s + 256] = yi.view(-1, X, Y_, Z).permute(1, 2, 3, 0).double().cpu().numpy()
             return A_t, Yi, Yv
+
+    def _ar1_refusals(self, loader, gamma_c):
+        """What ``update_footprints(solver='ar1')`` does not take: the smoothing term, several channels, a sharded time axis."""
+        who = "update_footprints(solver='ar1')"
+        if not (gamma_c is None or gamma_c == 0):
+            raise ValueError(f"{who}: gamma_c={gamma_c!r}: the AR(1) model replaces the smoothing term, pass gamma_c=0")
+        if self._nchan() != 1:
+            raise ValueError(f"{who}: one channel only (MultiChannelDNMF is not supported)")
+        if self.group is not None or getattr(loader, "T_total", None) != getattr(loader, "T", None):
+            raise ValueError(f"{who}: a model or loader sharded over ranks is not supported: the row step needs every frame of "
+                             "a neuron's trace in one place")
+
+    def _ar1_temporal(self, G, r, Csel, sweeps, ar_g, ar_penalty, ar_baseline):
+        """``sweeps`` sweeps of K32 from ``Csel`` (K, T) fp32, the frames in time order, on the dense Gram data -> the new traces;
+        fills ``self.last_temporal_ar``."""
+        if G.shape[0] > ops.AR1_MAX_FRAMES or G.shape[1] > ops.AR1_MAX_K:
+            raise ValueError(f"update_footprints(solver='ar1'): K={G.shape[1]}, T={G.shape[0]}: at most {ops.AR1_MAX_K} neurons "
+                             f"and {ops.AR1_MAX_FRAMES} frames")
+        if ar_g is None:
+            est = ops.deconvolve_traces(Csel, penalty=0.0, baseline=0.0)[2]
+            ar_g = torch.where(est["ok"], est["g"], torch.zeros_like(est["g"]))
+        f0 = _ar1_objective(G, r, Csel.double(), ar_g, ar_penalty, ar_baseline)
+        Cnew, s, info = ops.ar1_temporal(G, r, Csel.clone(), ar_g, ar_penalty, ar_baseline, sweeps=sweeps, nbr=self._gram_nbr)
+        f1 = _ar1_objective(G, r, info["state"], ar_g, ar_penalty, ar_baseline)
+        K = Cnew.shape[0]
+        per = lambda v: torch.as_tensor(v, dtype=torch.float64).detach().cpu().expand(K).clone()   # noqa: E731
+        self.last_temporal_ar = dict(g=per(ar_g), penalty=per(ar_penalty), baseline=per(ar_baseline), s=s, colour=info["colour"],
+                                     n_colours=info["n_colours"], n_pools=info["n_pools"].cpu(),
+                                     n_weightless=info["n_weightless"].cpu(), F=(f0, f1))
+        if self.verbose:
+            print('AR(1) temporal: F %.6e -> %.6e, %d colours' % (f0, f1, info["n_colours"]))
+        return Cnew
 
     def _lists_layout_for_fused_update(self, gamma_c):
         """The K3n layout when update_footprints can run as K3n + K4-on-slots (one channel, no neighbour term, the
@@ -2314,10 +2372,12 @@ class DeformableNMF:
 
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
-            background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, learn_colours=0, motion_order=None):
+            background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, learn_colours=0, ar_g=None, ar_penalty=0.0,
+            ar_baseline=0.0, motion_order=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
-        that call's (``'hals'``: the exact trace solver K4h); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
+        that call's (``'hals'``: the exact trace solver K4h; ``'ar1'``: the AR(1)-constrained update K32, with its ``ar_g``,
+        ``ar_penalty`` and ``ar_baseline`` and ``iter_c`` sweeps); ``motion_solver`` is ``update_motion``'s (``'gn'``: damped
         Gauss-Newton, ``optimizer`` may then be None) and ``motion_smooth`` the temporal prior's weight for the calls made
         here (``'gn'`` only; None: the model's ``motion_smooth``, 0 unless set; the attribute is put back afterwards);
         ``registered`` is ``update_footprints``' (``'linear'``: K17).  ``background=n > 0`` (K19): every sweep ends with
@@ -2348,6 +2408,10 @@ class DeformableNMF:
         if background:
             self._background_refusals(dataloader, "fit(background=)")
             self._background_refusals(testloader, "fit(background=)")
+        _check_trace_solver(solver)
+        if solver == 'ar1':
+            self._ar1_refusals(testloader, gamma_c)
+        ar = dict(ar_g=ar_g, ar_penalty=ar_penalty, ar_baseline=ar_baseline) if solver == 'ar1' else {}
         out = (None, None, None)
         self.motion_smooth, self.motion_order = motion_smooth, motion_order
         try:
@@ -2356,7 +2420,7 @@ class DeformableNMF:
                 self.update_motion(train, optimizer, gamma=gamma, epochs=epochs, solver=motion_solver)
                 out = self.update_footprints(test, batch_size, self.fp.sz_list, gamma_c=gamma_c, gamma_a=gamma_a,
                                              iter_c=iter_c, live_spatial=spatial, solver=solver, registered=registered,
-                                             spatial_solver=spatial_solver, grow=grow, iter_a=iter_a)
+                                             spatial_solver=spatial_solver, grow=grow, iter_a=iter_a, **ar)
                 if learn_colours:
                     self.update_colours(test, sweeps=int(learn_colours))
                 if background:
@@ -2425,6 +2489,8 @@ class MultiChannelDNMF(DeformableNMF):
         ``live_spatial`` all channels are registered by one K7 call (one search per lattice point, a gather per channel;
         ``registered='linear'``: one K17 call, one solve per lattice point) and ``fp.A`` takes ``iter_a`` steps of
         ``spatial_step``."""
+        if solver == 'ar1':
+            raise ValueError("MultiChannelDNMF.update_footprints: solver='ar1' is a single-channel solver")
         if return_dense:
             raise NotImplementedError("MultiChannelDNMF.update_footprints: return_dense")
         return super().update_footprints(testloader, batch_size, sz, gamma_c=gamma_c, gamma_a=gamma_a, iter_c=iter_c,
@@ -2581,6 +2647,30 @@ SOLVERS = ('mu', 'hals')
 def _check_solver(solver):
     if solver not in SOLVERS:
         raise ValueError(f"solver={solver!r}: expected one of {SOLVERS}")
+
+
+TRACE_SOLVERS = SOLVERS + ('ar1',)   # update_footprints and fit: 'ar1' (K32) is a trace solver of the model only
+
+
+def _check_trace_solver(solver):
+    if solver not in TRACE_SOLVERS:
+        raise ValueError(f"solver={solver!r}: expected one of {TRACE_SOLVERS}")
+
+
+def _ar1_objective(G, r, C, g, penalty, baseline, chunk=256):
+    """K32's objective F(C) = sum_t (1/2 c_t^T G_t c_t - r_t^T c_t) + sum_k penalty_k sum_t s_kt of a float64 state C (K, T) on
+    the Gram data G (T, K, K), r (T, K), in float64, ``chunk`` frames at a time (tests/ar1_restatement.py: ``objective``)."""
+    K, T = C.shape
+    per = lambda v: torch.as_tensor(v, dtype=torch.float64).to(C.device).expand(K)   # noqa: E731
+    f = torch.zeros((), dtype=torch.float64, device=C.device)
+    for t0 in range(0, T, chunk):
+        c = C[:, t0:t0 + chunk].t()                                   # (n, K)
+        Gc = torch.einsum("tkl,tl->tk", G[t0:t0 + chunk].double(), c)
+        f += (0.5 * (c * Gc).sum() - (r[t0:t0 + chunk].double() * c).sum())
+    x = C - per(baseline)[:, None]
+    s = x.clone()
+    s[:, 1:] -= per(g)[:, None] * x[:, :-1]
+    return float(f + (per(penalty) * s.sum(1)).sum())
 
 
 def _check_spatial_solver(solver, sweeps, grow, who):

@@ -125,6 +125,7 @@ SIGNATURES = {
                                _vp]),
     "dnmf_deconvolve_traces_workspace": (_sz, [_i, _i]),
     "dnmf_deconvolve_traces": (_i, [_vp, _l, _i, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _l, _vp, _vp, _sz, _vp]),
+    "dnmf_ar1_temporal_step": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _l, _vp, _vp]),
     "dnmf_high_pass_frames": (_i, [_vp, _l, _vp, _vp, _i, _vp, _i, _vp, _l, _vp]),
     "dnmf_component_stats_workspace": (_sz, [_vp, _vp, _i, _i, _i]),
     "dnmf_component_stats": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _vp, _i, _vp, _l, _vp, _l, _i, _i, _i, _vp, _sz,

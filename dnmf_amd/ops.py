@@ -2397,6 +2397,156 @@ def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, b
     return c, s, info
 
 
+AR1_MAX_FRAMES = 6144   # K32: a row's pool records (24 bytes a frame) live in LDS
+AR1_MAX_K = 4096
+
+
+def trace_colours(nbr_or_pattern):
+    """K32's colours of the overlap graph, on the host (numpy) -> ``(colour (K,) int32, n_colours)``: a greedy colouring, k
+    ascending, the smallest colour no neighbour holds.  ``nbr_or_pattern``: a neighbour table (K, NN) of integers (row k names the
+    columns of G that can be non-zero in row k; entries outside [0, K) are padding), or a (K, K) bool pattern; array or tensor.  k
+    and l are neighbours when either names the other.  Neurons of one colour share no Gram entry."""
+    a = nbr_or_pattern.detach().cpu().numpy() if isinstance(nbr_or_pattern, torch.Tensor) else np.asarray(nbr_or_pattern)
+    if a.ndim != 2:
+        raise ValueError(f"trace_colours: a neighbour table (K, NN) or a pattern (K, K), got {a.shape}")
+    K = a.shape[0]
+    if a.dtype == np.bool_:
+        if a.shape[1] != K:
+            raise ValueError(f"trace_colours: a pattern is (K, K), got {a.shape}")
+        adj = a.copy()
+    else:
+        adj = np.zeros((K, K), dtype=bool)
+        rows = np.repeat(np.arange(K), a.shape[1])
+        cols = a.reshape(-1).astype(np.int64)
+        ok = (cols >= 0) & (cols < K)
+        adj[rows[ok], cols[ok]] = True
+    adj |= adj.T
+    adj[np.arange(K), np.arange(K)] = False
+    colour = np.full(K, -1, dtype=np.int32)
+    for k in range(K):
+        taken = np.zeros(K + 1, dtype=bool)
+        held = colour[adj[k]]
+        taken[held[held >= 0]] = True
+        colour[k] = int(np.flatnonzero(~taken)[0])
+    return colour, (int(colour.max()) + 1 if K else 0)
+
+
+def _ar1_lists(nbr, K):
+    """A neighbour table as K32 walks it: row k's valid columns and k itself, ascending, each once, padded with -1 (A1 of
+    tests/ar1_restatement.py).  Device work only."""
+    n = nbr.to(torch.int64)
+    me = torch.arange(K, device=n.device, dtype=torch.int64)[:, None]
+    n = torch.cat([torch.where((n >= 0) & (n < K), n, torch.full_like(n, K)), me], 1).sort(1).values
+    dup = torch.zeros_like(n, dtype=torch.bool)
+    dup[:, 1:] = n[:, 1:] == n[:, :-1]
+    n = torch.where(dup, torch.full_like(n, K), n).sort(1).values
+    return torch.where(n < K, n, torch.full_like(n, -1)).to(torch.int32).contiguous()
+
+
+def _ar1_check(fn, G, r, C64, nbr):
+    if not (C64.is_cuda and C64.dtype == torch.float64 and C64.dim() == 2 and C64.stride(1) == 1):
+        raise ValueError(f"{fn}: the state must be float64 CUDA (K, T) with unit inner stride")
+    K, T = _hals_gram(fn, G, r, C64)
+    if T > AR1_MAX_FRAMES or K > AR1_MAX_K:
+        raise ValueError(f"{fn}: K={K}, T={T}: at most {AR1_MAX_K} neurons and {AR1_MAX_FRAMES} consecutive frames a call (a row's "
+                         "pool records live in LDS); a longer run is refused, not cut")
+    if nbr is not None and not (isinstance(nbr, torch.Tensor) and nbr.is_cuda and nbr.dim() == 2 and nbr.shape[0] == K
+                                and nbr.shape[1] >= 1 and not nbr.dtype.is_floating_point):
+        raise ValueError(f"{fn}: nbr must be an integer CUDA tensor of shape (K={K}, NN)")
+    return K, T
+
+
+def _ar1_params(fn, K, dev, g, penalty, baseline):
+    """``g``, ``penalty``, ``baseline`` (a number or K of them) as (K,) float64 tensors on ``dev``, checked on the host."""
+    out = []
+    for name, v in (("g", g), ("penalty", penalty), ("baseline", baseline)):
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.shape not in ((), (K,)):
+            raise ValueError(f"{fn}: {name} is a number or one value per neuron ({K}), got {a.shape}")
+        a = np.broadcast_to(a.astype(np.float64), (K,)).copy()
+        if name == "g" and not bool(((a >= 0.0) & (a < 1.0)).all()):
+            raise ValueError(f"{fn}: g must lie in [0, 1), got {a[~((a >= 0.0) & (a < 1.0))][:4]}")
+        if name == "penalty" and not bool((a >= 0.0).all() and np.isfinite(a).all()):
+            raise ValueError(f"{fn}: penalty must be finite and >= 0")
+        if name == "baseline" and not bool(np.isfinite(a).all()):
+            raise ValueError(f"{fn}: baseline must be finite")
+        out.append(torch.from_numpy(a).to(dev))
+    return out
+
+
+def _ar1_step(G, r, C64, ids, g, penalty, baseline, lists, s, counts):
+    K, T = C64.shape
+    with _timed("ar1_temporal_step"):
+        rc = _lib.load().dnmf_ar1_temporal_step(G.data_ptr(), r.data_ptr(), C64.data_ptr(), C64.stride(0), K, T, ids.data_ptr(),
+                                                ids.numel(), g.data_ptr(), penalty.data_ptr(), baseline.data_ptr(), _ptr(lists),
+                                                0 if lists is None else lists.shape[1], s.data_ptr(), s.stride(0), counts.data_ptr(),
+                                                _stream())
+    _lib.check(rc, "dnmf_ar1_temporal_step")
+
+
+def ar1_temporal_step(G, r, C64, ids, g, penalty, baseline, nbr=None, s=None):
+    """K32, one launch: the row step A3 of tests/ar1_restatement.py for the neurons ``ids`` (a list, array or tensor of distinct
+    indices) on the float64 state ``C64`` (K, T), in place.  G (T, K, K), r (T, K) fp32 Gram data of T consecutive frames in time
+    order.  The listed neurons must share no Gram entry (one colour of ``trace_colours``): their steps then do not see each other.
+    ``g`` in [0, 1), ``penalty`` >= 0, ``baseline``: a number or (K,) each.  ``nbr`` (K, NN) integers: the columns of G that can be
+    non-zero per row (``pack_footprints_lists``); None: all K.  ``s`` (K, T) float64 receives the spikes of the listed rows (a new
+    tensor of zeros without it) -> ``(C64, s, counts)``, counts (K, 2) int32: the pools and the frames without weight of the listed
+    rows (zero elsewhere)."""
+    fn = "ar1_temporal_step"
+    K, T = _ar1_check(fn, G, r, C64, nbr)
+    dev = C64.device
+    idh = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+    idh = idh.astype(np.int64).reshape(-1)
+    if idh.size < 1 or idh.min() < 0 or idh.max() >= K or np.unique(idh).size != idh.size:
+        raise ValueError(f"{fn}: ids are distinct neurons in [0, {K}), at least one")
+    g, penalty, baseline = _ar1_params(fn, K, dev, g, penalty, baseline)
+    if s is None:
+        s = torch.zeros((K, T), dtype=torch.float64, device=dev)
+    elif not (s.is_cuda and s.dtype == torch.float64 and tuple(s.shape) == (K, T) and s.stride(1) == 1):
+        raise ValueError(f"{fn}: s must be float64 CUDA ({K}, {T}) with unit inner stride")
+    counts = torch.zeros((K, 2), dtype=torch.int32, device=dev)
+    _ar1_step(G, r, C64, torch.from_numpy(idh.astype(np.int32)).to(dev), g, penalty, baseline,
+              None if nbr is None else _ar1_lists(nbr, K), s, counts)
+    return C64, s, counts
+
+
+def ar1_temporal(G, r, C, g, penalty=0.0, baseline=0.0, sweeps=1, nbr=None):
+    """K32, the AR(1)-constrained trace update of tests/ar1_restatement.py (``ar1_temporal``) on the GPU: ``sweeps`` sweeps of block
+    coordinate descent over the neurons on
+
+        F(C) = sum_t (1/2 c_t^T G_t c_t - r_t^T c_t) + sum_k penalty_k sum_t s_kt,   x = C[k] - baseline_k,  s_kt = x_t - g_k x_{t-1} >= 0
+
+    (s_k0 = x_0 >= 0).  A row step replaces neuron k's row by the deconvolution of its own residual trace, every frame weighted by
+    G_t[k,k]: the exact minimiser of F over that row (K21's pool-adjacent-violators with weights).  A sweep goes colour by colour of
+    ``trace_colours`` (of ``nbr``, else of the pattern of G, which costs one pass over G), one launch a colour.  G (T, K, K),
+    r (T, K) fp32: the Gram data of T consecutive frames in time order; C (K, T) fp32 CUDA with unit inner stride, any row stride,
+    updated in place: the float64 state is kept across the sweeps and rounded to fp32 once at the end.  ``g`` in [0, 1) (0: the
+    plain non-negative step for that neuron), ``penalty`` >= 0, ``baseline``: a number or (K,) each.  -> ``(C, s, info)``: s (K, T)
+    float64, the spikes; ``info``: ``colour`` (K,) int32 numpy and ``n_colours``, ``n_pools`` and ``n_weightless`` (K,) int32 of
+    every row's last step, and ``state``, the float64 (K, T) state before the rounding.  T <= 6144 and K <= 4096: anything larger
+    is refused.  Sums in a fixed order without floating-point atomics: the same input gives the same bits."""
+    fn = "ar1_temporal"
+    if not (isinstance(C, torch.Tensor) and C.dim() == 2):
+        raise ValueError(f"{fn}: C is a (K, T) tensor")
+    _rows(C, fn, "C")
+    if int(sweeps) != sweeps or sweeps < 0:
+        raise ValueError(f"{fn}: sweeps={sweeps!r}, a whole number >= 0")
+    state = C.double().contiguous()
+    K, T = _ar1_check(fn, G, r, state, nbr)
+    dev = C.device
+    g, penalty, baseline = _ar1_params(fn, K, dev, g, penalty, baseline)
+    colour, n_colours = trace_colours(nbr if nbr is not None else ((G != 0).any(0)).cpu().numpy())
+    groups = [torch.from_numpy(np.flatnonzero(colour == c).astype(np.int32)).to(dev) for c in range(n_colours)]
+    lists = None if nbr is None else _ar1_lists(nbr, K)
+    s = torch.zeros((K, T), dtype=torch.float64, device=dev)
+    counts = torch.zeros((K, 2), dtype=torch.int32, device=dev)
+    for _ in range(int(sweeps)):
+        for ids in groups:
+            _ar1_step(G, r, state, ids, g, penalty, baseline, lists, s, counts)
+    C.copy_(state)
+    return C, s, dict(colour=colour, n_colours=n_colours, n_pools=counts[:, 0], n_weightless=counts[:, 1], state=state)
+
+
 def histogram_match(a, b, nbins, nonneg=False, out=None, quantiles=False):
     """K25, the quantile-matched rescaling of tests/histmatch_restatement.py (``histogram_match``) on the GPU: per row the affine
     map ``a beta0 + beta1`` that carries the ``nbins`` quantiles of the moving trace ``a`` onto those of the reference trace ``b``

@@ -5,7 +5,12 @@ truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
                                         [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
-                                        [--clean-footprints] [--add N] [--dff W]
+                                        [--clean-footprints] [--add N] [--dff W] [--ar1 [SWEEPS] [--ar-penalty L]]
+
+``--ar1``: after the fit, read the traces out twice from the fitted ``C`` on the same Gram data, with SWEEPS (default 10) sweeps of
+the exact solver (``update_footprints(solver='hals')``, K4h) and of the AR(1)-constrained update (``solver='ar1'``, K32: the
+simulator's decay e^-0.3, penalty ``--ar-penalty``, the baseline taken from the 'hals' traces), and print the median correlation of
+the simulator's traces with ``C`` for each.  The fitted ``C`` is put back afterwards.
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -55,6 +60,8 @@ def main():
     ap.add_argument("--spatial-solver", choices=("mu", "hals"), default=None)
     ap.add_argument("--grow", type=int, default=0)
     ap.add_argument("--iter-a", type=int, default=5)
+    ap.add_argument("--ar1", type=int, nargs="?", const=10, default=0, metavar="SWEEPS")
+    ap.add_argument("--ar-penalty", type=float, default=0.0)
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -88,8 +95,25 @@ def main():
     corr = [np.corrcoef(C[k], dataset.traces[k])[0, 1] for k in range(K)]
     print("A_t", A_t.shape, "Y_i", Y_i.shape, "Y", Y.shape)
     print("trace correlation with ground truth: min %.3f  median %.3f" % (min(corr), float(np.median(corr))))
+    if a.ar1:
+        fitted, truth = dnmf.C.clone(), np.asarray(dataset.traces, np.float64)
+
+        def median_corr_of(**kw):
+            dnmf.C = fitted.clone()
+            dnmf.update_footprints(testloader, batch_size, sz, gamma_c=0, iter_c=a.ar1, return_dense=False, **kw)
+            X = dnmf.C.cpu().numpy().astype(np.float64)
+            return float(np.median([np.corrcoef(X[k], truth[k])[0, 1] for k in range(K)]))
+
+        hals = median_corr_of(solver='hals')
+        base = torch.quantile(dnmf.C.float(), 0.08, dim=1).double().cpu()     # the HALS traces' own 8th percentile, per neuron
+        ar1 = median_corr_of(solver='ar1', ar_g=float(np.exp(-0.3)), ar_penalty=a.ar_penalty, ar_baseline=base)
+        info = dnmf.last_temporal_ar
+        print("median trace correlation with ground truth after %d sweeps from the fitted C: 'hals' %.4f  'ar1' %.4f  (g = e^-0.3, "
+              "penalty %g, baseline = the 8th percentile of the 'hals' traces; %d colours, F %.6e -> %.6e)"
+              % (a.ar1, hals, ar1, a.ar_penalty, info["n_colours"], info["F"][0], info["F"][1]))
+        dnmf.C = fitted
     if a.clean is not None:
-        cleaned = dnmf.clean_traces(a.clean)[0].cpu().numpy().astype(np.float64)
+        cleaned =dnmf.clean_traces(a.clean)[0].cpu().numpy().astype(np.float64)
 
         def median_corr(X):
             cc = []

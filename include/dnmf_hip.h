@@ -939,6 +939,31 @@ int dnmf_deconvolve_traces(const float *traces, long ldt, int K, int T, const do
                            const double *noise, double baseline_percentile, float *c, float *s, long ldo, double *info, void *workspace,
                            size_t workspace_bytes, dnmf_stream_t stream);
 
+/* ---- K32: AR(1)-constrained trace update: one row step of block coordinate descent per listed neuron ------------------------------------
+ * tests/ar1_restatement.py (row_terms, row_step) is the definition, in float64.  On the Gram data G (T,K,K), r (T,K) of T consecutive
+ * frames in time order and the float64 state C (K rows of ldc >= T doubles), for every listed neuron k = ids[i], i < n_ids, row k is
+ * replaced by the exact minimiser over that row, the other rows fixed, of
+ *     F(C) = sum_t (1/2 c_t^T G_t c_t - r_t^T c_t) + sum_k penalty_k sum_t s_kt,   x = C[k,:] - baseline_k,
+ *     s_k0 = x_0 >= 0,  s_kt = x_t - g_k x_{t-1} >= 0:
+ * with w_t = G_t[k,k] and y_t = C[k,t] + (r_t[k] - sum_l G_t[k,l] C[l,t]) / w_t (the sum over the columns nbr lists for row k, in
+ * the order of the list, entries outside [0, K) skipped; without nbr over all columns ascending) the row becomes baseline_k plus the
+ * minimiser of 1/2 sum_t w_t (y_t - baseline_k - x_t)^2 + penalty_k sum_t s_t -- K21's problem with the weight w_t where K21 has 1,
+ * solved the same way (per-lane pool-adjacent-violators, a stitch, the expansion).  A frame whose w_t is not finite or <= 0, or
+ * whose y_t is not finite, carries no weight: the trace decays through it.  g_k = 0: the plain coordinate step
+ * max(0, y_t - baseline_k - penalty_k / w_t) + baseline_k, 0 + baseline_k on a frame without weight.
+ * The listed neurons must share no Gram entry (one colour of the overlap graph): their steps then do not see each other and one
+ * launch runs them side by side, one workgroup each.  A list must name row k itself where G_t[k,k] != 0.
+ *   g, penalty, baseline   K doubles each on the device: g in [0, 1), penalty >= 0, baseline finite (the caller's to ensure)
+ *   s                      K rows of lds >= T doubles: row k receives the spikes s_kt of the new row
+ *   counts                 K rows of 2 ints: row k receives the number of pools (T with g_k = 0) and of frames without weight
+ * Rows that are not listed are only read.  Float64 inside, sums in a fixed order without floating-point atomics: the same input
+ * gives the same bits.  One launch, no host synchronisation, nothing launched on an error.
+ * DNMF_E_NULL: any pointer but nbr NULL;  DNMF_E_SHAPE: K, T or n_ids < 1, n_ids > K, ldc or lds < T, NN < 1 with nbr;
+ * DNMF_E_UNSUPPORTED: T above 6144 (24 bytes of pool record a frame, in LDS) or K above 4096: refused, nothing is truncated. */
+int dnmf_ar1_temporal_step(const float *G, const float *r, double *C, long ldc, int K, int T, const int *ids, int n_ids,
+                           const double *g, const double *penalty, const double *baseline, const int *nbr, int NN, double *s,
+                           long lds, int *counts, dnmf_stream_t stream);
+
 /* ---- K22: spatial high-pass of every frame (the filter MotionCorrect's gSig_filt registers on) -----------------------------------------
  * For B frames of a volume (X, Y, Z) (rows of ldf >= P floats, voxel p = (x Y + y) Z + z; row frame_ids[b] of frames, or b) and an
  * (n, n) array of fp32 taps on the device, n odd, h = n / 2:
