@@ -617,6 +617,8 @@ class DeformableNMF:
 
     # footprint width the constructor builds ``fp`` with: the reference's 3; from_image sets its own on the instance first
     _shape_std = 3
+    # the volume-preserving prior of update_motion(solver='gn') is off unless an instance sets a weight (see __init__)
+    motion_jacobian = 0.0
 
     def __init__(self, sz, K, T, positions=None):
         self.SpatialModel = ExponentialFP
@@ -675,9 +677,14 @@ class DeformableNMF:
         # 'quadratic' (the default: all of them, the path as it was), 'graded' = the three in turn, or any sequence of
         # (order, iterations) stages.  An attribute for the same reason
         self.motion_order = 'quadratic'
+        # weight of the volume-preserving prior of update_motion(solver='gn') (K16j, see _update_motion_gn): mean squared error
+        # per squared unit of log det J of a frame's map at the corners and the centre of the volume; a map that folds there is
+        # never accepted.  0 = none, the path as it was.  An attribute for the same reason
+        self.motion_jacobian = 0.0
         self._stage_buf = None     # device copy of the frames a host loader served in its last pass
-        # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam -- and prior when smooth > 0 -- (CUDA
-        # tensors, (T,)), and stages when motion_order is set: a list, per stage a dict(order, sse0, sse); else None
+        # after update_motion(solver='gn'): per frame sse0, sse, accepted, rejected, lam -- and prior when smooth > 0, jac and
+        # min_det when motion_jacobian > 0 -- (CUDA tensors, (T,)), and stages when motion_order is set: a list, per stage a
+        # dict(order, sse0, sse); else None
         self.last_motion_gn = None
         self._reg_buf = None       # registered frames (K7 / K17) of the last update_footprints(live_spatial=True)
         self.last_registered_bad = None   # registered_video('linear'): lattice points the warp had no solution for
@@ -1989,6 +1996,9 @@ class DeformableNMF:
         same way) chooses the coefficients that are fitted: ``'translation'``, ``'affine'``, ``'quadratic'`` (the default: all),
         ``'graded'`` -- the three in turn with ``iters`` iterations each, which reaches a warp several voxels away where the full
         order diverges -- or a sequence of ``(order, iterations)`` stages (K16o, see ``_update_motion_gn``).
+        ``self.motion_jacobian`` > 0 (``solver='gn'`` only, checked the same way) adds the volume-preserving prior
+        ``motion_jacobian`` * mean_p (log det J(u_p))^2 over the corners and the centre of the volume to the mean squared error
+        (K16j, see ``_update_motion_gn``): a step to a map that folds at one of those points is never accepted.
 
         A ``ResidentLoader`` hands over rows that already live on the GPU.  Any other loader (the stock
         ``torch.utils.data.DataLoader`` of demo.py:33-35) is iterated once per epoch by a background thread while this
@@ -1997,8 +2007,9 @@ class DeformableNMF:
         _check_motion_solver(solver, "update_motion")
         smooth = _check_motion_smooth(self.motion_smooth, solver, "update_motion")
         order = _check_motion_order(self.motion_order, solver, "update_motion")
+        jacobian = _check_motion_jacobian(self.motion_jacobian, solver, "update_motion")
         if solver == 'gn':
-            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma, smooth, order)
+            return self._update_motion_gn(dataloader, epochs if iters is None else iters, damping, gamma, smooth, order, jacobian)
         fp = self.fp
         beta = fp.beta
         # reconstruction images of all frames (C is constant inside this call): built when first needed -- the fused
@@ -2059,7 +2070,7 @@ class DeformableNMF:
                     print('Recon: ' + str(out["loss"][0]))
                     print('Reg: ' + str(out["reg"]))
 
-    def _update_motion_gn(self, dataloader, iters, damping, gamma=0, smooth=0.0, order='quadratic'):
+    def _update_motion_gn(self, dataloader, iters, damping, gamma=0, smooth=0.0, order='quadratic', jacobian=0.0):
         """``update_motion(solver='gn')``: Levenberg-Marquardt on the 30 (12 at Z = 1) coefficients of every frame.
 
         The loss is a sum over frames and frame t only sees ``beta[:, :, t]``, so the frames are independent small dense
@@ -2114,7 +2125,43 @@ class DeformableNMF:
         A chunk's images are still built once.  ``last_motion_gn`` gains ``stages``: a list with, per stage, dict(order, sse0,
         sse), per frame as above; the other keys describe the call: ``sse0`` from the first stage, ``sse`` / ``lam`` / ``prior``
         from the last, the counts summed.  ``'quadratic'``, the default, is the loop above, launch for launch, and its
-        ``last_motion_gn`` has the keys it had: no ``stages``."""
+        ``last_motion_gn`` has the keys it had: no ``stages``.
+
+        ``jacobian`` (the model's ``motion_jacobian``) > 0 (K16j, ``dnmf_lm_step_jac``; tests/gn_jac_restatement.py is the
+        definition): the paper's regulariser made to act.  With Jx the Jacobian of a frame's map in voxel coordinates -- the TRUE
+        one, not the reference's ``log_det_jac`` with its xz / yz rows swapped -- at the sample points u_p
+        (``ops.warp_jacobian_points``: the corners and the centre of the volume, 9 points, 5 at Z = 1), rho_p = log det Jx(u_p)
+        (+inf where det Jx <= 0) and m_j = ``jacobian`` n, the objective becomes
+            F(beta) = sum_t [sse_t + m_j mean_p rho_p^2],
+        F / n = mse + ``jacobian`` * mean_p rho_p^2.  The step adds the term's exact Gauss-Newton Hessian and gradient on the
+        unknowns of the stage's order; the accept test compares sse + temporal prior + this term, so a trial that folds at a
+        sample point is never accepted after a frame's first call, and a start that folds is left at the first admissible
+        trial.  det Jx is a cubic polynomial in u: nothing is claimed between the sample points.  No extra launches, no colours
+        of its own; ``last_motion_gn`` gains ``jac`` (the term of the result) and ``min_det`` (its smallest det Jx over the
+        sample points) per frame, NaN for frames not served.  0, the default, makes the calls and keeps the keys it had.
+        * WHAT IT BUYS.  Float64 definition, K16o's problems (48 x 40 x Z, K = 6, T = 4, shift L), 16 full-order iterations from
+          the identity, field error (voxels) / smallest det Jx, per weight 0 | 1e-4 | 1e-3 | 1e-2:
+              Z 2 L 3 seed 0   1e-5 / 0.985  | 0.015 / 0.987  | 0.048 / 0.990 | 0.043 / 0.992
+              Z 2 L 3 seed 1   19.1 / -5.7   | 0.047 / 0.983  | 0.031 / 0.984 | 0.057 / 0.986
+              Z 2 L 3 seed 2   20.3 / -7.8   | 0.076 / 0.966  | 0.120 / 0.967 | 0.110 / 0.974
+              Z 2 L 6 seed 0   81.9 / -31    | 8.8 / 0.076    | 7.0 / 0.81    | 16.1 / 0.79
+              Z 2 L 6 seed 1   612 / -1430   | 20.6 / 0.060   | 41.8 / 0.010  | 48.9 / 0.55
+              Z 2 L 6 seed 2   1390 / -121   | 16.2 / 0.14    | 0.069 / 0.966 | 0.26 / 0.90
+              Z 1 L 3 seed 0   7e-6 / 0.980  | 0.0018 / 0.980 | 0.017 / 0.980 | 0.12 / 0.979
+              Z 1 L 3 seed 1   2e-5 / 0.985  | 0.0028 / 0.985 | 0.023 / 0.985 | 0.10 / 0.988
+              Z 1 L 3 seed 2   8e-6 / 0.974  | 0.0036 / 0.974 | 0.031 / 0.976 | 0.15 / 0.981
+              Z 1 L 6 seed 0   73.4 / -0.26  | 52.6 / 0.037   | 68.1 / 0.44   | 38.8 / 0.74
+              Z 1 L 6 seed 1   52.7 / 0.15   | 42.0 / 0.19    | 48.6 / 0.60   | 44.8 / 1.00
+              Z 1 L 6 seed 2   8e-6 / 0.974  | 0.0099 / 0.974 | 0.069 / 0.975 | 0.21 / 0.980
+          (a fit that leaves the basin is chaotic: its figure changes with the BLAS's rounding).  No cell with the prior ends
+          folded; it rescues the two-slice fits 3 voxels away and one 6-voxel cell; ``'graded'`` stays the advice for far starts.
+        * BIAS.  It pulls det Jx to 1.  Planted in-plane dilation by 1.03 on tests/gn_restatement.py's warps, 3 frames, 8
+          iterations from the identity, largest distance (voxels) between fitted and true warp per frame:
+              24x20x1  0     0       0       0             24x20x2  0     0       0       0
+              24x20x1  1e-4  0.0004  0.0006  0.0011        24x20x2  1e-4  0.019   0.044   0.036
+              24x20x1  1e-3  0.0042  0.0057  0.0102        24x20x2  1e-3  0.051   0.082   0.140
+              24x20x1  1e-2  0.041   0.047   0.070         24x20x2  1e-2  0.065   0.137   0.164
+          (0: below 5e-5).  Two slices say little about d q_z / d z, so there the prior moves that entry to buy det = 1."""
         fp = self.fp
         iters = int(iters)
         if iters < 0:
@@ -2142,6 +2189,11 @@ class DeformableNMF:
         if smooth:
             stats["prior"] = torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)
             beta_ref = beta.clone()      # every frame's accepted coefficients: the neighbours a step reads
+        step_kw = {}
+        if jacobian:                     # the default keeps the keys and the call it had
+            stats["jac"] = torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)
+            stats["min_det"] = torch.full((fp.T,), float('nan'), dtype=torch.float64, device=device)
+            step_kw["jacobian"] = jacobian
         bufs = {}
 
         def fit(frames, fid, times, host_times):
@@ -2178,7 +2230,7 @@ class DeformableNMF:
                                 bufs["ws"] = eqs["workspace"]
                             w[1] = eqs
                             ops.lm_step(state, eqs, fp.sz_list, beta, ct, lam0=damping, accept_only=it == stage_iters,
-                                        smooth=smooth, n_residuals=row, beta_ref=beta_ref, order=stage_order)
+                                        smooth=smooth, n_residuals=row, beta_ref=beta_ref, order=stage_order, **step_kw)
                     for (_, _, ct), (state, _) in zip(colours, work):
                         idx = ct.long()
                         if "stages" in stats:
@@ -2190,6 +2242,8 @@ class DeformableNMF:
                         stats["rejected"][idx] += state["counts"][:, 1]
                         if smooth:
                             stats["prior"][idx] = state["prior"]
+                        if jacobian:
+                            stats["jac"][idx], stats["min_det"][idx] = state["jac"], state["min_det"]
                         if self.verbose:
                             print(f"GN frames {int(ct[0])}.. ({stage_order}): sse {float(state['sse0'].sum()):.6g} -> "
                                   f"{float(state['sse'].sum()):.6g}")
@@ -2373,7 +2427,7 @@ class DeformableNMF:
     def fit(self, dataloader, testloader, optimizer, batch_size, outer=5, gamma=1, epochs=10, gamma_c=0, iter_c=50,
             spatial=False, gamma_a=1e0, solver='mu', motion_solver='adam', registered='nearest', motion_smooth=None,
             background=0, background_rank=1, spatial_solver='mu', grow=0, iter_a=1, learn_colours=0, ar_g=None, ar_penalty=0.0,
-            ar_baseline=0.0, motion_order=None):
+            ar_baseline=0.0, motion_jacobian=None, motion_order=None):
         """Convenience wrapper of the loop ``demo.py:44-46`` writes out (not part of the reference).  ``spatial=True``
         also updates the footprints after every temporal update (``update_footprints(live_spatial=True)``); ``solver`` is
         that call's (``'hals'``: the exact trace solver K4h; ``'ar1'``: the AR(1)-constrained update K32, with its ``ar_g``,
@@ -2386,13 +2440,15 @@ class DeformableNMF:
         because a background fitted before the model explains anything would take the neurons' mean light with it.  0: no
         background term, the path of a call without the argument.  ``background_rank=R``, 2 .. 8 (K23): those updates fit R
         images with R time courses (``update_background_rank``); 1: the rank-1 term.  ``motion_order`` is the model's
-        ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``).
+        ``motion_order`` for the calls made here, as ``motion_smooth`` is (``'gn'`` only; K16o, see ``update_motion``), and
+        ``motion_jacobian`` the model's ``motion_jacobian`` in the same way (``'gn'`` only; K16j).
         ``spatial_solver``, ``grow`` and ``iter_a`` are ``update_footprints``' (``'hals'``: the exact footprint solver K6h,
         ``iter_a`` sweeps on supports grown by ``grow`` voxels; with ``verbose`` its max and median KKT are printed).
         ``learn_colours=n > 0`` (K29, ``MultiChannelDNMF`` only): every sweep ends with ``update_colours(testloader, sweeps=n)``
         on the frames the sweep's other steps read; 0: the colours stay, the path of a call without the argument."""
         _check_motion_solver(motion_solver, "fit")
-        kept, kept_order = self.motion_smooth, self.motion_order
+        kept, kept_order, kept_jacobian = self.motion_smooth, self.motion_order, self.motion_jacobian
+        motion_jacobian = _check_motion_jacobian(kept_jacobian if motion_jacobian is None else motion_jacobian, motion_solver, "fit")
         motion_smooth = _check_motion_smooth(kept if motion_smooth is None else motion_smooth, motion_solver, "fit")
         motion_order = kept_order if motion_order is None else motion_order
         _check_motion_order(motion_order, motion_solver, "fit")
@@ -2413,7 +2469,7 @@ class DeformableNMF:
             self._ar1_refusals(testloader, gamma_c)
         ar = dict(ar_g=ar_g, ar_penalty=ar_penalty, ar_baseline=ar_baseline) if solver == 'ar1' else {}
         out = (None, None, None)
-        self.motion_smooth, self.motion_order = motion_smooth, motion_order
+        self.motion_smooth, self.motion_order, self.motion_jacobian = motion_smooth, motion_order, motion_jacobian
         try:
             train, test = dataloader, testloader
             for sweep in range(outer):
@@ -2441,7 +2497,7 @@ class DeformableNMF:
                         else:
                             train = self.background_loader(dataloader)
         finally:
-            self.motion_smooth, self.motion_order = kept, kept_order
+            self.motion_smooth, self.motion_order, self.motion_jacobian = kept, kept_order, kept_jacobian
         return out
 
 
@@ -2706,6 +2762,17 @@ def _check_motion_smooth(smooth, solver, who):
         raise ValueError(f"{who}: motion_smooth={smooth} is supported by the motion solver 'gn' only (got {solver!r}); "
                          "Adam steps on the reference's loss, which has no temporal term")
     return smooth
+
+
+def _check_motion_jacobian(jacobian, solver, who):
+    """The volume-preserving prior's weight as a float: finite, >= 0, and non-zero only with the Gauss-Newton solver."""
+    jacobian = float(jacobian)
+    if not 0.0 <= jacobian < float('inf'):
+        raise ValueError(f"{who}: motion_jacobian={jacobian}: the volume-preserving prior's weight must be finite and >= 0")
+    if jacobian and solver != 'gn':
+        raise ValueError(f"{who}: motion_jacobian={jacobian} is supported by the motion solver 'gn' only (got {solver!r}); "
+                         "Adam steps on the reference's loss, whose reg term carries no gradient")
+    return jacobian
 
 
 MOTION_GRADED = ('translation', 'affine', 'quadratic')

@@ -107,6 +107,8 @@ SIGNATURES = {
                                  _d, _i, _vp, _d, _vp, _vp]),
     "dnmf_lm_step_order": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d, _d,
                                 _d, _i, _vp, _d, _vp, _vp]),
+    "dnmf_lm_step_jac": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _d, _d,
+                              _d, _d, _i, _vp, _d, _vp, _d, _vp, _vp, _vp]),
     "dnmf_warp_pullback": (_i, [_vp, _l, _l, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _l, _l, _i, C.c_float, _vp, _vp, _vp]),
     "dnmf_summary_images_workspace": (_sz, [_vp, _i, _i, _i]),
     "dnmf_summary_images": (_i, [_vp, _l, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),

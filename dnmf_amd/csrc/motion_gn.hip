@@ -607,6 +607,220 @@ __global__ __launch_bounds__(64) void lm_step_order_kernel(const double *__restr
     if (j < 30 && GN_EX[a] + GN_EY[a] + GN_EZ[a] > order) beta[(long)j * T + t] = beta_acc[b * 30 + j];
 }
 
+// K16j: the volume-preserving prior.  The map of a frame in centred coordinates is q_d(u) = sum_a basis_a(u) theta[a,d]; its
+// Jacobian in voxel coordinates is Jx[d][e] = (sum_a d basis_a / d u_e theta[a,d]) / h_e with h_e = (S_e - 1) / 2, the TRUE
+// Jacobian of the model's map (csrc/tracks.hip's, not the reference's log_det_jac with its xz / yz rows swapped).  At the sample
+// points -- the corners u in {-1, +1}^n, first axis slowest, then the centre u = 0: 9 points, 5 at Z == 1 -- the residual is
+// rho_p = log det Jx(u_p): 0 for the identity, a rigid motion or a shear, +inf where det Jx <= 0 or is not finite.
+struct JacHalf {
+    double h[3];    // (S_e - 1) / 2; 1 on the z axis at Z == 1 (it is not used there)
+};
+
+__device__ __forceinline__ int lm_jac_points(int nfull) { return nfull == 30 ? 9 : 5; }
+
+// sample point p of lm_jac_points(nfull)
+__device__ __forceinline__ void lm_jac_point(int nfull, int p, double (&u)[3]) {
+    const int nc = nfull == 30 ? 8 : 4;
+    u[0] = u[1] = u[2] = 0.0;
+    if (p < nc) {
+        if (nfull == 30) u[0] = p & 4 ? 1.0 : -1.0, u[1] = p & 2 ? 1.0 : -1.0, u[2] = p & 1 ? 1.0 : -1.0;
+        else u[0] = p & 2 ? 1.0 : -1.0, u[1] = p & 1 ? 1.0 : -1.0;
+    }
+}
+
+// d basis_a / d u_e at u, basis = [1, u0, u1, u2, u0^2, u1^2, u2^2, u0 u1, u0 u2, u1 u2]
+__device__ __forceinline__ double lm_jac_dbasis(int a, int e, const double (&u)[3]) {
+    const double u0 = u[0], u1 = u[1], u2 = u[2];
+    if (e == 0) return a == 1 ? 1.0 : a == 4 ? 2.0 * u0 : a == 7 ? u1 : a == 8 ? u2 : 0.0;
+    if (e == 1) return a == 2 ? 1.0 : a == 5 ? 2.0 * u1 : a == 7 ? u0 : a == 9 ? u2 : 0.0;
+    return a == 3 ? 1.0 : a == 6 ? 2.0 * u2 : a == 8 ? u0 : a == 9 ? u1 : 0.0;
+}
+
+// lm_step_order_kernel with the prior J = mj / NP sum_p rho_p^2 on top (mj == 0: without it): the accept test compares
+// sse + temporal prior + J on both sides, so a trial that folds at a sample point (J = +inf) is never accepted after the first call
+// and an accepted point that folds is beaten by any admissible trial.  The step adds the exact Gauss-Newton terms
+// mj / NP sum_p jrho_p jrho_p^T to H' and mj / NP sum_p rho_p jrho_p to g' at the point kept, jrho_p[a*3+d] = sum_e (Jx^-1)[e][d]
+// (d basis_a / d u_e)(u_p) / h_e on the selected unknowns (the value of rho sees the whole map); a point whose rho is not finite
+// adds nothing.  The accepted column's rho is recomputed from beta_acc in every call: no state beyond lm_step_order_kernel's.
+// The dense H' and g' are staged in LDS and the damped solve is lm_step_kernel's instantiation on them.  Sums over p run in
+// the order of p in every thread: no atomics, the same bits on every run.  jac (B): J of the point kept; min_det (B): its smallest
+// det Jx over the sample points.
+__global__ __launch_bounds__(64) void lm_step_jac_kernel(const double *__restrict__ H, const double *__restrict__ g,
+                                                         const double *__restrict__ sse, int nfull, int order,
+                                                         const double *__restrict__ M, const double *__restrict__ Minv,
+                                                         float *__restrict__ beta, int T, const int *__restrict__ times,
+                                                         double *__restrict__ Hacc, double *__restrict__ gacc,
+                                                         double *__restrict__ sse_acc, double *__restrict__ sse0,
+                                                         double *__restrict__ lam, float *__restrict__ beta_acc,
+                                                         int *__restrict__ counts, double nu, double lam0, double lam_min,
+                                                         double lam_max, int accept_only, float *beta_ref, double m,
+                                                         double *__restrict__ prior, double mj, JacHalf half,
+                                                         double *__restrict__ jac, double *__restrict__ min_det) {
+    __shared__ double thn[2][30];       // theta of the neighbours in use
+    __shared__ double sq[2][30];        // squared distances to them: [0] of the trial, [1] of the accepted point
+    __shared__ double thf[2][30];       // theta on every active unknown: [0] the trial, [1] the accepted point
+    __shared__ double rho[2][9], dets[2][9], inv[2][9][9];
+    __shared__ double jr[9][30];        // jrho_p of the point kept
+    __shared__ double Hs[900], gs[30];  // H' and g'
+    const int b = blockIdx.x, j = threadIdx.x, t = times[b];
+    const int a = j / 3, d = j - a * 3;
+    const int nact = lm_order_count(nfull, order);
+    const int npts = lm_jac_points(nfull);
+    auto selected = [&](int i) {        // parameter index i is an unknown of the order
+        const int ai = i / 3, di = i - ai * 3;
+        return GN_EX[ai] + GN_EY[ai] + GN_EZ[ai] <= order && (nfull == 30 || (GN_EZ[ai] == 0 && di < 2));
+    };
+    const bool active = j < 30 && (nfull == 30 || (GN_EZ[a] == 0 && d < 2));
+    const bool unknown = j < 30 && selected(j);
+    const bool first = counts[b * 3 + 2] == 0;
+    // theta of a column held with stride ld between its 30 entries, on every active unknown
+    auto theta = [&](const float *col, long ld) {
+        double v = 0.0;
+        if (active)
+            for (int c = 0; c < 10; ++c) v = fma(Minv[a * 10 + c], (double)col[(long)(c * 3 + d) * ld], v);
+        return v;
+    };
+    int nn = 0;                         // block-uniform
+    double p_trial = 0.0, p_acc = 0.0;
+    const double tf_trial = theta(beta + t, T);
+    const double tf_old = first ? 0.0 : theta(beta_acc + b * 30, 1);
+    const double th_trial = unknown ? tf_trial : 0.0, th_old = unknown ? tf_old : 0.0;
+    if (j < 30) thf[0][j] = tf_trial, thf[1][j] = tf_old;
+    if (m != 0.0) {
+        for (int side = -1; side <= 1; side += 2) {
+            const int s = t + side;
+            if (s < 0 || s >= T) continue;
+            const float v = j < 30 ? beta_ref[(long)j * T + s] : 0.0f;
+            if (!__all(v - v == 0.0f)) continue;    // a column with a NaN or an inf is no neighbour
+            if (j < 30) thn[nn][j] = unknown ? theta(beta_ref + s, T) : 0.0;
+            ++nn;
+        }
+    }
+    __syncthreads();
+    if (m != 0.0 && j < 30) {
+        double qt = 0.0, qa = 0.0;
+        for (int i = 0; i < nn; ++i) {
+            const double dt = th_trial - thn[i][j], da = th_old - thn[i][j];
+            qt += dt * dt, qa += da * da;
+        }
+        sq[0][j] = qt, sq[1][j] = qa;
+    }
+    // lanes 0 .. npts-1: the trial at point p; lanes 16 .. 16+npts-1: the accepted point
+    {
+        const int col = j >> 4, p = j & 15;
+        if (col < 2 && p < npts) {
+            double u[3], J[3][3];
+            lm_jac_point(nfull, p, u);
+#pragma unroll
+            for (int dd = 0; dd < 3; ++dd)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    double v = 0.0;
+#pragma unroll
+                    for (int aa = 1; aa < 10; ++aa) v += lm_jac_dbasis(aa, e, u) * thf[col][aa * 3 + dd];
+                    J[dd][e] = v / half.h[e];
+                }
+            if (nfull != 30) J[2][2] = 1.0;     // x and y only: the 2 x 2 determinant and inverse
+            const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1], c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2],
+                         c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
+            const double det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
+            const bool ok = det > 0.0 && det - det == 0.0;
+            const double r = 1.0 / det;
+            double *iv = inv[col][p];           // Jx^-1 [e][d] at e*3+d: the adjugate over the determinant
+            iv[0] = c00 * r, iv[3] = c01 * r, iv[6] = c02 * r;
+            iv[1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * r;
+            iv[4] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * r;
+            iv[7] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) * r;
+            iv[2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) * r;
+            iv[5] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * r;
+            iv[8] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) * r;
+            dets[col][p] = det;
+            rho[col][p] = ok ? log(det) : __builtin_inf();
+        }
+    }
+    __syncthreads();
+    if (m != 0.0 && nn > 0) {           // every thread adds the 30 terms in the same order: one value in the whole wave
+        for (int i = 0; i < 30; ++i) p_trial += sq[0][i], p_acc += sq[1][i];
+        p_trial *= m, p_acc *= m;
+    }
+    const double wj = mj / (double)npts;
+    double j_trial = 0.0, j_acc = 0.0;
+    if (mj != 0.0) {
+        for (int p = 0; p < npts; ++p) j_trial += rho[0][p] * rho[0][p], j_acc += rho[1][p] * rho[1][p];
+        j_trial *= wj, j_acc *= wj;
+    }
+    const double st = sse[b], sa = sse_acc[b];
+    const double ft = (st + p_trial) + j_trial, fa = (sa + p_acc) + j_acc;
+    const bool accept = first || (ft - ft == 0.0 && ft < fa);   // finite and below
+    const int kept = accept ? 0 : 1;
+    double l = first ? lam0 : lam[b];
+    if (!first) l = accept ? fmax(l / nu, lam_min) : fmin(l * nu, lam_max);
+    double dmin = dets[kept][0];
+    for (int p = 1; p < npts; ++p) dmin = dets[kept][p] < dmin || dets[kept][p] != dets[kept][p] ? dets[kept][p] : dmin;
+    __syncthreads();   // every thread has read the state before it changes
+    if (accept && j < 30) {
+        const float bt = beta[(long)j * T + t];
+        beta_acc[b * 30 + j] = bt;
+        if (m != 0.0) beta_ref[(long)j * T + t] = bt;
+    }
+    if (j < 30) {       // the rows jrho_p of the point kept and g'
+        double gj = 0.0;
+        for (int p = 0; p < npts; ++p) {
+            const double r = rho[kept][p];
+            double v = 0.0;
+            if (unknown && r - r == 0.0) {
+                double u[3];
+                lm_jac_point(nfull, p, u);
+#pragma unroll
+                for (int e = 0; e < 3; ++e) v += inv[kept][p][e * 3 + d] * (lm_jac_dbasis(a, e, u) / half.h[e]);
+                gj += r * v;
+            }
+            jr[p][j] = v;
+        }
+        double gv = accept ? g[b * 30 + j] : gacc[b * 30 + j];
+        if (accept) gacc[b * 30 + j] = gv;
+        if (m != 0.0) {
+            const double th = accept ? th_trial : th_old;
+            double ga = 0.0;
+            for (int i = 0; i < nn; ++i) ga += th - thn[i][j];
+            gv += m * ga;
+        }
+        if (mj != 0.0) gv += wj * gj;
+        gs[j] = gv;
+    }
+    __syncthreads();
+    const double hadd = m * (double)nn;
+    for (int i = j; i < 900; i += 64) {
+        const int r = i / 30, c = i - r * 30;
+        double v = accept ? H[(long)b * 900 + i] : Hacc[(long)b * 900 + i];
+        if (accept) Hacc[(long)b * 900 + i] = v;
+        if (m != 0.0 && r == c && selected(r)) v += hadd;
+        if (mj != 0.0) {
+            double s = 0.0;
+            for (int p = 0; p < npts; ++p) s += jr[p][r] * jr[p][c];
+            v += wj * s;
+        }
+        Hs[i] = v;
+    }
+    if (j == 0) {
+        lam[b] = l;
+        if (m != 0.0) prior[b] = accept ? p_trial : p_acc;
+        jac[b] = accept ? j_trial : j_acc;
+        min_det[b] = dmin;
+        if (accept) sse_acc[b] = st;
+        if (first) sse0[b] = st, counts[b * 3 + 2] = 1;
+        else counts[b * 3 + (accept ? 0 : 1)] += 1;
+    }
+    __syncthreads();
+    if (accept_only) {
+        if (j < 30) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+        return;
+    }
+    lm_damped_solve<false>(Hs, gs, l, nact, nfull, M, beta_acc + b * 30, beta, T, t, 0.0, nullptr);
+    // thread j wrote entry j a moment ago: its own store, in program order
+    if (j < 30 && GN_EX[a] + GN_EY[a] + GN_EZ[a] > order) beta[(long)j * T + t] = beta_acc[b * 30 + j];
+}
+
 }  // namespace dnmf
 
 extern "C" {
@@ -716,6 +930,34 @@ int dnmf_lm_step_order(const double *H, const double *g, const double *sse, int 
                        M, Minv, beta, T, times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max,
                        accept_only, beta_ref, m, prior);
     return check_launch("dnmf_lm_step_order");
+}
+
+int dnmf_lm_step_jac(const double *H, const double *g, const double *sse, int B, int X, int Y, int Z, int order, const double *M,
+                     const double *Minv, float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc,
+                     double *sse0, double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min,
+                     double lam_max, int accept_only, float *beta_ref, double m, double *prior, double mj, double *jac,
+                     double *min_det, dnmf_stream_t stream) {
+    using namespace dnmf;
+    DNMF_REQUIRE(H && g && sse && M && Minv && beta && times && H_acc && g_acc && sse_acc && sse0 && lam && beta_acc && counts &&
+                     jac && min_det,
+                 DNMF_E_NULL, "dnmf_lm_step_jac: NULL buffer");
+    DNMF_REQUIRE(B > 0 && X > 1 && Y > 1 && Z > 0 && T > 0, DNMF_E_SHAPE,
+                 "dnmf_lm_step_jac: B=%d X=%d Y=%d Z=%d T=%d (the x and y axes need two voxels at least)", B, X, Y, Z, T);
+    DNMF_REQUIRE(order >= 0 && order <= 2, DNMF_E_SHAPE, "dnmf_lm_step_jac: order=%d (0 translation, 1 affine, 2 quadratic)", order);
+    DNMF_REQUIRE(nu > 1.0 && lam0 > 0.0 && lam_min > 0.0 && lam_max >= lam_min, DNMF_E_SHAPE,
+                 "dnmf_lm_step_jac: nu=%g lam0=%g lam_min=%g lam_max=%g (want nu > 1, 0 < lam_min <= lam_max, lam0 > 0)", nu, lam0,
+                 lam_min, lam_max);
+    DNMF_REQUIRE(m >= 0.0 && m - m == 0.0 && mj >= 0.0 && mj - mj == 0.0, DNMF_E_SHAPE,
+                 "dnmf_lm_step_jac: m=%g mj=%g (want finite weights >= 0)", m, mj);
+    DNMF_REQUIRE(m == 0.0 || (beta_ref && prior), DNMF_E_NULL, "dnmf_lm_step_jac: NULL beta_ref or prior with m != 0");
+    DNMF_REQUIRE(m == 0.0 || beta_ref != beta, DNMF_E_SHAPE,
+                 "dnmf_lm_step_jac: beta_ref must not be beta (it holds accepted points only)");
+    JacHalf half;
+    half.h[0] = 0.5 * (double)(X - 1), half.h[1] = 0.5 * (double)(Y - 1), half.h[2] = Z > 1 ? 0.5 * (double)(Z - 1) : 1.0;
+    hipLaunchKernelGGL(lm_step_jac_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, H, g, sse, Z > 1 ? 30 : 12, order, M,
+                       Minv, beta, T, times, H_acc, g_acc, sse_acc, sse0, lam, beta_acc, counts, nu, lam0, lam_min, lam_max,
+                       accept_only, beta_ref, m, prior, mj, half, jac, min_det);
+    return check_launch("dnmf_lm_step_jac");
 }
 
 }  // extern "C"

@@ -380,8 +380,18 @@ def _centred(sz, dev):
     return _CENTRED_M[key]
 
 
+def warp_jacobian_points(sz):
+    """(NP,3) float64 numpy: the sample points of the volume-preserving prior (K16j, ``lm_step(jacobian=...)``) in centred
+    coordinates, in the kernel's order -- the corners u in {-1, +1}^n counted with the first axis slowest, then the centre u = 0.
+    NP = 9; 5 at Z = 1, where u_2 = 0 throughout."""
+    import itertools
+    import numpy as np
+    n = 3 if int(sz[2]) > 1 else 2
+    return np.array([list(c) + [0.0] * (3 - n) for c in itertools.product((-1.0, 1.0), repeat=n)] + [[0.0, 0.0, 0.0]])
+
+
 def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_max=1e9, accept_only=False, smooth=0.0,
-            n_residuals=None, beta_ref=None, order="quadratic"):
+            n_residuals=None, beta_ref=None, jacobian=0.0, order="quadratic"):
     """One Levenberg-Marquardt step per frame on the device (``dnmf_lm_step``).  ``eqs``: ``warp_normal_eqs``' result at the
     trial coefficients ``beta[:, :, times]``; ``state``: ``lm_state(B, device)``.  The trial is accepted when its sse is finite
     and below the accepted one (always on a frame's first call), ``beta[:, :, times]`` then receives the next trial -- or, with
@@ -394,9 +404,18 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
 
     ``order`` (``WARP_ORDERS``): ``'translation'`` or ``'affine'`` step on the rows of the centred basis of that degree only
     (K16o, ``dnmf_lm_step_order``; with or without the prior) and leave the other rows of ``beta[:, :, times]`` as they are, bit
-    for bit; ``eqs`` is the same.  ``'quadratic'``, the default, is the two entries above."""
+    for bit; ``eqs`` is the same.  ``'quadratic'``, the default, is the two entries above.
+
+    ``jacobian`` != 0: the step with the volume-preserving prior (K16j, ``dnmf_lm_step_jac``, whatever ``order`` and ``smooth``
+    are), weight m_j = ``jacobian`` * ``n_residuals``: J = m_j mean_p (log det Jx(u_p))^2 over ``warp_jacobian_points(sz)``, Jx the
+    Jacobian of the frame's map in voxel coordinates, +inf for a map that folds at a sample point -- so a folded trial is never
+    accepted after a frame's first call.  ``state`` gains ``jac`` (B) float64, J of the point kept, and ``min_det`` (B), its
+    smallest det Jx over the sample points.  0.0, the default, takes the entries above."""
     if order not in WARP_ORDERS:
         raise ValueError(f"lm_step: order must be one of {sorted(WARP_ORDERS)}, got {order!r}")
+    jacobian = float(jacobian)
+    if not (jacobian >= 0.0 and jacobian != float("inf")):
+        raise ValueError(f"lm_step: jacobian={jacobian}: expected a finite weight >= 0")
     dev = beta.device
     _f32(beta, "beta")
     smooth = float(smooth)
@@ -423,6 +442,20 @@ def lm_step(state, eqs, sz, beta, times, nu=10.0, lam0=1e-3, lam_min=1e-9, lam_m
     if smooth != 0.0 and ("prior" not in state or state["prior"].shape[0] < B):
         state["prior"] = torch.zeros((state["counts"].shape[0],), dtype=torch.float64, device=dev)
     n = int(sz[0]) * int(sz[1]) * int(sz[2]) if n_residuals is None else int(n_residuals)
+    if jacobian != 0.0:
+        for key in ("jac", "min_det"):
+            if key not in state or state[key].shape[0] < B:
+                state[key] = torch.zeros((state["counts"].shape[0],), dtype=torch.float64, device=dev)
+        rc = _lib.load().dnmf_lm_step_jac(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[0]), int(sz[1]), int(sz[2]),
+                                          WARP_ORDERS[order], M.data_ptr(), Minv.data_ptr(), beta.data_ptr(), beta.shape[2],
+                                          tt.data_ptr(), state["H"].data_ptr(), state["g"].data_ptr(), state["sse"].data_ptr(),
+                                          state["sse0"].data_ptr(), state["lam"].data_ptr(), state["beta"].data_ptr(),
+                                          state["counts"].data_ptr(), float(nu), float(lam0), float(lam_min), float(lam_max),
+                                          1 if accept_only else 0, beta_ref.data_ptr() if smooth else None, smooth * n,
+                                          state["prior"].data_ptr() if smooth else None, jacobian * n, state["jac"].data_ptr(),
+                                          state["min_det"].data_ptr(), _stream())
+        _lib.check(rc, "dnmf_lm_step_jac")
+        return state
     if order != "quadratic":
         rc = _lib.load().dnmf_lm_step_order(H.data_ptr(), g.data_ptr(), sse.data_ptr(), B, int(sz[2]), WARP_ORDERS[order], M.data_ptr(),
                                             Minv.data_ptr(), beta.data_ptr(), beta.shape[2], tt.data_ptr(), state["H"].data_ptr(),

@@ -6,7 +6,7 @@ their patches (``apply_shifts_points``) and compare with the simulator's own per
 MI355X.
 
     python examples/init_positions.py [--size 128] [--neurons 30] [--frames 50] [--stride 12] [--detect] [--track [--exclude R]] [--follow]
-                                      [--gn [--motion-smooth S] [--motion-order ORDER]]
+                                      [--gn [--motion-smooth S] [--motion-order ORDER] [--motion-jacobian W]]
                                       [--detect-image {template,corr,max,std,temporal_median,pnr,corr_pnr}]
 
 ``--detect``: the centres come from the registration template (``MotionCorrect.detect_points``, K14) instead of the simulator's
@@ -36,6 +36,9 @@ gives that fit the temporal prior (``fit(..., motion_smooth=S)``, K16s: S in mea
 frame-to-frame change of a warp coefficient); the numbers with it are unmeasured.  ``--motion-order ORDER`` fits only the
 coefficients of that order -- ``translation``, ``affine``, ``quadratic`` (the default: all) -- or, with ``graded``, the three in
 turn with ``--gn-iters`` iterations each (``fit(..., motion_order=ORDER)``, K16o); the numbers with it are unmeasured too.
+``--motion-jacobian W`` gives that fit the volume-preserving prior (``fit(..., motion_jacobian=W)``, K16j: W in mean squared error
+per squared unit of log det J at the corners and the centre of the volume; a step to a map that folds there is never accepted) and
+prints the smallest det J the fit ends with; the numbers with it are unmeasured as well.
 """
 import argparse
 import os
@@ -72,12 +75,15 @@ def main():
     ap.add_argument("--motion-smooth", type=float, default=0.0, help="--gn: weight of the temporal smoothness prior (0: none)")
     ap.add_argument("--motion-order", choices=("translation", "affine", "quadratic", "graded"), default="quadratic",
                     help="--gn: the coefficients the fit moves; graded: translation, then affine, then all")
+    ap.add_argument("--motion-jacobian", type=float, default=0.0, help="--gn: weight of the volume-preserving prior (0: none)")
     ap.add_argument("--gsig", type=float, default=None, help="register on high-pass-filtered frames: gSig_filt=(S, S) (K22)")
     ap.add_argument("--search", type=int, default=3, help="--track, --follow: voxels searched in x and y around the prediction")
     a = ap.parse_args()
     a.detect = a.detect or a.detect_image is not None
     if a.motion_smooth and not a.gn:
         ap.error("--motion-smooth needs --gn (the Adam fit has no temporal term)")
+    if a.motion_jacobian and not a.gn:
+        ap.error("--motion-jacobian needs --gn (the Adam fit's reg term carries no gradient)")
     if a.motion_order != "quadratic" and not a.gn:
         ap.error("--motion-order needs --gn (the Adam fit steps on all of beta)")
     image = a.detect_image or "template"
@@ -148,7 +154,9 @@ def main():
             loader = dataset.loader(a.batch)
             if solver == "gn":
                 dn.fit(loader, loader, None, a.batch, outer=1, epochs=a.gn_iters, gamma_c=0, iter_c=30, motion_solver='gn',
-                       motion_smooth=a.motion_smooth, motion_order=a.motion_order)
+                       motion_smooth=a.motion_smooth, motion_order=a.motion_order, motion_jacobian=a.motion_jacobian)
+                if a.motion_jacobian:
+                    print(f"smallest det J at the sample points: {float(dn.last_motion_gn['min_det'].min()):.3f}")
             else:
                 dn.fit(loader, loader, torch.optim.Adam([dn.fp.beta], lr=a.lr), a.batch, outer=1, epochs=a.epochs, gamma_c=0, iter_c=30)
             where = dn.positions()
@@ -159,6 +167,7 @@ def main():
             label = start
             if solver == "gn":
                 label += (f" (gn, {a.gn_iters} iterations" + (f", smooth {a.motion_smooth:g}" if a.motion_smooth else "")
+                          + (f", jacobian {a.motion_jacobian:g}" if a.motion_jacobian else "")
                           + (f", order {a.motion_order})" if a.motion_order != "quadratic" else ")"))
             print(f"{label} start: mean distance of dnmf.positions() from the simulator's centres {dist:.2f} voxels; median "
                   f"correlation with the simulator's traces: dnmf.C {median_corr(dn.C.cpu().numpy()):.3f}, ROI traces on "

@@ -744,6 +744,37 @@ int dnmf_lm_step_order(const double *H, const double *g, const double *sse, int 
                        double *sse0, double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min,
                        double lam_max, int accept_only, float *beta_ref, double m, double *prior, dnmf_stream_t stream);
 
+/* K16j: the step with a volume-preserving prior (csrc/motion_gn.hip, lm_step_jac_kernel).  dnmf_lm_step_order's arguments, the
+ * volume's X, Y, Z in place of Z, and mj, jac, min_det.  With theta a frame's coefficients in the centred basis on the active
+ * unknowns, the frame's map is q_d(u) = sum_a basis_a(u) theta[a,d], basis(u) = [1, u0, u1, u2, u0^2, u1^2, u2^2, u0 u1, u0 u2,
+ * u1 u2], and its Jacobian in voxel coordinates Jx[d][e] = (d q_d / d u_e) / h_e, h_e = (S_e - 1) / 2 -- 3 x 3, or 2 x 2 over (x, y)
+ * at Z == 1.  This is the TRUE Jacobian of the model's map (K11 / K12's), not the reference's log_det_jac, which swaps the xz and
+ * yz rows.  Sample points: the corners u in {-1, +1}^n in the order of counting with the first axis slowest, then the centre
+ * u = 0: NP = 9, or 5 at Z == 1.
+ *   rho_p    log det Jx(u_p): 0 for the identity, a rigid motion in voxel coordinates or a shear; +inf where det Jx(u_p) <= 0
+ *            or is not finite.
+ *   J        mj / NP sum_p rho_p^2, the frame's prior; +inf for a map that folds at a sample point.
+ *   accept   first call: always.  Later: sse + temporal prior + J of the trial finite and below that of the accepted point
+ *            (recomputed from beta_acc).  A trial that folds at a sample point is therefore never accepted after the first call,
+ *            and an accepted point that folds is beaten by any admissible trial.
+ *   step     H' gains mj / NP sum_p jrho_p jrho_p^T and g' gains mj / NP sum_p rho_p jrho_p at the point kept, on the unknowns
+ *            of the order, jrho_p[a*3+d] = sum_e (Jx^-1)[e][d] (d basis_a / d u_e)(u_p) / h_e: the exact Gauss-Newton terms of
+ *            the sum of squares J.  A point whose rho is not finite adds nothing.  rho itself sees the whole map, not the
+ *            order's unknowns alone.  Then dnmf_lm_step's damped solve on the dense H' (the same device function).
+ *   jac      (B) float64 out: J of the point kept.   min_det (B) float64 out: its smallest det Jx over the sample points.
+ * det Jx is a cubic polynomial in u: positive at the sample points does not prove positive everywhere.
+ * mj == 0: no such prior (jac = 0; min_det is still written), the steps of dnmf_lm_step_order up to the rounding of its sums.
+ * m != 0: dnmf_lm_step_smooth's CONTRACT holds; m == 0: beta_ref and prior may be NULL.  Minv is always read.
+ * Sums over p run in a fixed order, no atomics: the same input gives the same bits.  One wave per frame, float64, no host
+ * synchronisation, no workspace.  tests/gn_jac_restatement.py is the definition.
+ * DNMF_E_NULL: a NULL buffer (beta_ref, prior: only with m != 0);  DNMF_E_SHAPE: as dnmf_lm_step_order, X or Y < 2, mj < 0 or not
+ * finite. */
+int dnmf_lm_step_jac(const double *H, const double *g, const double *sse, int B, int X, int Y, int Z, int order, const double *M,
+                     const double *Minv, float *beta, int T, const int *times, double *H_acc, double *g_acc, double *sse_acc,
+                     double *sse0, double *lam, float *beta_acc, int *counts, double nu, double lam0, double lam_min,
+                     double lam_max, int accept_only, float *beta_ref, double m, double *prior, double mj, double *jac,
+                     double *min_det, dnmf_stream_t stream);
+
 /* ---- K17: the trilinear registered movie under the fitted warp ----------------------------------------------------------------
  * For every frame j < B (column t = times[j] of beta, or j when times is NULL; row frame_ids[j] of frames, or j) and every lattice
  * point u = (i, j, k) of the footprint volume: the x with q_t(x) = u, and the frame sampled trilinearly at x.  Conventions as K11 /

@@ -13,7 +13,11 @@ off the identity (bench.py's ``displaced_beta``):
              ``affine`` and ``quadratic`` (3 / 12 / 30 unknowns; 2 / 6 / 12 at Z = 1) -- and, for O other than ``quadratic``, an LM
              iteration with ``model.motion_order = O`` in the ``iteration`` line (``graded``: a round of its three stages)
 
-    python tools/time_motion_gn.py [--frames 4000] [--neurons 100] [--smooth 1e-4] [--order graded]
+  --jacobian W  ``steps``: the step with the volume-preserving prior (``ops.lm_step(jacobian=W)``, ``dnmf_lm_step_jac``) beside
+             the plain ``dnmf_lm_step`` on the same K16 output, and an LM iteration with ``model.motion_jacobian = W`` in the
+             ``iteration`` line
+
+    python tools/time_motion_gn.py [--frames 4000] [--neurons 100] [--smooth 1e-4] [--order graded] [--jacobian 1e-3]
 
 Every measurement is a process of its own under a time limit; the first one that fails ends the script.  One JSON line each.
 """
@@ -80,7 +84,7 @@ def step_kernels(Z, K, T):
     return {"step": "kernels", "Z": Z, "K": K, "T": T, "k2_ms": t2, "k16_ms": t16, "ratio": t16 / t2}
 
 
-def step_steps(Z, K, T):
+def step_steps(Z, K, T, jacobian=0.0):
     """The step alone, B = T frames: one K16 evaluation, then each entry on a fresh state (the first call: accept + solve)."""
     import torch
     from dnmf_amd import _lib, ops
@@ -110,10 +114,17 @@ def step_steps(Z, K, T):
     out = {"step": "steps", "Z": Z, "K": K, "T": T, "lm_step_ms": median_ms(lambda: run(None))}
     for name, order in ops.WARP_ORDERS.items():
         out[f"lm_step_order_{name}_ms"] = median_ms(lambda: run(order))
+    if jacobian:
+        def run_jac():
+            state["counts"].zero_()
+            beta.copy_(start)
+            ops.lm_step(state, eqs, sz, beta, times, jacobian=jacobian)
+
+        out.update(jacobian=jacobian, lm_step_jac_ms=median_ms(run_jac))
     return out
 
 
-def step_iteration(Z, K, T, smooth=0.0, order="quadratic"):
+def step_iteration(Z, K, T, smooth=0.0, order="quadratic", jacobian=0.0):
     import torch
     dNMF, model, sz, frames = setup(Z, K, T)
     loader = dNMF.ResidentLoader(frames, sz, 100)
@@ -152,6 +163,12 @@ def step_iteration(Z, K, T, smooth=0.0, order="quadratic"):
         o5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
         model.motion_order = "quadratic"
         out.update(order=order, gn_order_iters1_ms=o1, gn_order_iters5_ms=o5, lm_order_iteration_ms=(o5 - o1) / 4)
+    if jacobian:
+        model.motion_jacobian = jacobian
+        j1 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=1))
+        j5 = wall(lambda: model.update_motion(loader, None, solver='gn', iters=5))
+        model.motion_jacobian = 0.0
+        out.update(jacobian=jacobian, gn_jac_iters1_ms=j1, gn_jac_iters5_ms=j5, lm_jac_iteration_ms=(j5 - j1) / 4)
     return out
 
 
@@ -164,17 +181,19 @@ def main():
     ap.add_argument("--smooth", type=float, default=0.0, help="also time an LM iteration with this temporal prior weight")
     ap.add_argument("--order", choices=["translation", "affine", "quadratic", "graded"], default=None,
                     help="also time the step per warp order, and an LM iteration with this motion_order")
+    ap.add_argument("--jacobian", type=float, default=0.0,
+                    help="also time the step and an LM iteration with this volume-preserving prior weight")
     ap.add_argument("--limit", type=int, default=240, help="seconds a measurement may take")
     a = ap.parse_args()
     if a.step:
-        out = step_kernels(a.z, a.neurons, a.frames) if a.step == "kernels" else step_steps(a.z, a.neurons, a.frames) \
-            if a.step == "steps" else step_iteration(a.z, a.neurons, a.frames, a.smooth, a.order or "quadratic")
+        out = step_kernels(a.z, a.neurons, a.frames) if a.step == "kernels" else step_steps(a.z, a.neurons, a.frames, a.jacobian) \
+            if a.step == "steps" else step_iteration(a.z, a.neurons, a.frames, a.smooth, a.order or "quadratic", a.jacobian)
         print(json.dumps(out), flush=True)
         return 0
     for z in (1, 2):
-        for step in ("kernels", "iteration") + (("steps",) if a.order else ()):
+        for step in ("kernels", "iteration") + (("steps",) if a.order or a.jacobian else ()):
             cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--step", step, "--z", str(z),
-                   "--frames", str(a.frames), "--neurons", str(a.neurons), "--smooth", str(a.smooth)]
+                   "--frames", str(a.frames), "--neurons", str(a.neurons), "--smooth", str(a.smooth), "--jacobian", str(a.jacobian)]
             if a.order:
                 cmd += ["--order", a.order]
             rc = subprocess.run(cmd, cwd=ROOT).returncode
