@@ -139,7 +139,7 @@ def test_lm_step_zero_H_and_nan_frame():
 
 def test_fit_gn_converges_on_the_test_problems():
     """The problems tests/test_gpu_gn.py fits on the GPU: float64 sums reach 0.01 voxel within 8 iterations."""
-    for sz in [(24, 20, 2), (24, 20, 1)]:
+    for sz in [(24, 20, 2), (24, 20, 1), (24, 20, 5)]:
         p = GN.fit_problem(sz)
         T = p["C"].shape[1]
         beta, st, hist = GN.fit_gn(p["A"], p["C"], O.identity_beta(T), sz, range(T), p["frames"], iters=8)

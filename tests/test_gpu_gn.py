@@ -3,6 +3,9 @@ inputs, against K2 and the reference's captured gradient, and update_motion(solv
 
 Tolerances:
   H      |dH_ij| <= 1e-4 sqrt(H_ii H_jj), g: |dg_i| <= 1e-4 max|g|   fp32 sums of P terms in another order (K2's gradient bound)
+         -- a bound by the diagonal and by the largest entry: an entry that is small beside them may be wrong by many times its
+         own size, and no shape of check_eqs has Z > 3, where alone the z exponents 3 and 4 differ from 1 and 2.  The bound by
+         the entry's own absolute sum, at shapes with Z = 4 and 5, is tests/test_gpu_k16_float64.py's; these tests stay.
   sse    rtol 1e-5
   step   the device writes the next trial as fp32(beta_acc + d beta); against fp32 of the restatement's float64 sum it may differ
          by 100 kappa 2.2e-16 max|d beta| (kappa: condition number of the damped scaled system) plus one fp32 rounding
@@ -243,11 +246,12 @@ def test_lm_step_zero_H_leaves_beta(M):
 
 # ---- the fit ---------------------------------------------------------------------------------------------------------
 ITERS = 8
+FIT_SHAPES = [(24, 20, 2), (24, 20, 1), (24, 20, 5)]
 
 
 @pytest.fixture(scope="module")
 def problems():
-    return {sz: GN.fit_problem(sz) for sz in [(24, 20, 2), (24, 20, 1)]}
+    return {sz: GN.fit_problem(sz) for sz in FIT_SHAPES}
 
 
 def make_model(M, sz, p, cls=None, **kw):
@@ -263,12 +267,13 @@ def resident(M, sz, frames, batch=2):
     return M.ResidentLoader(dev(frames.reshape(frames.shape[0], -1)), sz, batch)
 
 
-@pytest.mark.parametrize("sz", [(24, 20, 2), (24, 20, 1)])
+@pytest.mark.parametrize("sz", FIT_SHAPES)
 def test_fit_converges_without_a_step_size(M, problems, monkeypatch, sz):
     """fit_problem(sz): shift <= 0.6 voxel, affine <= 0.03, quadratic terms <= 0.25 voxel at the far corner, in-plane, start at
-    the identity 0.87 .. 1.92 voxels off (24x20x2; 0.72 .. 1.78 at 24x20x1).  The float64 restatement (fit_gn, 8 iterations) ends
-    at most 3.2e-5 (24x20x2) / 3.7e-6 (24x20x1) voxel off with sse / sse0 <= 7e-12 / 3e-11 -- tests/test_gn_host.py asserts
-    < 0.01 voxel and <= 1e-6."""
+    the identity 0.87 .. 1.92 voxels off (24x20x2; 0.72 .. 1.78 at 24x20x1; up to 1.99 at 24x20x5, the one fit at Z > 2: all 30
+    unknowns with u_z at five values).  The float64 restatement (fit_gn, 8 iterations) ends at most 3.2e-5 (24x20x2) / 3.7e-6
+    (24x20x1) / 4.9e-6 (24x20x5) voxel off with sse / sse0 <= 7e-12 / 3e-11 / 8e-12 -- tests/test_gn_host.py asserts < 0.01 voxel
+    and <= 1e-6."""
     from dnmf_amd import ops
     p = problems[sz]
     T = p["C"].shape[1]
