@@ -435,6 +435,31 @@ class MotionCorrect(object):
         info = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()}
         return movie.cpu().numpy().reshape(T, *sz), info
 
+    def denoise_movie(self, video=None, **kw):
+        """The corrected movie denoised by local low-rank approximation (K34, ``ExponentialFP.denoise_movie``; ``kw``: ``patch``,
+        ``overlap``, ``rank``, ``keep``, ``threshold``, ``iters``, ``scale``) -> ``(movie, info)``: of an (X, Y, Z, T) ``video``, the
+        layout of ``mc``, or, without one, of the stored corrected movie (``save_corrected=True``; several videos count as one
+        movie), a float32 numpy (X, Y, Z, T) movie and the numpy ``kept``, ``lam``, ``ok``, ``explained``, ``U``, ``Q`` and ``plan``.
+        The stored movie is held on the GPU whole while the call runs; the kernels take it in pieces of at most 1 GiB.  A patch
+        that holds a sample the correction left NaN is left out, and its voxels come back as they are where no other patch covers
+        them."""
+        from .dNMF import ExponentialFP, _denoise_rows
+        if video is not None:
+            return ExponentialFP.denoise_movie(video, **kw)
+        pieces, sz = self._stored_pieces("denoise_movie")
+        held = list(pieces())
+        edges = np.cumsum([0] + [p.shape[0] for p in held])
+
+        def rows_of(r0, r1):
+            first, last = np.searchsorted(edges, r0, side="right") - 1, np.searchsorted(edges, r1, side="left") - 1
+            if first == last:
+                return held[first][r0 - edges[first]:r1 - edges[first]]
+            return torch.cat([held[i][max(r0, edges[i]) - edges[i]:min(r1, edges[i + 1]) - edges[i]] for i in range(first, last + 1)])
+        T = int(edges[-1])
+        movie, info = _denoise_rows(rows_of, T, sz, kw.pop("scale", 'noise'), **kw)
+        info = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()}
+        return movie.view(T, *sz).permute(1, 2, 3, 0).cpu().numpy(), info
+
     def detect_points(self, K, shape_std=3, **kw):
         """The (n, 3) centres of the up to K neurons found in the template -- ``total_template_els`` when the piecewise pass
         made one, else ``total_template_rig`` -- by ``ExponentialFP.detect_positions`` (K14; ``kw``: ``min_distance``,

@@ -52,6 +52,24 @@ def _sz_list(sz):
     return [int(s) for s in (sz.tolist() if isinstance(sz, torch.Tensor) else sz)]
 
 
+def _denoise_rows(rows_of, T, sz, scale='noise', **kw):
+    """K34 on a movie of ``T`` frames that ``rows_of(r0, r1)`` serves as fp32 CUDA rows in time order: the centre is K18's mean,
+    the scale K30's noise (``'noise'``), ones (``None``) or an (X, Y, Z) image -> ``ops.lowrank_denoise``'s (movie, info)."""
+    P = sz[0] * sz[1] * sz[2]
+    step = _gib_rows(T, P)
+
+    def pieces():
+        return (rows_of(r0, min(T, r0 + step)) for r0 in range(0, T, step))
+    state = images = None
+    for r0, fr in zip(range(0, T, step), pieces()):
+        images, state = ops.summary_images(fr, sz, neighbours='face', state=state, first=r0 == 0, finish=r0 + step >= T)
+    if isinstance(scale, str):
+        if scale != 'noise':
+            raise ValueError(f"denoise_movie: scale must be 'noise', None or an (X, Y, Z) image, got {scale!r}")
+        scale = ops.noise_image(pieces, sz)
+    return ops.lowrank_denoise(rows_of, sz, images["mean"], scale, T=T, **kw)
+
+
 def _gib_rows(n, P):
     """How many of ``n`` rows of ``P`` fp32 values go through at a time: what 1 GiB holds, at least one."""
     return max(1, min(n, (1 << 30) // (4 * P)))
@@ -527,6 +545,35 @@ class ExponentialFP(nn.Module):
         return movie.cpu().numpy().reshape(rows.shape[0], *sz), info
 
     @staticmethod
+    def denoise_movie(video, patch=(16, 16, None), overlap=(8, 8, 0), rank=8, keep='auto', threshold=1.0, iters=4, scale='noise'):
+        """A registered (or nearly static) ``video`` denoised by local low-rank approximation (K34, ``ops.lowrank_denoise``;
+        tests/denoise_restatement.py): the volume is covered by overlapping patches of ``patch`` voxels (``None`` in z: min(Z, 4);
+        at most 1024 voxels), in each the ``rank`` <= 8 leading singular pairs of (y - mean) / scale are found by ``iters`` steps of
+        subspace iteration, those above ``threshold`` x the noise edge sqrt n + sqrt T are kept (``keep='auto'``; a number keeps
+        that many), and the patches are blended by tent weights -> ``(movie, info)``.  ``scale``: ``'noise'`` (K30's noise image,
+        which makes the noise of every voxel unit), ``None`` (ones) or an (X, Y, Z) image.  Inside a patch a registered movie is a
+        handful of components plus independent noise; in frame coordinates a moving animal is not, so register first
+        (``DeformableNMF.denoise_movie(registered=)``).  ``info``: ``plan``, ``kept`` (NP,), ``lam`` (NP, R), ``ok``, ``explained``
+        and the factors ``U`` (NP, n, R), ``Q`` (NP, T, R) -- a compressed form of the movie.  A patch with a sample that is not
+        finite, or a voxel of zero noise, is left out (``ok`` = 0); a voxel no other patch covers comes back as it is.
+        ``video``: (X, Y, Z, T) values (numpy or torch) give a float32 numpy (X, Y, Z, T) movie and numpy ``info``; CUDA rows with
+        their volume ``(rows (T, P), sz)`` or a ``ResidentLoader`` give CUDA rows (T, P) and CUDA ``info``, as ``dff_movie``."""
+        if hasattr(video, "frames_2d") or (isinstance(video, (tuple, list)) and len(video) == 2):
+            rows, sz, on_gpu = ExponentialFP._video_rows(video, "denoise_movie")
+        else:
+            v = video if isinstance(video, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(video))
+            if v.dim() != 4:
+                raise ValueError(f"denoise_movie: a video is (X, Y, Z, T), (rows (T, P), sz) or a ResidentLoader, got {tuple(v.shape)}")
+            sz, on_gpu = [int(n) for n in v.shape[:3]], False
+            rows = v.to(device, torch.float32).permute(3, 0, 1, 2).reshape(v.shape[3], -1).contiguous()
+        movie, info = _denoise_rows(lambda r0, r1: rows[r0:r1], rows.shape[0], sz, scale, patch=patch, overlap=overlap, rank=rank,
+                                    keep=keep, threshold=threshold, iters=iters)
+        if on_gpu:
+            return movie, info
+        info = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in info.items()}
+        return movie.view(-1, *sz).permute(1, 2, 3, 0).cpu().numpy(), info
+
+    @staticmethod
     def background(video, iters=3):
         """The rank-1 background of ``video`` as it is (K19, ``ops.background_fit``): ``(b (X, Y, Z), f (T,))`` fp32, both >= 0
         with mean(f) = 1, after ``iters`` alternations of the two exact coordinate steps of ``min |video - b f|^2`` from b = 1.
@@ -712,6 +759,8 @@ class DeformableNMF:
         self.last_footprint_clean = None
         # after add_components: centres, boxes, explained, energy, ok, kept, added and K of that call
         self.last_add = None
+        # after denoise_movie: plan, kept, lam, ok, explained and the factors U, Q of that call
+        self.last_denoise = None
         self._warned = set()
 
     @classmethod
@@ -1115,6 +1164,30 @@ class DeformableNMF:
             movie, info = ops.dff_rows(rows_of, frames.shape[0], fp.sz_list, kw.pop("window"), kw.pop("stride", None), percentile / 100.0,
                                        **kw)
         self.last_dff = info
+        return movie
+
+    def denoise_movie(self, loader, registered=None, **kw):
+        """The movie of every frame ``loader`` serves, in the order of the frame times, denoised by local low-rank approximation
+        (``ExponentialFP.denoise_movie``, K34; ``kw``: ``patch``, ``overlap``, ``rank``, ``keep``, ``threshold``, ``iters``,
+        ``scale``): (T, P) fp32 CUDA rows.  ``registered='linear'`` (K17) or ``'nearest'`` (K7) registers the frames under the current
+        ``fp.beta`` first, as ``robust_images`` does -- in frame coordinates a moving animal is not locally low-rank, so
+        ``registered=None`` is for a movie that is static already.  The frames go through in pieces of at most 1 GiB, once per pass
+        (registered frames are made anew each time).  ``self.last_denoise`` receives ``plan``, ``kept``, ``lam``, ``ok``,
+        ``explained`` and the factors ``U``, ``Q``.  One channel, and a loader that holds every frame."""
+        if registered is not None:
+            _check_registered(registered, "denoise_movie")
+        self._single_model_only("denoise_movie", loader, "the loader holds a shard of the frames (a patch's factors need all of "
+                                                         "its frames)")
+        fp = self.fp
+        with torch.no_grad():
+            frames, order = self._frames_in_time_order(loader)
+
+            def rows_of(r0, r1):
+                if registered is None:
+                    return frames[r0:r1]
+                return fp.registered_video(frames[r0:r1], times=order[r0:r1], interpolation=registered)
+            movie, info = _denoise_rows(rows_of, frames.shape[0], fp.sz_list, kw.pop("scale", 'noise'), **kw)
+        self.last_denoise = info
         return movie
 
     def detrend_traces(self, window, traces=None, **kw):

@@ -150,6 +150,13 @@ SIGNATURES = {
     "dnmf_running_windows": (_l, [_l, _i, _i]),
     "dnmf_running_quantile": (_i, [_vp, _l, _vp, _vp, _i, _l, _l, _i, _i, _d, _i, _vp, _vp, _vp, _l, _vp, _vp]),
     "dnmf_baseline_apply": (_i, [_vp, _l, _vp, _vp, _i, _l, _vp, _l, _vp, _i, _i, _d, _vp, _l, _vp]),
+    "dnmf_lowrank_patches": (_l, [_vp, _vp]),
+    "dnmf_lowrank_tile_frames": (_i, [_i]),
+    "dnmf_lowrank_accumulate": (_i, [_vp, _l, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dnmf_lowrank_orthonormalise": (_i, [_l, _i, _i, _vp, _vp, _vp, _vp]),
+    "dnmf_lowrank_project": (_i, [_vp, _l, _vp, _vp, _i, _l, _l, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dnmf_lowrank_ritz": (_i, [_l, _i, _l, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dnmf_lowrank_reconstruct": (_i, [_vp, _l, _vp, _vp, _i, _l, _l, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "dnmf_comm_unique_id": (_i, [_vp]),
     "dnmf_comm_init": (_i, [_vp, _vp, _i, _i]),
     "dnmf_allreduce_sum_f32": (_i, [_vp, _vp, _sz, _vp]),

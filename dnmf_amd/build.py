@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, "libdnmf_hip.so")
 SOURCES = ["api_common.hip", "warp_gather.hip", "recon_image.hip", "warp_recon_grad.hip", "motion_gn.hip", "warp_gram_rhs.hip", "warp_gram_sparse.hip", "warp_gram_lists.hip", "warp_gram_lists_z.hip", "recon_lists.hip",
            "mu_temporal.hip", "hals_temporal.hip", "render_frames.hip", "adam_epoch.hip", "spatial_update.hip", "image_iwarp.hip", "register_patches.hip", "apply_pwrigid.hip", "nearest_points.hip",
            "tracks.hip", "detect_neurons.hip", "track_neurons.hip", "follow_neurons.hip", "track_exclusive.hip", "warp_pullback.hip", "summary_images.hip", "background.hip", "clean_traces.hip", "deconvolve_traces.hip", "ar1_temporal.hip", "high_pass.hip", "component_stats.hip",
-           "histogram_match.hip", "merge_components.hip", "footprint_clean.hip", "add_components.hip", "colours.hip", "robust_images.hip", "running_baseline.hip", "collective.hip"]
+           "histogram_match.hip", "merge_components.hip", "footprint_clean.hip", "add_components.hip", "colours.hip", "robust_images.hip", "running_baseline.hip", "lowrank_denoise.hip", "collective.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
 

@@ -1851,6 +1851,14 @@ def robust_images(pieces, sz, percentiles=(), noise='diff'):
     return dict(median=median, max=mx, mad=mad, noise=sigma, pnr=pnr, n=n, percentile={p: values[2 + i] for i, p in enumerate(ps)})
 
 
+def noise_image(pieces, sz):
+    """The ``noise`` image of ``robust_images(noise='diff')`` alone (one selection, 9 passes): float64 CUDA (X, Y, Z)."""
+    if isinstance(pieces, torch.Tensor):
+        rows = pieces
+        pieces = lambda: (rows,)     # noqa: E731
+    return _quantiles_of_pieces(pieces, sz, [0.5], 'absdiff')["value"][0] * NOISE_DIFF_SCALE
+
+
 RUNNING_MAX_WINDOW = 2048                                                # a window of K31a lives in LDS
 BASELINE_MODES = {"baseline": 0, "df": 1, "dff": 2, "dfsqrtf": 3}        # DNMF_BASELINE_* of include/dnmf_hip.h
 
@@ -2026,6 +2034,236 @@ def dff_rows(rows_of, T, sz, window, stride=None, q=0.08, mode='dff', offset=0.0
         r1 = min(T, r0 + step)
         baseline_apply(rows_of(r0, r1), sz, knots, plan["centres"], mode, offset, row0=r0, out=movie[r0:r1])
     return movie[:T, :P], dict(knots=knots, centres=plan["centres"], n=n, starts=plan["starts"], ends=plan["ends"])
+
+
+LOWRANK_MAX_VOXELS = 1024      # a patch of K34 lives in LDS (csrc/lowrank_denoise.hip: LR_MAX_VOXELS)
+LOWRANK_MAX_RANK = 8
+LOWRANK_SWEEPS = 10            # the Jacobi sweeps of K34d: a parameter of the algorithm, not a tolerance
+
+
+def lowrank_patch_plan(sz, patch=(16, 16, None), overlap=(8, 8, 0)):
+    """The patches K34 covers a volume with (tests/denoise_restatement.py L1; host only, integers): along each axis the stride is
+    patch - overlap, patch i starts at min(i stride, max(extent - patch, 0)) -- the clamp of ``running_window_plan`` -- and the last
+    one ends at the extent; a patch larger than the axis is the axis; ``None`` in z is min(Z, 4).  Every patch has the same
+    ``shape``; ``n``, its voxels, is at most 1024 (ValueError beyond: a patch is never cut).  -> a dict ``boxes`` (NP, 6) int32
+    inclusive [x0, x1, y0, y1, z0, z1], x slowest as K24's, ``counts``, ``shape``, ``strides`` per axis, ``starts`` and ``n``."""
+    fn = "lowrank_patch_plan"
+    sz = [int(s) for s in sz]
+    if len(sz) != 3 or min(sz) < 1 or len(patch) != 3 or len(overlap) != 3:
+        raise ValueError(f"{fn}: sz={sz}, patch={patch!r}, overlap={overlap!r}: three axes, extents of at least 1")
+    patch = [patch[0], patch[1], min(sz[2], 4) if patch[2] is None else patch[2]]
+    starts, lens, strides = [], [], []
+    for a, (ext, pa, ov) in enumerate(zip(sz, patch, overlap)):
+        if int(pa) != pa or int(ov) != ov or int(pa) < 1 or not 0 <= int(ov) < int(pa):
+            raise ValueError(f"{fn}: axis {a}: patch={pa!r}, overlap={ov!r}: whole numbers with 0 <= overlap < patch")
+        pa, ov = int(pa), int(ov)
+        stride = pa - ov
+        count = 1 if ext <= pa else -((pa - ext) // stride) + 1
+        starts.append(np.minimum(np.arange(count, dtype=np.int64) * stride, max(ext - pa, 0)))
+        lens.append(min(pa, ext))
+        strides.append(stride)
+    n = lens[0] * lens[1] * lens[2]
+    if n > LOWRANK_MAX_VOXELS:
+        raise ValueError(f"{fn}: a patch of {lens[0]}x{lens[1]}x{lens[2]} = {n} voxels, at most {LOWRANK_MAX_VOXELS} (a patch lives "
+                         f"in LDS; it is never cut)")
+    sx, sy, s_z = np.meshgrid(*starts, indexing="ij")
+    lo = np.stack([sx.ravel(), sy.ravel(), s_z.ravel()], 1)
+    boxes = np.empty((lo.shape[0], 6), dtype=np.int32)
+    boxes[:, 0::2], boxes[:, 1::2] = lo, lo + np.array(lens) - 1
+    return dict(boxes=boxes, counts=tuple(len(s) for s in starts), shape=tuple(lens), strides=tuple(strides), starts=tuple(starts),
+                n=n, sz=tuple(sz))
+
+
+def _lowrank_plan(plan):
+    """(the 9 ints of the C ABI, NP, n) of a ``lowrank_patch_plan``."""
+    ints = [v for a in range(3) for v in (plan["counts"][a], plan["strides"][a], plan["shape"][a])]
+    return (ctypes.c_int * 9)(*ints), len(plan["boxes"]), plan["n"]
+
+
+def _lowrank_image(fn, name, img, P, dev):
+    if img is None:
+        return None
+    t = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    if t.numel() != P:
+        raise ValueError(f"{fn}: {name} must be an (X, Y, Z) image of {P} voxels, got {tuple(t.shape)}")
+    return t.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _lowrank_rank(fn, rank):
+    if int(rank) != rank or not 1 <= int(rank) <= LOWRANK_MAX_RANK:
+        raise ValueError(f"{fn}: rank={rank!r} outside [1, {LOWRANK_MAX_RANK}]")
+    return int(rank)
+
+
+def lowrank_state(plan, rank, T, device="cuda"):
+    """The state of K34 for the patches of ``plan``, ``rank`` = R columns and a movie of ``T`` frames, float64 on the device: ``U``,
+    ``W`` (NP, n, R), ``Q`` (NP, T, R), ``energy`` (NP, T), ``lam`` (NP, R), ``explained`` (NP,), and ``kept``, ``ok`` (NP,) int32
+    (ok = 1).  U is the orthonormalised start U0[v, j] = cos(pi (v + 1/2) j / n) (K34b on the host's table), W is zero."""
+    fn = "lowrank_state"
+    R = _lowrank_rank(fn, rank)
+    if int(T) != T or int(T) < 1:
+        raise ValueError(f"{fn}: T={T!r} frames")
+    _, NP, n = _lowrank_plan(plan)
+    f64 = dict(dtype=torch.float64, device=device)
+    v = np.arange(n, dtype=np.float64)[:, None]
+    u0 = torch.from_numpy(np.cos(np.pi * (v + 0.5) * np.arange(R, dtype=np.float64)[None, :] / n)).to(device)
+    state = dict(plan=plan, rank=R, T=int(T), U=torch.zeros((NP, n, R), **f64), W=u0[None].repeat(NP, 1, 1).contiguous(),
+                 Q=torch.zeros((NP, int(T), R), **f64), energy=torch.zeros((NP, int(T)), **f64), lam=torch.zeros((NP, R), **f64),
+                 explained=torch.zeros((NP,), **f64), kept=torch.zeros((NP,), dtype=torch.int32, device=device),
+                 ok=torch.ones((NP,), dtype=torch.int32, device=device))
+    return lowrank_orthonormalise(state)
+
+
+def _lowrank_call(fn, frames, sz, plan, state, centre, scale, frame_ids, row0):
+    """The checks every pass of K34 over frames shares -> (fid, B, P, plan ints, centre, scale)."""
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if tuple(plan["sz"]) != (X, Y, Z) or state["plan"] is not plan and state["plan"]["boxes"].shape != plan["boxes"].shape:
+        raise ValueError(f"{fn}: the plan is one of a volume {plan['sz']}, the state one of {state['plan']['sz']}, sz={(X, Y, Z)}")
+    fid, B = _frame_rows(fn, frames, None, frame_ids, P)
+    if B < 1:
+        raise ValueError(f"{fn}: no rows")
+    if fid is not None and (int(fid.min()) < 0 or int(fid.max()) >= frames.shape[0]):
+        raise ValueError(f"{fn}: frame_ids must be row indices in [0, {frames.shape[0]})")
+    if int(row0) < 0 or int(row0) + B > state["T"]:
+        raise ValueError(f"{fn}: rows {row0} .. {int(row0) + B} of a movie of T={state['T']} frames")
+    dev = frames.device
+    c = _lowrank_image(fn, "centre", centre, P, dev)
+    if c is None:
+        raise ValueError(f"{fn}: centre is required (scale=None means ones)")
+    return fid, B, P, _lowrank_plan(plan)[0], c, _lowrank_image(fn, "scale", scale, P, dev)
+
+
+def lowrank_accumulate(frames, sz, plan, state, centre, scale=None, frame_ids=None, row0=0):
+    """K34a.  ``state['W'] += D (D^T U)`` per patch over the fp32 CUDA rows ``frames`` (rows, ld >= X Y Z), the frames ``row0 ..``
+    of the movie: one pass over the movie per subspace iteration, in as many calls as the movie has pieces -- the same bits
+    however it is cut.  D = (y - centre) / scale with float64 (X, Y, Z) images (``scale=None``: ones).  Clears ``state['ok']`` of a
+    patch with a sample or centre that is not finite, or a scale that is not finite or <= 0.  -> state."""
+    fn = "lowrank_accumulate"
+    fid, B, P, plan9, c, s = _lowrank_call(fn, frames, sz, plan, state, centre, scale, frame_ids, row0)
+    with _timed(fn):
+        rc = _lib.load().dnmf_lowrank_accumulate(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3(sz), B, plan9, state["rank"],
+                                                 c.data_ptr(), _ptr(s), state["U"].data_ptr(), state["W"].data_ptr(),
+                                                 state["ok"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_lowrank_accumulate")
+    return state
+
+
+def lowrank_orthonormalise(state):
+    """K34b.  ``U = MGS(W)`` per patch, in column order (a column whose norm after the projections is <= 1e-12 x its norm before
+    becomes zero), and ``W = 0``; U = 0 where ok = 0.  -> state."""
+    _, NP, n = _lowrank_plan(state["plan"])
+    with _timed("lowrank_orthonormalise"):
+        rc = _lib.load().dnmf_lowrank_orthonormalise(NP, n, state["rank"], state["U"].data_ptr(), state["W"].data_ptr(),
+                                                     state["ok"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_lowrank_orthonormalise")
+    return state
+
+
+def lowrank_project(frames, sz, plan, state, centre, scale=None, frame_ids=None, row0=0):
+    """K34c.  Rows ``row0 ..`` of ``state['Q']`` = D^T U and of ``state['energy']`` = sum_v D^2, for the rows given.  -> state."""
+    fn = "lowrank_project"
+    fid, B, P, plan9, c, s = _lowrank_call(fn, frames, sz, plan, state, centre, scale, frame_ids, row0)
+    with _timed(fn):
+        rc = _lib.load().dnmf_lowrank_project(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3(sz), B, int(row0), state["T"], plan9,
+                                              state["rank"], c.data_ptr(), _ptr(s), state["U"].data_ptr(), state["Q"].data_ptr(),
+                                              state["energy"].data_ptr(), state["ok"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_lowrank_project")
+    return state
+
+
+def lowrank_edge(n, T, threshold=1.0):
+    """(threshold (sqrt n + sqrt T))^2: the Marchenko-Pastur edge of the largest eigenvalue of N^T N for n x T unit noise."""
+    return (float(threshold) * (math.sqrt(float(n)) + math.sqrt(float(T)))) ** 2
+
+
+def lowrank_ritz(state, keep='auto', threshold=1.0, n=None, T=None, sweeps=LOWRANK_SWEEPS):
+    """K34d.  Per patch B = Q^T Q, ``sweeps`` sweeps of cyclic Jacobi, ``lam`` descending (ties by index), U and Q rotated to match;
+    ``kept``: ``keep='auto'`` the number of lam > (threshold (sqrt n + sqrt T))^2, ``keep=r`` the number of lam > 0 among the first r;
+    ``explained`` = the kept lam over sum D^2.  ``n``, ``T``: those of the edge (None: the state's).  -> state."""
+    fn = "lowrank_ritz"
+    _, NP, pn = _lowrank_plan(state["plan"])
+    n, T = pn if n is None else int(n), state["T"] if T is None else int(T)
+    threshold = float(threshold)
+    if keep == 'auto':
+        if not (math.isfinite(threshold) and threshold >= 0.0):
+            raise ValueError(f"{fn}: threshold={threshold!r}: a finite factor >= 0")
+        k, e = -1, lowrank_edge(n, T, threshold)
+    else:
+        if isinstance(keep, str) or int(keep) != keep or int(keep) < 0:
+            raise ValueError(f"{fn}: keep must be 'auto' or a number of columns >= 0, got {keep!r}")
+        k, e = min(int(keep), state["rank"]), 0.0
+    if int(sweeps) != sweeps or not 0 <= int(sweeps) <= 64:
+        raise ValueError(f"{fn}: sweeps={sweeps!r} outside [0, 64]")
+    with _timed(fn):
+        rc = _lib.load().dnmf_lowrank_ritz(NP, pn, state["T"], state["rank"], k, e, int(sweeps), state["U"].data_ptr(),
+                                           state["Q"].data_ptr(), state["energy"].data_ptr(), state["ok"].data_ptr(),
+                                           state["lam"].data_ptr(), state["kept"].data_ptr(), state["explained"].data_ptr(), _stream())
+    _lib.check(rc, "dnmf_lowrank_ritz")
+    return state
+
+
+def lowrank_reconstruct(frames, sz, plan, state, centre, scale=None, frame_ids=None, row0=0, out=None):
+    """K34e.  The blended movie of the rows ``row0 ..``: per voxel the tent-weighted mean, over the ok patches that hold it, of
+    centre + scale sum_{j < kept} U[v, j] Q[t, j], float64 rounded once -> (rows, P) fp32.  ``frames`` is read only where no ok patch
+    holds the voxel: those samples come back bit for bit."""
+    fn = "lowrank_reconstruct"
+    fid, B, P, plan9, c, s = _lowrank_call(fn, frames, sz, plan, state, centre, scale, frame_ids, row0)
+    out = _out_rows(fn, out, B, P, frames.device)
+    with _timed(fn):
+        rc = _lib.load().dnmf_lowrank_reconstruct(frames.data_ptr(), _ld(frames, P), _ptr(fid), _int3(sz), B, int(row0), state["T"], plan9,
+                                                  state["rank"], c.data_ptr(), _ptr(s), state["U"].data_ptr(), state["Q"].data_ptr(),
+                                                  state["kept"].data_ptr(), state["ok"].data_ptr(), out.data_ptr(), _ld(out, P),
+                                                  _stream())
+    _lib.check(rc, "dnmf_lowrank_reconstruct")
+    return out[:B, :P]
+
+
+def lowrank_denoise(frames, sz, centre, scale=None, patch=(16, 16, None), overlap=(8, 8, 0), rank=8, keep='auto', threshold=1.0, iters=4,
+                    sweeps=LOWRANK_SWEEPS, T=None, limit=None, out=None):
+    """K34 (tests/denoise_restatement.py): the movie denoised by local low-rank approximation -> ``(out (T, P) fp32 CUDA, info)``.
+    ``frames``: fp32 CUDA rows (T, ld >= X Y Z) of a registered movie, or a callable ``rows_of(r0, r1)`` that serves the rows
+    [r0, r1) of a movie of ``T`` frames; it goes through in pieces of at most 1 GiB (``limit`` rows, for tests), once per pass:
+    ``iters`` >= 1 passes of K34a + K34b, one of K34c, K34d, one of K34e.  Per patch of ``lowrank_patch_plan(sz, patch, overlap)``
+    the ``rank`` <= 8 leading singular pairs of D = (y - centre) / scale, of which ``keep`` are used ('auto': those above
+    ``threshold`` x the noise edge sqrt n + sqrt T of unit noise, which presumes ``scale`` is the noise level).  ``info``: ``plan``,
+    ``kept``, ``lam`` (the squared singular values), ``ok``, ``explained`` and the factors ``U`` (NP, n, R), ``Q`` (NP, T, R).
+    The same bits on every run and for every ``limit``."""
+    fn = "lowrank_denoise"
+    X, Y, Z = (int(s) for s in sz)
+    P = X * Y * Z
+    if int(iters) != iters or int(iters) < 1:
+        raise ValueError(f"{fn}: iters={iters!r}: at least one pass (the first one finds the patches that cannot be used)")
+    if isinstance(frames, torch.Tensor):
+        rows = frames
+        T, rows_of, dev = rows.shape[0], (lambda r0, r1: rows[r0:r1]), rows.device
+    else:
+        rows_of = frames
+        if T is None:
+            raise ValueError(f"{fn}: a callable frames needs T")
+        dev = rows_of(0, 1).device
+    T = int(T)
+    plan = lowrank_patch_plan((X, Y, Z), patch, overlap)
+    step = max(1, min(T, (1 << 30) // (4 * P) if limit is None else int(limit)))
+    state = lowrank_state(plan, rank, T, dev)
+    c, s = _lowrank_image(fn, "centre", centre, P, dev), _lowrank_image(fn, "scale", scale, P, dev)
+
+    def pieces():
+        for r0 in range(0, T, step):
+            yield r0, rows_of(r0, min(T, r0 + step))
+    for _ in range(int(iters)):
+        for r0, fr in pieces():
+            lowrank_accumulate(fr, sz, plan, state, c, s, row0=r0)
+        lowrank_orthonormalise(state)
+    for r0, fr in pieces():
+        lowrank_project(fr, sz, plan, state, c, s, row0=r0)
+    lowrank_ritz(state, keep, threshold, sweeps=sweeps)
+    movie = _out_rows(fn, out, T, P, dev)
+    for r0, fr in pieces():
+        lowrank_reconstruct(fr, sz, plan, state, c, s, row0=r0, out=movie[r0:r0 + fr.shape[0]])
+    info = dict(plan=plan, kept=state["kept"], lam=state["lam"], ok=state["ok"], explained=state["explained"], U=state["U"],
+                Q=state["Q"])
+    return movie[:T, :P], info
 
 
 def _pass_rows(frames, sub, fid, P):

@@ -5,12 +5,16 @@ truth.  Needs an MI355X.
 
     python examples/demo_headless.py [--outer 5] [--epochs 10] [--iter-c 50] [--clean FPS] [--deconvolve] [--match]
                                         [--evaluate] [--merge] [--spatial-solver hals [--grow G] [--iter-a N]]
-                                        [--clean-footprints] [--add N] [--dff W] [--ar1 [SWEEPS] [--ar-penalty L]]
+                                        [--clean-footprints] [--add N] [--dff W] [--ar1 [SWEEPS] [--ar-penalty L]] [--denoise]
 
 ``--ar1``: after the fit, read the traces out twice from the fitted ``C`` on the same Gram data, with SWEEPS (default 10) sweeps of
 the exact solver (``update_footprints(solver='hals')``, K4h) and of the AR(1)-constrained update (``solver='ar1'``, K32: the
 simulator's decay e^-0.3, penalty ``--ar-penalty``, the baseline taken from the 'hals' traces), and print the median correlation of
 the simulator's traces with ``C`` for each.  The fitted ``C`` is put back afterwards.
+
+``--denoise``: after the fit, denoise the registered movie by local low-rank approximation (``DeformableNMF.denoise_movie``, K34,
+``registered='linear'``) and print the median number of components kept per patch and the peak of K18's ``corr`` image on the raw
+and on the denoised registered movie.
 
 ``--clean FPS``: also clean the traces up (``DeformableNMF.clean_traces``, K20) as if the video ran at FPS frames per second and
 print the median correlation of the simulator's traces with ``C`` and with the cleaned ``C``.
@@ -62,6 +66,7 @@ def main():
     ap.add_argument("--iter-a", type=int, default=5)
     ap.add_argument("--ar1", type=int, nargs="?", const=10, default=0, metavar="SWEEPS")
     ap.add_argument("--ar-penalty", type=float, default=0.0)
+    ap.add_argument("--denoise", action="store_true")
     a = ap.parse_args()
     torch.manual_seed(0)
     np.random.seed(0)
@@ -112,6 +117,15 @@ def main():
               "penalty %g, baseline = the 8th percentile of the 'hals' traces; %d colours, F %.6e -> %.6e)"
               % (a.ar1, hals, ar1, a.ar_penalty, info["n_colours"], info["F"][0], info["F"][1]))
         dnmf.C = fitted
+    if a.denoise:
+        sz_list = [int(n) for n in sz]
+        den = dnmf.denoise_movie(testloader, registered='linear')
+        raw = dnmf.summary_images(testloader, registered='linear')["corr"]
+        after = ExponentialFP.summary_images((den, sz_list))["corr"]
+        print("denoise: median kept per patch %g of rank %d (%d patches, %d usable); peak of the corr image: raw registered %.3f  "
+              "denoised %.3f" % (float(dnmf.last_denoise["kept"].float().median()), dnmf.last_denoise["lam"].shape[1],
+                                 dnmf.last_denoise["kept"].numel(), int(dnmf.last_denoise["ok"].sum()),
+                                 float(raw.nan_to_num(-1.0).max()), float(after.nan_to_num(-1.0).max())))
     if a.clean is not None:
         cleaned =dnmf.clean_traces(a.clean)[0].cpu().numpy().astype(np.float64)
 

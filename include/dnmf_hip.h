@@ -1320,6 +1320,47 @@ int dnmf_baseline_apply(const float *frames, long ldf, const int *frame_ids, con
                         long ldv, const double *centres, int J, int mode, double offset, float *out, long ldo,
                         dnmf_stream_t stream);
 
+/* ---- K34: local low-rank denoising of a registered movie: patch-wise truncated SVD, blended ----------------------------------------
+ * (csrc/lowrank_denoise.hip; tests/denoise_restatement.py is the definition.)  The volume is covered by patches of one shape:
+ * `plan` is a HOST array of 9 ints, per axis (count, stride, len) -- patch i of an axis starts at min(i stride, extent - len) and holds
+ * len <= extent voxels; the last one ends at the extent (count - 1) stride >= extent - len, no patch repeats it, stride <= len.  Patch
+ * p = (ix cy + iy) cz + iz; a voxel's index v in its patch runs z fastest; n = lenx leny lenz <= 1024 (dnmf_lowrank_patches: the
+ * number of patches NP, 0 on a bad plan; dnmf_lowrank_tile_frames(n): the frames K34a stages at once, 32, 16 above 256 voxels, 8
+ * above 512; 0 for n outside [1, 1024]).  All state is float64 on the device: U, W (NP, n, R), Q (NP, T, R), energy (NP, T), lam
+ * (NP, R), explained (NP); kept, ok (NP) int32.  1 <= R = rank <= 8.  centre, scale: (P) float64 images, scale NULL = ones;
+ * D[v, t] = (y[v, t] - centre[v]) / scale[v].  frames: B rows of ldf >= P floats, row frame_ids[i] (or i) the i-th of the call.
+ *
+ * K34a, dnmf_lowrank_accumulate.  W[p] += D_p (D_p^T U[p]) over the rows of the call: per frame q = D_t^T U (the voxels in order),
+ * then W[v, :] += D[v, t] q, the frames in order -- the same bits however the movie is cut into calls.  A sample or centre that is not
+ * finite, or a scale that is not finite or <= 0, sets ok[p] = 0 (the caller starts it at 1); a patch with ok = 0 is skipped.
+ * K34b, dnmf_lowrank_orthonormalise.  U[p] = MGS(W[p]) in column order -- a column whose norm after the projections is <= 1e-12 x
+ * its norm before becomes zero -- and W[p] = 0; U[p] = 0 where ok[p] = 0.
+ * K34c, dnmf_lowrank_project.  Q[p, row0 + i, :] = D_t^T U[p] and energy[p, row0 + i] = sum_v D[v, t]^2 for the rows of the call.
+ * K34d, dnmf_lowrank_ritz.  B = Q^T Q, `sweeps` sweeps of cyclic Jacobi (a parameter of the algorithm, not a tolerance), lam =
+ * the eigenvalues in descending order (ties by index), U and Q rotated to match; kept[p] = the number of lam > edge (keep < 0), or of
+ * lam > 0 among the first keep; explained[p] = sum of the kept lam / sum_t energy[p, t] (0 where that is 0).  ok[p] = 0: lam = 0,
+ * kept = 0, explained = 0.
+ * K34e, dnmf_lowrank_reconstruct.  out[i ldo + v] = fp32( sum_p w_p (centre + scale sum_{j < kept[p]} U[p, v, j] Q[p, row0 + i, j])
+ * / sum_p w_p ) over the patches p with ok[p] = 1 that hold v, ascending, w_p = prod_axes min(i + 1, len - i) for the in-patch
+ * coordinates i; frames[..] itself, bit for bit, where no such patch holds v (frames is read nowhere else).
+ * One workgroup per patch (a-d), one thread per voxel and 8 frames (e).  No floating-point atomics, no scratch, no workspace, no host
+ * synchronisation.  DNMF_E_NULL: a required pointer NULL;  DNMF_E_SHAPE: a size < 1, a plan that does not tile the volume, rank
+ * outside [1, 8], rows outside the movie, a leading dimension below P, sweeps outside [0, 64];  DNMF_E_UNSUPPORTED: n > 1024, 2^31
+ * voxels or patches or more, B > 8 x 65535 (K34e).  Nothing is launched on an error. */
+long dnmf_lowrank_patches(const int *sz, const int *plan);
+int dnmf_lowrank_tile_frames(int n);
+int dnmf_lowrank_accumulate(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, const int *plan, int rank,
+                            const double *centre, const double *scale, const double *U, double *W, int *ok, dnmf_stream_t stream);
+int dnmf_lowrank_orthonormalise(long NP, int n, int rank, double *U, double *W, const int *ok, dnmf_stream_t stream);
+int dnmf_lowrank_project(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, long row0, long T, const int *plan,
+                         int rank, const double *centre, const double *scale, const double *U, double *Q, double *energy, int *ok,
+                         dnmf_stream_t stream);
+int dnmf_lowrank_ritz(long NP, int n, long T, int rank, int keep, double edge, int sweeps, double *U, double *Q, const double *energy,
+                      const int *ok, double *lam, int *kept, double *explained, dnmf_stream_t stream);
+int dnmf_lowrank_reconstruct(const float *frames, long ldf, const int *frame_ids, const int *sz, int B, long row0, long T, const int *plan,
+                             int rank, const double *centre, const double *scale, const double *U, const double *Q, const int *kept,
+                             const int *ok, float *out, long ldo, dnmf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
