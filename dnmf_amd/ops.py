@@ -220,11 +220,13 @@ def recon_image(Apk: torch.Tensor, K: int, sz, C: torch.Tensor, times, out: torc
 
 def recon_image_lists(layout, K: int, sz, C: torch.Tensor, times, out: torch.Tensor | None = None,
                       skip_empty: bool = False) -> torch.Tensor:
-    """S as ``recon_image`` from the K3n layout (``pack_footprints_lists``): compact footprints, static tile lists.
-    ``skip_empty``: tiles without a neuron are left alone -- only for an ``out`` whose rows an earlier call with the same
-    layout and ``skip_empty=False`` has written (they hold zeros there)."""
+    """S as ``recon_image`` from the K3n layout (``pack_footprints_lists``): compact footprints, static tile lists.  C (K,T)
+    with any row stride, as there.  ``skip_empty``: tiles without a neuron are left alone -- only for an ``out`` whose rows
+    an earlier call with the same layout and ``skip_empty=False`` has written (they hold zeros there)."""
     X, Y, Z = (int(s) for s in sz)
-    _f32(C, "C")
+    _rows(C, "recon_image_lists", "C")
+    if C.dim() != 2 or C.shape[0] < K:
+        raise ValueError(f"recon_image_lists: C must be (K, T) with K = {K} rows, got {tuple(C.shape)}")
     tt = _i32(times, C.device)
     B = tt.numel()
     lds = halo_voxels(sz)
