@@ -7,25 +7,21 @@
 //      the sum over the listed columns in their order (all columns without a list), one product and one addition a term.  A frame
 //      whose w_t is not finite or <= 0, or whose y_t is not finite, carries no weight.  The pool record of the frame is written
 //      straight from them: num = w_t (y_t - b) - lam mu_t, den = w_t (0 without weight), mu_t = 1 - g, 1 on the last frame;
-//   2  lane i runs pool-adjacent-violators on its own `per` contiguous frames, then the stitch in log2(AR_THREADS) levels, then every
-//      lane expands the pools over its frames -- K21's scheme (deconvolve_traces.hip, whose comment explains it) with den = w_t
-//      where K21 has 1.  The device functions below restate K21's: that kernel stays as it is, bit for bit;
+//   2  the local pools of every lane's frames, the stitch, the expansion: ar1_pools.hpp's solver (that header explains the
+//      scheme), which K21 (deconvolve_traces.hip) uses with den = 1 where this kernel has w_t;
 //   3  row k of the state becomes b + c, the row of s the spikes.
 // g = 0 is the plain coordinate step max(0, y_t - b - lam / w_t) + b, a branch of its own (block-uniform) that never forms log 0.
-// The records take 24 bytes a frame and live in LDS: T <= AR_LDS_FRAMES.  No floating-point atomics, no scratch, counts are
-// integers: the same input gives the same bits.
+// The records live in LDS: T <= POOL_LDS_FRAMES.  No floating-point atomics, no scratch, counts are integers: the same input gives
+// the same bits.
 #include <cmath>
 #include <cstdint>
 
-#include "block_ops.hpp"
+#include "ar1_pools.hpp"
 
 namespace dnmf {
 namespace {
 
 constexpr int AR_THREADS = 1024;
-constexpr int AR_STATIC_LDS = 16 * 1024;                           // bytes set aside for the static arrays below (they take 8.2 KiB)
-constexpr int AR_RECORD = 24;                                      // bytes of a pool record: num, den (double), len, prev (int)
-constexpr int AR_LDS_FRAMES = (160 * 1024 - AR_STATIC_LDS) / AR_RECORD;   // 6144
 constexpr int AR_MAX_K = 4096;
 
 struct ArArgs {
@@ -38,38 +34,6 @@ struct ArArgs {
     double *s;
     int *counts;   // (K, 2): pools, weightless frames of row k
 };
-
-struct ArPools {
-    double *num, *den;
-    int *len, *prev;
-    double lng;
-};
-
-__device__ __forceinline__ bool violates(const ArPools &P, int p, int q) {
-    const double dp = P.den[p];
-    if (!(dp > 0.0)) return false;   // only a leading run of weightless frames: never merged into
-    const double dq = P.den[q];
-    if (!(dq > 0.0)) return true;    // weightless frames merge backwards
-    return P.num[q] / dq < (P.num[p] / dp) * exp((double)P.len[p] * P.lng);
-}
-
-__device__ __forceinline__ void merge(const ArPools &P, int p, int q) {
-    const double gl = exp((double)P.len[p] * P.lng);
-    P.num[p] = P.num[p] + gl * P.num[q];
-    P.den[p] = P.den[p] + gl * gl * P.den[q];
-    P.len[p] = P.len[p] + P.len[q];
-    P.len[q] = 0;
-}
-
-// merge p backwards while it violates -> the pool it ends up in
-__device__ __forceinline__ int settle(const ArPools &P, int p) {
-    for (;;) {
-        const int pp = P.prev[p];
-        if (pp < 0 || !violates(P, pp, p)) return p;
-        merge(P, pp, p);
-        p = pp;
-    }
-}
 
 __global__ __launch_bounds__(AR_THREADS) void ar1_temporal_kernel(ArArgs a) {
     extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -84,10 +48,7 @@ __global__ __launch_bounds__(AR_THREADS) void ar1_temporal_kernel(ArArgs a) {
     const int nl = a.nbr ? a.NN : K;
     const bool plain = !(g > 0.0);
 
-    ArPools P;
-    P.num = dyn, P.den = dyn + T;
-    P.len = reinterpret_cast<int *>(dyn + 2 * (size_t)T), P.prev = P.len + T;
-    P.lng = plain ? 0.0 : log(g);
+    const Pools P = pools_over<AR_THREADS>(dyn, T, plain ? 0.0 : log(g));
     const double mu = 1.0 - g;
 
     // ---- 1: weights, targets, records
@@ -117,69 +78,9 @@ __global__ __launch_bounds__(AR_THREADS) void ar1_temporal_kernel(ArArgs a) {
         return;
     }
 
-    // ---- 2: PAVA on the lane's own frames, the stitch, the expansion
-    const int per = (T + AR_THREADS - 1) / AR_THREADS;
-    const int c0 = (int)min((long)T, (long)tid * per), c1 = min(T, c0 + per);
-    int top = -1;
-    for (int t = c0; t < c1; ++t) {
-        P.len[t] = 1, P.prev[t] = top;
-        top = settle(P, t);
-    }
-    s_top[tid] = top;
-    __syncthreads();
-    // block [tid, tid + s) of segments takes in block [tid + s, tid + 2 s)
-    for (int s = 1; s < AR_THREADS; s <<= 1) {
-        if ((tid & (2 * s - 1)) == 0) {
-            const long first = (long)(tid + s) * per;
-            if (first < T) {
-                const int end = (int)min((long)T, (long)(tid + 2 * s) * per);
-                int p = s_top[tid], q = (int)first;
-                while (q < end) {
-                    if (!violates(P, p, q)) {
-                        P.prev[q] = p;
-                        break;
-                    }
-                    const int nxt = q + max(P.len[q], 1);   // a pool start: len >= 1
-                    merge(P, p, q);
-                    p = settle(P, p);
-                    q = nxt;
-                }
-                s_top[tid] = q >= end ? p : s_top[tid + s];
-            }
-        }
-        __syncthreads();
-    }
-    // the last pool start at or before the end of every lane's frames
-    int last = -1;
-    for (int t = c0; t < c1; ++t)
-        if (P.len[t] > 0) last = t;
-    s_last[tid] = last;
-    __syncthreads();
-    int pools = 0;
-    if (c0 < c1) {
-        int cur = -1;                                   // the pool that covers frame c0 - 1
-        for (int l = tid - 1; l >= 0 && cur < 0; --l) cur = s_last[l];
-        double cv = 0.0, cprev = 0.0;                   // the pool's max(v, 0); c of the frame before
-        if (cur >= 0) {
-            const double d = P.den[cur];
-            cv = d > 0.0 ? fmax(P.num[cur] / d, 0.0) : 0.0;
-            cprev = cv * exp((double)(c0 - 1 - cur) * P.lng);
-        }
-        for (int t = c0; t < c1; ++t) {
-            double c, s = 0.0;
-            if (P.len[t] > 0) {
-                cur = t, ++pools;
-                const double d = P.den[t];
-                cv = d > 0.0 ? fmax(P.num[t] / d, 0.0) : 0.0;
-                c = cv;
-                s = t == 0 ? c : fmax(c - g * cprev, 0.0);
-            } else {
-                c = cv * exp((double)(t - cur) * P.lng);
-            }
-            cprev = c;
-            crow[t] = b + c, srow[t] = s;
-        }
-    }
+    // ---- 2, 3: the local pools (the records are complete), the stitch, the expansion into the rows
+    pools_stitch<AR_THREADS>(P, pools_local(P, [](int) {}), s_top);
+    int pools = pools_expand<AR_THREADS>(P, g, s_last, [&](int t, double c, double s) { crow[t] = b + c, srow[t] = s; });
     pools = block_reduce<AR_THREADS>(pools, OpSum(), red);
     if (tid == 0) a.counts[2 * k] = pools, a.counts[2 * k + 1] = weightless;
 }
@@ -196,18 +97,15 @@ int dnmf_ar1_temporal_step(const float *G, const float *r, double *C, long ldc, 
     DNMF_REQUIRE(G && r && C && ids && g && penalty && baseline && s && counts, DNMF_E_NULL, "dnmf_ar1_temporal_step: NULL argument");
     DNMF_REQUIRE(K >= 1 && T >= 1 && ldc >= T && lds >= T && n_ids >= 1 && n_ids <= K && (!nbr || NN >= 1), DNMF_E_SHAPE,
                  "dnmf_ar1_temporal_step: K=%d T=%d ldc=%ld lds=%ld n_ids=%d NN=%d", K, T, ldc, lds, n_ids, NN);
-    DNMF_REQUIRE(T <= AR_LDS_FRAMES && K <= AR_MAX_K, DNMF_E_UNSUPPORTED,
+    DNMF_REQUIRE(T <= POOL_LDS_FRAMES && K <= AR_MAX_K, DNMF_E_UNSUPPORTED,
                  "dnmf_ar1_temporal_step: K=%d, T=%d: at most %d neurons and %d frames (a row's pool records must fit LDS)", K, T,
-                 AR_MAX_K, AR_LDS_FRAMES);
+                 AR_MAX_K, POOL_LDS_FRAMES);
     ArArgs a;
     a.G = G, a.r = r, a.C = C, a.ldc = ldc, a.lds = lds, a.K = K, a.T = T, a.n_ids = n_ids, a.NN = nbr ? NN : 0;
     a.ids = ids, a.nbr = nbr, a.g = g, a.penalty = penalty, a.baseline = baseline, a.s = s, a.counts = counts;
-    const unsigned lds_bytes = ((unsigned)T * AR_RECORD + 15u) & ~15u;
-    if (lds_bytes > 48u * 1024u) {   // beyond the default limit of dynamic LDS
-        const hipError_t e = hipFuncSetAttribute((const void *)ar1_temporal_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds_bytes);
-        if (e != hipSuccess) return fail((int)e, "dnmf_ar1_temporal_step: %u bytes of LDS: %s", lds_bytes, hipGetErrorString(e));
-    }
+    const unsigned lds_bytes = ((unsigned)T * POOL_RECORD + 15u) & ~15u;
+    const int rl = allow_dynamic_lds("dnmf_ar1_temporal_step", (const void *)ar1_temporal_kernel, lds_bytes);
+    if (rl != DNMF_OK) return rl;
     hipLaunchKernelGGL(ar1_temporal_kernel, dim3((unsigned)n_ids), dim3(AR_THREADS), lds_bytes, (hipStream_t)stream, a);
     return check_launch("dnmf_ar1_temporal_step");
 }

@@ -17,7 +17,7 @@
 //   NN == 0 (dense):  K/64 entries per lane straight from global memory, the next row in flight while this one is used;
 //   NN in {8,16,32}:  the NN listed entries of every row staged in LDS once (from a dense G or from the K3n slot tables),
 //                     NN lanes each touching one entry of g.
-#include "common.hpp"
+#include "trace_calls.hpp"
 
 namespace dnmf {
 
@@ -57,12 +57,7 @@ __global__ __launch_bounds__(256) void hals_temporal_kernel(const float *__restr
     (void)rows;
 
     const float *Gt = src + (SLOTS ? (long)t * nchunks * nslot : (long)t * K * K);
-    auto slot_sum = [&](int slot) {   // what gram_lists_finish_kernel would have written: ordered sum over the chunks
-        float s = 0.0f;
-        if ((unsigned)slot < (unsigned)(nslot - 1))   // the trash slot nslot - 1 stands for an exact zero
-            for (int ch = 0; ch < nchunks; ++ch) s += Gt[(long)ch * nslot + slot];
-        return s;
-    };
+    auto slot_sum = [&](int slot) { return slot_chunk_sum(Gt, nchunks, nslot, slot); };   // as gram_lists_finish_kernel sums
     auto column = [&](int k, int j) {   // the j-th listed column of row k; -1 for an entry outside [0,K), which then
         const int l = nbr[k * NN + j];  // contributes nothing anywhere (the contract wants none: no read out of bounds)
         return (unsigned)l < (unsigned)K ? l : -1;
@@ -182,20 +177,12 @@ static int hals_launch(const char *what, bool slots, const float *src, const flo
     const int wpb = (int)(wb * 4 <= 61440 ? 4 : (wb * 2 <= 61440 ? 2 : 1));   // <= 60 KiB of LDS per workgroup
     const dim3 grid((unsigned)((nframes + wpb - 1) / wpb)), block(64 * wpb);
     const size_t lds = wb * wpb;
-#define DNMF_HALS(NN_, SL_)                                                                                              \
-    hipLaunchKernelGGL((hals_temporal_kernel<NN_, SL_>), grid, block, lds, st, src, r, nchunks, nslot, pair_slot, nbr, C32, \
-                       C64, ldc, K, T, nframes, iters, gamma, parity, kkt, (unsigned)wb)
-    if (slots) {
-        if (NN == 8) DNMF_HALS(8, true);
-        else if (NN == 16) DNMF_HALS(16, true);
-        else DNMF_HALS(32, true);
-    } else {
-        if (NN == 0) DNMF_HALS(0, false);
-        else if (NN == 8) DNMF_HALS(8, false);
-        else if (NN == 16) DNMF_HALS(16, false);
-        else DNMF_HALS(32, false);
-    }
-#undef DNMF_HALS
+    auto launch = [&](auto nn, auto sl) {
+        hipLaunchKernelGGL((hals_temporal_kernel<decltype(nn)::value, decltype(sl)::value>), grid, block, lds, st, src, r, nchunks,
+                           nslot, pair_slot, nbr, C32, C64, ldc, K, T, nframes, iters, gamma, parity, kkt, (unsigned)wb);
+    };
+    if (slots) with_list_width<false>(NN, [&](auto nn) { launch(nn, std::true_type{}); });
+    else with_list_width<true>(NN, [&](auto nn) { launch(nn, std::false_type{}); });
     return check_launch(what);
 }
 
@@ -207,11 +194,9 @@ int dnmf_hals_temporal(const float *G, const float *r, float *C, long ldc, int K
                        double *kkt, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(G && r && C, DNMF_E_NULL, "dnmf_hals_temporal: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && iters >= 0, DNMF_E_SHAPE, "dnmf_hals_temporal: K=%d T=%d ldc=%ld iters=%d", K,
-                 T, ldc, iters);
     if (!nbr) NN = 0;
-    DNMF_REQUIRE(K <= 256 && (NN == 0 || NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_hals_temporal: K=%d (<= 256), NN=%d (8, 16 or 32 with nbr)", K, NN);
+    const int rc = check_trace_call("dnmf_hals_temporal", K, T, ldc, LISTS_OR_DENSE, NN, iters >= 0, " iters=%d", iters);
+    if (rc != DNMF_OK) return rc;
     return hals_launch("dnmf_hals_temporal", false, G, r, 0, 0, nullptr, nbr, NN, C, nullptr, ldc, K, T, iters, 0.0, -1, kkt,
                        (hipStream_t)stream);
 }
@@ -220,10 +205,9 @@ int dnmf_hals_temporal_slots(const float *slab, int nchunks, int nslot, const in
                              int T, int iters, const int *nbr, int NN, double *kkt, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(slab && pair_slot && C && nbr, DNMF_E_NULL, "dnmf_hals_temporal_slots: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && iters >= 0 && nchunks > 0 && nslot > K, DNMF_E_SHAPE,
-                 "dnmf_hals_temporal_slots: K=%d T=%d ldc=%ld iters=%d nchunks=%d nslot=%d", K, T, ldc, iters, nchunks, nslot);
-    DNMF_REQUIRE(K <= 256 && (NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_hals_temporal_slots: K=%d (<= 256), NN=%d (8, 16 or 32)", K, NN);
+    const int rc = check_trace_call("dnmf_hals_temporal_slots", K, T, ldc, LISTS_ONLY, NN, iters >= 0 && nchunks > 0 && nslot > K,
+                                    " iters=%d nchunks=%d nslot=%d", iters, nchunks, nslot);
+    if (rc != DNMF_OK) return rc;
     return hals_launch("dnmf_hals_temporal_slots", true, slab, nullptr, nchunks, nslot, pair_slot, nbr, NN, C, nullptr, ldc, K,
                        T, iters, 0.0, -1, kkt, (hipStream_t)stream);
 }
@@ -232,11 +216,10 @@ int dnmf_hals_temporal_step(const float *G, const float *r, double *C, long ldc,
                             const int *nbr, int NN, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(G && r && C, DNMF_E_NULL, "dnmf_hals_temporal_step: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && (parity == 0 || parity == 1), DNMF_E_SHAPE,
-                 "dnmf_hals_temporal_step: K=%d T=%d ldc=%ld parity=%d (0 or 1)", K, T, ldc, parity);
     if (!nbr) NN = 0;
-    DNMF_REQUIRE(K <= 256 && (NN == 0 || NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_hals_temporal_step: K=%d (<= 256), NN=%d (8, 16 or 32 with nbr)", K, NN);
+    const int rc = check_trace_call("dnmf_hals_temporal_step", K, T, ldc, LISTS_OR_DENSE, NN, parity == 0 || parity == 1,
+                                    " parity=%d (0 or 1)", parity);
+    if (rc != DNMF_OK) return rc;
     return hals_launch("dnmf_hals_temporal_step", false, G, r, 0, 0, nullptr, nbr, NN, nullptr, C, ldc, K, T, 1, gamma, parity,
                        nullptr, (hipStream_t)stream);
 }
@@ -245,10 +228,9 @@ int dnmf_hals_temporal_kkt(const float *G, const float *r, const double *C, long
                            const int *nbr, int NN, double *kkt, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(G && r && C && kkt, DNMF_E_NULL, "dnmf_hals_temporal_kkt: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T, DNMF_E_SHAPE, "dnmf_hals_temporal_kkt: K=%d T=%d ldc=%ld", K, T, ldc);
     if (!nbr) NN = 0;
-    DNMF_REQUIRE(K <= 256 && (NN == 0 || NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_hals_temporal_kkt: K=%d (<= 256), NN=%d (8, 16 or 32 with nbr)", K, NN);
+    const int rc = check_trace_call("dnmf_hals_temporal_kkt", K, T, ldc, LISTS_OR_DENSE, NN, true, "");
+    if (rc != DNMF_OK) return rc;
     // iters == 0: the kernel reads C and writes kkt only
     return hals_launch("dnmf_hals_temporal_kkt", false, G, r, 0, 0, nullptr, nbr, NN, nullptr, const_cast<double *>(C), ldc, K,
                        T, 0, gamma, -1, kkt, (hipStream_t)stream);

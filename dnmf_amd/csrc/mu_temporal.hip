@@ -5,7 +5,7 @@
 // iter_c rounds although neither depends on C; here they come from K3 once and only
 //   c_t <- c_t * (r_t + gamma*nbr_t) / (G_t c_t + 2 gamma c_t + 1e-32)
 // is iterated.  One workgroup per frame, thread k owns c[k]; arithmetic in fp64 (numpy's dtype there).
-#include "common.hpp"
+#include "trace_calls.hpp"
 
 namespace dnmf {
 
@@ -50,64 +50,36 @@ __global__ __launch_bounds__(256) void mu_temporal_kernel(const float *__restric
 // the two part: the dense form, like the reference's numpy, turns the whole frame NaN through 0 * inf, this form only
 // the rows whose list names the overflowing neuron -- and, a round later each, the rows that list those, padding
 // columns included (tests/test_gpu_mu_temporal.py::test_overflowing_trace).
-template <int NN>
-__global__ __launch_bounds__(256) void mu_temporal_nbr_kernel(const float *__restrict__ G, const float *__restrict__ r,
-                                                              float *__restrict__ C, long ldc, int K, int iters,
-                                                              const int *__restrict__ nbr) {
-    __shared__ double cs[256];
-    const int t = blockIdx.x;
-    const int k = threadIdx.x;
-    const float *Gt = G + (long)t * K * K;
-    const bool live = k < K;
-    double g[NN];
-    int li[NN];
-#pragma unroll
-    for (int j = 0; j < NN; ++j) {
-        li[j] = live ? nbr[k * NN + j] : 0;
-        g[j] = live ? (double)Gt[(long)li[j] * K + k] : 0.0;
-    }
-    const double rk = live ? (double)r[(long)t * K + k] : 0.0;
-    double c = live ? (double)C[(long)k * ldc + t] : 0.0;
-    for (int it = 0; it < iters; ++it) {
-        cs[k] = c;
-        __syncthreads();
-        double dot = 0.0;
-#pragma unroll
-        for (int j = 0; j < NN; ++j) dot = fma(g[j], cs[li[j]], dot);
-        c = (c * rk) / (dot + 1e-32);
-        __syncthreads();
-    }
-    if (live) C[(long)k * ldc + t] = (float)c;
-}
-
-// The same again, reading the slot tables K3n left in its workspace instead of a dense G: entry (k,l) is the ordered
-// sum over the chunks of slot pair_slot[k][l] -- exactly what gram_lists_finish_kernel would have written -- and r[k]
-// the sum of slot k.  Saves writing and re-reading (T,K,K).  Equal to mu_temporal_nbr_kernel on the finished G, r bit
-// for bit, and so to the dense form under the same condition: while every trace of the frame is finite.
-template <int NN>
-__global__ __launch_bounds__(256) void mu_temporal_slots_kernel(const float *__restrict__ slab, int nchunks, int nslot,
-                                                                const int *__restrict__ pair_slot,
+//
+// SLOTS: the same again, reading the slot tables K3n left in its workspace (src: (T, nchunks, nslot) floats) instead of a dense G:
+// entry (k,l) is slot pair_slot[k][l] and r[k] slot k, each summed over the chunks as gram_lists_finish_kernel sums them
+// (slot_chunk_sum).  Saves writing and re-reading (T,K,K).  Equal to the form on the finished G, r bit for bit, and so to the
+// dense form under the same condition: while every trace of the frame is finite.
+template <int NN, bool SLOTS>
+__global__ __launch_bounds__(256) void mu_temporal_lists_kernel(const float *__restrict__ src, const float *__restrict__ r,
+                                                                int nchunks, int nslot, const int *__restrict__ pair_slot,
                                                                 float *__restrict__ C, long ldc, int K, int iters,
                                                                 const int *__restrict__ nbr) {
     __shared__ double cs[256];
     const int t = blockIdx.x;
     const int k = threadIdx.x;
-    const float *src = slab + (long)t * nchunks * nslot;
+    const float *Gt = src + (SLOTS ? (long)t * nchunks * nslot : (long)t * K * K);
     const bool live = k < K;
-    auto slot_sum = [&](int slot) {
-        float s = 0.0f;
-        if (slot != nslot - 1)
-            for (int c = 0; c < nchunks; ++c) s += src[(long)c * nslot + slot];
-        return s;
-    };
     double g[NN];
     int li[NN];
 #pragma unroll
     for (int j = 0; j < NN; ++j) {
         li[j] = live ? nbr[k * NN + j] : 0;
-        g[j] = live ? (double)slot_sum(pair_slot[(long)li[j] * K + k]) : 0.0;
+        if constexpr (SLOTS)
+            g[j] = live ? (double)slot_chunk_sum(Gt, nchunks, nslot, pair_slot[(long)li[j] * K + k]) : 0.0;
+        else
+            g[j] = live ? (double)Gt[(long)li[j] * K + k] : 0.0;
     }
-    const double rk = live ? (double)slot_sum(k) : 0.0;
+    double rk = 0.0;
+    if constexpr (SLOTS)
+        rk = live ? (double)slot_chunk_sum(Gt, nchunks, nslot, k) : 0.0;
+    else
+        rk = live ? (double)r[(long)t * K + k] : 0.0;
     double c = live ? (double)C[(long)k * ldc + t] : 0.0;
     for (int it = 0; it < iters; ++it) {
         cs[k] = c;
@@ -153,10 +125,8 @@ int dnmf_mu_temporal(const float *G, const float *r, float *C, long ldc, int K, 
                      dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(G && r && C, DNMF_E_NULL, "dnmf_mu_temporal: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && iters >= 0, DNMF_E_SHAPE, "dnmf_mu_temporal: K=%d T=%d ldc=%ld iters=%d", K,
-                 T, ldc, iters);
-    DNMF_REQUIRE(K <= 256, DNMF_E_UNSUPPORTED, "dnmf_mu_temporal: K=%d > 256 (not built yet)", K);
-    if (iters == 0) return DNMF_OK;
+    const int rc = check_trace_call("dnmf_mu_temporal", K, T, ldc, DENSE_ONLY, 0, iters >= 0, " iters=%d", iters);
+    if (rc != DNMF_OK || iters == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)T);
     if (K <= 32)
@@ -174,19 +144,13 @@ int dnmf_mu_temporal_nbr(const float *G, const float *r, float *C, long ldc, int
                          int NN, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(G && r && C && nbr, DNMF_E_NULL, "dnmf_mu_temporal_nbr: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && iters >= 0, DNMF_E_SHAPE, "dnmf_mu_temporal_nbr: K=%d T=%d ldc=%ld iters=%d",
-                 K, T, ldc, iters);
-    DNMF_REQUIRE(K <= 256 && (NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_mu_temporal_nbr: K=%d (<= 256), NN=%d (8, 16 or 32)", K, NN);
-    if (iters == 0) return DNMF_OK;
-    hipStream_t st = (hipStream_t)stream;
+    const int rc = check_trace_call("dnmf_mu_temporal_nbr", K, T, ldc, LISTS_ONLY, NN, iters >= 0, " iters=%d", iters);
+    if (rc != DNMF_OK || iters == 0) return rc;
     const dim3 grid((unsigned)T), block(K <= 64 ? 64 : (K <= 128 ? 128 : 256));
-    if (NN == 8)
-        hipLaunchKernelGGL(mu_temporal_nbr_kernel<8>, grid, block, 0, st, G, r, C, ldc, K, iters, nbr);
-    else if (NN == 16)
-        hipLaunchKernelGGL(mu_temporal_nbr_kernel<16>, grid, block, 0, st, G, r, C, ldc, K, iters, nbr);
-    else
-        hipLaunchKernelGGL(mu_temporal_nbr_kernel<32>, grid, block, 0, st, G, r, C, ldc, K, iters, nbr);
+    with_list_width<false>(NN, [&](auto nn) {
+        hipLaunchKernelGGL((mu_temporal_lists_kernel<decltype(nn)::value, false>), grid, block, 0, (hipStream_t)stream, G, r, 0, 0,
+                           nullptr, C, ldc, K, iters, nbr);
+    });
     return check_launch("dnmf_mu_temporal_nbr");
 }
 
@@ -194,19 +158,14 @@ int dnmf_mu_temporal_slots(const float *slab, int nchunks, int nslot, const int 
                            int T, int iters, const int *nbr, int NN, dnmf_stream_t stream) {
     using namespace dnmf;
     DNMF_REQUIRE(slab && pair_slot && C && nbr, DNMF_E_NULL, "dnmf_mu_temporal_slots: NULL buffer");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T && iters >= 0 && nchunks > 0 && nslot > K, DNMF_E_SHAPE,
-                 "dnmf_mu_temporal_slots: K=%d T=%d ldc=%ld iters=%d nchunks=%d nslot=%d", K, T, ldc, iters, nchunks, nslot);
-    DNMF_REQUIRE(K <= 256 && (NN == 8 || NN == 16 || NN == 32), DNMF_E_UNSUPPORTED,
-                 "dnmf_mu_temporal_slots: K=%d (<= 256), NN=%d (8, 16 or 32)", K, NN);
-    if (iters == 0) return DNMF_OK;
-    hipStream_t st = (hipStream_t)stream;
+    const int rc = check_trace_call("dnmf_mu_temporal_slots", K, T, ldc, LISTS_ONLY, NN, iters >= 0 && nchunks > 0 && nslot > K,
+                                    " iters=%d nchunks=%d nslot=%d", iters, nchunks, nslot);
+    if (rc != DNMF_OK || iters == 0) return rc;
     const dim3 grid((unsigned)T), block(K <= 64 ? 64 : (K <= 128 ? 128 : 256));
-    if (NN == 8)
-        hipLaunchKernelGGL(mu_temporal_slots_kernel<8>, grid, block, 0, st, slab, nchunks, nslot, pair_slot, C, ldc, K, iters, nbr);
-    else if (NN == 16)
-        hipLaunchKernelGGL(mu_temporal_slots_kernel<16>, grid, block, 0, st, slab, nchunks, nslot, pair_slot, C, ldc, K, iters, nbr);
-    else
-        hipLaunchKernelGGL(mu_temporal_slots_kernel<32>, grid, block, 0, st, slab, nchunks, nslot, pair_slot, C, ldc, K, iters, nbr);
+    with_list_width<false>(NN, [&](auto nn) {
+        hipLaunchKernelGGL((mu_temporal_lists_kernel<decltype(nn)::value, true>), grid, block, 0, (hipStream_t)stream, slab,
+                           nullptr, nchunks, nslot, pair_slot, C, ldc, K, iters, nbr);
+    });
     return check_launch("dnmf_mu_temporal_slots");
 }
 
@@ -215,8 +174,8 @@ int dnmf_mu_temporal_step(const float *G, const float *r, const double *Cin, dou
     using namespace dnmf;
     DNMF_REQUIRE(G && r && Cin && Cout, DNMF_E_NULL, "dnmf_mu_temporal_step: NULL buffer");
     DNMF_REQUIRE(Cin != Cout, DNMF_E_SHAPE, "dnmf_mu_temporal_step: Cin and Cout must be distinct buffers");
-    DNMF_REQUIRE(K > 0 && T > 0 && ldc >= T, DNMF_E_SHAPE, "dnmf_mu_temporal_step: K=%d T=%d ldc=%ld", K, T, ldc);
-    DNMF_REQUIRE(K <= 256, DNMF_E_UNSUPPORTED, "dnmf_mu_temporal_step: K=%d > 256 (not built yet)", K);
+    const int rc = check_trace_call("dnmf_mu_temporal_step", K, T, ldc, DENSE_ONLY, 0, true, "");
+    if (rc != DNMF_OK) return rc;
     const int block = K <= 64 ? 64 : (K <= 128 ? 128 : 256);
     hipLaunchKernelGGL(mu_temporal_step_kernel, dim3((unsigned)T), dim3(block), 0, (hipStream_t)stream, G, r, Cin, Cout,
                        ldc, K, T, gamma, c_left, c_right);

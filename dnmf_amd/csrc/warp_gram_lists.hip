@@ -144,9 +144,7 @@ __global__ __launch_bounds__(256) void gram_lists_finish_kernel(const float *__r
     const float *src = slab + (long)b * nchunks * nslot;
     for (int e = threadIdx.x; e < K * K + K; e += blockDim.x) {
         const int slot = e < K * K ? pair_slot[e] : e - K * K;
-        float s = 0.0f;
-        if (slot != nslot - 1)
-            for (int c = 0; c < nchunks; ++c) s += src[(long)c * nslot + slot];
+        const float s = slot_chunk_sum(src, nchunks, nslot, slot);
         if (e < K * K)
             G[(long)b * K * K + e] = s;
         else

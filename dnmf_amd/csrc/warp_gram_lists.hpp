@@ -77,6 +77,19 @@ __host__ __device__ inline long axis_masks_offset(const Volume &vol, int d, int 
 }
 __host__ __device__ inline long axis_masks_entries(const Volume &vol) { return 2L * (vol.X + vol.Y + vol.Z + 6); }
 
+// ---- reading the slot tables -----------------------------------------------------------------------------
+// The value of `slot` in a frame whose nchunks tables of nslot floats start at `tables`: the sum over the chunks in their order.
+// This is what gram_lists_finish_kernel writes to G and r, and what the slot forms of K4 and K4h read in its place (trace_calls.hpp),
+// so the three agree bit for bit.  The trash slot nslot - 1 stands for an exact zero.  The unsigned comparison also makes a zero
+// of a negative slot or of one >= nslot instead of reading out of bounds; the layout produces neither (an rhs slot is a neuron
+// index below K <= nslot - 1, pair_slot holds pattern slots and the trash slot only).
+__device__ __forceinline__ float slot_chunk_sum(const float *__restrict__ tables, int nchunks, int nslot, int slot) {
+    float s = 0.0f;
+    if ((unsigned)slot < (unsigned)(nslot - 1))
+        for (int c = 0; c < nchunks; ++c) s += tables[(long)c * nslot + slot];
+    return s;
+}
+
 // PASS 1: the tiles with at most LISTS_NG neurons; PASS 2: the other tiles, into tables of their own (the consumers sum
 // a frame's tables in order), launched on a side stream so that the two run side by side: pass 2 alone is a chain of
 // memory round trips per tile with nothing to hide them behind.  Two kernels because the compiler allocates registers for the union

@@ -522,13 +522,18 @@ def warp_gram_rhs(Apk, K, sz, beta, times, frames, frame_ids=None, a_frame_strid
     return G, r, workspace
 
 
+def _state(fn, C, dtype, name="C", shape=""):
+    """The (K,T) state of a trace update (K4, K4h, K32) as the kernels take it: ``dtype`` CUDA, unit inner stride, any row stride."""
+    if not (C.is_cuda and C.dtype == dtype and C.dim() == 2 and C.stride(1) == 1):
+        raise ValueError(f"{fn}: {name} must be {str(dtype).split('.')[-1]} CUDA{shape} with unit inner stride")
+
+
 def mu_temporal(G, r, C, iters: int, nbr=None):
     """K4 without the neighbour term: C (K,T) fp32 updated in place.  ``nbr`` (K,NN) int32: the columns of G that
     can be non-zero per row (``pack_footprints_lists``) -- same result while every trace is finite, NN instead of K terms
     per row."""
     _f32(G, "G"), _f32(r, "r")
-    if not (C.is_cuda and C.dtype == torch.float32 and C.stride(1) == 1):
-        raise ValueError("mu_temporal: C must be float32 CUDA with unit inner stride")
+    _state("mu_temporal", C, torch.float32)
     T, K = r.shape
     if nbr is not None:
         _lib.check(_lib.load().dnmf_mu_temporal_nbr(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T, int(iters),
@@ -542,9 +547,7 @@ def mu_temporal(G, r, C, iters: int, nbr=None):
 def mu_temporal_step(G, r, Cin, Cout, gamma: float, c_left=None, c_right=None):
     """K4, one round with the neighbour term; Cin/Cout (K,T) float64 with the same row stride (the ABI has one ldc)."""
     _f32(G, "G"), _f32(r, "r")
-    for t, n in ((Cin, "Cin"), (Cout, "Cout")):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.stride(1) == 1):
-            raise ValueError(f"mu_temporal_step: {n} must be float64 CUDA with unit inner stride")
+    _state("mu_temporal_step", Cin, torch.float64, "Cin"), _state("mu_temporal_step", Cout, torch.float64, "Cout")
     if Cout.stride(0) != Cin.stride(0):
         raise ValueError(f"mu_temporal_step: Cin and Cout must have the same row stride, got Cin.stride(0)="
                          f"{Cin.stride(0)} and Cout.stride(0)={Cout.stride(0)}")
@@ -555,7 +558,7 @@ def mu_temporal_step(G, r, Cin, Cout, gamma: float, c_left=None, c_right=None):
     return Cout
 
 
-def _hals_nbr(fn, nbr, K):
+def _nbr_table(fn, nbr, K):
     """``(pointer, NN)`` of an optional (K,NN) int32 neighbour table."""
     if nbr is None:
         return 0, 0
@@ -564,7 +567,7 @@ def _hals_nbr(fn, nbr, K):
     return nbr.data_ptr(), nbr.shape[1]
 
 
-def _hals_gram(fn, G, r, C):
+def _gram_against_state(fn, G, r, C):
     """Shapes of G (T,K,K), r (T,K) against the state C (K,T); returns (K, T)."""
     _f32(G, "G"), _f32(r, "r")
     K, T = C.shape
@@ -578,12 +581,11 @@ def hals_temporal(G, r, C, iters: int, nbr=None, kkt=False):
     ``1/2 c^T G_t c - r_t^T c, c >= 0`` per frame; C (K,T) fp32 updated in place.  ``nbr`` as for ``mu_temporal``.
     ``kkt=True``: returns ``(C, kkt)``, kkt (T) float64 = the largest projected-gradient entry per frame after the last
     sweep (zero at the NNLS solution)."""
-    if not (C.is_cuda and C.dtype == torch.float32 and C.dim() == 2 and C.stride(1) == 1):
-        raise ValueError("hals_temporal: C must be float32 CUDA with unit inner stride")
-    K, T = _hals_gram("hals_temporal", G, r, C)
+    _state("hals_temporal", C, torch.float32)
+    K, T = _gram_against_state("hals_temporal", G, r, C)
     if int(iters) < 0:
         raise ValueError(f"hals_temporal: iters={iters} < 0")
-    pn, NN = _hals_nbr("hals_temporal", nbr, K)
+    pn, NN = _nbr_table("hals_temporal", nbr, K)
     out = torch.empty((T,), dtype=torch.float64, device=C.device) if kkt else None
     with _timed("hals_temporal"):
         rc = _lib.load().dnmf_hals_temporal(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T, int(iters), pn, NN,
@@ -595,12 +597,11 @@ def hals_temporal(G, r, C, iters: int, nbr=None, kkt=False):
 def hals_temporal_step(G, r, C, gamma: float, parity: int, nbr=None):
     """K4h, one half sweep with the neighbour term on the fp64 state C (K,T), in place: the frames ``parity, parity + 2,
     ...`` are updated.  A sweep is parity 0, then parity 1."""
-    if not (C.is_cuda and C.dtype == torch.float64 and C.dim() == 2 and C.stride(1) == 1):
-        raise ValueError("hals_temporal_step: C must be float64 CUDA with unit inner stride")
+    _state("hals_temporal_step", C, torch.float64)
     if parity not in (0, 1):
         raise ValueError(f"hals_temporal_step: parity={parity!r}, expected 0 or 1")
-    K, T = _hals_gram("hals_temporal_step", G, r, C)
-    pn, NN = _hals_nbr("hals_temporal_step", nbr, K)
+    K, T = _gram_against_state("hals_temporal_step", G, r, C)
+    pn, NN = _nbr_table("hals_temporal_step", nbr, K)
     with _timed("hals_temporal_step"):
         rc = _lib.load().dnmf_hals_temporal_step(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T, float(gamma),
                                                  int(parity), pn, NN, _stream())
@@ -611,10 +612,9 @@ def hals_temporal_step(G, r, C, gamma: float, parity: int, nbr=None):
 def hals_temporal_kkt(G, r, C, gamma: float = 0.0, nbr=None):
     """(T) float64: the largest projected-gradient entry per frame of the fp64 state C (K,T) under ``gamma`` (the measure
     ``hals_temporal(..., kkt=True)`` returns, for any state and with the neighbour term)."""
-    if not (C.is_cuda and C.dtype == torch.float64 and C.dim() == 2 and C.stride(1) == 1):
-        raise ValueError("hals_temporal_kkt: C must be float64 CUDA with unit inner stride")
-    K, T = _hals_gram("hals_temporal_kkt", G, r, C)
-    pn, NN = _hals_nbr("hals_temporal_kkt", nbr, K)
+    _state("hals_temporal_kkt", C, torch.float64)
+    K, T = _gram_against_state("hals_temporal_kkt", G, r, C)
+    pn, NN = _nbr_table("hals_temporal_kkt", nbr, K)
     out = torch.empty((T,), dtype=torch.float64, device=C.device)
     with _timed("hals_temporal_kkt"):
         rc = _lib.load().dnmf_hals_temporal_kkt(G.data_ptr(), r.data_ptr(), C.data_ptr(), C.stride(0), K, T,
@@ -963,8 +963,7 @@ def warp_gram_rhs_lists(layout, K, sz, beta, times, frames, frame_ids=None, work
 def mu_temporal_slots(layout, workspace, sz, C, iters: int, passes=None, chunks=None):
     """K4 straight from the slot tables ``warp_gram_rhs_lists(..., finish=False)`` left in ``workspace``; C (K,T) fp32
     updated in place (T = the frames of that launch, ``passes`` and ``chunks`` those of that launch).  Needs ``layout["nbr"]``."""
-    if not (C.is_cuda and C.dtype == torch.float32 and C.stride(1) == 1):
-        raise ValueError("mu_temporal_slots: C must be float32 CUDA with unit inner stride")
+    _state("mu_temporal_slots", C, torch.float32)
     K, T = C.shape
     lib = _lib.load()
     nbr = layout["nbr"]
@@ -980,8 +979,7 @@ def hals_temporal_slots(layout, workspace, sz, C, iters: int, kkt=False, passes=
     """K4h straight from the slot tables ``warp_gram_rhs_lists(..., finish=False)`` left in ``workspace``; C (K,T) fp32
     updated in place (T = the frames of that launch, ``passes`` and ``chunks`` those of that launch).  Needs
     ``layout["nbr"]``.  ``kkt`` as for ``hals_temporal``."""
-    if not (C.is_cuda and C.dtype == torch.float32 and C.dim() == 2 and C.stride(1) == 1):
-        raise ValueError("hals_temporal_slots: C must be float32 CUDA with unit inner stride")
+    _state("hals_temporal_slots", C, torch.float32)
     if int(iters) < 0:
         raise ValueError(f"hals_temporal_slots: iters={iters} < 0")
     K, T = C.shape
@@ -2670,7 +2668,7 @@ def deconvolve_traces(traces, g=None, penalty=None, baseline=None, noise=None, b
     return c, s, info
 
 
-AR1_MAX_FRAMES = 6144   # K32: a row's pool records (24 bytes a frame) live in LDS
+AR1_MAX_FRAMES = 6144   # K32: POOL_LDS_FRAMES of csrc/ar1_pools.hpp, where the number and its reason live
 AR1_MAX_K = 4096
 
 
@@ -2717,9 +2715,8 @@ def _ar1_lists(nbr, K):
 
 
 def _ar1_check(fn, G, r, C64, nbr):
-    if not (C64.is_cuda and C64.dtype == torch.float64 and C64.dim() == 2 and C64.stride(1) == 1):
-        raise ValueError(f"{fn}: the state must be float64 CUDA (K, T) with unit inner stride")
-    K, T = _hals_gram(fn, G, r, C64)
+    _state(fn, C64, torch.float64, "the state", " (K, T)")
+    K, T = _gram_against_state(fn, G, r, C64)
     if T > AR1_MAX_FRAMES or K > AR1_MAX_K:
         raise ValueError(f"{fn}: K={K}, T={T}: at most {AR1_MAX_K} neurons and {AR1_MAX_FRAMES} consecutive frames a call (a row's "
                          "pool records live in LDS); a longer run is refused, not cut")
@@ -2796,8 +2793,8 @@ def ar1_temporal(G, r, C, g, penalty=0.0, baseline=0.0, sweeps=1, nbr=None):
     updated in place: the float64 state is kept across the sweeps and rounded to fp32 once at the end.  ``g`` in [0, 1) (0: the
     plain non-negative step for that neuron), ``penalty`` >= 0, ``baseline``: a number or (K,) each.  -> ``(C, s, info)``: s (K, T)
     float64, the spikes; ``info``: ``colour`` (K,) int32 numpy and ``n_colours``, ``n_pools`` and ``n_weightless`` (K,) int32 of
-    every row's last step, and ``state``, the float64 (K, T) state before the rounding.  T <= 6144 and K <= 4096: anything larger
-    is refused.  Sums in a fixed order without floating-point atomics: the same input gives the same bits."""
+    every row's last step, and ``state``, the float64 (K, T) state before the rounding.  T <= ``AR1_MAX_FRAMES`` and
+    K <= ``AR1_MAX_K``: anything larger is refused.  Sums in a fixed order without floating-point atomics: the same input gives the same bits."""
     fn = "ar1_temporal"
     if not (isinstance(C, torch.Tensor) and C.dim() == 2):
         raise ValueError(f"{fn}: C is a (K, T) tensor")

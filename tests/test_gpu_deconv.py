@@ -23,7 +23,9 @@ import deconv_restatement as DR
 pytestmark = pytest.mark.gpu
 
 G = float(np.exp(-0.3))
-SIZES = [1, 2, 63, 65, 257, 1000, 4099]
+# 1023 .. 1025: one frame a lane, then the first size with two; 6144 / 6145: the last size with the records in LDS, the first with
+# them in the workspace
+SIZES = [1, 2, 63, 65, 257, 1000, 1023, 1024, 1025, 4099, 6144, 6145]
 MODES = ["given", "g_given", "estimated"]
 LAM = 0.3
 BASE = np.array([1.0, 1.0, 1.0, 7.25, 0.0, 0.0, 0.0, 1.0])      # the baselines of the rows of make_traces, for the mode "given"
